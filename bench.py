@@ -15,8 +15,17 @@ timing.  `python bench.py --gpus N` with no torchrun environment starts torchrun
 child process (this parent never touches the GPU).  At N > 1 the line also carries C4 (the C3
 workload at per-GPU batch 1024 on every rank).  --dry-run rehearses the launcher, the slicing
 and the seeding with gloo on the CPU (no GPU work).
+
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the result line: nothing else.  --full adds every side measurement to the line
+(`extra`: C3, two streams, C5, the interpolation methods, the host-to-host and JPEG paths, C1,
+aeon_path_cpp, C4 at N > 1) and the CPU baselines (`cpu_baseline`); --no-extra and
+--no-cpu-baseline take either group out of a --full run again.  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs) so that two builds can be compared output for output: the
+sources, the params and the dumped sample depend on the arguments alone.
 """
 import argparse
+import ctypes
 import json
 import os
 import socket
@@ -41,9 +50,14 @@ def parse():
     ap.add_argument("--config", default="C2", choices=["C2", "C3"])
     ap.add_argument("--batch", type=int, default=0, help="records per step (default: config's)")
     ap.add_argument("--pool-mib", type=int, default=400, help="source pool size per GPU")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 and end-to-end side runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (the line's `extra`) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output batch (a fixed sample of its records when it "
+                         "is larger than 64 MB) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the C3 and end-to-end side runs")
     ap.add_argument("--streams", type=int, default=1, help="development: alternate batches over N streams")
     ap.add_argument("--timing-every", type=int, default=0,
                     help="development: also bracket the kernels of one step in N with HIP events (0 = none; the "
@@ -192,6 +206,26 @@ def real_pool(torch, n, w, h):
     return base.repeat(reps)[:n * w * h * 3].contiguous()
 
 
+def draw_windows(A, C, aug, batch, steps, seed, w, h):
+    """The params of `steps` consecutive windows of `batch` w x h records, one AugParams array per window
+    (marshalled once, as aeon's host fills it), drawn natively window by window (aeon_decoder_draw_params,
+    host only).  The decoder's slot engines are A.seed_slots(seed, batch) and its draw is
+    ParamFactory.make_params per slot, so these are the params of that loop written in Python, which
+    costs ~2 us per record (tests/test_host.py compares the two)."""
+    dec = A.Decoder({"etl": [C.IMAGE_224], "augmentation": [aug], "batch_size": batch, "random_seed": seed})
+    pixel = ctypes.c_uint8(0)  # (the draw reads the records' sizes alone)
+    recs = (A.RecordElem * batch)(*[A.RecordElem(ctypes.addressof(pixel), w, h, 3, w * 3) for _ in range(batch)])
+    windows = []
+    for _ in range(steps):
+        ps = (A.AugParams * batch)()
+        rc = A.lib().aeon_decoder_draw_params(dec._h, batch, recs, ps, 0)
+        if rc != 0:
+            raise A.AeonHipError(rc, A.lib().aeon_decoder_last_error().decode())
+        windows.append(ps)
+    dec.close()
+    return windows
+
+
 class Workload:
     """Synthetic already-decoded sources in HBM + pre-drawn params for every step."""
 
@@ -221,17 +255,8 @@ class Workload:
                     for _ in range(2)]
         # aeon deterministic mode: decoder seed = random_seed + node_id (src/loader.cpp:174),
         # one engine per decode slot, persisting across windows (src/batch_decoder.cpp:47-70)
-        f = A.ParamFactory(self.aug)
-        states = A.seed_slots(seed, batch)
         t0 = time.perf_counter()
-        self.params = []
-        for s in range(steps):
-            ps = []
-            for i in range(batch):
-                st = states[i:i + 1]
-                ps.append(f.make_params(st, w, h, 224, 224))
-                states[i] = st[0]
-            self.params.append((A.AugParams * batch)(*ps))  # marshalled once, as aeon's host fills it
+        self.params = draw_windows(A, C, self.aug, batch, steps, seed, w, h)
         self.param_us = (time.perf_counter() - t0) / max(1, steps * batch) * 1e6
 
     def step(self, ctx, s, stream):
@@ -248,8 +273,27 @@ def step_bytes(params):
     return float(sum(p.crop_w * p.crop_h * 3 + p.out_w * p.out_h * 3 * 4 for p in params))
 
 
+DUMP_MAX_BYTES = 60_000_000  # all ranks' files together stay under 64 MB, headers included
+
+
+def dump_outputs(torch, out_dir, wl, step, rank=0, world=1):
+    """--dump-outputs: the batch that step `step` of the workload wrote (what a caller of
+    aeon_hip_augment_batch receives: `batch` items of 3x224x224 float32 CHW), as
+    out_dir/augmented.npy (augmented_rank<r>.npy with more than one rank).  A batch over the byte
+    budget is cut to whole records drawn once with a fixed seed, in ascending order, so the same
+    arguments give the same records from run to run and from build to build."""
+    item = 3 * 224 * 224
+    n = min(wl.batch, DUMP_MAX_BYTES // world // (item * 4))
+    idx = np.sort(np.random.default_rng(0xD0C5).choice(wl.batch, n, replace=False))
+    dst = wl.dst[step & 1].view(torch.float32).view(wl.batch, 3, 224, 224)
+    arr = dst[torch.from_numpy(idx).to(dst.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    name = "augmented.npy" if world == 1 else f"augmented_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), arr)
+
+
 def run_device(A, C, torch, cfg, batch, steps, warmup, rank, world, pool_mib, dist, timing=8, streams=1,
-               region=False, real=False):
+               region=False, real=False, dump=None):
     """region: time the kernels as the timed region runs them, back to back -- one HIP event pair on
     the launch stream around steps 2..K (the first step only fills the queue), kt['augment'] = (that
     span, the steps' algorithmic bytes, K - 1).  A step of this workload is one tile-kernel launch
@@ -297,6 +341,8 @@ def run_device(A, C, torch, cfg, batch, steps, warmup, rank, world, pool_mib, di
         ctx.synchronize(st)
     kt = ctx.kernel_times()
     ctx.set_timing(False)
+    if dump and steps > 0:
+        dump_outputs(torch, dump, wl, warmup + steps - 1, rank, world)
     if region and steps > 1 and streams == 1:
         kt["augment"] = (ev[0].elapsed_time(ev[1]),
                          sum(step_bytes(wl.params[s]) for s in range(warmup + 1, warmup + steps)), steps - 1)
@@ -855,7 +901,7 @@ def main():
     timing = args.timing_every or (0 if region else 10)
     elapsed, kt, param_us, submit_s = run_device(A, C, torch, args.config, batch, args.steps, args.warmup,
                                                  rank, world, args.pool_mib, dist, timing, args.streams,
-                                                 region=region)
+                                                 region=region, dump=args.dump_outputs)
     total = batch * args.steps * world
     value = total / elapsed
     k_ms, k_bytes, k_n = kt["augment"]
@@ -865,8 +911,11 @@ def main():
     achieved = k_bytes / (k_ms * 1e-3) / 1e9 if k_ms else 0.0
     bytes_per_launch = k_bytes / max(k_n, 1)
 
+    # the side measurements and the CPU baselines: --full only
+    side_runs = args.full and not args.no_extra
+    cpu_baselines = args.full and not args.no_cpu_baseline
     extra = {}
-    if world > 1 and not args.no_extra:
+    if world > 1 and side_runs:
         # C4 (BASELINE configs[3]): the full augment_image workload at per-GPU batch 1024 on every
         # rank, each its own node slice and seed; global batch 1024 * N
         # (the rate from an untimed run -- an event pair around a launch idles the queue around it --
@@ -880,7 +929,7 @@ def main():
                        "augment_kernel_avg_launch_ms": m4 / max(n4, 1),
                        "what": "C3 workload on every rank (node slice + seed 1 + node_id), max over ranks; "
                                "rate untimed, kernel time from a second run timing every launch"}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and side_runs:
         if args.config == "C2":
             # rate untimed (an event pair between a step's launches costs ~10 us of GPU time there),
             # the kernel durations from a second run timing every launch
@@ -951,7 +1000,7 @@ def main():
             "what": "encoded JPEG records (aeon's img_2112_70.jpg / flowers.jpg) -> aeon_decoder submit/wait "
                     "(two windows in flight): extract on the JPEG stage + C2 augmentation, 512-record windows "
                     "(decode_size = 2 x batch 256)"})
-        if not args.no_cpu_baseline:
+        if cpu_baselines:
             for key, fn in (("e2e_jpeg_decoder", lambda: cpu_baseline_jpeg(A, C, args.cpu_extra_seconds)),
                             ("C1", lambda: cpu_baseline(A, C, args.cpu_extra_seconds, "C1")),
                             ("C3", lambda: cpu_baseline(A, C, args.cpu_extra_seconds, "C3")),
@@ -997,7 +1046,9 @@ def main():
     }
     if extra:
         line["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        line["dump_outputs"] = args.dump_outputs
+    if rank == 0 and world == 1 and cpu_baselines:
         line["cpu_baseline"] = cpu_baseline(A, C, args.cpu_seconds, args.config)
     if rank == 0:
         print(json.dumps(line), flush=True)

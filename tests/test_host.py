@@ -164,6 +164,110 @@ def test_bench_synthetic_pool_matches_synthetic_image():
         assert np.array_equal(pool[k * L:(k + 1) * L], A.synthetic_image(g, 19, 11, 3).reshape(-1))
 
 
+def _bench():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def _slot_engine_windows(aug, batch, steps, seed, w, h):
+    """The bench's params as aeon draws them: one engine per decode slot, persisting across windows."""
+    f = A.ParamFactory(aug)
+    states = A.seed_slots(seed, batch)
+    windows = []
+    for _ in range(steps):
+        ps = []
+        for i in range(batch):
+            st = states[i:i + 1]
+            ps.append(f.make_params(st, w, h, 224, 224))
+            states[i] = st[0]
+        windows.append(ps)
+    return windows
+
+
+@pytest.mark.parametrize("aug,batch,seed", [(C.C2_AUG, 7, 1), (C.C3_AUG, 66, 2),
+                                            (dict(C.C2_AUG, interpolation_method="CUBIC"), 33, 1)])
+def test_bench_windows_are_the_slot_engine_draws(aug, batch, seed):
+    """bench.draw_windows (one native window draw per step) gives, byte for byte, the AugParams of
+    make_params called per slot and step with the slots' engines carried from step to step; odd and
+    even batches, so the lighting draw's cached normal value is both kept and spent at window ends."""
+    import ctypes
+    got = _bench().draw_windows(A, C, aug, batch, 4, seed, 256, 256)
+    ref = _slot_engine_windows(aug, batch, 4, seed, 256, 256)
+    assert len(got) == 4 and all(len(g) == batch for g in got)
+    for g, r in zip(got, ref):
+        assert bytes(g) == b"".join(bytes(p) for p in r)
+    assert ctypes.sizeof(got[0]) == batch * ctypes.sizeof(A.AugParams)
+    assert bytes(got[0]) != bytes(got[1])
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """--dump-outputs: a batch over the byte budget is written as a fixed sample of whole records in
+    ascending order, float32, under 64 MB, the same records on every call; a smaller batch whole."""
+    import torch
+    bench = _bench()
+    item = 3 * 224 * 224
+
+    class Stub:
+        def __init__(self, batch):
+            self.batch = batch
+            recs = torch.arange(batch, dtype=torch.float32)[:, None].expand(batch, item).contiguous()
+            self.dst = [torch.zeros(batch * item * 4, dtype=torch.uint8), recs.view(torch.uint8).reshape(-1)]
+
+    big = Stub(128)
+    bench.dump_outputs(torch, str(tmp_path / "a"), big, 5)  # (step 5 wrote the second buffer)
+    bench.dump_outputs(torch, str(tmp_path / "b"), big, 5)
+    a, b = np.load(tmp_path / "a" / "augmented.npy"), np.load(tmp_path / "b" / "augmented.npy")
+    assert os.path.getsize(tmp_path / "a" / "augmented.npy") <= 64_000_000
+    assert a.dtype == np.float32 and a.shape[1:] == (3, 224, 224) and 90 <= a.shape[0] < 128
+    ids = a[:, 0, 0, 0]
+    assert np.all(np.diff(ids) > 0) and np.array_equal(a, np.broadcast_to(ids[:, None, None, None], a.shape))
+    assert np.array_equal(a, b)
+    bench.dump_outputs(torch, str(tmp_path / "z"), big, 4)
+    assert not np.load(tmp_path / "z" / "augmented.npy").any()  # (step 4: the first buffer)
+    small = Stub(5)
+    bench.dump_outputs(torch, str(tmp_path / "s"), small, 1)
+    assert np.array_equal(np.load(tmp_path / "s" / "augmented.npy")[:, 1, 2, 3], np.arange(5, dtype=np.float32))
+    bench.dump_outputs(torch, str(tmp_path / "r"), big, 5, rank=1, world=2)
+    assert np.load(tmp_path / "r" / "augmented_rank1.npy").shape[0] == a.shape[0] // 2
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py --steps N --warmup W` prints the headline line alone (no side measurements,
+    no CPU baseline), times N steps, and --dump-outputs holds what step W + N - 1 wrote: the oracle's
+    output for that step's records (pool batch (W + N - 1) mod pool size) and params, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    from tests import helpers as H
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    batch, steps, warmup, pool_mib = 6, 3, 2, 4
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warmup), "--batch", str(batch), "--pool-mib", str(pool_mib), "--dump-outputs",
+                        str(tmp_path)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert abs(line["value"] - batch / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert "extra" not in line and "cpu_baseline" not in line
+    got = np.load(tmp_path / "augmented.npy")
+    assert got.dtype == np.float32 and got.shape == (batch, 3, 224, 224)
+    last = warmup + steps - 1
+    n_pool = (pool_mib << 20) // (batch * 256 * 256 * 3)
+    assert n_pool == 3  # (so the last step's pool batch is neither the first nor step `last` itself)
+    first = (last % n_pool) * batch
+    imgs = [A.synthetic_image(first + i, 256, 256, 3) for i in range(batch)]
+    params = _slot_engine_windows(C.C2_AUG, batch, last + 1, 1, 256, 256)[last]
+    ref = H.oracle_records(imgs, params, C.out_desc_for(C.IMAGE_224, C.C2_AUG))
+    assert np.array_equal(got, np.stack(ref))
+
+
 def _param_tuple(p):
     return (p.crop_x, p.crop_y, p.crop_w, p.crop_h, p.flip, p.angle, p.hue, p.contrast, p.brightness,
             p.saturation, tuple(p.lighting[:3]), p.n_lighting)
