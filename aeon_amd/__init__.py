@@ -96,6 +96,22 @@ class EncodedRecords:
         return self.n
 
 
+BOX_BOUNDINGBOX, BOX_SSD = 0, 1
+EMIT_NONE, EMIT_CENTER, EMIT_MIN_OVERLAP = 0, 1, 2
+
+
+class BoxRecord(ctypes.Structure):
+    """aeon_box_record: a record's boxes in the box table of an aeon_hip_box_targets_batch call."""
+    _fields_ = [("first", ctypes.c_uint32), ("count", ctypes.c_int32)]
+
+
+class BoxOut(ctypes.Structure):
+    """aeon_box_out: target kind, sizes, emit constraint and the output buffers of a box call."""
+    _fields_ = [("kind", ctypes.c_int32), ("max_boxes", ctypes.c_int32), ("out_w", ctypes.c_int32),
+                ("out_h", ctypes.c_int32), ("emit_type", ctypes.c_int32), ("emit_min_overlap", ctypes.c_float),
+                ("buf", ctypes.c_void_p * 5), ("item_stride", ctypes.c_uint64 * 5)]
+
+
 class AeonHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"aeon_hip error {code}: {msg}")
@@ -143,6 +159,13 @@ def lib():
                                            ctypes.c_int, P(ctypes.c_float), ctypes.c_int, P(AugParams)]
         L.aeon_batch_sample_patches.argtypes = [vp, ctypes.c_int, P(ctypes.c_uint32), P(ctypes.c_float),
                                                 ctypes.c_int, P(ctypes.c_float), ctypes.c_int, P(ctypes.c_int)]
+        L.aeon_param_factory_emit.argtypes = [vp, P(ctypes.c_int), P(ctypes.c_float)]
+        L.aeon_box_extract.argtypes = ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 3 +
+                                       [P(ctypes.c_float), P(ctypes.c_int32), P(ctypes.c_int32), ctypes.c_int,
+                                        P(ctypes.c_int)])
+        L.aeon_box_last_error.restype = ctypes.c_char_p
+        L.aeon_hip_box_targets_batch.argtypes = [vp, ctypes.c_int, P(BoxRecord), P(ctypes.c_float), P(ctypes.c_int32),
+                                                 P(ctypes.c_int32), P(AugParams), P(BoxOut), vp]
         L.aeon_seed_slots.argtypes = [ctypes.c_uint32, ctypes.c_int, P(ctypes.c_uint32)]
         L.aeon_unbiased_round.argtypes = [ctypes.c_float, P(ctypes.c_int64)]
         L.aeon_calculate_scale.argtypes = [ctypes.c_int] * 4 + [P(ctypes.c_float)]
@@ -259,6 +282,103 @@ class ParamFactory:
                                           ctypes.byref(p)))
         state[0] = st.value
         return p
+
+    def emit(self):
+        """(EMIT_* code, emit_constraint_min_overlap) of the factory (aeon_param_factory_emit): what a
+        box call takes next to the params this factory draws."""
+        t, m = ctypes.c_int(), ctypes.c_float()
+        _check(lib().aeon_param_factory_emit(self._h, ctypes.byref(t), ctypes.byref(m)))
+        return t.value, m.value
+
+
+def box_extract(class_names, text):
+    """boundingbox::extractor::extract (aeon src/etl_boundingbox.cpp:64-132) of one record's JSON
+    metadata: {"width", "height", "depth", "boxes" (n x 4 float32: xmin, ymin, xmax, ymax), "labels",
+    "difficult" (int32)}.  AeonHipError with aeon's message for malformed metadata."""
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    names = json.dumps(list(class_names)).encode()
+    w, h, d, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    cap = 64
+    while True:
+        boxes, labels, diff = np.zeros((cap, 4), np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        rc = lib().aeon_box_extract(names, data, len(data), ctypes.byref(w), ctypes.byref(h), ctypes.byref(d),
+                                    boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                    labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                    diff.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cap, ctypes.byref(n))
+        if rc != 0:
+            raise AeonHipError(rc, lib().aeon_box_last_error().decode())
+        if n.value <= cap:
+            break
+        cap = n.value
+    k = n.value
+    return {"width": w.value, "height": h.value, "depth": d.value, "boxes": boxes[:k].copy(),
+            "labels": labels[:k].copy(), "difficult": diff[:k].copy()}
+
+
+SSD_OUTPUTS = ("image_shape", "gt_boxes", "gt_box_count", "gt_class_count", "difficult_flag")
+
+
+def box_targets(ctx, records, params, kind=BOX_SSD, max_boxes=64, out_w=0, out_h=0, emit=(EMIT_NONE, 0.0),
+                item_bytes=None, out_ptrs=None, stream=0):
+    """aeon_hip_box_targets_batch for len(records) records: records[i] = a box_extract() dict or a
+    (boxes n x 4, labels, difficult) tuple, params[i] = the AugParams of the record's image, emit = the
+    factory's ParamFactory.emit().  Without out_ptrs the kernel stores into pinned device-mapped buffers
+    filled with 0xCD beforehand, and the result comes back as numpy arrays: BOX_BOUNDINGBOX one float32
+    array (n, item_bytes / 4) (item_bytes: aeon's max_bbox_count * 16 * sizeof(output_type), default
+    float), BOX_SSD a dict of the five outputs by aeon's names.  With out_ptrs (device addresses, one per
+    output) the call is left asynchronous on `stream` and returns None."""
+    n = len(records)
+    recs = (BoxRecord * max(n, 1))()
+    bx, lb, df = [], [], []
+    first = 0
+    for i, r in enumerate(records):
+        b, l, d = (r["boxes"], r["labels"], r["difficult"]) if isinstance(r, dict) else r
+        b = np.asarray(b, np.float32).reshape(-1, 4)
+        recs[i] = BoxRecord(first, len(b))
+        bx.append(b), lb.append(np.asarray(l, np.int32).reshape(-1)), df.append(np.asarray(d, np.int32).reshape(-1))
+        if not len(b) == len(lb[-1]) == len(df[-1]):
+            raise ValueError(f"record {i}: {len(b)} boxes, {len(lb[-1])} labels, {len(df[-1])} difficult flags")
+        first += len(b)
+    boxes = np.ascontiguousarray(np.concatenate(bx) if bx else np.zeros((0, 4), np.float32))
+    labels = np.ascontiguousarray(np.concatenate(lb) if lb else np.zeros(0, np.int32))
+    diff = np.ascontiguousarray(np.concatenate(df) if df else np.zeros(0, np.int32))
+    p = params if isinstance(params, ctypes.Array) else (AugParams * max(n, 1))(*params)
+    if len(p) < n:
+        raise ValueError(f"{len(p)} params for {n} records")
+    if kind == BOX_SSD:
+        strides = [8, max_boxes * 16, 4, max_boxes * 4, max_boxes * 4]
+    else:
+        strides = [item_bytes if item_bytes is not None else max_boxes * 16 * 4]
+    o = BoxOut(kind=kind, max_boxes=max_boxes, out_w=out_w, out_h=out_h, emit_type=emit[0], emit_min_overlap=emit[1])
+    own = []
+    try:
+        for k, s in enumerate(strides):
+            o.item_stride[k] = s
+            if out_ptrs is not None:
+                o.buf[k] = out_ptrs[k]
+            else:
+                q = ctypes.c_void_p()
+                _check(lib().aeon_hip_host_alloc(max(n * s, 16), ctypes.byref(q)))
+                own.append(q)
+                ctypes.memset(q, 0xCD, max(n * s, 16))
+                o.buf[k] = q.value
+        fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
+        _check(lib().aeon_hip_box_targets_batch(ctx._h, n, recs, boxes.ctypes.data_as(fp), labels.ctypes.data_as(ip),
+                                                diff.ctypes.data_as(ip), p, ctypes.byref(o),
+                                                ctypes.c_void_p(stream or 0)))
+        if out_ptrs is not None:
+            return None
+        ctx.synchronize(stream)
+        outs = [np.frombuffer(ctypes.string_at(q, n * s), np.uint8).copy() for q, s in zip(own, strides)]
+    finally:
+        for q in own:
+            lib().aeon_hip_host_free(q)
+    if kind != BOX_SSD:
+        return outs[0].view(np.float32).reshape(n, -1)
+    res = {"image_shape": outs[0].view(np.int32).reshape(n, 2), "gt_boxes": outs[1].view(np.float32).reshape(n, max_boxes, 4),
+           "gt_box_count": outs[2].view(np.int32).reshape(n), "gt_class_count": outs[3].view(np.int32).reshape(n, max_boxes),
+           "difficult_flag": outs[4].view(np.int32).reshape(n, max_boxes)}
+    return res
 
 
 def seed_slots(seed, n):
@@ -562,11 +682,18 @@ def _check_host(rc):
 
 
 class Decoder:
-    """aeon batch_decoder over provider_factory::create(config): decode windows of decoded
-    records (one HWC uint8 array per ETL element) into the provider output buffers."""
+    """aeon batch_decoder over provider_factory::create(config): decode windows of records (per ETL
+    element an HWC uint8 array, an encoded JPEG / PNG file, or -- boundingbox and localization_ssd
+    elements -- the JSON metadata as bytes or str) into the provider output buffers.  A provider may own
+    several output buffers (localization_ssd: five), so records have n_inputs elements and windows
+    len(outputs) buffers, in get_output_shapes() order."""
 
     def __init__(self, config, device=0):
         text = config if isinstance(config, str) else json.dumps(config)
+        try:
+            self.n_inputs = len(json.loads(text)["etl"])
+        except (ValueError, KeyError, TypeError):
+            self.n_inputs = 0  # the library reports what is wrong with the config
         h = ctypes.c_void_p()
         _check_host(lib().aeon_decoder_create(text.encode(), device, ctypes.byref(h)))
         self._h = h
@@ -605,12 +732,14 @@ class Decoder:
         """aeon_encoded_elem array for records whose elements are JPEG bytes or HWC uint8 arrays."""
         if isinstance(records, EncodedRecords):
             return records.elems, records.keep
-        n, ne = len(records), len(self.outputs)
+        n, ne = len(records), self.n_inputs
         keep = []
         elems = (EncodedElem * (n * ne))()
         for i, rec in enumerate(records):
             for k in range(ne):
                 x = rec[k]
+                if isinstance(x, str):
+                    x = x.encode()
                 if isinstance(x, (bytes, bytearray, memoryview)):
                     b = bytes(x)
                     keep.append(b)
@@ -627,10 +756,10 @@ class Decoder:
         """records: list of tuples, one element per ETL provider: HWC uint8 arrays or encoded JPEG
         bytes.  Returns one numpy array per output buffer, shape (n,) + item shape."""
         n = len(records)
-        ne = len(self.outputs)
+        ne = self.n_inputs
         outs = [np.zeros((n,) + o["shape"], o["dtype"]) for o in self.outputs]
-        ptrs = (ctypes.c_void_p * ne)(*[o.ctypes.data for o in outs])
-        if any(isinstance(x, (bytes, bytearray, memoryview)) for rec in records for x in rec):
+        ptrs = (ctypes.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        if any(isinstance(x, (str, bytes, bytearray, memoryview)) for rec in records for x in rec):
             elems, keep = self._encoded(records)
             _check_host(lib().aeon_decoder_decode_encoded(self._h, n, elems, ptrs, 0, ctypes.c_void_p(stream or 0)))
             return outs
@@ -646,11 +775,15 @@ class Decoder:
         _check_host(lib().aeon_decoder_decode(self._h, n, elems, ptrs, 0, ctypes.c_void_p(stream or 0)))
         return outs
 
+    def decode_named(self, records, stream=0):
+        """decode() with the outputs by buffer name (aeon's fixed_buffer_map keys)."""
+        return {o["name"]: a for o, a in zip(self.outputs, self.decode(records, stream))}
+
     def draw_params(self, sizes, serial=False):
         """The draw phase of one window alone (aeon_decoder_draw_params, host only): sizes = one
         (width, height) per record (of its first element; the others get the same size); returns
         the records' AugParams.  The slot engines advance as in a real window."""
-        n, ne = len(sizes), len(self.outputs)
+        n, ne = len(sizes), self.n_inputs
         elems = (RecordElem * (n * ne))()
         dummy = ctypes.c_uint8(0)
         for i, (w, h) in enumerate(sizes):
@@ -665,9 +798,9 @@ class Decoder:
         output k (pinned host memory, or device memory with on_device); complete after wait().
         records: a list of tuples, or an EncodedRecords from encoded() (kept alive by the caller
         until the window's wait())."""
-        n, ne = len(records), len(self.outputs)
+        n = len(records)
         elems, keep = self._encoded(records)
-        ptrs = (ctypes.c_void_p * ne)(*output_ptrs)
+        ptrs = (ctypes.c_void_p * len(self.outputs))(*output_ptrs)
         _check_host(lib().aeon_decoder_submit(self._h, n, elems, ptrs, int(on_device)))
 
     def wait(self):

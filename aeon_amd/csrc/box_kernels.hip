@@ -1,0 +1,158 @@
+// box_kernels.hip -- boundingbox / localization_ssd targets of a decode window in one launch.
+//
+// aeon transforms a record's object boxes with the params that cropped, expanded and flipped its
+// image (boundingbox::transformer::transform_box, src/etl_boundingbox.cpp:146-261, with
+// boundingbox::box::expand / rescale / coverage / normalize, src/boundingbox.cpp:78-163, box.hpp:51-93)
+// and loads the survivors, in input order, into zero-padded fixed-size items:
+//   provider::boundingbox        loader (etl_boundingbox.cpp:296-318): max_bbox_count x 4 floats
+//   provider::localization::ssd  loader (etl_localization_ssd.cpp:116-150): image_shape, gt_boxes
+//                                (normalized), gt_box_count, gt_class_count, difficult_flag
+// One wave (64 lanes) per record, four records per 256-thread workgroup, no LDS: lanes take the
+// record's boxes 64 at a time, each decides keep / drop, and the kept ones are compacted in order with
+// a ballot and the popcount of the lower lanes on top of a wave-uniform running count.  Slots past
+// max_boxes are not written (aeon's min(max, size)); the rest of every item is zero-filled.
+//
+// Arithmetic: float32, every operation rounded once and in aeon's order (-ffp-contract=off; the
+// divisions are the correctly rounded ones), so the outputs equal aeon's bit for bit.  aeon's range
+// check in normalized_box::box's constructor (normalized_box.cpp:90-107: a coordinate outside [0, 1]
+// throws) is NOT reproduced: the normalized values are written as computed.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/aeon_hip.h"
+#include "box_job.hpp"
+
+namespace aeon_hip {
+
+namespace {
+
+// box::size (box.hpp:58-69): inclusive, 0 when inverted
+__device__ inline float box_size(float xmin, float ymin, float xmax, float ymax)
+{
+    if (xmax < xmin || ymax < ymin) return 0.0f;
+    const float w = xmax - xmin + 1.0f;
+    const float h = ymax - ymin + 1.0f;
+    return w * h;
+}
+
+// transform_box for one box; false = dropped
+__device__ inline bool transform_box(const BoxRec& r, int emit_type, float emit_min_overlap, float4& b)
+{
+    float xmin = b.x, ymin = b.y, xmax = b.z, ymax = b.w;
+    if (r.expand) { // box::expand -> operator+(cv::Point)
+        xmin = xmin + (float)r.expand_x;
+        ymin = ymin + (float)r.expand_y;
+        xmax = xmax + (float)r.expand_x;
+        ymax = ymax + (float)r.expand_y;
+    }
+    if (emit_type != AEON_EMIT_NONE) { // meet_emit_constraint
+        const float cx0 = (float)r.crop_x, cy0 = (float)r.crop_y;
+        const float cx1 = (float)(r.crop_x + r.crop_w - 1), cy1 = (float)(r.crop_y + r.crop_h - 1);
+        if (emit_type == AEON_EMIT_CENTER) {
+            // box::xcenter (box.hpp:92): the float difference, halved and added in double, narrowed
+            const float xc = (float)((double)xmin + (double)(xmax - xmin) / 2.);
+            const float yc = (float)((double)ymin + (double)(ymax - ymin) / 2.);
+            if (!(xc >= cx0 && xc <= cx1 && yc >= cy0 && yc <= cy1)) return false;
+        } else { // input_bbox.coverage(crop_bbox) >= emit_min_overlap
+            float isz = 0.0f;
+            if (!(cx0 > xmax || cx1 < xmin || cy0 > ymax || cy1 < ymin)) {
+                const float ix0 = xmin < cx0 ? cx0 : xmin, iy0 = ymin < cy0 ? cy0 : ymin; // std::max(a, b)
+                const float ix1 = cx1 < xmax ? cx1 : xmax, iy1 = cy1 < ymax ? cy1 : ymax; // std::min(a, b)
+                isz = box_size(ix0, iy0, ix1, iy1);
+            }
+            float coverage = 0.0f;
+            if (isz > 0) coverage = isz / box_size(xmin, ymin, xmax, ymax);
+            if (!(coverage >= emit_min_overlap)) return false;
+        }
+    }
+    const float cx = (float)r.crop_x, cy = (float)r.crop_y;
+    const float cxe = (float)(r.crop_x + r.crop_w), cye = (float)(r.crop_y + r.crop_h);
+    const float cw = (float)r.crop_w, ch = (float)r.crop_h;
+    if (xmax < cx || xmin >= cxe || ymax < cy || ymin >= cye) return false;
+    xmin = xmin < cx ? 0.0f : xmin - cx;
+    ymin = ymin < cy ? 0.0f : ymin - cy;
+    xmax = xmax >= cxe ? (float)(r.crop_w - 1) : xmax - cx;
+    ymax = ymax >= cye ? (float)(r.crop_h - 1) : ymax - cy;
+    if (r.flip) {
+        const float old_xmax = xmax;
+        xmax = cw - xmin - 1.0f;
+        xmin = cw - old_xmax - 1.0f;
+    }
+    const float xs = (float)r.out_w / cw;
+    const float ys = (float)r.out_h / ch;
+    b.x = xmin * xs;
+    b.y = ymin * ys;
+    b.z = (xmax + 1.0f) * xs - 1.0f;
+    b.w = (ymax + 1.0f) * ys - 1.0f;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void box_targets(BoxLaunch L)
+{
+    const int lane = threadIdx.x & 63;
+    const int rec  = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (rec >= L.n) return; // the whole wave leaves: no barrier anywhere below
+    const BoxRec   r     = L.recs[rec];
+    const float4*  boxes = (const float4*)L.boxes + r.first;
+    const int32_t* lab   = L.labels + r.first;
+    const int32_t* dif   = L.difficult + r.first;
+    const bool     ssd   = L.kind == AEON_BOX_SSD;
+    const int      bi    = ssd ? 1 : 0; // the boxes' buffer
+    float4*  out_box = (float4*)(L.buf[bi] + (uint64_t)rec * L.stride[bi]);
+    int32_t* out_cls = ssd ? (int32_t*)(L.buf[3] + (uint64_t)rec * L.stride[3]) : nullptr;
+    int32_t* out_dif = ssd ? (int32_t*)(L.buf[4] + (uint64_t)rec * L.stride[4]) : nullptr;
+
+    int kept = 0; // wave-uniform
+    for (int base = 0; base < r.count; base += 64) {
+        const int i    = base + lane;
+        bool      keep = false;
+        float4    b    = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < r.count) {
+            b    = boxes[i];
+            keep = transform_box(r, L.emit_type, L.emit_min_overlap, b);
+        }
+        const unsigned long long mask = __ballot(keep);
+        const int slot = kept + __popcll(mask & ((1ull << lane) - 1ull));
+        if (keep && slot < L.max_boxes) {
+            if (ssd) { // bbox::normalize (boundingbox.cpp:150-156)
+                b.x = b.x / L.norm_w;
+                b.y = b.y / L.norm_h;
+                b.z = (b.z + 1.0f) / L.norm_w;
+                b.w = (b.w + 1.0f) / L.norm_h;
+                out_cls[slot] = lab[i];
+                out_dif[slot] = dif[i] != 0 ? 1 : 0;
+            }
+            out_box[slot] = b;
+        }
+        kept += __popcll(mask);
+    }
+    const int filled = kept < L.max_boxes ? kept : L.max_boxes;
+    for (int s = filled + lane; s < L.max_boxes; s += 64) {
+        out_box[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ssd) out_cls[s] = 0, out_dif[s] = 0;
+    }
+    if (ssd) {
+        if (lane == 0) {
+            int32_t* shape = (int32_t*)(L.buf[0] + (uint64_t)rec * L.stride[0]);
+            shape[0] = L.shape_w;
+            shape[1] = L.shape_h;
+            *(int32_t*)(L.buf[2] + (uint64_t)rec * L.stride[2]) = filled;
+        }
+    } else {
+        // aeon's item is max_bbox_count x 16 elements of output_type, of which the loader writes the
+        // first max_bbox_count x 4 floats: the rest is zeroed here (16 bytes per lane and step)
+        const int n16 = (int)(L.stride[0] / 16);
+        for (int s = L.max_boxes + lane; s < n16; s += 64) out_box[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+} // namespace
+
+hipError_t launch_box_targets(const BoxLaunch& L, hipStream_t stream)
+{
+    if (L.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(box_targets, dim3((unsigned)((L.n + 3) / 4)), dim3(256), 0, stream, L);
+    return hipGetLastError();
+}
+
+} // namespace aeon_hip

@@ -1,5 +1,6 @@
 // host.cpp -- provider plugin surface + decode stage of the HIP image path (see host.hpp).
 #include "host.hpp"
+#include "box_job.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -14,6 +15,7 @@
 #include <set>
 #include <sstream>
 #include <stdexcept>
+#include <unordered_map>
 
 namespace aeon_hip {
 
@@ -271,6 +273,146 @@ private:
     std::string   m_name;
 };
 
+// boundingbox::config (etl_boundingbox.cpp:27-49, etl_boundingbox.hpp) and localization::ssd::config
+// (etl_localization_ssd.cpp:30-78, etl_localization_ssd.hpp) in one struct: the sizes, the class names
+// and the output shapes, in aeon's order.
+struct box_config {
+    int                                  kind = AEON_BOX_BOUNDINGBOX;
+    int64_t                              height = 0, width = 0, max_boxes = 64;
+    std::vector<std::string>             class_names;
+    std::string                          name, output_type_name = "float";
+    std::unordered_map<std::string, int> label_map;
+    std::vector<shape_type>              shapes;
+
+    box_config(const Json& js, int kind_) : kind(kind_)
+    {
+        const bool ssd = kind == AEON_BOX_SSD;
+        if (js.is_null()) throw std::runtime_error(ssd ? "missing ssd config in json config" : "missing bbox config in json config");
+        const char* max_key = ssd ? "max_gt_boxes" : "max_bbox_count";
+        for (const char* key : {"height", "width", "class_names"})
+            if (!js.has(key)) invalid(std::string("Required Argument: '") + key + "' not set");
+        if (!ssd && !js.has(max_key)) invalid(std::string("Required Argument: '") + max_key + "' not set");
+        get_num(js, "height", height);
+        get_num(js, "width", width);
+        get_num(js, max_key, max_boxes);
+        get_str(js, "name", name);
+        for (const Json& n : js.at("class_names").array()) class_names.push_back(n.str());
+        if (ssd) {
+            verify_config("localization_ssd", {"type", "height", "width", "class_names", "name", "max_gt_boxes"}, js);
+            // localization::ssd::config::validate
+            if (width <= 0) invalid("invalid width");
+            if (height <= 0) invalid("invalid height");
+            if (max_boxes <= 0) invalid("invalid max_gt_boxes");
+            if (class_names.empty()) invalid("class_names cannot be empty");
+        } else {
+            get_str(js, "output_type", output_type_name);
+            if (!output_type::is_valid_type(output_type_name)) invalid("value for 'output_type' out of range");
+            verify_config("bbox", {"type", "height", "width", "class_names", "name", "max_bbox_count", "output_type"}, js);
+            // aeon's boundingbox::config::validate is empty; this stage needs sizes it can launch with
+            if (width <= 0) invalid("invalid width");
+            if (height <= 0) invalid("invalid height");
+            if (max_boxes <= 0) invalid("invalid max_bbox_count");
+        }
+        if (max_boxes > (1 << 24) || width > (1 << 30) || height > (1 << 30)) invalid("box config out of range");
+        label_map = box_label_map(class_names);
+        auto add = [&](std::vector<size_t> s, const char* t) {
+            shape_type st;
+            st.shape = std::move(s);
+            st.otype = output_type(t);
+            shapes.push_back(st);
+        };
+        const size_t m = (size_t)max_boxes;
+        if (ssd) {
+            add({2, 1}, "int32_t");
+            add({m, 4}, "float");
+            add({1, 1}, "int32_t");
+            add({m, 1}, "int32_t");
+            add({m, 1}, "int32_t");
+        } else {
+            // aeon's quirk (etl_boundingbox.cpp:41): {max_bbox_count, 4 * sizeof(float)} elements of
+            // output_type, of which the loader writes the first max_bbox_count * 4 floats
+            add({m, 4 * sizeof(float)}, output_type_name.c_str());
+        }
+    }
+};
+
+// provider::boundingbox (provider.cpp:395-439) and provider::localization::ssd (provider.cpp:289-346):
+// extract the record's JSON metadata, draw (make_params / make_ssd_params over the extracted boxes)
+// when the record has no params yet; transform + load run in the window's box launch (post_process).
+class box_provider : public etl_provider {
+public:
+    box_provider(const Json& js, const Json& aug, int kind) : m_cfg(js, kind), m_factory(aug)
+    {
+        static const char* const ssd_names[5] = {"image_shape", "gt_boxes", "gt_box_count", "gt_class_count",
+                                                 "difficult_flag"};
+        if (kind == AEON_BOX_SSD)
+            for (const char* n : ssd_names) m_names.push_back(create_name(m_cfg.name, n));
+        else
+            m_names.push_back(create_name(m_cfg.name, "boundingbox"));
+    }
+    void provide(int, const decoded_element&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
+                 light_split*) const override
+    {
+        throw std::logic_error("box providers take their element through provide_boxes");
+    }
+    void extract(const decoded_element& in, box_metadata& m) const override
+    {
+        box_extract(m_cfg.label_map, in.data, in.size, m);
+    }
+    void provide_boxes(const box_metadata& m, augmentation& aug, std::minstd_rand0& random, aeon_aug_params& params,
+                       light_split* ls) const override
+    {
+        if (!aug.has) {
+            const int W = (int)m_cfg.width, H = (int)m_cfg.height, nb = (int)m.labels.size();
+            if (m_cfg.kind == AEON_BOX_SSD) {
+                if (ls)
+                    m_factory.make_ssd_params_split(random, m.width, m.height, W, H, m.boxes.data(), nb, ls->entry_avail,
+                                                    &aug.image, &ls->exit_saved);
+                else
+                    m_factory.make_ssd_params(random, m.width, m.height, W, H, m.boxes.data(), nb, &aug.image);
+            } else {
+                if (ls)
+                    m_factory.make_params_split(random, m.width, m.height, W, H, ls->entry_avail, &aug.image,
+                                                &ls->exit_saved);
+                else
+                    m_factory.make_params(random, m.width, m.height, W, H, &aug.image);
+            }
+            aug.has = true;
+        }
+        params = aug.image;
+    }
+    const param_factory& factory() const override { return m_factory; }
+    bool               is_mask() const override { return false; }
+    const shape_type&  shape() const override { return m_cfg.shapes[0]; }
+    const std::string& buffer_name() const override { return m_names[0]; }
+    aeon_out_desc      out_desc() const override { return aeon_out_desc{}; }
+    std::vector<std::pair<std::string, shape_type>> output_shapes() const override
+    {
+        std::vector<std::pair<std::string, shape_type>> v;
+        for (size_t i = 0; i < m_names.size(); i++) v.emplace_back(m_names[i], m_cfg.shapes[i]);
+        return v;
+    }
+    int          box_kind() const override { return m_cfg.kind; }
+    aeon_box_out box_out() const override
+    {
+        aeon_box_out o{};
+        o.kind      = m_cfg.kind;
+        o.max_boxes = (int)m_cfg.max_boxes;
+        o.out_w = (int)m_cfg.width, o.out_h = (int)m_cfg.height;
+        // param_factory::emit_constraint_type, lower-cased and validated by the factory
+        const std::string& e = m_factory.emit_constraint_type;
+        o.emit_type          = e == "center" ? AEON_EMIT_CENTER : e == "min_overlap" ? AEON_EMIT_MIN_OVERLAP : AEON_EMIT_NONE;
+        o.emit_min_overlap   = m_factory.emit_constraint_min_overlap;
+        for (size_t i = 0; i < m_cfg.shapes.size(); i++) o.item_stride[i] = m_cfg.shapes[i].byte_size();
+        return o;
+    }
+
+private:
+    box_config               m_cfg;
+    param_factory            m_factory;
+    std::vector<std::string> m_names;
+};
+
 } // namespace
 
 provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const Json& aug)
@@ -282,15 +424,19 @@ provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const
         std::unique_ptr<etl_provider> p;
         if (type == "image") p.reset(new image_provider(j, aug));
         else if (type == "pixelmask") p.reset(new pixelmask_provider(j, aug));
-        else if (type == "label" || type == "localization_rcnn" || type == "localization_ssd" ||
-                 type == "boundingbox" || type == "blob" || type == "video" || type == "char_map" ||
-                 type == "label_map")
+        else if (type == "boundingbox") p.reset(new box_provider(j, aug, AEON_BOX_BOUNDINGBOX));
+        else if (type == "localization_ssd") p.reset(new box_provider(j, aug, AEON_BOX_SSD));
+        else if (type == "label" || type == "localization_rcnn" || type == "blob" || type == "video" ||
+                 type == "char_map" || type == "label_map")
             throw std::runtime_error("etl type '" + type + "' is outside the HIP image stage");
         else
             invalid("unsupported etl type '" + type + "'");
-        m_output_shapes.emplace_back(p->buffer_name(), p->shape());
+        m_out_first.push_back((int)m_output_shapes.size());
+        for (auto& s : p->output_shapes()) m_output_shapes.push_back(std::move(s));
+        m_has_boxes = m_has_boxes || p->box_kind() >= 0;
         m_providers.push_back(std::move(p));
     }
+    m_out_first.push_back((int)m_output_shapes.size());
 }
 
 void provider_base::provide(int idx, const decoded_element* elems, decode_window& w,
@@ -306,6 +452,18 @@ void provider_base::draw(int idx, const decoded_element* elems, decode_window& w
     augmentation aug;
     for (size_t k = 0; k < m_providers.size(); k++) {
         const decoded_element& e = elems[k];
+        if (m_providers[k]->box_kind() >= 0) { // metadata: extract, then the record's (shared) params
+            if (!e.data || e.size == 0) {
+                std::stringstream ss;
+                ss << "received " << (m_providers[k]->box_kind() == AEON_BOX_SSD ? "localization_ssd data" : "boundingbox")
+                   << " with size 0, at idx " << idx;
+                throw std::runtime_error(ss.str());
+            }
+            box_metadata& m = w.boxes[k][idx];
+            m_providers[k]->extract(e, m);
+            m_providers[k]->provide_boxes(m, aug, random, w.params[k][idx], ls);
+            continue;
+        }
         if (!e.data || e.width <= 0 || e.height <= 0) {
             std::stringstream ss;
             ss << "received " << (m_providers[k]->is_mask() ? "pixelmask" : "encoded image")
@@ -359,7 +517,7 @@ void provider_base::stage(int idx, const decoded_element* elems, decode_window& 
 {
     for (size_t k = 0; k < m_providers.size(); k++) {
         const decoded_element& e = elems[k];
-        if (e.encoded) continue; // decoded on the device, straight into the source arena
+        if (e.encoded || e.metadata) continue; // decoded on the device, straight into the source arena / no pixels
         const size_t row = (size_t)e.width * e.channels * e.elem_bytes;
         uint8_t*     dst = w.arena + w.offset[k][idx];
         if (e.png_mode >= 0) { // extract on this pool thread, straight into the pinned arena
@@ -377,7 +535,8 @@ void provider_base::post_process(aeon_hip_ctx* ctx, decode_window& w, const uint
 {
     // image + pixelmask with the same params per record (provider.cpp:365-393): one pair call, whose
     // masks run inside the image launch
-    if (m_providers.size() == 2 && !m_providers[0]->is_mask() && m_providers[1]->is_mask() && w.n > 0 &&
+    if (m_providers.size() == 2 && m_providers[0]->box_kind() < 0 && !m_providers[0]->is_mask() &&
+        m_providers[1]->is_mask() && w.n > 0 &&
         std::memcmp(w.params[0].data(), w.params[1].data(), (size_t)w.n * sizeof(aeon_aug_params)) == 0) {
         aeon_out_desc io = m_providers[0]->out_desc(), mo = m_providers[1]->out_desc();
         check(aeon_hip_augment_pair_batch(ctx, w.n, w.descs[0].data(), dev_arena, w.descs[1].data(), dev_arena,
@@ -386,13 +545,61 @@ void provider_base::post_process(aeon_hip_ctx* ctx, decode_window& w, const uint
     }
     for (size_t k = 0; k < m_providers.size(); k++) {
         const etl_provider& p = *m_providers[k];
-        aeon_out_desc       o = p.out_desc();
+        void* const*        out = outputs + m_out_first[k];
+        if (p.box_kind() >= 0) { // the window's box launch, over the table staged with the pixels
+            aeon_box_out bo = p.box_out();
+            for (int j = 0; j < m_out_first[k + 1] - m_out_first[k]; j++) bo.buf[j] = out[j];
+            check(box_targets_staged(ctx, w.n, dev_arena + w.box_offset[k], w.box_total[k], bo, stream));
+            continue;
+        }
+        aeon_out_desc o = p.out_desc();
         if (p.is_mask())
-            check(aeon_hip_mask_batch(ctx, w.n, w.descs[k].data(), dev_arena, w.params[k].data(), &o,
-                                      outputs[k], stream));
+            check(aeon_hip_mask_batch(ctx, w.n, w.descs[k].data(), dev_arena, w.params[k].data(), &o, out[0], stream));
         else
-            check(aeon_hip_augment_batch(ctx, w.n, w.descs[k].data(), dev_arena, w.params[k].data(), &o,
-                                         outputs[k], stream));
+            check(aeon_hip_augment_batch(ctx, w.n, w.descs[k].data(), dev_arena, w.params[k].data(), &o, out[0], stream));
+    }
+}
+
+size_t provider_base::layout_boxes(decode_window& w, size_t offset) const
+{
+    w.box_offset.assign(m_providers.size(), 0);
+    w.box_total.assign(m_providers.size(), 0);
+    for (size_t k = 0; k < m_providers.size(); k++) {
+        if (m_providers[k]->box_kind() < 0) continue;
+        size_t total = 0;
+        for (int i = 0; i < w.n; i++) total += w.boxes[k][i].labels.size();
+        if (total > ((size_t)1 << 26)) invalid("box table too large");
+        w.box_offset[k] = offset;
+        w.box_total[k]  = total;
+        offset += (box_table_bytes(w.n, total) + 15) & ~(size_t)15;
+    }
+    return offset;
+}
+
+void provider_base::stage_boxes(decode_window& w) const
+{
+    for (size_t k = 0; k < m_providers.size(); k++) {
+        if (m_providers[k]->box_kind() < 0) continue;
+        const size_t total = w.box_total[k];
+        uint8_t*     t     = w.arena + w.box_offset[k];
+        BoxRec*      R     = (BoxRec*)t;
+        float*       bx    = (float*)(t + box_rec_bytes(w.n));
+        int32_t*     lb    = (int32_t*)(t + box_rec_bytes(w.n) + total * 16);
+        int32_t*     df    = (int32_t*)(t + box_rec_bytes(w.n) + total * 20);
+        size_t       first = 0;
+        for (int i = 0; i < w.n; i++) {
+            const box_metadata& m   = w.boxes[k][i];
+            const int           cnt = (int)m.labels.size();
+            if (const char* why = box_refusal(w.params[k][i], m.boxes.data(), cnt))
+                invalid(std::string(why) + ", at idx " + std::to_string(i));
+            R[i] = box_rec((uint32_t)first, cnt, w.params[k][i]);
+            if (cnt) {
+                std::memcpy(bx + 4 * first, m.boxes.data(), sizeof(float) * 4 * (size_t)cnt);
+                std::memcpy(lb + first, m.labels.data(), sizeof(int32_t) * (size_t)cnt);
+                std::memcpy(df + first, m.difficult.data(), sizeof(int32_t) * (size_t)cnt);
+            }
+            first += (size_t)cnt;
+        }
     }
 }
 
@@ -741,13 +948,29 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     w.descs.assign(ne, std::vector<aeon_img_desc>(n));
     w.params.assign(ne, std::vector<aeon_aug_params>(n));
     w.offset.assign(ne, std::vector<size_t>(n));
-    // source arena: decoded elements first (staged + one H2D), then the device-decoded JPEGs
-    size_t staged = 0, total = 0;
+    w.boxes.resize(ne);
+    for (int k = 0; k < ne; k++)
+        if (m_provider->providers()[k]->box_kind() >= 0) w.boxes[k].resize(n);
+    // batch_decoder::process: the slot engine of record i draws its params (deterministic mode
+    // swaps the slot engine in and out, batch_decoder.cpp:62-71).  With slot engines the draws run
+    // on the pool (draw_window: aeon's in-order params exactly), and with them the extraction of the
+    // box providers' metadata, which make_ssd_params draws over.
+    {
+        phase_range r("aeon.draw");
+        if (m_deterministic) {
+            m_provider->draw_window(n, records.data(), w, m_random, *m_pool);
+        } else { // one engine for the window: in record order
+            for (int i = 0; i < n; i++) m_provider->draw(i, records.data() + (size_t)i * ne, w, m_local_random);
+        }
+    }
+    // source arena: the box tables and the decoded elements first (staged + one H2D), then the
+    // device-decoded JPEGs
+    size_t staged = m_provider->layout_boxes(w, 0), total = staged;
     for (int pass = 0; pass < 2; pass++)
         for (int i = 0; i < n; i++)
             for (int k = 0; k < ne; k++) {
                 const decoded_element& e = records[(size_t)i * ne + k];
-                if (e.encoded != (pass == 1)) continue;
+                if (e.encoded != (pass == 1) || e.metadata) continue;
                 const size_t b = (size_t)std::max(e.width, 0) * std::max(e.height, 0) * std::max(e.channels, 0) *
                                  e.elem_bytes;
                 w.offset[k][i] = total;
@@ -765,21 +988,11 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     }
     grow_dev(ws.dev_src, ws.dev_src_cap, total);
     w.arena = ws.pinned;
-    // batch_decoder::process: the slot engine of record i draws its params (deterministic mode
-    // swaps the slot engine in and out, batch_decoder.cpp:62-71).  With slot engines the draws run
-    // on the pool (draw_window: aeon's in-order params exactly); then the pool threads stage the
-    // pixels into the pinned arena.
-    {
-        phase_range r("aeon.draw");
-        if (m_deterministic) {
-            m_provider->draw_window(n, records.data(), w, m_random, *m_pool);
-        } else { // one engine for the window: in record order
-            for (int i = 0; i < n; i++) m_provider->draw(i, records.data() + (size_t)i * ne, w, m_local_random);
-        }
-    }
+    // the pool threads stage the pixels into the pinned arena, next to the window's box tables
     if (staged) {
         {
             phase_range r("aeon.stage");
+            m_provider->stage_boxes(w);
             m_pool->run(n, [&](int i) { m_provider->stage(i, records.data() + (size_t)i * ne, w); });
         }
         phase_range r("aeon.h2d_enqueue");
@@ -799,12 +1012,15 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
             check(aeon_hip_decode_jpeg_batch(m_ctx, (int)files.size(), files.data(), sizes.data(), descs.data(),
                                              ws.dev_src, stream));
     }
-    std::vector<void*> outs(ne);
-    std::vector<bool>  copy_out(ne, false); // staged on the device, then one D2H into outputs[k]
-    ws.dev_out.resize(ne, nullptr), ws.dev_out_cap.resize(ne, 0);
-    ws.dev_tmp.resize(ne, nullptr), ws.dev_tmp_cap.resize(ne, 0);
-    for (int k = 0; k < ne; k++) {
-        const size_t bytes = (size_t)n * m_provider->providers()[k]->shape().byte_size();
+    // outputs[] follow get_output_shapes(): a provider may own several buffers (localization_ssd: five)
+    const auto& oshapes = m_provider->get_output_shapes();
+    const int   no      = (int)oshapes.size();
+    std::vector<void*> outs(no);
+    std::vector<bool>  copy_out(no, false); // staged on the device, then one D2H into outputs[k]
+    ws.dev_out.resize(no, nullptr), ws.dev_out_cap.resize(no, 0);
+    ws.dev_tmp.resize(no, nullptr), ws.dev_tmp_cap.resize(no, 0);
+    for (int k = 0; k < no; k++) {
+        const size_t bytes = (size_t)n * oshapes[k].second.byte_size();
         if (on_device) outs[k] = outputs[k];
         else if (void* v = zero_copy_view(outputs[k])) outs[k] = v;
         else {
@@ -817,14 +1033,14 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     if (m_batch_major) {
         m_provider->post_process(m_ctx, w, ws.dev_src, outs.data(), stream);
     } else {
-        std::vector<void*> tmp(ne);
-        for (int k = 0; k < ne; k++) {
-            grow_dev(ws.dev_tmp[k], ws.dev_tmp_cap[k], (size_t)n * m_provider->providers()[k]->shape().byte_size());
+        std::vector<void*> tmp(no);
+        for (int k = 0; k < no; k++) {
+            grow_dev(ws.dev_tmp[k], ws.dev_tmp_cap[k], (size_t)n * oshapes[k].second.byte_size());
             tmp[k] = ws.dev_tmp[k];
         }
         m_provider->post_process(m_ctx, w, ws.dev_src, tmp.data(), stream);
-        for (int k = 0; k < ne; k++) {
-            const shape_type& sh    = m_provider->providers()[k]->shape();
+        for (int k = 0; k < no; k++) {
+            const shape_type& sh    = oshapes[k].second;
             const size_t      esize = sh.otype.size;
             const size_t      item  = sh.byte_size();
             for (int b = 0; b < n / m_batch_size; b++) {
@@ -834,10 +1050,10 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
             }
         }
     }
-    for (int k = 0; k < ne; k++)
+    for (int k = 0; k < no; k++)
         if (copy_out[k]) {
             phase_range d2h("aeon.d2h_enqueue");
-            hip_check(hipMemcpyAsync(outputs[k], outs[k], (size_t)n * m_provider->providers()[k]->shape().byte_size(),
+            hip_check(hipMemcpyAsync(outputs[k], outs[k], (size_t)n * oshapes[k].second.byte_size(),
                                      hipMemcpyDeviceToHost, stream),
                       "hipMemcpyAsync");
         }
@@ -854,6 +1070,9 @@ void batch_decoder::draw_params(int n, const decoded_element* records, aeon_aug_
     decode_window w;
     w.n = n;
     w.params.assign(ne, std::vector<aeon_aug_params>(n));
+    w.boxes.resize(ne);
+    for (int k = 0; k < ne; k++)
+        if (m_provider->providers()[k]->box_kind() >= 0) w.boxes[k].resize(n);
     if (m_deterministic && !serial) {
         m_provider->draw_window(n, records, w, m_random, *m_pool);
     } else {
@@ -969,6 +1188,10 @@ std::vector<aeon_hip::decoded_element> to_elements(aeon_decoder* d, int n, const
         const aeon_encoded_elem& e = elems[i];
         aeon_hip::decoded_element& r = recs[i];
         r.data = (const uint8_t*)e.data;
+        if (d->d->provider().providers()[i % ne]->box_kind() >= 0) { // JSON metadata: data / size
+            r.metadata = true, r.size = e.size;
+            continue;
+        }
         if (e.width > 0) {
             r.width = e.width, r.height = e.height, r.channels = e.channels;
             r.stride = e.stride ? e.stride : e.width * e.channels;
@@ -1038,6 +1261,9 @@ int aeon_decoder_decode(aeon_decoder* d, int n, const aeon_record_elem* elems, v
 {
     return host_guarded([&] {
         if (!d || (n > 0 && (!elems || !outputs))) throw std::invalid_argument("null argument");
+        if (d->d->provider().has_boxes())
+            throw std::invalid_argument("aeon_record_elem carries no byte size for the metadata of a boundingbox / "
+                                        "localization_ssd element: use aeon_decoder_decode_encoded");
         const int ne = (int)d->d->provider().get_input_count();
         std::vector<aeon_hip::decoded_element> recs((size_t)n * ne);
         for (size_t i = 0; i < recs.size(); i++)
@@ -1053,6 +1279,9 @@ int aeon_decoder_draw_params(aeon_decoder* d, int n, const aeon_record_elem* ele
 {
     return host_guarded([&] {
         if (!d || (n > 0 && (!elems || !params))) throw std::invalid_argument("null argument");
+        if (d->d->provider().has_boxes())
+            throw std::invalid_argument("aeon_record_elem carries no byte size for the metadata of a boundingbox / "
+                                        "localization_ssd element: the draws of such a config need the records");
         const int ne = (int)d->d->provider().get_input_count();
         std::vector<aeon_hip::decoded_element> recs((size_t)n * ne);
         for (size_t i = 0; i < recs.size(); i++)

@@ -5,6 +5,8 @@
 //   provider_factory::create src/provider_factory.cpp:24-51
 //   provider::image          src/provider.cpp:145-184          (etl type "image")
 //   provider::pixelmask      src/provider.cpp:353-393          (etl type "pixelmask")
+//   provider::boundingbox    src/provider.cpp:395-439          (etl type "boundingbox")
+//   provider::localization::ssd src/provider.cpp:289-346       (etl type "localization_ssd")
 //   image::config            src/etl_image.hpp:56-96, etl_image.cpp:25-65
 //   batch_decoder            src/batch_decoder.cpp:24-99        (thread pool + deterministic slots)
 //   thread_pool              src/thread_pool.hpp:82-175         (dynamic atomic task counter)
@@ -29,6 +31,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/aeon_hip.h"
+#include "box_host.hpp"
 #include "json.hpp"
 #include "param_factory.hpp"
 
@@ -69,6 +72,7 @@ struct decoded_element {
     size_t         size    = 0;     // encoded bytes
     bool           encoded = false; // JPEG file: decoded on the device (jpeg_host.cpp)
     int            png_mode   = -1; // PNG file: AEON_PNG_* decode on the host while staging
+    bool           metadata   = false; // JSON text of a box provider (data / size), no pixels
     int            elem_bytes = 1;  // bytes per sample (2: a 16-bit mask / depth map)
 };
 
@@ -79,6 +83,11 @@ struct decode_window {
     std::vector<std::vector<aeon_aug_params>> params; // [provider][record]
     std::vector<std::vector<size_t>>          offset; // [provider][record] in the pinned arena
     uint8_t*                                  arena = nullptr;
+    // box providers: the records' extracted metadata, and where the provider's box table (BoxRec per
+    // record, then boxes, labels, difficult flags; box_job.hpp) lies in the arena
+    std::vector<std::vector<box_metadata>>    boxes;      // [provider][record]
+    std::vector<size_t>                       box_offset; // [provider]
+    std::vector<size_t>                       box_total;  // [provider] boxes of the window
 };
 
 // augmentation shared by the ETL providers of one record (provider.cpp:109-119)
@@ -127,6 +136,22 @@ public:
     virtual const shape_type&  shape() const = 0;
     virtual const std::string& buffer_name() const = 0;
     virtual aeon_out_desc      out_desc() const = 0;
+    // the provider's output buffers in aeon's get_output_shapes() order (one for pixel providers)
+    virtual std::vector<std::pair<std::string, shape_type>> output_shapes() const
+    {
+        return {{buffer_name(), shape()}};
+    }
+    // box providers (boundingbox, localization_ssd): AEON_BOX_*; -1 for pixel providers.  Their element
+    // is the record's JSON metadata: extract() parses it, provide_boxes() is provide() with it (the
+    // first element of a record draws: localization_ssd make_ssd_params over the extracted boxes,
+    // boundingbox make_params), box_out() the box call's description without its buffers.
+    virtual int  box_kind() const { return -1; }
+    virtual void extract(const decoded_element&, box_metadata&) const {}
+    virtual void provide_boxes(const box_metadata&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
+                               light_split* = nullptr) const
+    {
+    }
+    virtual aeon_box_out box_out() const { return aeon_box_out{}; }
 };
 
 class provider_base : public provider_interface {
@@ -147,9 +172,20 @@ public:
     void post_process(aeon_hip_ctx* ctx, decode_window& w, const uint8_t* dev_arena, void* const* outputs,
                       void* stream) const;
     const std::vector<std::unique_ptr<etl_provider>>& providers() const { return m_providers; }
+    // outputs[] of the decoder calls follow get_output_shapes(): provider k's buffers are
+    // output_first(k) .. output_first(k + 1) - 1
+    int  output_first(size_t k) const { return m_out_first[k]; }
+    bool has_boxes() const { return m_has_boxes; }
+    // the box tables of the window's box providers: their size after the window's pixels at `offset`
+    // of the arena (layout_boxes), and the tables themselves written there (stage_boxes, which also
+    // makes the host-side refusals: rotation, boundingbox::box::expand's precondition)
+    size_t layout_boxes(decode_window& w, size_t offset) const;
+    void   stage_boxes(decode_window& w) const;
 
 private:
     std::vector<std::unique_ptr<etl_provider>> m_providers;
+    std::vector<int>                           m_out_first; // size providers + 1
+    bool                                       m_has_boxes = false;
 };
 
 struct provider_factory {
@@ -261,6 +297,12 @@ std::vector<int> thread_affinity_map(const std::string& cpu_list);
 int aeon_thread_count(const std::string& cpu_list); // thread_affinity_map(cpu_list).size()
 // the decoder's pool runs its context's JPEG entropy decoding too (stage.cpp)
 void ctx_share_pool(aeon_hip_ctx* ctx, thread_pool* pool);
+// aeon_hip_box_targets_batch over a box table that already lies in device memory (the decoder stages it
+// in the window's arena with the pixels, so a window makes one H2D): table = n BoxRec, then `total`
+// boxes, labels and difficult flags (box_job.hpp).  out and the result as in the C call; the records'
+// refusals (box_refusal) are the caller's to make while it stages.
+int box_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t total, const aeon_box_out& out,
+                        void* stream);
 // a map stretched or cut to n workers (decode_thread_count / AEON_HIP_JPEG_THREADS): worker i on map[i % size]
 std::vector<int> affinity_for(const std::vector<int>& map, int n);
 

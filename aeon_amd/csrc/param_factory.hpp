@@ -132,6 +132,16 @@ public:
     void make_ssd_params(URNG& random, int in_w, int in_h, int out_w, int out_h, const float* boxes, int n_boxes,
                          aeon_aug_params* p) const;
 
+    template <typename URNG>
+    void make_ssd_params_split(URNG& random, int in_w, int in_h, int out_w, int out_h, const float* boxes, int n_boxes,
+                               bool entry_avail, aeon_aug_params* p, float* exit_saved) const;
+
+private:
+    template <typename URNG>
+    void ssd_tail(URNG& random, int in_w, int in_h, int out_w, int out_h, const float* boxes, int n_boxes,
+                  aeon_aug_params* p) const;
+
+public:
     std::vector<batch_sampler>                    batch_samplers;
     mutable std::uniform_real_distribution<float> expand_distribution{0.0f, 1.0f};
     std::string                                   emit_constraint_type;
@@ -289,6 +299,24 @@ void param_factory::make_ssd_params(URNG& random, int in_w, int in_h, int out_w,
                                     int n_boxes, aeon_aug_params* p) const
 {
     make_params(random, in_w, in_h, out_w, out_h, p);
+    ssd_tail(random, in_w, in_h, out_w, out_h, boxes, n_boxes, p);
+}
+
+// make_ssd_params of one record of a decode window drawn out of order: make_params_split (the lighting
+// draws are make_params' last, whatever follows them), then the same expand / patch draws
+template <typename URNG>
+void param_factory::make_ssd_params_split(URNG& random, int in_w, int in_h, int out_w, int out_h, const float* boxes,
+                                          int n_boxes, bool entry_avail, aeon_aug_params* p, float* exit_saved) const
+{
+    make_params_split(random, in_w, in_h, out_w, out_h, entry_avail, p, exit_saved);
+    ssd_tail(random, in_w, in_h, out_w, out_h, boxes, n_boxes, p);
+}
+
+// make_ssd_params after its make_params call (augment_image.cpp:246-301)
+template <typename URNG>
+void param_factory::ssd_tail(URNG& random, int in_w, int in_h, int out_w, int out_h, const float* boxes, int n_boxes,
+                             aeon_aug_params* p) const
+{
     p->out_w = out_w, p->out_h = out_h; // "use warping"
     float     ratio   = expand_ratio(random);
     const bool enabled = expand_distribution(random) < expand_probability;

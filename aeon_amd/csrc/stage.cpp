@@ -19,6 +19,7 @@
 
 #include "../../include/aeon_hip.h"
 #include "aug_job.hpp"
+#include "box_job.hpp"
 #include "host.hpp"
 #include "jpeg.hpp"
 #include "mask16.hpp"
@@ -47,6 +48,7 @@ hipError_t contrast_records_lds_limit(int bytes);
 hipError_t launch_split(bool tail, int occ, const LaunchArgs& a, const SplitArgs& s, int grid, hipStream_t stream,
                         hipEvent_t start, hipEvent_t stop);
 hipError_t split_lds_limit(int bytes);
+hipError_t launch_box_targets(const BoxLaunch& L, hipStream_t stream);
 hipError_t split_occupancy(bool tail, int occ, const LaunchArgs& a, int* blocks);
 hipError_t launch_resize_generic(const ResizeJob* jobs, const uint8_t* table, int n_jobs, int max_tiles, int TR, int CW,
                                  int NR, int xs, int amax, int cn_max, int SW, const float* lut, int bgr, int chm,
@@ -1996,6 +1998,87 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     return 0;
 }
 
+// The output side of a box call: every buffer holds n items of its stride, and the kernel writes exactly
+// max_boxes * 16 (boxes; boundingbox: the whole item), 8 (image_shape), 4 (count) or max_boxes * 4 bytes.
+void check_box_out(const aeon_box_out& o)
+{
+    if (o.kind != AEON_BOX_BOUNDINGBOX && o.kind != AEON_BOX_SSD) fail(AEON_HIP_EINVAL, "unknown box target kind");
+    if (o.max_boxes <= 0) fail(AEON_HIP_EINVAL, o.kind == AEON_BOX_SSD ? "invalid max_gt_boxes" : "invalid max_bbox_count");
+    if (o.emit_type < AEON_EMIT_NONE || o.emit_type > AEON_EMIT_MIN_OVERLAP)
+        fail(AEON_HIP_EINVAL, "Invalid emit constraint type");
+    const bool ssd = o.kind == AEON_BOX_SSD;
+    if (ssd && (o.out_w <= 0 || o.out_h <= 0)) fail(AEON_HIP_EINVAL, "invalid width / height of the box config");
+    const uint64_t box_bytes = (uint64_t)o.max_boxes * 16, cls_bytes = (uint64_t)o.max_boxes * 4;
+    const int      bi        = ssd ? 1 : 0;
+    if (!o.buf[bi] || ((uintptr_t)o.buf[bi] & 15) || (o.item_stride[bi] & 15) || o.item_stride[bi] < box_bytes)
+        fail(AEON_HIP_EINVAL, "box buffer: 16-byte aligned items of at least max_boxes*16 bytes");
+    if (ssd) {
+        const uint64_t need[5] = {8, 0, 4, cls_bytes, cls_bytes};
+        for (int k : {0, 2, 3, 4})
+            if (!o.buf[k] || ((uintptr_t)o.buf[k] & 3) || (o.item_stride[k] & 3) || o.item_stride[k] < need[k])
+                fail(AEON_HIP_EINVAL, "box buffers: 4-byte aligned int32 items of the output's size");
+    }
+}
+
+// One launch over a box table in device memory (box_job.hpp's layout).
+void launch_box_table(int n, const uint8_t* dev_table, size_t total, const aeon_box_out& o, hipStream_t stream)
+{
+    const size_t rec_bytes = box_rec_bytes(n);
+    BoxLaunch    L{};
+    L.recs      = (const BoxRec*)dev_table;
+    L.boxes     = (const float*)(dev_table + rec_bytes);
+    L.labels    = (const int32_t*)(dev_table + rec_bytes + total * 16);
+    L.difficult = (const int32_t*)(dev_table + rec_bytes + total * 20);
+    L.n = n, L.kind = o.kind, L.max_boxes = o.max_boxes, L.emit_type = o.emit_type;
+    L.emit_min_overlap = o.emit_min_overlap;
+    L.norm_w = (float)o.out_w, L.norm_h = (float)o.out_h;
+    L.shape_w = o.out_w, L.shape_h = o.out_h;
+    for (int k = 0; k < 5; k++) L.buf[k] = (uint8_t*)o.buf[k], L.stride[k] = o.item_stride[k];
+    HIP_OK(launch_box_targets(L, stream));
+}
+
+// aeon_hip_box_targets_batch: the call's table (records, boxes, labels, difficult flags) is written into
+// a ring slot's pinned buffer, copied to the slot's device table on `stream`, and read by one launch.
+int run_box_targets(aeon_hip_ctx* ctx, int n, const aeon_box_record* recs, const float* boxes, const int32_t* labels,
+                    const int32_t* difficult, const aeon_aug_params* params, const aeon_box_out* out, void* stream_)
+{
+    if (!ctx || !out) fail(AEON_HIP_EINVAL, "null argument");
+    if (n < 0) fail(AEON_HIP_EINVAL, "negative record count");
+    if (n == 0) return 0;
+    if (!recs || !params) fail(AEON_HIP_EINVAL, "null argument");
+    check_box_out(*out);
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (recs[i].count < 0) fail(AEON_HIP_EINVAL, "negative box count");
+        total = std::max(total, (size_t)recs[i].first + (size_t)recs[i].count);
+    }
+    if (total > 0 && (!boxes || !labels || !difficult)) fail(AEON_HIP_EINVAL, "null box table");
+    if (total > ((size_t)1 << 26)) fail(AEON_HIP_EINVAL, "box table too large");
+    for (int i = 0; i < n; i++)
+        if (const char* why = box_refusal(params[i], recs[i].count ? boxes + 4 * (size_t)recs[i].first : nullptr, recs[i].count))
+            fail(AEON_HIP_EINVAL, why);
+    hipStream_t stream = (hipStream_t)stream_;
+
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_OK(hipSetDevice(ctx->device));
+    const size_t rec_bytes = box_rec_bytes(n);
+    const size_t blob      = box_table_bytes(n, total);
+    int          slot;
+    Slot&        s = take_slot(ctx, stream, slot);
+    ensure_ring(ctx, blob, 0, 0);
+    BoxRec* R = (BoxRec*)s.host;
+    for (int i = 0; i < n; i++) R[i] = box_rec(recs[i].first, recs[i].count, params[i]);
+    if (total) {
+        std::memcpy(s.host + rec_bytes, boxes, total * 16);
+        std::memcpy(s.host + rec_bytes + total * 16, labels, total * 4);
+        std::memcpy(s.host + rec_bytes + total * 20, difficult, total * 4);
+    }
+    HIP_OK(hipMemcpyAsync(s.dev, s.host, blob, hipMemcpyHostToDevice, stream));
+    launch_box_table(n, s.dev, total, *out, stream);
+    release_slot(ctx, slot, stream);
+    return 0;
+}
+
 // std::minstd_rand0 whose state word can be read back (an LCG's state is its last output).
 struct TrackedEngine {
     using result_type = std::minstd_rand0::result_type;
@@ -2034,6 +2117,21 @@ namespace aeon_hip {
 void ctx_share_pool(aeon_hip_ctx* ctx, thread_pool* pool)
 {
     if (ctx && !ctx->jpeg) ctx->host_pool = pool;
+}
+
+int box_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t total, const aeon_box_out& out,
+                       void* stream)
+{
+    return guarded([&] {
+        if (!ctx || (n > 0 && !dev_table)) fail(AEON_HIP_EINVAL, "null argument");
+        if (n <= 0) return 0;
+        if ((uintptr_t)dev_table & 15) fail(AEON_HIP_EINVAL, "box table not 16-byte aligned");
+        check_box_out(out);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_OK(hipSetDevice(ctx->device));
+        launch_box_table(n, (const uint8_t*)dev_table, total, out, (hipStream_t)stream);
+        return 0;
+    });
 }
 } // namespace aeon_hip
 
@@ -2365,6 +2463,24 @@ int aeon_make_ssd_params(aeon_param_factory* f, uint32_t* state, int in_w, int i
         *state = eng.last;
         return 0;
     });
+}
+
+int aeon_param_factory_emit(aeon_param_factory* f, int* type, float* min_overlap)
+{
+    return guarded([&] {
+        if (!f || !type || !min_overlap) fail(AEON_HIP_EINVAL, "null argument");
+        const std::string& e = f->f.emit_constraint_type; // lower-cased and validated by the constructor
+        *type        = e == "center" ? AEON_EMIT_CENTER : e == "min_overlap" ? AEON_EMIT_MIN_OVERLAP : AEON_EMIT_NONE;
+        *min_overlap = f->f.emit_constraint_min_overlap;
+        return 0;
+    });
+}
+
+int aeon_hip_box_targets_batch(aeon_hip_ctx* ctx, int n, const aeon_box_record* recs, const float* boxes,
+                               const int32_t* labels, const int32_t* difficult, const aeon_aug_params* params,
+                               const aeon_box_out* out, void* stream)
+{
+    return guarded([&] { return run_box_targets(ctx, n, recs, boxes, labels, difficult, params, out, stream); });
 }
 
 int aeon_png_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* color_type)

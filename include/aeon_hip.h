@@ -260,6 +260,60 @@ int aeon_decode_png(const void* data, size_t size, int mode, void* dst, size_t s
 int aeon_batch_sample_patches(aeon_param_factory* f, int sampler, uint32_t* engine_state, const float* nboxes, int n,
                               float* out, int cap, int* n_out);
 
+/* param_factory::emit_constraint_type / emit_constraint_min_overlap (src/augment_image.cpp:86-98): the
+ * factory's emit constraint as an AEON_EMIT_* code.  The type compares lower-cased as in aeon
+ * ("MIN_OVERLAP" is valid); anything but "center", "min_overlap" or "" fails the factory's creation. */
+#define AEON_EMIT_NONE        0
+#define AEON_EMIT_CENTER      1
+#define AEON_EMIT_MIN_OVERLAP 2
+int aeon_param_factory_emit(aeon_param_factory* f, int* type, float* min_overlap);
+
+/* ---- object boxes: provider::boundingbox / provider::localization::ssd targets ----------------
+ * boundingbox::extractor::extract (src/etl_boundingbox.cpp:64-132): the JSON metadata of one record
+ * ({"object": [{"bndbox": {"xmin", "ymin", "xmax", "ymax"}, "name", "difficult", "truncated"}, ...],
+ * "size": {"width", "height", "depth"}}) -> image size and up to cap boxes (4 floats each: xmin, ymin,
+ * xmax, ymax; pixel coordinates, xmax / ymax inclusive), label indices into class_names_json (a JSON
+ * array of names) and difficult flags.  *n_boxes receives the full count even above cap.  Host only,
+ * no context; errors (aeon's texts, e.g. "'xmax' missing from metadata", "label 'x' not found in
+ * metadata label list") in aeon_box_last_error(). */
+int aeon_box_extract(const char* class_names_json, const void* data, size_t size, int* width, int* height,
+                     int* depth, float* boxes, int32_t* labels, int32_t* difficult, int cap, int* n_boxes);
+const char* aeon_box_last_error(void);
+
+/* boundingbox::transformer::transform_box (src/etl_boundingbox.cpp:146-261) + the loaders
+ * (etl_boundingbox.cpp:296-318, etl_localization_ssd.cpp:116-150) for n records in one launch: record
+ * i's boxes boxes[recs[i].first .. + recs[i].count) are expanded, tested against the emit constraint,
+ * cropped, flipped and rescaled with params[i] (the params of the record's image), the survivors
+ * written in input order, at most max_boxes of them, and the rest of the item zero-filled.
+ *   AEON_BOX_BOUNDINGBOX: buf[0] item i = max_boxes x (xmin, ymin, xmax, ymax) floats in output pixels;
+ *     the whole item (item_stride[0] bytes: aeon's shape {max_bbox_count, 4*sizeof(float)} of
+ *     output_type, of which its loader writes the first max_boxes*16 bytes) is written.
+ *   AEON_BOX_SSD: buf[0] image_shape (out_w, out_h) int32; buf[1] gt_boxes max_boxes x 4 floats
+ *     normalized by out_w / out_h (xmin/W, ymin/H, (xmax+1)/W, (ymax+1)/H); buf[2] gt_box_count int32;
+ *     buf[3] gt_class_count, buf[4] difficult_flag: max_boxes int32 each.  aeon's range check on the
+ *     normalized values (normalized_box.cpp:90-107) is not made.
+ * out_w / out_h: the ETL config's width / height.  The rescale itself uses params[i].out_w / out_h over
+ * params[i].crop_w / crop_h, as aeon's.  emit_type / emit_min_overlap: aeon_param_factory_emit.
+ * Box buffers and strides must be multiples of 16 bytes, the int32 ones of 4.  params[i].angle != 0
+ * (aeon's transformer returns null there) and a box failing boundingbox::box::expand's precondition
+ * (src/boundingbox.cpp:88-105) are AEON_HIP_EINVAL.  Asynchronous on `stream`; recs, boxes, labels,
+ * difficult and params are host arrays, consumed before return; buf[] are device addresses. */
+#define AEON_BOX_BOUNDINGBOX 0
+#define AEON_BOX_SSD         1
+typedef struct aeon_box_record {
+    uint32_t first; /* index of the record's first box in the box table */
+    int32_t  count;
+} aeon_box_record;
+typedef struct aeon_box_out {
+    int32_t  kind, max_boxes, out_w, out_h, emit_type;
+    float    emit_min_overlap;
+    void*    buf[5];
+    uint64_t item_stride[5]; /* boundingbox uses buf[0] only */
+} aeon_box_out;
+int aeon_hip_box_targets_batch(aeon_hip_ctx* ctx, int n, const aeon_box_record* recs, const float* boxes,
+                               const int32_t* labels, const int32_t* difficult, const aeon_aug_params* params,
+                               const aeon_box_out* out, void* stream);
+
 /* batch_decoder deterministic mode (src/batch_decoder.cpp:47-54): slot engine state words. */
 int aeon_seed_slots(uint32_t seed, int n, uint32_t* states);
 
@@ -275,10 +329,21 @@ int aeon_cropbox_max_proportional(float in_w, float in_h, float out_w, float out
 
 /* ---- decode stage: provider_factory + batch_decoder (host C++ above the kernels) --------------
  * aeon_decoder = batch_decoder (src/batch_decoder.cpp:24-99) over provider_factory::create
- * (src/provider_factory.cpp:24-51) with "image" / "pixelmask" ETL providers.  config_json is the
+ * (src/provider_factory.cpp:24-51) with "image" / "pixelmask" / "boundingbox" / "localization_ssd" ETL
+ * providers.  config_json is the
  * aeon loader configuration ({"batch_size", "random_seed", "node_id", "cpu_list", "etl": [...],
  * "augmentation": [...]}, src/loader.hpp:50-109; unknown keys are rejected like verify_config).
- * Records arrive decoded (image::extractor::extract stays with the caller). */
+ * Records arrive decoded (image::extractor::extract stays with the caller).
+ * A provider may own several output buffers (localization_ssd: image_shape, gt_boxes, gt_box_count,
+ * gt_class_count, difficult_flag): outputs[] of the decoder calls and aeon_decoder_output_count / _info
+ * follow get_output_shapes() order (aeon's fixed_buffer_map order), which for "image" / "pixelmask"
+ * configs is the provider order.  The element of a box provider is the record's JSON metadata, an
+ * aeon_encoded_elem with width == 0 (data / size = the text): aeon_decoder_decode and
+ * aeon_decoder_draw_params, whose aeon_record_elem carries no byte size, return AEON_HIP_EINVAL for a
+ * config that holds a box ETL.  The first element of a record draws its (shared) params
+ * (src/provider.cpp:109-119): localization_ssd make_ssd_params over the extracted boxes, boundingbox and
+ * image make_params.  A window fails with AEON_HIP_EINVAL when a box provider meets params.angle != 0
+ * or a box that fails boundingbox::box::expand's precondition. */
 typedef struct aeon_decoder aeon_decoder;
 
 /* One decoded element of a record: HWC uint8 (BGR) pixels in host memory. */
@@ -306,7 +371,8 @@ int aeon_decoder_decode(aeon_decoder* d, int n, const aeon_record_elem* elems, v
 int aeon_decoder_draw_params(aeon_decoder* d, int n, const aeon_record_elem* elems, aeon_aug_params* params,
                              int serial);
 /* A record element as aeon's encoded_record holds it (src/buffer_batch.hpp:45-152): an encoded
- * JPEG file (width == 0: data/size, decoded by the JPEG stage with the provider's channel count),
+ * JPEG file (width == 0: data/size, decoded by the JPEG stage with the provider's channel count;
+ * for a boundingbox / localization_ssd provider the JSON metadata text),
  * or -- width > 0 -- decoded HWC uint8 pixels as in aeon_record_elem (pixel masks must be). */
 typedef struct aeon_encoded_elem {
     const void* data;
