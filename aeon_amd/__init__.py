@@ -96,7 +96,7 @@ class EncodedRecords:
         return self.n
 
 
-BOX_BOUNDINGBOX, BOX_SSD = 0, 1
+BOX_BOUNDINGBOX, BOX_SSD, BOX_RCNN = 0, 1, 2
 EMIT_NONE, EMIT_CENTER, EMIT_MIN_OVERLAP = 0, 1, 2
 
 
@@ -110,6 +110,25 @@ class BoxOut(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("max_boxes", ctypes.c_int32), ("out_w", ctypes.c_int32),
                 ("out_h", ctypes.c_int32), ("emit_type", ctypes.c_int32), ("emit_min_overlap", ctypes.c_float),
                 ("buf", ctypes.c_void_p * 5), ("item_stride", ctypes.c_uint64 * 5)]
+
+
+class RcnnInfo(ctypes.Structure):
+    """aeon_rcnn_info: the derived numbers of a localization_rcnn config and this build's limits."""
+    _fields_ = [("total_anchors", ctypes.c_int64), ("rois_per_image", ctypes.c_int32), ("num_fg", ctypes.c_int32),
+                ("max_gt_boxes", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("negative_overlap", ctypes.c_float), ("positive_overlap", ctypes.c_float),
+                ("max_total_anchors", ctypes.c_int32), ("max_rois_per_image", ctypes.c_int32),
+                ("max_boxes_per_record", ctypes.c_int32)]
+
+
+class RcnnOut(ctypes.Structure):
+    """aeon_rcnn_out: sizes, thresholds, emit constraint, anchors and the ten output buffers of an rcnn call."""
+    _fields_ = [("total_anchors", ctypes.c_int32), ("max_gt_boxes", ctypes.c_int32), ("rois_per_image", ctypes.c_int32),
+                ("num_fg", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("emit_type", ctypes.c_int32), ("emit_min_overlap", ctypes.c_float),
+                ("negative_overlap", ctypes.c_float), ("positive_overlap", ctypes.c_float),
+                ("fixed_scaling_factor", ctypes.c_float), ("anchors", ctypes.POINTER(ctypes.c_float)),
+                ("anchors_key", ctypes.c_uint64), ("buf", ctypes.c_void_p * 10), ("item_stride", ctypes.c_uint64 * 10)]
 
 
 class AeonHipError(RuntimeError):
@@ -166,6 +185,14 @@ def lib():
         L.aeon_box_last_error.restype = ctypes.c_char_p
         L.aeon_hip_box_targets_batch.argtypes = [vp, ctypes.c_int, P(BoxRecord), P(ctypes.c_float), P(ctypes.c_int32),
                                                  P(ctypes.c_int32), P(AugParams), P(BoxOut), vp]
+        L.aeon_rcnn_anchors.argtypes = [ctypes.c_char_p, P(ctypes.c_float), ctypes.c_int, P(ctypes.c_int)]
+        L.aeon_rcnn_config_info.argtypes = [ctypes.c_char_p, P(RcnnInfo)]
+        L.aeon_rcnn_sample_anchors.argtypes = [P(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               P(ctypes.c_uint32), P(ctypes.c_int32), P(ctypes.c_int)]
+        L.aeon_rcnn_last_error.restype = ctypes.c_char_p
+        L.aeon_hip_rcnn_targets_batch.argtypes = [vp, ctypes.c_int, P(BoxRecord), P(ctypes.c_float), P(ctypes.c_int32),
+                                                  P(ctypes.c_int32), P(AugParams), P(ctypes.c_uint32), ctypes.c_int,
+                                                  P(RcnnOut), vp]
         L.aeon_seed_slots.argtypes = [ctypes.c_uint32, ctypes.c_int, P(ctypes.c_uint32)]
         L.aeon_unbiased_round.argtypes = [ctypes.c_float, P(ctypes.c_int64)]
         L.aeon_calculate_scale.argtypes = [ctypes.c_int] * 4 + [P(ctypes.c_float)]
@@ -379,6 +406,147 @@ def box_targets(ctx, records, params, kind=BOX_SSD, max_boxes=64, out_w=0, out_h
            "gt_box_count": outs[2].view(np.int32).reshape(n), "gt_class_count": outs[3].view(np.int32).reshape(n, max_boxes),
            "difficult_flag": outs[4].view(np.int32).reshape(n, max_boxes)}
     return res
+
+
+# ---- localization_rcnn ---------------------------------------------------------------------------
+RCNN_OUTPUTS = ("bbtargets", "bbtargets_mask", "labels_flat", "labels_mask", "image_shape", "gt_boxes",
+                "gt_box_count", "gt_class_count", "image_scale", "difficult_flag")
+
+
+def _check_rcnn(rc):
+    if rc != 0:
+        raise AeonHipError(rc, lib().aeon_rcnn_last_error().decode())
+
+
+def _rcnn_text(config):
+    return (config if isinstance(config, str) else json.dumps(config)).encode()
+
+
+def rcnn_config_info(config):
+    """localization::rcnn::config of an ETL object (dict or JSON text): total_anchors, rois_per_image,
+    num_fg, max_gt_boxes, the thresholds, and this build's limits, as a dict (aeon_rcnn_config_info).
+    AeonHipError for a missing or unknown key or a fraction outside [0, 1]."""
+    info = RcnnInfo()
+    _check_rcnn(lib().aeon_rcnn_config_info(_rcnn_text(config), ctypes.byref(info)))
+    return {k: getattr(info, k) for k, _ in RcnnInfo._fields_}
+
+
+def rcnn_anchors(config):
+    """anchor::generate (aeon src/etl_localization_rcnn.cpp:430-469): (total_anchors, 4) float32, base
+    anchors outermost, then shift rows, then shift columns."""
+    n = ctypes.c_int()
+    text = _rcnn_text(config)
+    _check_rcnn(lib().aeon_rcnn_anchors(text, None, 0, ctypes.byref(n)))
+    out = np.zeros((n.value, 4), np.float32)
+    _check_rcnn(lib().aeon_rcnn_anchors(text, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), n.value,
+                                        ctypes.byref(n)))
+    return out
+
+
+def rcnn_sample_anchors(labels, rois_per_image, num_fg, shuffle=True, state=None):
+    """transformer::sample_anchors (aeon src/etl_localization_rcnn.cpp:222-261) with the real std::shuffle
+    over std::minstd_rand0.  state: np.uint32 array of one element (the engine's state word, updated in
+    place); returns the sampled anchor indices, foreground first."""
+    lab = np.ascontiguousarray(labels, np.int32)
+    out = np.zeros(max(int(rois_per_image), 1), np.int32)
+    st = ctypes.c_uint32(int(state[0]) if state is not None else 1)
+    n = ctypes.c_int()
+    ip = ctypes.POINTER(ctypes.c_int32)
+    _check_rcnn(lib().aeon_rcnn_sample_anchors(lab.ctypes.data_as(ip), len(lab), int(rois_per_image), int(num_fg),
+                                               int(bool(shuffle)), ctypes.byref(st), out.ctypes.data_as(ip),
+                                               ctypes.byref(n)))
+    if state is not None:
+        state[0] = st.value
+    return out[:n.value].copy()
+
+
+class RcnnCall:
+    """The marshalled arguments of aeon_hip_rcnn_targets_batch for one window, for calls made again and
+    again (tools/rcnn_window_timing.py): launch() is the C call alone."""
+
+    def __init__(self, ctx, config, records, params, emit=(EMIT_NONE, 0.0), fixed_scaling_factor=-1.0):
+        info = rcnn_config_info(config)
+        self.ctx, self.info, self.anchors = ctx, info, rcnn_anchors(config)
+        self.n = n = len(records)
+        A, m = int(info["total_anchors"]), info["max_gt_boxes"]
+        self.recs = (BoxRecord * max(n, 1))()
+        bx, lb, df = [], [], []
+        first = 0
+        for i, r in enumerate(records):
+            b, l, d = (r["boxes"], r["labels"], r["difficult"]) if isinstance(r, dict) else r
+            b = np.asarray(b, np.float32).reshape(-1, 4)
+            self.recs[i] = BoxRecord(first, len(b))
+            bx.append(b), lb.append(np.asarray(l, np.int32).reshape(-1)), df.append(np.asarray(d, np.int32).reshape(-1))
+            if not len(b) == len(lb[-1]) == len(df[-1]):
+                raise ValueError(f"record {i}: {len(b)} boxes, {len(lb[-1])} labels, {len(df[-1])} difficult flags")
+            first += len(b)
+        self.boxes = np.ascontiguousarray(np.concatenate(bx) if bx else np.zeros((0, 4), np.float32))
+        self.labels = np.ascontiguousarray(np.concatenate(lb) if lb else np.zeros(0, np.int32))
+        self.diff = np.ascontiguousarray(np.concatenate(df) if df else np.zeros(0, np.int32))
+        self.params = params if isinstance(params, ctypes.Array) else (AugParams * max(n, 1))(*params)
+        if len(self.params) < n:
+            raise ValueError(f"{len(self.params)} params for {n} records")
+        self.strides = [16 * A, 16 * A, 8 * A, 8 * A, 8, 16 * m, 4, 4 * m, 4, 4 * m]
+        self.shapes = [(4 * A,), (4 * A,), (1, 2 * A), (2 * A, 1), (2, 1), (m, 4), (1, 1), (m, 1), (1, 1), (m, 1)]
+        self.dtypes = [np.float32, np.float32, np.int32, np.int32, np.int32, np.float32, np.int32, np.int32, np.float32,
+                       np.int32]
+        self.out = RcnnOut(total_anchors=A, max_gt_boxes=m, rois_per_image=info["rois_per_image"],
+                           num_fg=info["num_fg"], width=info["width"], height=info["height"], emit_type=emit[0],
+                           emit_min_overlap=emit[1], negative_overlap=info["negative_overlap"],
+                           positive_overlap=info["positive_overlap"], fixed_scaling_factor=fixed_scaling_factor)
+        self.out.anchors = self.anchors.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        for k, s in enumerate(self.strides):
+            self.out.item_stride[k] = s
+
+    def launch(self, out_ptrs, states=None, shuffle=True, stream=0):
+        """states: a contiguous np.uint32 array of n engine states, updated in place (the call then
+        synchronizes the stream), or None (asynchronous; shuffle must be off)."""
+        for k, q in enumerate(out_ptrs):
+            self.out.buf[k] = q
+        fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
+        _check(lib().aeon_hip_rcnn_targets_batch(
+            self.ctx._h, self.n, self.recs, self.boxes.ctypes.data_as(fp), self.labels.ctypes.data_as(ip),
+            self.diff.ctypes.data_as(ip), self.params,
+            states.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if states is not None else None, int(bool(shuffle)),
+            ctypes.byref(self.out), ctypes.c_void_p(stream or 0)))
+
+
+def rcnn_targets(ctx, config, records, params, states=None, shuffle=True, emit=(EMIT_NONE, 0.0),
+                 fixed_scaling_factor=-1.0, out_ptrs=None, stream=0):
+    """aeon_hip_rcnn_targets_batch for len(records) records of the localization_rcnn ETL object `config`:
+    records[i] = a box_extract() dict or a (boxes n x 4, labels, difficult) tuple, params[i] = the
+    AugParams of the record's image, emit = the factory's ParamFactory.emit(), fixed_scaling_factor the
+    factory's.  states: np.uint32 array of one engine state per record, updated in place to the states
+    after the shuffles (required with shuffle).  The kernel stores into pinned device-mapped buffers filled
+    with 0xCD beforehand; returns the ten outputs by aeon's names, each (n, ...) as aeon shapes them.  With
+    out_ptrs (ten device addresses) the outputs stay there and the call returns None; it is asynchronous
+    on `stream` unless it hands engine states back."""
+    call = RcnnCall(ctx, config, records, params, emit, fixed_scaling_factor)
+    n = call.n
+    st = None
+    if states is not None:
+        if len(states) < n:
+            raise ValueError(f"{len(states)} engine states for {n} records")
+        st = np.ascontiguousarray(states[:n], np.uint32).copy()
+    own = []
+    try:
+        if out_ptrs is None:
+            for s in call.strides:
+                q = ctypes.c_void_p()
+                _check(lib().aeon_hip_host_alloc(max(n * s, 16), ctypes.byref(q)))
+                own.append(q)
+                ctypes.memset(q, 0xCD, max(n * s, 16))
+        call.launch(out_ptrs if out_ptrs is not None else [q.value for q in own], st, shuffle, stream)
+        if st is not None:
+            states[:n] = st
+        if out_ptrs is not None:
+            return None
+        ctx.synchronize(stream)
+        outs = [np.frombuffer(ctypes.string_at(q, n * s), np.uint8).copy() for q, s in zip(own, call.strides)]
+    finally:
+        for q in own:
+            lib().aeon_hip_host_free(q)
+    return {name: a.view(dt).reshape((n,) + sh) for name, a, dt, sh in zip(RCNN_OUTPUTS, outs, call.dtypes, call.shapes)}
 
 
 def seed_slots(seed, n):
@@ -683,9 +851,9 @@ def _check_host(rc):
 
 class Decoder:
     """aeon batch_decoder over provider_factory::create(config): decode windows of records (per ETL
-    element an HWC uint8 array, an encoded JPEG / PNG file, or -- boundingbox and localization_ssd
-    elements -- the JSON metadata as bytes or str) into the provider output buffers.  A provider may own
-    several output buffers (localization_ssd: five), so records have n_inputs elements and windows
+    element an HWC uint8 array, an encoded JPEG / PNG file, or -- boundingbox, localization_ssd and
+    localization_rcnn elements -- the JSON metadata as bytes or str) into the provider output buffers.  A provider may own
+    several output buffers (localization_ssd: five, localization_rcnn: ten), so records have n_inputs elements and windows
     len(outputs) buffers, in get_output_shapes() order."""
 
     def __init__(self, config, device=0):

@@ -1,6 +1,7 @@
 // host.cpp -- provider plugin surface + decode stage of the HIP image path (see host.hpp).
 #include "host.hpp"
 #include "box_job.hpp"
+#include "rcnn_job.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -413,6 +414,96 @@ private:
     std::vector<std::string> m_names;
 };
 
+// provider::localization::rcnn (provider.cpp:222-287): extract the record's JSON metadata, draw
+// make_params over its image size when the record has no params yet; transform, sample_anchors and load
+// run in the window's targets launch (post_process).  aeon reads the input size from a member of its
+// decoded type that nothing sets (etl_localization_rcnn.hpp:159); here it is the metadata's size, as
+// for boundingbox.
+class rcnn_provider : public etl_provider {
+public:
+    rcnn_provider(const Json& js, const Json& aug) : m_cfg(js), m_factory(aug)
+    {
+        if (m_cfg.total_anchors() > kRcnnMaxAnchors)
+            throw unsupported_error("localization_rcnn: total_anchors " + std::to_string(m_cfg.total_anchors()) +
+                                    " above this build's 65536");
+        if (m_cfg.rois_per_image > kRcnnMaxRois)
+            throw unsupported_error("localization_rcnn: rois_per_image above this build's 1024");
+        m_label_map = box_label_map(m_cfg.class_names);
+        m_anchors   = rcnn_generate_anchors(m_cfg);
+        static std::atomic<uint64_t> next_key{1}; // one key per table of this process
+        m_anchors_key = next_key.fetch_add(1);
+        const size_t A = (size_t)m_cfg.total_anchors(), m = (size_t)m_cfg.max_gt_boxes;
+        auto add = [&](const char* name, std::vector<size_t> s, const char* t) {
+            shape_type st;
+            st.shape = std::move(s);
+            st.otype = output_type(t);
+            m_shapes.emplace_back(create_name(m_cfg.name, name), st);
+        };
+        add("bbtargets", {A * 4}, "float");
+        add("bbtargets_mask", {A * 4}, "float");
+        add("labels_flat", {1, A * 2}, "int32_t");
+        add("labels_mask", {A * 2, 1}, "int32_t");
+        add("image_shape", {2, 1}, "int32_t");
+        add("gt_boxes", {m, 4}, "float");
+        add("gt_box_count", {1, 1}, "int32_t");
+        add("gt_class_count", {m, 1}, "int32_t");
+        add("image_scale", {1, 1}, "float");
+        add("difficult_flag", {m, 1}, "int32_t");
+    }
+    void provide(int, const decoded_element&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
+                 light_split*) const override
+    {
+        throw std::logic_error("box providers take their element through provide_boxes");
+    }
+    void extract(const decoded_element& in, box_metadata& m) const override { box_extract(m_label_map, in.data, in.size, m); }
+    void provide_boxes(const box_metadata& m, augmentation& aug, std::minstd_rand0& random, aeon_aug_params& params,
+                       light_split* ls) const override
+    {
+        if (!aug.has) {
+            const int W = (int)m_cfg.width, H = (int)m_cfg.height;
+            if (ls)
+                m_factory.make_params_split(random, m.width, m.height, W, H, ls->entry_avail, &aug.image, &ls->exit_saved);
+            else
+                m_factory.make_params(random, m.width, m.height, W, H, &aug.image);
+            aug.has = true;
+        }
+        params = aug.image;
+    }
+    const param_factory& factory() const override { return m_factory; }
+    bool               is_mask() const override { return false; }
+    const shape_type&  shape() const override { return m_shapes[0].second; }
+    const std::string& buffer_name() const override { return m_shapes[0].first; }
+    aeon_out_desc      out_desc() const override { return aeon_out_desc{}; }
+    std::vector<std::pair<std::string, shape_type>> output_shapes() const override { return m_shapes; }
+    int           box_kind() const override { return AEON_BOX_RCNN; }
+    aeon_rcnn_out rcnn_out() const override
+    {
+        aeon_rcnn_out o{};
+        o.total_anchors  = (int32_t)m_cfg.total_anchors();
+        o.max_gt_boxes   = (int32_t)m_cfg.max_gt_boxes;
+        o.rois_per_image = (int32_t)m_cfg.rois_per_image;
+        o.num_fg         = m_cfg.num_fg();
+        o.width = (int32_t)m_cfg.width, o.height = (int32_t)m_cfg.height;
+        const std::string& e = m_factory.emit_constraint_type;
+        o.emit_type          = e == "center" ? AEON_EMIT_CENTER : e == "min_overlap" ? AEON_EMIT_MIN_OVERLAP : AEON_EMIT_NONE;
+        o.emit_min_overlap   = m_factory.emit_constraint_min_overlap;
+        o.negative_overlap = m_cfg.negative_overlap, o.positive_overlap = m_cfg.positive_overlap;
+        o.fixed_scaling_factor = m_factory.fixed_scaling_factor;
+        o.anchors              = m_anchors.data();
+        o.anchors_key          = m_anchors_key;
+        for (size_t i = 0; i < m_shapes.size(); i++) o.item_stride[i] = m_shapes[i].second.byte_size();
+        return o;
+    }
+
+private:
+    rcnn_config                                     m_cfg;
+    param_factory                                   m_factory;
+    std::unordered_map<std::string, int>            m_label_map;
+    std::vector<float>                              m_anchors;
+    uint64_t                                        m_anchors_key = 0;
+    std::vector<std::pair<std::string, shape_type>> m_shapes;
+};
+
 } // namespace
 
 provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const Json& aug)
@@ -426,7 +517,11 @@ provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const
         else if (type == "pixelmask") p.reset(new pixelmask_provider(j, aug));
         else if (type == "boundingbox") p.reset(new box_provider(j, aug, AEON_BOX_BOUNDINGBOX));
         else if (type == "localization_ssd") p.reset(new box_provider(j, aug, AEON_BOX_SSD));
-        else if (type == "label" || type == "localization_rcnn" || type == "blob" || type == "video" ||
+        else if (type == "localization_rcnn") {
+            if (m_has_rcnn) invalid("one localization_rcnn element per record");
+            p.reset(new rcnn_provider(j, aug));
+            m_has_rcnn = true;
+        } else if (type == "label" || type == "blob" || type == "video" ||
                  type == "char_map" || type == "label_map")
             throw std::runtime_error("etl type '" + type + "' is outside the HIP image stage");
         else
@@ -455,7 +550,9 @@ void provider_base::draw(int idx, const decoded_element* elems, decode_window& w
         if (m_providers[k]->box_kind() >= 0) { // metadata: extract, then the record's (shared) params
             if (!e.data || e.size == 0) {
                 std::stringstream ss;
-                ss << "received " << (m_providers[k]->box_kind() == AEON_BOX_SSD ? "localization_ssd data" : "boundingbox")
+                const int kind = m_providers[k]->box_kind();
+                ss << "received "
+                   << (kind == AEON_BOX_SSD ? "localization_ssd data" : kind == AEON_BOX_RCNN ? "localization_rcnn data" : "boundingbox")
                    << " with size 0, at idx " << idx;
                 throw std::runtime_error(ss.str());
             }
@@ -547,6 +644,20 @@ void provider_base::post_process(aeon_hip_ctx* ctx, decode_window& w, const uint
         const etl_provider& p = *m_providers[k];
         void* const*        out = outputs + m_out_first[k];
         if (p.box_kind() >= 0) { // the window's box launch, over the table staged with the pixels
+            if (p.box_kind() == AEON_BOX_RCNN) {
+                aeon_rcnn_out ro = p.rcnn_out();
+                for (int j = 0; j < 10; j++) ro.buf[j] = out[j];
+                check(rcnn_targets_staged(ctx, w.n, dev_arena + w.box_offset[k], w.box_total[k], ro, 1, w.rcnn_states_dev,
+                                          stream));
+                if (w.rcnn_states_dev) { // the engines' end states, right behind the kernel
+                    hip_check(hipMemcpyAsync(w.rcnn_states_host, w.rcnn_states_dev, (size_t)w.n * sizeof(uint32_t),
+                                             hipMemcpyDeviceToHost, (hipStream_t)stream),
+                              "hipMemcpyAsync");
+                    hip_check(hipEventRecord(w.rcnn_states_done, (hipStream_t)stream), "hipEventRecord");
+                    w.rcnn_states_queued = true;
+                }
+                continue;
+            }
             aeon_box_out bo = p.box_out();
             for (int j = 0; j < m_out_first[k + 1] - m_out_first[k]; j++) bo.buf[j] = out[j];
             check(box_targets_staged(ctx, w.n, dev_arena + w.box_offset[k], w.box_total[k], bo, stream));
@@ -571,7 +682,8 @@ size_t provider_base::layout_boxes(decode_window& w, size_t offset) const
         if (total > ((size_t)1 << 26)) invalid("box table too large");
         w.box_offset[k] = offset;
         w.box_total[k]  = total;
-        offset += (box_table_bytes(w.n, total) + 15) & ~(size_t)15;
+        const bool rcnn = m_providers[k]->box_kind() == AEON_BOX_RCNN;
+        offset += ((rcnn ? rcnn_table_bytes(w.n, total) : box_table_bytes(w.n, total)) + 15) & ~(size_t)15;
     }
     return offset;
 }
@@ -587,9 +699,17 @@ void provider_base::stage_boxes(decode_window& w) const
         int32_t*     lb    = (int32_t*)(t + box_rec_bytes(w.n) + total * 16);
         int32_t*     df    = (int32_t*)(t + box_rec_bytes(w.n) + total * 20);
         size_t       first = 0;
+        const bool   rcnn  = m_providers[k]->box_kind() == AEON_BOX_RCNN;
+        RcnnRec*     X     = rcnn ? (RcnnRec*)(t + rcnn_ext_offset(w.n, total)) : nullptr;
+        const aeon_rcnn_out ro = rcnn ? m_providers[k]->rcnn_out() : aeon_rcnn_out{};
         for (int i = 0; i < w.n; i++) {
             const box_metadata& m   = w.boxes[k][i];
             const int           cnt = (int)m.labels.size();
+            if (rcnn) {
+                if (cnt > kRcnnMaxBoxes)
+                    throw unsupported_error("localization_rcnn: more than 1024 boxes in a record, at idx " + std::to_string(i));
+                X[i] = rcnn_rec(w.params[k][i], ro.fixed_scaling_factor, ro.width, ro.height, w.rcnn_engine[i]);
+            }
             if (const char* why = box_refusal(w.params[k][i], m.boxes.data(), cnt))
                 invalid(std::string(why) + ", at idx " + std::to_string(i));
             R[i] = box_rec((uint32_t)first, cnt, w.params[k][i]);
@@ -835,6 +955,11 @@ batch_decoder::~batch_decoder()
     (void)hipSetDevice(m_device);
     for (auto& ws : m_slots)
         if (ws.pending) (void)hipEventSynchronize(ws.done);
+    for (auto& ws : m_slots) {
+        if (ws.states_done) (void)hipEventDestroy(ws.states_done);
+        if (ws.states_dev) (void)hipFree(ws.states_dev);
+        if (ws.states_host) (void)hipHostFree(ws.states_host);
+    }
     aeon_hip_ctx_destroy(m_ctx);
     for (auto& ws : m_slots) {
         if (ws.done) (void)hipEventDestroy(ws.done);
@@ -845,6 +970,15 @@ batch_decoder::~batch_decoder()
             for (auto* p : *v)
                 if (p) (void)hipFree(p);
     }
+}
+
+// The slot engines take over the states an earlier localization_rcnn window's device shuffles left.
+void batch_decoder::adopt_states()
+{
+    if (!m_states_from) return;
+    hip_check(hipEventSynchronize(m_states_from->states_done), "hipEventSynchronize");
+    for (int i = 0; i < m_states_n && i < (int)m_random.size(); i++) m_random[i].seed(m_states_from->states_host[i]);
+    m_states_from = nullptr;
 }
 
 // Deterministic mode: engine i of the decode window is seeded with the i-th output of
@@ -955,13 +1089,37 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     // swaps the slot engine in and out, batch_decoder.cpp:62-71).  With slot engines the draws run
     // on the pool (draw_window: aeon's in-order params exactly), and with them the extraction of the
     // box providers' metadata, which make_ssd_params draws over.
+    const bool rcnn = m_provider->has_rcnn();
     {
         phase_range r("aeon.draw");
+        if (rcnn) w.rcnn_engine.resize(n);
         if (m_deterministic) {
+            // aeon's shuffles draw from the slot engine after make_params and leave it advanced
+            // (batch_decoder.cpp:62-71): an earlier window's end states first, then this window's draws
+            if (rcnn) adopt_states();
             m_provider->draw_window(n, records.data(), w, m_random, *m_pool);
+            for (int i = 0; rcnn && i < n; i++) w.rcnn_engine[i] = minstd_state(m_random[i]);
         } else { // one engine for the window: in record order
-            for (int i = 0; i < n; i++) m_provider->draw(i, records.data() + (size_t)i * ne, w, m_local_random);
+            // (aeon's result depends on its thread scheduling here; a record's shuffle engine is seeded by
+            // one further draw of the window's engine)
+            for (int i = 0; i < n; i++) {
+                m_provider->draw(i, records.data() + (size_t)i * ne, w, m_local_random);
+                if (rcnn) w.rcnn_engine[i] = (uint32_t)m_local_random();
+            }
         }
+    }
+    if (rcnn && m_deterministic) {
+        if ((size_t)n > ws.states_cap) {
+            if (ws.states_dev) hip_check(hipFree(ws.states_dev), "hipFree");
+            if (ws.states_host) hip_check(hipHostFree(ws.states_host), "hipHostFree");
+            ws.states_dev = ws.states_host = nullptr, ws.states_cap = 0;
+            hip_check(hipMalloc((void**)&ws.states_dev, (size_t)n * sizeof(uint32_t)), "hipMalloc");
+            hip_check(hipHostMalloc((void**)&ws.states_host, (size_t)n * sizeof(uint32_t), hipHostMallocDefault),
+                      "hipHostMalloc");
+            ws.states_cap = (size_t)n;
+        }
+        if (!ws.states_done) hip_check(hipEventCreateWithFlags(&ws.states_done, hipEventDisableTiming), "hipEventCreate");
+        w.rcnn_states_dev = ws.states_dev, w.rcnn_states_host = ws.states_host, w.rcnn_states_done = ws.states_done;
     }
     // source arena: the box tables and the decoded elements first (staged + one H2D), then the
     // device-decoded JPEGs
@@ -1030,6 +1188,17 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
         }
     }
     phase_range launch("aeon.launch");
+    // once post_process has queued the engine states' copy and its event, the next window adopts them,
+    // whatever happens to the rest of this one
+    struct adopt_later {
+        batch_decoder& d;
+        decode_window& w;
+        window_slot&   ws;
+        ~adopt_later()
+        {
+            if (w.rcnn_states_queued) d.m_states_from = &ws, d.m_states_n = w.n;
+        }
+    } adopt_guard{*this, w, ws};
     if (m_batch_major) {
         m_provider->post_process(m_ctx, w, ws.dev_src, outs.data(), stream);
     } else {
@@ -1172,6 +1341,9 @@ int host_guarded(F&& f)
     } catch (const std::invalid_argument& e) {
         g_host_err = e.what();
         return AEON_HIP_EINVAL;
+    } catch (const aeon_hip::unsupported_error& e) {
+        g_host_err = e.what();
+        return AEON_HIP_EUNSUPPORTED;
     } catch (const std::exception& e) {
         g_host_err = e.what();
         return AEON_HIP_ERUNTIME;

@@ -7,6 +7,7 @@
 //   provider::pixelmask      src/provider.cpp:353-393          (etl type "pixelmask")
 //   provider::boundingbox    src/provider.cpp:395-439          (etl type "boundingbox")
 //   provider::localization::ssd src/provider.cpp:289-346       (etl type "localization_ssd")
+//   provider::localization::rcnn src/provider.cpp:222-287      (etl type "localization_rcnn")
 //   image::config            src/etl_image.hpp:56-96, etl_image.cpp:25-65
 //   batch_decoder            src/batch_decoder.cpp:24-99        (thread pool + deterministic slots)
 //   thread_pool              src/thread_pool.hpp:82-175         (dynamic atomic task counter)
@@ -34,6 +35,7 @@
 #include "box_host.hpp"
 #include "json.hpp"
 #include "param_factory.hpp"
+#include "rcnn_host.hpp"
 
 namespace aeon_hip {
 
@@ -88,6 +90,14 @@ struct decode_window {
     std::vector<std::vector<box_metadata>>    boxes;      // [provider][record]
     std::vector<size_t>                       box_offset; // [provider]
     std::vector<size_t>                       box_total;  // [provider] boxes of the window
+    // localization_rcnn: the minstd_rand0 state record i's shuffles start from (its engine after the params
+    // draw); in deterministic mode the states after the shuffles are copied from rcnn_states_dev to
+    // rcnn_states_host right behind the targets kernel, and rcnn_states_done is recorded after the copy
+    std::vector<uint32_t>                     rcnn_engine; // [record]
+    uint32_t*                                 rcnn_states_dev  = nullptr;
+    uint32_t*                                 rcnn_states_host = nullptr;
+    hipEvent_t                                rcnn_states_done = nullptr;
+    bool                                      rcnn_states_queued = false; // the copy and its event are on the stream
 };
 
 // augmentation shared by the ETL providers of one record (provider.cpp:109-119)
@@ -152,6 +162,8 @@ public:
     {
     }
     virtual aeon_box_out box_out() const { return aeon_box_out{}; }
+    // AEON_BOX_RCNN: the targets call's description without its buffers
+    virtual aeon_rcnn_out rcnn_out() const { return aeon_rcnn_out{}; }
 };
 
 class provider_base : public provider_interface {
@@ -176,6 +188,7 @@ public:
     // output_first(k) .. output_first(k + 1) - 1
     int  output_first(size_t k) const { return m_out_first[k]; }
     bool has_boxes() const { return m_has_boxes; }
+    bool has_rcnn() const { return m_has_rcnn; }
     // the box tables of the window's box providers: their size after the window's pixels at `offset`
     // of the arena (layout_boxes), and the tables themselves written there (stage_boxes, which also
     // makes the host-side refusals: rotation, boundingbox::box::expand's precondition)
@@ -185,7 +198,7 @@ public:
 private:
     std::vector<std::unique_ptr<etl_provider>> m_providers;
     std::vector<int>                           m_out_first; // size providers + 1
-    bool                                       m_has_boxes = false;
+    bool                                       m_has_boxes = false, m_has_rcnn = false;
 };
 
 struct provider_factory {
@@ -262,7 +275,16 @@ private:
         size_t                dev_src_cap = 0;
         std::vector<uint8_t*> dev_out, dev_tmp;
         std::vector<size_t>   dev_out_cap, dev_tmp_cap;
+        // localization_rcnn, deterministic mode: the window's engine end states (device, pinned host)
+        uint32_t*             states_dev = nullptr, *states_host = nullptr;
+        size_t                states_cap = 0;
+        hipEvent_t            states_done = nullptr;
     };
+    // the slot engines take over the states an earlier rcnn window's shuffles left (waits for that
+    // window's small copy alone)
+    void adopt_states();
+    window_slot*                   m_states_from = nullptr; // window whose end states are not adopted yet
+    int                            m_states_n    = 0;
     void enqueue(window_slot& ws, int n, const decoded_element* records, void* const* outputs, bool on_device,
                  hipStream_t stream);
     void                           grow_slot_engines(int n);
@@ -303,6 +325,10 @@ void ctx_share_pool(aeon_hip_ctx* ctx, thread_pool* pool);
 // refusals (box_refusal) are the caller's to make while it stages.
 int box_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t total, const aeon_box_out& out,
                         void* stream);
+// aeon_hip_rcnn_targets_batch over a staged rcnn table (rcnn_job.hpp: the box table, then RcnnRec[n]);
+// states_dev (n words, or null) receives the engines' states after the shuffles
+int rcnn_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t total, const aeon_rcnn_out& out,
+                        int shuffle, uint32_t* states_dev, void* stream);
 // a map stretched or cut to n workers (decode_thread_count / AEON_HIP_JPEG_THREADS): worker i on map[i % size]
 std::vector<int> affinity_for(const std::vector<int>& map, int n);
 

@@ -1,0 +1,67 @@
+// rcnn_job.hpp -- what the host (stage.cpp, host.cpp) and the device (rcnn_kernels.hip) share about one
+// localization_rcnn targets launch: the limits, the per-record extension of the box table and the
+// launch description.
+//
+// Device table of a call: the box table of box_job.hpp (BoxRec[n], boxes, labels, difficult flags),
+// padded to 16 bytes, then RcnnRec[n].
+//
+// Limits (a config or record beyond them is AEON_HIP_EUNSUPPORTED, never a wrong answer).  The kernel
+// keeps a record's state in LDS: three bits per anchor (foreground, background, sampled) and a running
+// count per 64 anchors, the transformed gt boxes, and the sampled ranks.
+//   total_anchors   <= kRcnnMaxAnchors (65 536; aeon's 1000 x 1000 default has 34 596)
+//   boxes per record <= kRcnnMaxBoxes   (1024, before the crop drops any)
+//   rois_per_image  <= kRcnnMaxRois    (1024; aeon's default is 256)
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "box_job.hpp"
+#include "rcnn_shuffle.hpp"
+
+namespace aeon_hip {
+
+constexpr int kRcnnMaxAnchors = 65536;
+constexpr int kRcnnMaxBoxes   = 1024;
+constexpr int kRcnnMaxRois    = 1024;
+
+// Per record, next to its BoxRec: transformer::transform's image scale and scaled image size
+// (etl_localization_rcnn.cpp:101-118), and the minstd_rand0 state its shuffles start from.
+struct RcnnRec {
+    float    im_scale;
+    int32_t  im_w, im_h;
+    uint32_t engine;
+};
+static_assert(sizeof(RcnnRec) == 16, "RcnnRec is read as one 16-byte load");
+
+// host: transformer::transform's first lines for one record
+int   unbiased_round(float x);                         // param_factory.cpp
+float calculate_scale(int w, int h, int ow, int oh);   // param_factory.cpp
+inline RcnnRec rcnn_rec(const aeon_aug_params& p, float fixed_scaling_factor, int width, int height, uint32_t engine)
+{
+    engine = rcnn_engine_word(engine);
+    const float im_scale = fixed_scaling_factor > 0 ? fixed_scaling_factor : calculate_scale(p.crop_w, p.crop_h, width, height);
+    return RcnnRec{im_scale, unbiased_round(p.crop_w * im_scale), unbiased_round(p.crop_h * im_scale), engine};
+}
+
+inline size_t rcnn_ext_offset(int n, size_t total) { return (box_table_bytes(n, total) + 15) & ~(size_t)15; }
+inline size_t rcnn_table_bytes(int n, size_t total) { return rcnn_ext_offset(n, total) + (size_t)n * sizeof(RcnnRec); }
+
+struct RcnnLaunch {
+    const BoxRec*  recs;
+    const float*   boxes; // 16-byte aligned, 4 floats per box
+    const int32_t* labels;
+    const int32_t* difficult;
+    const RcnnRec* ext;
+    const float*   anchors;    // 16-byte aligned, 4 floats per anchor (anchor::generate, uploaded once)
+    uint32_t*      states_out; // n engine states after the shuffles, or null
+    int32_t        n, total_anchors, max_gt_boxes, emit_type;
+    float          emit_min_overlap;
+    float          negative_overlap, positive_overlap;
+    int32_t        rois_per_image, num_fg, shuffle;
+    // bbtargets, bbtargets_mask, labels_flat, labels_mask, image_shape, gt_boxes, gt_box_count,
+    // gt_class_count, image_scale, difficult_flag
+    uint8_t*       buf[10];
+    uint64_t       stride[10];
+};
+
+} // namespace aeon_hip

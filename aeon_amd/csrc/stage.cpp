@@ -20,6 +20,7 @@
 #include "../../include/aeon_hip.h"
 #include "aug_job.hpp"
 #include "box_job.hpp"
+#include "rcnn_job.hpp"
 #include "host.hpp"
 #include "jpeg.hpp"
 #include "mask16.hpp"
@@ -49,6 +50,7 @@ hipError_t launch_split(bool tail, int occ, const LaunchArgs& a, const SplitArgs
                         hipEvent_t start, hipEvent_t stop);
 hipError_t split_lds_limit(int bytes);
 hipError_t launch_box_targets(const BoxLaunch& L, hipStream_t stream);
+hipError_t launch_rcnn_targets(const RcnnLaunch& L, hipStream_t stream);
 hipError_t split_occupancy(bool tail, int occ, const LaunchArgs& a, int* blocks);
 hipError_t launch_resize_generic(const ResizeJob* jobs, const uint8_t* table, int n_jobs, int max_tiles, int TR, int CW,
                                  int NR, int xs, int amax, int cn_max, int SW, const float* lut, int bgr, int chm,
@@ -930,6 +932,13 @@ struct aeon_hip_ctx {
     std::vector<int>     direct_order;       // (run_direct) their table order: largest crop first
     JpegState*           jpeg = nullptr;     // JPEG decode stage (pool, staging ring), on first use
     thread_pool*         host_pool = nullptr; // the owning decoder's pool (ctx_share_pool), for the JPEG stage
+    // localization_rcnn: the anchor table of the last config seen stays resident (uploaded once), and the
+    // direct call's engine end states pass through a small device array
+    std::vector<float>   rcnn_anchors_host;
+    float*               rcnn_anchors_dev = nullptr;
+    uint64_t             rcnn_anchors_key = 0; // aeon_rcnn_out::anchors_key of the resident table (0: none given)
+    uint32_t*            rcnn_states_dev  = nullptr;
+    size_t               rcnn_states_cap  = 0;
     std::unique_ptr<thread_pool> plan_pool;        // the context's own, made for the first call with many Lanczos4 taps
     std::vector<int> open_slots; // used since the last completion event, on open_stream
     hipStream_t      open_stream = nullptr;
@@ -2079,16 +2088,139 @@ int run_box_targets(aeon_hip_ctx* ctx, int n, const aeon_box_record* recs, const
     return 0;
 }
 
-// std::minstd_rand0 whose state word can be read back (an LCG's state is its last output).
-struct TrackedEngine {
-    using result_type = std::minstd_rand0::result_type;
-    std::minstd_rand0 e;
-    result_type       last;
-    static constexpr result_type min() { return std::minstd_rand0::min(); }
-    static constexpr result_type max() { return std::minstd_rand0::max(); }
-    explicit TrackedEngine(uint32_t s) : e(s), last(s % 2147483647u == 0 ? 1 : s % 2147483647u) {}
-    result_type operator()() { return last = e(); }
-};
+// ---- localization_rcnn targets ----------------------------------------------------------------
+// The output side of an rcnn call: ten buffers of n items; the kernel writes 4A floats (bbtargets,
+// bbtargets_mask), 2A int32 (labels_flat, labels_mask), 8 bytes (image_shape), max_gt_boxes * 16
+// (gt_boxes), max_gt_boxes * 4 (gt_class_count, difficult_flag) and 4 bytes (gt_box_count, image_scale).
+void check_rcnn_out(const aeon_rcnn_out& o)
+{
+    if (o.total_anchors <= 0) fail(AEON_HIP_EINVAL, "invalid total_anchors");
+    if (o.total_anchors > kRcnnMaxAnchors)
+        fail(AEON_HIP_EUNSUPPORTED, "localization_rcnn: total_anchors above 65536 (the per-record LDS state)");
+    if (o.rois_per_image < 0 || o.num_fg < 0 || o.num_fg > o.rois_per_image)
+        fail(AEON_HIP_EINVAL, "invalid rois_per_image / num_fg");
+    if (o.rois_per_image > kRcnnMaxRois) fail(AEON_HIP_EUNSUPPORTED, "localization_rcnn: rois_per_image above 1024");
+    if (o.max_gt_boxes <= 0) fail(AEON_HIP_EINVAL, "invalid max_gt_boxes");
+    if (o.emit_type < AEON_EMIT_NONE || o.emit_type > AEON_EMIT_MIN_OVERLAP)
+        fail(AEON_HIP_EINVAL, "Invalid emit constraint type");
+    if (!o.anchors) fail(AEON_HIP_EINVAL, "null anchors");
+    const uint64_t A = (uint64_t)o.total_anchors, m = (uint64_t)o.max_gt_boxes;
+    const uint64_t need[10] = {16 * A, 16 * A, 8 * A, 8 * A, 8, 16 * m, 4, 4 * m, 4, 4 * m};
+    for (int k = 0; k < 10; k++)
+        if (!o.buf[k] || ((uintptr_t)o.buf[k] & 3) || (o.item_stride[k] & 3) || o.item_stride[k] < need[k])
+            fail(AEON_HIP_EINVAL, "rcnn buffers: 4-byte aligned items of the output's size");
+    if (((uintptr_t)o.buf[5] & 15) || (o.item_stride[5] & 15)) fail(AEON_HIP_EINVAL, "gt_boxes buffer: 16-byte aligned items");
+}
+
+// The config's anchor table on the device: uploaded when it differs from the resident one.  A caller that
+// keeps one table per key (aeon_rcnn_out::anchors_key != 0: the decoder's provider) is believed on the key;
+// without a key the table's content is compared.
+const float* resident_anchors(aeon_hip_ctx* ctx, const aeon_rcnn_out& o)
+{
+    const size_t words = 4 * (size_t)o.total_anchors;
+    if (ctx->rcnn_anchors_dev && ctx->rcnn_anchors_host.size() == words) {
+        if (o.anchors_key != 0 ? ctx->rcnn_anchors_key == o.anchors_key
+                               : std::memcmp(ctx->rcnn_anchors_host.data(), o.anchors, words * sizeof(float)) == 0)
+            return ctx->rcnn_anchors_dev;
+    }
+    HIP_OK(hipDeviceSynchronize()); // launches that read the resident table
+    if (ctx->rcnn_anchors_dev) HIP_OK(hipFree(ctx->rcnn_anchors_dev));
+    ctx->rcnn_anchors_dev = nullptr;
+    ctx->rcnn_anchors_host.assign(o.anchors, o.anchors + words);
+    ctx->rcnn_anchors_key = 0;
+    HIP_OK(hipMalloc((void**)&ctx->rcnn_anchors_dev, words * sizeof(float)));
+    HIP_OK(hipMemcpy(ctx->rcnn_anchors_dev, o.anchors, words * sizeof(float), hipMemcpyHostToDevice));
+    ctx->rcnn_anchors_key = o.anchors_key;
+    return ctx->rcnn_anchors_dev;
+}
+
+// One launch over an rcnn table in device memory (rcnn_job.hpp's layout).
+void launch_rcnn_table(aeon_hip_ctx* ctx, int n, const uint8_t* dev_table, size_t total, const aeon_rcnn_out& o,
+                       int shuffle, uint32_t* states_dev, hipStream_t stream)
+{
+    const size_t rec_bytes = box_rec_bytes(n);
+    RcnnLaunch   L{};
+    L.recs       = (const BoxRec*)dev_table;
+    L.boxes      = (const float*)(dev_table + rec_bytes);
+    L.labels     = (const int32_t*)(dev_table + rec_bytes + total * 16);
+    L.difficult  = (const int32_t*)(dev_table + rec_bytes + total * 20);
+    L.ext        = (const RcnnRec*)(dev_table + rcnn_ext_offset(n, total));
+    L.anchors    = resident_anchors(ctx, o);
+    L.states_out = states_dev;
+    L.n = n, L.total_anchors = o.total_anchors, L.max_gt_boxes = o.max_gt_boxes, L.emit_type = o.emit_type;
+    L.emit_min_overlap = o.emit_min_overlap;
+    L.negative_overlap = o.negative_overlap, L.positive_overlap = o.positive_overlap;
+    L.rois_per_image = o.rois_per_image, L.num_fg = o.num_fg, L.shuffle = shuffle ? 1 : 0;
+    for (int k = 0; k < 10; k++) L.buf[k] = (uint8_t*)o.buf[k], L.stride[k] = o.item_stride[k];
+    HIP_OK(launch_rcnn_targets(L, stream));
+}
+
+// aeon_hip_rcnn_targets_batch: the call's table goes through a ring slot like a box call's; with engine
+// states the end states come back (one small D2H behind the kernel, then the stream is synchronized).
+int run_rcnn_targets(aeon_hip_ctx* ctx, int n, const aeon_box_record* recs, const float* boxes, const int32_t* labels,
+                     const int32_t* difficult, const aeon_aug_params* params, uint32_t* engine_states, int shuffle,
+                     const aeon_rcnn_out* out, void* stream_)
+{
+    if (!ctx || !out) fail(AEON_HIP_EINVAL, "null argument");
+    if (n < 0) fail(AEON_HIP_EINVAL, "negative record count");
+    if (n == 0) return 0;
+    if (!recs || !params) fail(AEON_HIP_EINVAL, "null argument");
+    if (shuffle && !engine_states) fail(AEON_HIP_EINVAL, "shuffle needs the records' engine states");
+    check_rcnn_out(*out);
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (recs[i].count < 0) fail(AEON_HIP_EINVAL, "negative box count");
+        if (recs[i].count > kRcnnMaxBoxes) fail(AEON_HIP_EUNSUPPORTED, "localization_rcnn: more than 1024 boxes in a record");
+        total = std::max(total, (size_t)recs[i].first + (size_t)recs[i].count);
+    }
+    if (total > 0 && (!boxes || !labels || !difficult)) fail(AEON_HIP_EINVAL, "null box table");
+    if (total > ((size_t)1 << 26)) fail(AEON_HIP_EINVAL, "box table too large");
+    for (int i = 0; i < n; i++)
+        if (const char* why = box_refusal(params[i], recs[i].count ? boxes + 4 * (size_t)recs[i].first : nullptr, recs[i].count))
+            fail(AEON_HIP_EINVAL, why);
+    hipStream_t stream = (hipStream_t)stream_;
+
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_OK(hipSetDevice(ctx->device));
+    const size_t rec_bytes = box_rec_bytes(n);
+    const size_t blob      = rcnn_table_bytes(n, total);
+    int          slot;
+    Slot&        s = take_slot(ctx, stream, slot);
+    ensure_ring(ctx, blob, 0, 0);
+    BoxRec*  R = (BoxRec*)s.host;
+    RcnnRec* X = (RcnnRec*)(s.host + rcnn_ext_offset(n, total));
+    for (int i = 0; i < n; i++) {
+        R[i] = box_rec(recs[i].first, recs[i].count, params[i]);
+        X[i] = rcnn_rec(params[i], out->fixed_scaling_factor, out->width, out->height,
+                        engine_states ? engine_states[i] : 1u);
+    }
+    if (total) {
+        std::memcpy(s.host + rec_bytes, boxes, total * 16);
+        std::memcpy(s.host + rec_bytes + total * 16, labels, total * 4);
+        std::memcpy(s.host + rec_bytes + total * 20, difficult, total * 4);
+    }
+    HIP_OK(hipMemcpyAsync(s.dev, s.host, blob, hipMemcpyHostToDevice, stream));
+    uint32_t* states_dev = nullptr;
+    if (engine_states) {
+        if ((size_t)n > ctx->rcnn_states_cap) {
+            HIP_OK(hipDeviceSynchronize());
+            if (ctx->rcnn_states_dev) HIP_OK(hipFree(ctx->rcnn_states_dev));
+            ctx->rcnn_states_dev = nullptr, ctx->rcnn_states_cap = 0;
+            HIP_OK(hipMalloc((void**)&ctx->rcnn_states_dev, (size_t)n * 2 * sizeof(uint32_t)));
+            ctx->rcnn_states_cap = (size_t)n * 2;
+        }
+        states_dev = ctx->rcnn_states_dev;
+    }
+    launch_rcnn_table(ctx, n, s.dev, total, *out, shuffle, states_dev, stream);
+    release_slot(ctx, slot, stream);
+    if (engine_states) {
+        HIP_OK(hipMemcpyAsync(engine_states, states_dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+    }
+    return 0;
+}
+
+using TrackedEngine = tracked_engine; // rcnn_host.hpp
 
 template <typename F>
 int guarded(F&& f)
@@ -2130,6 +2262,20 @@ int box_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t t
         std::lock_guard<std::mutex> lock(ctx->mu);
         HIP_OK(hipSetDevice(ctx->device));
         launch_box_table(n, (const uint8_t*)dev_table, total, out, (hipStream_t)stream);
+        return 0;
+    });
+}
+int rcnn_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t total, const aeon_rcnn_out& out,
+                        int shuffle, uint32_t* states_dev, void* stream)
+{
+    return guarded([&] {
+        if (!ctx || (n > 0 && !dev_table)) fail(AEON_HIP_EINVAL, "null argument");
+        if (n <= 0) return 0;
+        if ((uintptr_t)dev_table & 15) fail(AEON_HIP_EINVAL, "rcnn table not 16-byte aligned");
+        check_rcnn_out(out);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_OK(hipSetDevice(ctx->device));
+        launch_rcnn_table(ctx, n, (const uint8_t*)dev_table, total, out, shuffle, states_dev, (hipStream_t)stream);
         return 0;
     });
 }
@@ -2271,6 +2417,8 @@ int aeon_hip_ctx_destroy(aeon_hip_ctx* c)
         if (c->d_error) (void)hipFree(c->d_error);
         if (c->d_tail) (void)hipFree(c->d_tail);
         if (c->d_hsv) (void)hipFree(c->d_hsv);
+        if (c->rcnn_anchors_dev) (void)hipFree(c->rcnn_anchors_dev);
+        if (c->rcnn_states_dev) (void)hipFree(c->rcnn_states_dev);
         delete c;
         return 0;
     });
@@ -2473,6 +2621,15 @@ int aeon_param_factory_emit(aeon_param_factory* f, int* type, float* min_overlap
         *type        = e == "center" ? AEON_EMIT_CENTER : e == "min_overlap" ? AEON_EMIT_MIN_OVERLAP : AEON_EMIT_NONE;
         *min_overlap = f->f.emit_constraint_min_overlap;
         return 0;
+    });
+}
+
+int aeon_hip_rcnn_targets_batch(aeon_hip_ctx* ctx, int n, const aeon_box_record* recs, const float* boxes,
+                                const int32_t* labels, const int32_t* difficult, const aeon_aug_params* params,
+                                uint32_t* engine_states, int shuffle, const aeon_rcnn_out* out, void* stream)
+{
+    return guarded([&] {
+        return run_rcnn_targets(ctx, n, recs, boxes, labels, difficult, params, engine_states, shuffle, out, stream);
     });
 }
 

@@ -314,6 +314,73 @@ int aeon_hip_box_targets_batch(aeon_hip_ctx* ctx, int n, const aeon_box_record* 
                                const int32_t* labels, const int32_t* difficult, const aeon_aug_params* params,
                                const aeon_box_out* out, void* stream);
 
+/* ---- localization_rcnn: provider::localization::rcnn anchor targets ---------------------------
+ * (src/etl_localization_rcnn.{hpp,cpp}, provider.cpp:222-287.)  config_json is the ETL object
+ * ({"type": "localization_rcnn", "height", "width", "class_names", and optionally "name",
+ * "rois_per_image" 256, "base_size" 16, "scaling_factor" 1/16, "ratios" [0.5, 1, 2], "scales" [8, 16, 32],
+ * "negative_overlap" 0.3, "positive_overlap" 0.7, "foreground_fraction" 0.5, "max_gt_boxes" 64}); unknown
+ * keys and fractions outside [0, 1] are AEON_HIP_EINVAL.  aeon validates nothing else; here a config that
+ * yields no launchable anchors is AEON_HIP_EINVAL too (height, width, base_size, max_gt_boxes, a ratio or
+ * a scale that is not positive, empty ratios / scales, a scaling_factor that is not positive and finite, an
+ * empty feature grid), and one that only this build cannot take is AEON_HIP_EUNSUPPORTED (height, width or
+ * max_gt_boxes above 2^24, a feature grid side above 2^24; more than 2^24 anchors at aeon_rcnn_anchors;
+ * the device limits below at the device entry and the decoder).  Host only; errors in aeon_rcnn_last_error().
+ *
+ * aeon_rcnn_anchors: anchor::generate's table, total_anchors x (xmin, ymin, xmax, ymax) -- base
+ * anchors outermost, then shift rows, then shift columns.  *n receives total_anchors; at most cap
+ * anchors are written (cap 0: the count alone).
+ * aeon_rcnn_config_info: the derived numbers a caller of the device entry needs, and this build's limits
+ * (a config or record beyond them is AEON_HIP_EUNSUPPORTED at the device entry and the decoder).
+ * aeon_rcnn_sample_anchors: transformer::sample_anchors over labels[n] (>= 1 foreground, 0 background,
+ * else ignored) with the real std::shuffle over std::minstd_rand0: the engine starts from *engine_state
+ * and is left at the state after the two shuffles; shuffle == 0 is aeon's debug_deterministic (no
+ * draws).  out receives at most rois_per_image anchor indices, foreground first.  This is the statement
+ * of aeon (and of this machine's libstdc++) that the device shuffle is tested against. */
+typedef struct aeon_rcnn_info {
+    int64_t total_anchors;
+    int32_t rois_per_image, num_fg, max_gt_boxes, width, height;
+    float   negative_overlap, positive_overlap;
+    int32_t max_total_anchors, max_rois_per_image, max_boxes_per_record;
+} aeon_rcnn_info;
+int aeon_rcnn_anchors(const char* config_json, float* out, int cap, int* n);
+int aeon_rcnn_config_info(const char* config_json, aeon_rcnn_info* info);
+int aeon_rcnn_sample_anchors(const int32_t* labels, int n, int rois_per_image, int num_fg, int shuffle,
+                             uint32_t* engine_state, int32_t* out, int* n_out);
+const char* aeon_rcnn_last_error(void);
+
+/* transformer::transform + sample_anchors + loader::load for n records in one launch, one workgroup per
+ * record.  recs / boxes / labels / difficult / params as in aeon_hip_box_targets_batch (the same
+ * refusals).  Per record: im_scale = fixed_scaling_factor when > 0, else calculate_scale over the
+ * cropbox and (width, height); im_size = unbiased_round(crop_w * im_scale) x (crop_h likewise); the
+ * record's boxes through transform_box (all K survivors count, only buf[5], [7], [9] stop at
+ * max_gt_boxes); anchors inside im_size labelled by bbox_overlaps against negative_overlap /
+ * positive_overlap and the per-box maxima (ties included); at most rois_per_image of them sampled,
+ * num_fg foreground at most.  engine_states (n words, may be NULL when shuffle == 0): record i's shuffles
+ * start from engine_states[i], which receives the state after them -- the call then synchronizes
+ * `stream`; without engine_states it is asynchronous.  shuffle == 0 is aeon's debug_deterministic.
+ *   buf[0] bbtargets, buf[1] bbtargets_mask: 4 * total_anchors float     buf[5] gt_boxes: max_gt_boxes x 4 float
+ *   buf[2] labels_flat, buf[3] labels_mask: 2 * total_anchors int32      buf[6] gt_box_count: int32
+ *   buf[4] image_shape: (im_w, im_h) int32                               buf[7] gt_class_count, buf[9]
+ *   buf[8] image_scale: float                                            difficult_flag: max_gt_boxes int32
+ * Every element of every item is written.  anchors: the host table of aeon_rcnn_anchors, uploaded when
+ * it differs from the context's resident one: with anchors_key 0 the tables' contents are compared on
+ * every call; a caller that gives every distinct table it uses on this context its own non-zero
+ * anchors_key is believed on the key (the decoder does).  engine_states words are taken as
+ * minstd_rand0::seed takes them (mod 2^31 - 1, 0 becomes 1).  total_anchors above 65536, rois_per_image above 1024
+ * or a record with more than 1024 boxes: AEON_HIP_EUNSUPPORTED. */
+#define AEON_BOX_RCNN 2
+typedef struct aeon_rcnn_out {
+    int32_t      total_anchors, max_gt_boxes, rois_per_image, num_fg, width, height, emit_type;
+    float        emit_min_overlap, negative_overlap, positive_overlap, fixed_scaling_factor;
+    const float* anchors;
+    uint64_t     anchors_key; /* 0, or the caller's name for this table: see above */
+    void*        buf[10];
+    uint64_t     item_stride[10];
+} aeon_rcnn_out;
+int aeon_hip_rcnn_targets_batch(aeon_hip_ctx* ctx, int n, const aeon_box_record* recs, const float* boxes,
+                                const int32_t* labels, const int32_t* difficult, const aeon_aug_params* params,
+                                uint32_t* engine_states, int shuffle, const aeon_rcnn_out* out, void* stream);
+
 /* batch_decoder deterministic mode (src/batch_decoder.cpp:47-54): slot engine state words. */
 int aeon_seed_slots(uint32_t seed, int n, uint32_t* states);
 
@@ -329,8 +396,8 @@ int aeon_cropbox_max_proportional(float in_w, float in_h, float out_w, float out
 
 /* ---- decode stage: provider_factory + batch_decoder (host C++ above the kernels) --------------
  * aeon_decoder = batch_decoder (src/batch_decoder.cpp:24-99) over provider_factory::create
- * (src/provider_factory.cpp:24-51) with "image" / "pixelmask" / "boundingbox" / "localization_ssd" ETL
- * providers.  config_json is the
+ * (src/provider_factory.cpp:24-51) with "image" / "pixelmask" / "boundingbox" / "localization_ssd" /
+ * "localization_rcnn" ETL providers.  config_json is the
  * aeon loader configuration ({"batch_size", "random_seed", "node_id", "cpu_list", "etl": [...],
  * "augmentation": [...]}, src/loader.hpp:50-109; unknown keys are rejected like verify_config).
  * Records arrive decoded (image::extractor::extract stays with the caller).
@@ -343,7 +410,14 @@ int aeon_cropbox_max_proportional(float in_w, float in_h, float out_w, float out
  * config that holds a box ETL.  The first element of a record draws its (shared) params
  * (src/provider.cpp:109-119): localization_ssd make_ssd_params over the extracted boxes, boundingbox and
  * image make_params.  A window fails with AEON_HIP_EINVAL when a box provider meets params.angle != 0
- * or a box that fails boundingbox::box::expand's precondition. */
+ * or a box that fails boundingbox::box::expand's precondition.
+ * localization_rcnn (ten buffers: bbtargets, bbtargets_mask, labels_flat, labels_mask, image_shape,
+ * gt_boxes, gt_box_count, gt_class_count, image_scale, difficult_flag) draws make_params over the
+ * metadata's image size; its shuffles run on the device from the record's engine after the params draw.
+ * With random_seed != 0 the engines' states after the shuffles come back with the window and are the
+ * slot engines of the next one, as aeon's: a later window waits for that small copy alone before it
+ * draws.  With random_seed 0 each record's shuffle engine is seeded by one further draw of the window's
+ * engine. */
 typedef struct aeon_decoder aeon_decoder;
 
 /* One decoded element of a record: HWC uint8 (BGR) pixels in host memory. */
