@@ -345,15 +345,10 @@ def box_extract(class_names, text):
 SSD_OUTPUTS = ("image_shape", "gt_boxes", "gt_box_count", "gt_class_count", "difficult_flag")
 
 
-def box_targets(ctx, records, params, kind=BOX_SSD, max_boxes=64, out_w=0, out_h=0, emit=(EMIT_NONE, 0.0),
-                item_bytes=None, out_ptrs=None, stream=0):
-    """aeon_hip_box_targets_batch for len(records) records: records[i] = a box_extract() dict or a
-    (boxes n x 4, labels, difficult) tuple, params[i] = the AugParams of the record's image, emit = the
-    factory's ParamFactory.emit().  Without out_ptrs the kernel stores into pinned device-mapped buffers
-    filled with 0xCD beforehand, and the result comes back as numpy arrays: BOX_BOUNDINGBOX one float32
-    array (n, item_bytes / 4) (item_bytes: aeon's max_bbox_count * 16 * sizeof(output_type), default
-    float), BOX_SSD a dict of the five outputs by aeon's names.  With out_ptrs (device addresses, one per
-    output) the call is left asynchronous on `stream` and returns None."""
+def _pack_box_call(records, params):
+    """The input side of a box / rcnn targets call: records[i] = a box_extract() dict or a (boxes n x 4, labels,
+    difficult) tuple, params[i] = the record's AugParams.  Returns (BoxRecord array, boxes, labels, difficult flags,
+    AugParams array), the three tables contiguous over all records."""
     n = len(records)
     recs = (BoxRecord * max(n, 1))()
     bx, lb, df = [], [], []
@@ -372,34 +367,61 @@ def box_targets(ctx, records, params, kind=BOX_SSD, max_boxes=64, out_w=0, out_h
     p = params if isinstance(params, ctypes.Array) else (AugParams * max(n, 1))(*params)
     if len(p) < n:
         raise ValueError(f"{len(p)} params for {n} records")
+    return recs, boxes, labels, diff, p
+
+
+def _into_pinned(ctx, n, strides, out_ptrs, stream, launch):
+    """launch(ptrs) with one output address per stride.  With out_ptrs those, and None comes back (the call
+    stays as asynchronous as launch leaves it); without, pinned device-mapped buffers of n items each, filled
+    with 0xCD beforehand, read back as uint8 arrays after a synchronize and freed."""
+    if out_ptrs is not None:
+        launch(out_ptrs)
+        return None
+    own = []
+    try:
+        for s in strides:
+            q = ctypes.c_void_p()
+            _check(lib().aeon_hip_host_alloc(max(n * s, 16), ctypes.byref(q)))
+            own.append(q)
+            ctypes.memset(q, 0xCD, max(n * s, 16))
+        launch([q.value for q in own])
+        ctx.synchronize(stream)
+        return [np.frombuffer(ctypes.string_at(q, n * s), np.uint8).copy() for q, s in zip(own, strides)]
+    finally:
+        for q in own:
+            lib().aeon_hip_host_free(q)
+
+
+def box_targets(ctx, records, params, kind=BOX_SSD, max_boxes=64, out_w=0, out_h=0, emit=(EMIT_NONE, 0.0),
+                item_bytes=None, out_ptrs=None, stream=0):
+    """aeon_hip_box_targets_batch for len(records) records: records[i] = a box_extract() dict or a
+    (boxes n x 4, labels, difficult) tuple, params[i] = the AugParams of the record's image, emit = the
+    factory's ParamFactory.emit().  Without out_ptrs the kernel stores into pinned device-mapped buffers
+    filled with 0xCD beforehand, and the result comes back as numpy arrays: BOX_BOUNDINGBOX one float32
+    array (n, item_bytes / 4) (item_bytes: aeon's max_bbox_count * 16 * sizeof(output_type), default
+    float), BOX_SSD a dict of the five outputs by aeon's names.  With out_ptrs (device addresses, one per
+    output) the call is left asynchronous on `stream` and returns None."""
+    n = len(records)
+    recs, boxes, labels, diff, p = _pack_box_call(records, params)
     if kind == BOX_SSD:
         strides = [8, max_boxes * 16, 4, max_boxes * 4, max_boxes * 4]
     else:
         strides = [item_bytes if item_bytes is not None else max_boxes * 16 * 4]
     o = BoxOut(kind=kind, max_boxes=max_boxes, out_w=out_w, out_h=out_h, emit_type=emit[0], emit_min_overlap=emit[1])
-    own = []
-    try:
-        for k, s in enumerate(strides):
-            o.item_stride[k] = s
-            if out_ptrs is not None:
-                o.buf[k] = out_ptrs[k]
-            else:
-                q = ctypes.c_void_p()
-                _check(lib().aeon_hip_host_alloc(max(n * s, 16), ctypes.byref(q)))
-                own.append(q)
-                ctypes.memset(q, 0xCD, max(n * s, 16))
-                o.buf[k] = q.value
+    for k, s in enumerate(strides):
+        o.item_stride[k] = s
+
+    def launch(ptrs):
+        for k in range(len(strides)):
+            o.buf[k] = ptrs[k]
         fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
         _check(lib().aeon_hip_box_targets_batch(ctx._h, n, recs, boxes.ctypes.data_as(fp), labels.ctypes.data_as(ip),
                                                 diff.ctypes.data_as(ip), p, ctypes.byref(o),
                                                 ctypes.c_void_p(stream or 0)))
-        if out_ptrs is not None:
-            return None
-        ctx.synchronize(stream)
-        outs = [np.frombuffer(ctypes.string_at(q, n * s), np.uint8).copy() for q, s in zip(own, strides)]
-    finally:
-        for q in own:
-            lib().aeon_hip_host_free(q)
+
+    outs = _into_pinned(ctx, n, strides, out_ptrs, stream, launch)
+    if outs is None:
+        return None
     if kind != BOX_SSD:
         return outs[0].view(np.float32).reshape(n, -1)
     res = {"image_shape": outs[0].view(np.int32).reshape(n, 2), "gt_boxes": outs[1].view(np.float32).reshape(n, max_boxes, 4),
@@ -469,23 +491,7 @@ class RcnnCall:
         self.ctx, self.info, self.anchors = ctx, info, rcnn_anchors(config)
         self.n = n = len(records)
         A, m = int(info["total_anchors"]), info["max_gt_boxes"]
-        self.recs = (BoxRecord * max(n, 1))()
-        bx, lb, df = [], [], []
-        first = 0
-        for i, r in enumerate(records):
-            b, l, d = (r["boxes"], r["labels"], r["difficult"]) if isinstance(r, dict) else r
-            b = np.asarray(b, np.float32).reshape(-1, 4)
-            self.recs[i] = BoxRecord(first, len(b))
-            bx.append(b), lb.append(np.asarray(l, np.int32).reshape(-1)), df.append(np.asarray(d, np.int32).reshape(-1))
-            if not len(b) == len(lb[-1]) == len(df[-1]):
-                raise ValueError(f"record {i}: {len(b)} boxes, {len(lb[-1])} labels, {len(df[-1])} difficult flags")
-            first += len(b)
-        self.boxes = np.ascontiguousarray(np.concatenate(bx) if bx else np.zeros((0, 4), np.float32))
-        self.labels = np.ascontiguousarray(np.concatenate(lb) if lb else np.zeros(0, np.int32))
-        self.diff = np.ascontiguousarray(np.concatenate(df) if df else np.zeros(0, np.int32))
-        self.params = params if isinstance(params, ctypes.Array) else (AugParams * max(n, 1))(*params)
-        if len(self.params) < n:
-            raise ValueError(f"{len(self.params)} params for {n} records")
+        self.recs, self.boxes, self.labels, self.diff, self.params = _pack_box_call(records, params)
         self.strides = [16 * A, 16 * A, 8 * A, 8 * A, 8, 16 * m, 4, 4 * m, 4, 4 * m]
         self.shapes = [(4 * A,), (4 * A,), (1, 2 * A), (2 * A, 1), (2, 1), (m, 4), (1, 1), (m, 1), (1, 1), (m, 1)]
         self.dtypes = [np.float32, np.float32, np.int32, np.int32, np.int32, np.float32, np.int32, np.int32, np.float32,
@@ -528,24 +534,11 @@ def rcnn_targets(ctx, config, records, params, states=None, shuffle=True, emit=(
         if len(states) < n:
             raise ValueError(f"{len(states)} engine states for {n} records")
         st = np.ascontiguousarray(states[:n], np.uint32).copy()
-    own = []
-    try:
-        if out_ptrs is None:
-            for s in call.strides:
-                q = ctypes.c_void_p()
-                _check(lib().aeon_hip_host_alloc(max(n * s, 16), ctypes.byref(q)))
-                own.append(q)
-                ctypes.memset(q, 0xCD, max(n * s, 16))
-        call.launch(out_ptrs if out_ptrs is not None else [q.value for q in own], st, shuffle, stream)
-        if st is not None:
-            states[:n] = st
-        if out_ptrs is not None:
-            return None
-        ctx.synchronize(stream)
-        outs = [np.frombuffer(ctypes.string_at(q, n * s), np.uint8).copy() for q, s in zip(own, call.strides)]
-    finally:
-        for q in own:
-            lib().aeon_hip_host_free(q)
+    outs = _into_pinned(ctx, n, call.strides, out_ptrs, stream, lambda ptrs: call.launch(ptrs, st, shuffle, stream))
+    if st is not None:
+        states[:n] = st
+    if outs is None:
+        return None
     return {name: a.view(dt).reshape((n,) + sh) for name, a, dt, sh in zip(RCNN_OUTPUTS, outs, call.dtypes, call.shapes)}
 
 

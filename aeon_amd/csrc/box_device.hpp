@@ -1,6 +1,6 @@
 // box_device.hpp -- boundingbox::transformer::transform_box (src/etl_boundingbox.cpp:146-261) for one box on
-// the device, shared by the box kernels (box_kernels.hip) and the localization_rcnn targets
-// (rcnn_kernels.hip).  Float32, every operation rounded once and in aeon's order: the including file is
+// the device and a wave's loop over a record's boxes, shared by the box kernels (box_kernels.hip) and the
+// localization_rcnn targets (rcnn_kernels.hip).  Float32, every operation rounded once and in aeon's order: the including file is
 // built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,6 +70,32 @@ __device__ inline bool transform_box(const BoxRec& r, int emit_type, float emit_
     b.z = (xmax + 1.0f) * xs - 1.0f;
     b.w = (ymax + 1.0f) * ys - 1.0f;
     return true;
+}
+
+// One wave (every lane calls this) over `count` boxes of record r, 64 at a time: each lane transforms its
+// box, and the kept ones are numbered in input order with a ballot and the popcount of the lower lanes on top
+// of a wave-uniform running count.  The lane of kept box i calls store(slot, i, b), whatever the slot; the
+// slots from the kept count up to max_out get pad(slot).  Returns the number of boxes kept (wave-uniform).
+template <typename Store, typename Pad>
+__device__ __forceinline__ int compact_boxes(const BoxRec& r, const float4* boxes, int count, int emit_type,
+                                             float emit_min_overlap, int max_out, int lane, Store store, Pad pad)
+{
+    int kept = 0;
+    for (int base = 0; base < count; base += 64) {
+        const int i    = base + lane;
+        bool      keep = false;
+        float4    b    = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < count) {
+            b    = boxes[i];
+            keep = transform_box(r, emit_type, emit_min_overlap, b);
+        }
+        const unsigned long long mask = __ballot(keep);
+        const int slot = kept + __popcll(mask & ((1ull << lane) - 1ull));
+        if (keep) store(slot, i, b);
+        kept += __popcll(mask);
+    }
+    for (int s = (kept < max_out ? kept : max_out) + lane; s < max_out; s += 64) pad(s);
+    return kept;
 }
 
 } // namespace aeon_hip

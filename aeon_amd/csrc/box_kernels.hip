@@ -32,28 +32,19 @@ __global__ __launch_bounds__(256) void box_targets(BoxLaunch L)
     const int lane = threadIdx.x & 63;
     const int rec  = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (rec >= L.n) return; // the whole wave leaves: no barrier anywhere below
-    const BoxRec   r     = L.recs[rec];
-    const float4*  boxes = (const float4*)L.boxes + r.first;
-    const int32_t* lab   = L.labels + r.first;
-    const int32_t* dif   = L.difficult + r.first;
-    const bool     ssd   = L.kind == AEON_BOX_SSD;
-    const int      bi    = ssd ? 1 : 0; // the boxes' buffer
+    const BoxRec   r   = L.t.recs[rec];
+    const int32_t* lab = L.t.labels + r.first;
+    const int32_t* dif = L.t.difficult + r.first;
+    const bool     ssd = L.kind == AEON_BOX_SSD;
+    const int      bi  = ssd ? 1 : 0; // the boxes' buffer
     float4*  out_box = (float4*)(L.buf[bi] + (uint64_t)rec * L.stride[bi]);
     int32_t* out_cls = ssd ? (int32_t*)(L.buf[3] + (uint64_t)rec * L.stride[3]) : nullptr;
     int32_t* out_dif = ssd ? (int32_t*)(L.buf[4] + (uint64_t)rec * L.stride[4]) : nullptr;
 
-    int kept = 0; // wave-uniform
-    for (int base = 0; base < r.count; base += 64) {
-        const int i    = base + lane;
-        bool      keep = false;
-        float4    b    = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < r.count) {
-            b    = boxes[i];
-            keep = transform_box(r, L.emit_type, L.emit_min_overlap, b);
-        }
-        const unsigned long long mask = __ballot(keep);
-        const int slot = kept + __popcll(mask & ((1ull << lane) - 1ull));
-        if (keep && slot < L.max_boxes) {
+    const int kept = compact_boxes(
+        r, (const float4*)L.t.boxes + r.first, r.count, L.emit_type, L.emit_min_overlap, L.max_boxes, lane,
+        [&](int slot, int i, float4 b) {
+            if (slot >= L.max_boxes) return;
             if (ssd) { // bbox::normalize (boundingbox.cpp:150-156)
                 b.x = b.x / L.norm_w;
                 b.y = b.y / L.norm_h;
@@ -63,20 +54,17 @@ __global__ __launch_bounds__(256) void box_targets(BoxLaunch L)
                 out_dif[slot] = dif[i] != 0 ? 1 : 0;
             }
             out_box[slot] = b;
-        }
-        kept += __popcll(mask);
-    }
-    const int filled = kept < L.max_boxes ? kept : L.max_boxes;
-    for (int s = filled + lane; s < L.max_boxes; s += 64) {
-        out_box[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ssd) out_cls[s] = 0, out_dif[s] = 0;
-    }
+        },
+        [&](int s) {
+            out_box[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ssd) out_cls[s] = 0, out_dif[s] = 0;
+        });
     if (ssd) {
         if (lane == 0) {
             int32_t* shape = (int32_t*)(L.buf[0] + (uint64_t)rec * L.stride[0]);
             shape[0] = L.shape_w;
             shape[1] = L.shape_h;
-            *(int32_t*)(L.buf[2] + (uint64_t)rec * L.stride[2]) = filled;
+            *(int32_t*)(L.buf[2] + (uint64_t)rec * L.stride[2]) = kept < L.max_boxes ? kept : L.max_boxes;
         }
     } else {
         // aeon's item is max_bbox_count x 16 elements of output_type, of which the loader writes the

@@ -282,7 +282,6 @@ struct box_config {
     int64_t                              height = 0, width = 0, max_boxes = 64;
     std::vector<std::string>             class_names;
     std::string                          name, output_type_name = "float";
-    std::unordered_map<std::string, int> label_map;
     std::vector<shape_type>              shapes;
 
     box_config(const Json& js, int kind_) : kind(kind_)
@@ -315,7 +314,6 @@ struct box_config {
             if (max_boxes <= 0) invalid("invalid max_bbox_count");
         }
         if (max_boxes > (1 << 24) || width > (1 << 30) || height > (1 << 30)) invalid("box config out of range");
-        label_map = box_label_map(class_names);
         auto add = [&](std::vector<size_t> s, const char* t) {
             shape_type st;
             st.shape = std::move(s);
@@ -337,20 +335,12 @@ struct box_config {
     }
 };
 
-// provider::boundingbox (provider.cpp:395-439) and provider::localization::ssd (provider.cpp:289-346):
-// extract the record's JSON metadata, draw (make_params / make_ssd_params over the extracted boxes)
-// when the record has no params yet; transform + load run in the window's box launch (post_process).
-class box_provider : public etl_provider {
+// What the box providers share: their element is the record's JSON metadata (extract), the first element of a
+// record draws (provide_boxes: make_params over the metadata's image size unless a provider draws otherwise),
+// and the transform + load run in the window's targets launch over the provider's box table (box_job.hpp),
+// staged in the arena with the pixels.
+class box_provider_base : public etl_provider {
 public:
-    box_provider(const Json& js, const Json& aug, int kind) : m_cfg(js, kind), m_factory(aug)
-    {
-        static const char* const ssd_names[5] = {"image_shape", "gt_boxes", "gt_box_count", "gt_class_count",
-                                                 "difficult_flag"};
-        if (kind == AEON_BOX_SSD)
-            for (const char* n : ssd_names) m_names.push_back(create_name(m_cfg.name, n));
-        else
-            m_names.push_back(create_name(m_cfg.name, "boundingbox"));
-    }
     void provide(int, const decoded_element&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
                  light_split*) const override
     {
@@ -358,113 +348,13 @@ public:
     }
     void extract(const decoded_element& in, box_metadata& m) const override
     {
-        box_extract(m_cfg.label_map, in.data, in.size, m);
+        box_extract(m_label_map, in.data, in.size, m);
     }
     void provide_boxes(const box_metadata& m, augmentation& aug, std::minstd_rand0& random, aeon_aug_params& params,
                        light_split* ls) const override
     {
         if (!aug.has) {
-            const int W = (int)m_cfg.width, H = (int)m_cfg.height, nb = (int)m.labels.size();
-            if (m_cfg.kind == AEON_BOX_SSD) {
-                if (ls)
-                    m_factory.make_ssd_params_split(random, m.width, m.height, W, H, m.boxes.data(), nb, ls->entry_avail,
-                                                    &aug.image, &ls->exit_saved);
-                else
-                    m_factory.make_ssd_params(random, m.width, m.height, W, H, m.boxes.data(), nb, &aug.image);
-            } else {
-                if (ls)
-                    m_factory.make_params_split(random, m.width, m.height, W, H, ls->entry_avail, &aug.image,
-                                                &ls->exit_saved);
-                else
-                    m_factory.make_params(random, m.width, m.height, W, H, &aug.image);
-            }
-            aug.has = true;
-        }
-        params = aug.image;
-    }
-    const param_factory& factory() const override { return m_factory; }
-    bool               is_mask() const override { return false; }
-    const shape_type&  shape() const override { return m_cfg.shapes[0]; }
-    const std::string& buffer_name() const override { return m_names[0]; }
-    aeon_out_desc      out_desc() const override { return aeon_out_desc{}; }
-    std::vector<std::pair<std::string, shape_type>> output_shapes() const override
-    {
-        std::vector<std::pair<std::string, shape_type>> v;
-        for (size_t i = 0; i < m_names.size(); i++) v.emplace_back(m_names[i], m_cfg.shapes[i]);
-        return v;
-    }
-    int          box_kind() const override { return m_cfg.kind; }
-    aeon_box_out box_out() const override
-    {
-        aeon_box_out o{};
-        o.kind      = m_cfg.kind;
-        o.max_boxes = (int)m_cfg.max_boxes;
-        o.out_w = (int)m_cfg.width, o.out_h = (int)m_cfg.height;
-        // param_factory::emit_constraint_type, lower-cased and validated by the factory
-        const std::string& e = m_factory.emit_constraint_type;
-        o.emit_type          = e == "center" ? AEON_EMIT_CENTER : e == "min_overlap" ? AEON_EMIT_MIN_OVERLAP : AEON_EMIT_NONE;
-        o.emit_min_overlap   = m_factory.emit_constraint_min_overlap;
-        for (size_t i = 0; i < m_cfg.shapes.size(); i++) o.item_stride[i] = m_cfg.shapes[i].byte_size();
-        return o;
-    }
-
-private:
-    box_config               m_cfg;
-    param_factory            m_factory;
-    std::vector<std::string> m_names;
-};
-
-// provider::localization::rcnn (provider.cpp:222-287): extract the record's JSON metadata, draw
-// make_params over its image size when the record has no params yet; transform, sample_anchors and load
-// run in the window's targets launch (post_process).  aeon reads the input size from a member of its
-// decoded type that nothing sets (etl_localization_rcnn.hpp:159); here it is the metadata's size, as
-// for boundingbox.
-class rcnn_provider : public etl_provider {
-public:
-    rcnn_provider(const Json& js, const Json& aug) : m_cfg(js), m_factory(aug)
-    {
-        if (m_cfg.total_anchors() > kRcnnMaxAnchors)
-            throw unsupported_error("localization_rcnn: total_anchors " + std::to_string(m_cfg.total_anchors()) +
-                                    " above this build's 65536");
-        if (m_cfg.rois_per_image > kRcnnMaxRois)
-            throw unsupported_error("localization_rcnn: rois_per_image above this build's 1024");
-        m_label_map = box_label_map(m_cfg.class_names);
-        m_anchors   = rcnn_generate_anchors(m_cfg);
-        static std::atomic<uint64_t> next_key{1}; // one key per table of this process
-        m_anchors_key = next_key.fetch_add(1);
-        const size_t A = (size_t)m_cfg.total_anchors(), m = (size_t)m_cfg.max_gt_boxes;
-        auto add = [&](const char* name, std::vector<size_t> s, const char* t) {
-            shape_type st;
-            st.shape = std::move(s);
-            st.otype = output_type(t);
-            m_shapes.emplace_back(create_name(m_cfg.name, name), st);
-        };
-        add("bbtargets", {A * 4}, "float");
-        add("bbtargets_mask", {A * 4}, "float");
-        add("labels_flat", {1, A * 2}, "int32_t");
-        add("labels_mask", {A * 2, 1}, "int32_t");
-        add("image_shape", {2, 1}, "int32_t");
-        add("gt_boxes", {m, 4}, "float");
-        add("gt_box_count", {1, 1}, "int32_t");
-        add("gt_class_count", {m, 1}, "int32_t");
-        add("image_scale", {1, 1}, "float");
-        add("difficult_flag", {m, 1}, "int32_t");
-    }
-    void provide(int, const decoded_element&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
-                 light_split*) const override
-    {
-        throw std::logic_error("box providers take their element through provide_boxes");
-    }
-    void extract(const decoded_element& in, box_metadata& m) const override { box_extract(m_label_map, in.data, in.size, m); }
-    void provide_boxes(const box_metadata& m, augmentation& aug, std::minstd_rand0& random, aeon_aug_params& params,
-                       light_split* ls) const override
-    {
-        if (!aug.has) {
-            const int W = (int)m_cfg.width, H = (int)m_cfg.height;
-            if (ls)
-                m_factory.make_params_split(random, m.width, m.height, W, H, ls->entry_avail, &aug.image, &ls->exit_saved);
-            else
-                m_factory.make_params(random, m.width, m.height, W, H, &aug.image);
+            draw(m, random, aug.image, ls);
             aug.has = true;
         }
         params = aug.image;
@@ -475,33 +365,164 @@ public:
     const std::string& buffer_name() const override { return m_shapes[0].first; }
     aeon_out_desc      out_desc() const override { return aeon_out_desc{}; }
     std::vector<std::pair<std::string, shape_type>> output_shapes() const override { return m_shapes; }
-    int           box_kind() const override { return AEON_BOX_RCNN; }
-    aeon_rcnn_out rcnn_out() const override
+    size_t box_table_bytes(int n, size_t total) const override { return aeon_hip::box_table_bytes(n, total, m_ext); }
+    void   stage_boxes(decode_window& w, size_t k) const override
+    {
+        const BoxTableHost t(w.arena + w.box_offset[k], w.n, w.box_total[k], m_ext);
+        size_t             first = 0;
+        for (int i = 0; i < w.n; i++) {
+            stage_record(t, i, first, w.boxes[k][i], w.params[k][i], w);
+            first += w.boxes[k][i].labels.size();
+        }
+    }
+
+protected:
+    box_provider_base(const Json& aug, size_t width, size_t height, const std::vector<std::string>& class_names, bool ext)
+        : m_factory(aug), m_width((int)width), m_height((int)height), m_label_map(box_label_map(class_names)), m_ext(ext)
+    {
+    }
+    void add_output(const std::string& name, const char* base, std::vector<size_t> shape, const std::string& type)
+    {
+        shape_type st;
+        st.shape = std::move(shape);
+        st.otype = output_type(type);
+        m_shapes.emplace_back(create_name(name, base), st);
+    }
+    virtual void draw(const box_metadata& m, std::minstd_rand0& random, aeon_aug_params& p, light_split* ls) const
+    {
+        if (ls) m_factory.make_params_split(random, m.width, m.height, m_width, m_height, ls->entry_avail, &p, &ls->exit_saved);
+        else m_factory.make_params(random, m.width, m.height, m_width, m_height, &p);
+    }
+    // record i of the window, whose boxes start at `first` of the table's: refused, or written into t
+    virtual void stage_record(const BoxTableHost& t, int i, size_t first, const box_metadata& m, const aeon_aug_params& p,
+                              const decode_window&) const
+    {
+        const int cnt = (int)m.labels.size();
+        if (const char* why = box_refusal(p, m.boxes.data(), cnt)) invalid(std::string(why) + ", at idx " + std::to_string(i));
+        t.recs[i] = box_rec((uint32_t)first, cnt, p);
+        if (cnt) {
+            std::memcpy(t.boxes + 4 * first, m.boxes.data(), sizeof(float) * 4 * (size_t)cnt);
+            std::memcpy(t.labels + first, m.labels.data(), sizeof(int32_t) * (size_t)cnt);
+            std::memcpy(t.difficult + first, m.difficult.data(), sizeof(int32_t) * (size_t)cnt);
+        }
+    }
+    param_factory                                   m_factory;
+    int                                             m_width, m_height; // the config's: what the params are drawn for
+    std::unordered_map<std::string, int>            m_label_map;
+    bool                                            m_ext; // the table carries the rcnn extension
+    std::vector<std::pair<std::string, shape_type>> m_shapes;
+};
+
+// provider::boundingbox (provider.cpp:395-439) and provider::localization::ssd (provider.cpp:289-346);
+// localization_ssd draws make_ssd_params over the extracted boxes.
+class box_provider : public box_provider_base {
+public:
+    box_provider(const Json& js, const Json& aug, int kind) : box_provider(box_config(js, kind), aug) {}
+    void draw(const box_metadata& m, std::minstd_rand0& random, aeon_aug_params& p, light_split* ls) const override
+    {
+        if (m_cfg.kind != AEON_BOX_SSD) return box_provider_base::draw(m, random, p, ls);
+        const int nb = (int)m.labels.size();
+        if (ls)
+            m_factory.make_ssd_params_split(random, m.width, m.height, m_width, m_height, m.boxes.data(), nb, ls->entry_avail,
+                                            &p, &ls->exit_saved);
+        else
+            m_factory.make_ssd_params(random, m.width, m.height, m_width, m_height, m.boxes.data(), nb, &p);
+    }
+    int  box_kind() const override { return m_cfg.kind; }
+    void launch_boxes(aeon_hip_ctx* ctx, decode_window& w, size_t k, const uint8_t* dev_table, void* const* out,
+                      void* stream) const override
+    {
+        aeon_box_out o{};
+        o.kind      = m_cfg.kind;
+        o.max_boxes = (int)m_cfg.max_boxes;
+        o.out_w = m_width, o.out_h = m_height;
+        o.emit_type = m_factory.emit_type(), o.emit_min_overlap = m_factory.emit_constraint_min_overlap;
+        for (size_t i = 0; i < m_shapes.size(); i++) o.item_stride[i] = m_shapes[i].second.byte_size(), o.buf[i] = out[i];
+        check(box_targets_staged(ctx, w.n, dev_table, w.box_total[k], o, stream));
+    }
+
+private:
+    box_provider(box_config cfg, const Json& aug)
+        : box_provider_base(aug, cfg.width, cfg.height, cfg.class_names, false), m_cfg(std::move(cfg))
+    {
+        static const char* const ssd_names[5] = {"image_shape", "gt_boxes", "gt_box_count", "gt_class_count",
+                                                 "difficult_flag"};
+        if (m_cfg.kind == AEON_BOX_SSD)
+            for (size_t i = 0; i < 5; i++) m_shapes.emplace_back(create_name(m_cfg.name, ssd_names[i]), m_cfg.shapes[i]);
+        else
+            m_shapes.emplace_back(create_name(m_cfg.name, "boundingbox"), m_cfg.shapes[0]);
+    }
+    box_config m_cfg;
+};
+
+// provider::localization::rcnn (provider.cpp:222-287): make_params over the record's image size; transform,
+// sample_anchors and load run in the window's targets launch.  aeon reads the input size from a member of
+// its decoded type that nothing sets (etl_localization_rcnn.hpp:159); here it is the metadata's size, as
+// for boundingbox.
+class rcnn_provider : public box_provider_base {
+public:
+    rcnn_provider(const Json& js, const Json& aug) : rcnn_provider(rcnn_config(js), aug) {}
+    int  box_kind() const override { return AEON_BOX_RCNN; }
+    void stage_record(const BoxTableHost& t, int i, size_t first, const box_metadata& m, const aeon_aug_params& p,
+                      const decode_window& w) const override
+    {
+        if (m.labels.size() > (size_t)kRcnnMaxBoxes)
+            throw unsupported_error("localization_rcnn: more than 1024 boxes in a record, at idx " + std::to_string(i));
+        t.ext[i] = rcnn_rec(p, m_factory.fixed_scaling_factor, m_width, m_height, w.rcnn_engine[i]);
+        box_provider_base::stage_record(t, i, first, m, p, w);
+    }
+    void launch_boxes(aeon_hip_ctx* ctx, decode_window& w, size_t k, const uint8_t* dev_table, void* const* out,
+                      void* stream) const override
     {
         aeon_rcnn_out o{};
         o.total_anchors  = (int32_t)m_cfg.total_anchors();
         o.max_gt_boxes   = (int32_t)m_cfg.max_gt_boxes;
         o.rois_per_image = (int32_t)m_cfg.rois_per_image;
         o.num_fg         = m_cfg.num_fg();
-        o.width = (int32_t)m_cfg.width, o.height = (int32_t)m_cfg.height;
-        const std::string& e = m_factory.emit_constraint_type;
-        o.emit_type          = e == "center" ? AEON_EMIT_CENTER : e == "min_overlap" ? AEON_EMIT_MIN_OVERLAP : AEON_EMIT_NONE;
-        o.emit_min_overlap   = m_factory.emit_constraint_min_overlap;
+        o.width = m_width, o.height = m_height;
+        o.emit_type = m_factory.emit_type(), o.emit_min_overlap = m_factory.emit_constraint_min_overlap;
         o.negative_overlap = m_cfg.negative_overlap, o.positive_overlap = m_cfg.positive_overlap;
         o.fixed_scaling_factor = m_factory.fixed_scaling_factor;
         o.anchors              = m_anchors.data();
         o.anchors_key          = m_anchors_key;
-        for (size_t i = 0; i < m_shapes.size(); i++) o.item_stride[i] = m_shapes[i].second.byte_size();
-        return o;
+        for (size_t i = 0; i < m_shapes.size(); i++) o.item_stride[i] = m_shapes[i].second.byte_size(), o.buf[i] = out[i];
+        check(rcnn_targets_staged(ctx, w.n, dev_table, w.box_total[k], o, 1, w.rcnn_states_dev, stream));
+        if (w.rcnn_states_dev) { // the engines' end states, right behind the kernel
+            hip_check(hipMemcpyAsync(w.rcnn_states_host, w.rcnn_states_dev, (size_t)w.n * sizeof(uint32_t),
+                                     hipMemcpyDeviceToHost, (hipStream_t)stream),
+                      "hipMemcpyAsync");
+            hip_check(hipEventRecord(w.rcnn_states_done, (hipStream_t)stream), "hipEventRecord");
+            w.rcnn_states_queued = true;
+        }
     }
 
 private:
-    rcnn_config                                     m_cfg;
-    param_factory                                   m_factory;
-    std::unordered_map<std::string, int>            m_label_map;
-    std::vector<float>                              m_anchors;
-    uint64_t                                        m_anchors_key = 0;
-    std::vector<std::pair<std::string, shape_type>> m_shapes;
+    rcnn_provider(rcnn_config cfg, const Json& aug)
+        : box_provider_base(aug, cfg.width, cfg.height, cfg.class_names, true), m_cfg(std::move(cfg))
+    {
+        if (m_cfg.total_anchors() > kRcnnMaxAnchors)
+            throw unsupported_error("localization_rcnn: total_anchors " + std::to_string(m_cfg.total_anchors()) +
+                                    " above this build's 65536");
+        if (m_cfg.rois_per_image > kRcnnMaxRois)
+            throw unsupported_error("localization_rcnn: rois_per_image above this build's 1024");
+        m_anchors = rcnn_generate_anchors(m_cfg);
+        static std::atomic<uint64_t> next_key{1}; // one key per table of this process
+        m_anchors_key = next_key.fetch_add(1);
+        const size_t A = (size_t)m_cfg.total_anchors(), m = (size_t)m_cfg.max_gt_boxes;
+        add_output(m_cfg.name, "bbtargets", {A * 4}, "float");
+        add_output(m_cfg.name, "bbtargets_mask", {A * 4}, "float");
+        add_output(m_cfg.name, "labels_flat", {1, A * 2}, "int32_t");
+        add_output(m_cfg.name, "labels_mask", {A * 2, 1}, "int32_t");
+        add_output(m_cfg.name, "image_shape", {2, 1}, "int32_t");
+        add_output(m_cfg.name, "gt_boxes", {m, 4}, "float");
+        add_output(m_cfg.name, "gt_box_count", {1, 1}, "int32_t");
+        add_output(m_cfg.name, "gt_class_count", {m, 1}, "int32_t");
+        add_output(m_cfg.name, "image_scale", {1, 1}, "float");
+        add_output(m_cfg.name, "difficult_flag", {m, 1}, "int32_t");
+    }
+    rcnn_config        m_cfg;
+    std::vector<float> m_anchors;
+    uint64_t           m_anchors_key = 0;
 };
 
 } // namespace
@@ -644,23 +665,7 @@ void provider_base::post_process(aeon_hip_ctx* ctx, decode_window& w, const uint
         const etl_provider& p = *m_providers[k];
         void* const*        out = outputs + m_out_first[k];
         if (p.box_kind() >= 0) { // the window's box launch, over the table staged with the pixels
-            if (p.box_kind() == AEON_BOX_RCNN) {
-                aeon_rcnn_out ro = p.rcnn_out();
-                for (int j = 0; j < 10; j++) ro.buf[j] = out[j];
-                check(rcnn_targets_staged(ctx, w.n, dev_arena + w.box_offset[k], w.box_total[k], ro, 1, w.rcnn_states_dev,
-                                          stream));
-                if (w.rcnn_states_dev) { // the engines' end states, right behind the kernel
-                    hip_check(hipMemcpyAsync(w.rcnn_states_host, w.rcnn_states_dev, (size_t)w.n * sizeof(uint32_t),
-                                             hipMemcpyDeviceToHost, (hipStream_t)stream),
-                              "hipMemcpyAsync");
-                    hip_check(hipEventRecord(w.rcnn_states_done, (hipStream_t)stream), "hipEventRecord");
-                    w.rcnn_states_queued = true;
-                }
-                continue;
-            }
-            aeon_box_out bo = p.box_out();
-            for (int j = 0; j < m_out_first[k + 1] - m_out_first[k]; j++) bo.buf[j] = out[j];
-            check(box_targets_staged(ctx, w.n, dev_arena + w.box_offset[k], w.box_total[k], bo, stream));
+            p.launch_boxes(ctx, w, k, dev_arena + w.box_offset[k], out, stream);
             continue;
         }
         aeon_out_desc o = p.out_desc();
@@ -682,45 +687,26 @@ size_t provider_base::layout_boxes(decode_window& w, size_t offset) const
         if (total > ((size_t)1 << 26)) invalid("box table too large");
         w.box_offset[k] = offset;
         w.box_total[k]  = total;
-        const bool rcnn = m_providers[k]->box_kind() == AEON_BOX_RCNN;
-        offset += ((rcnn ? rcnn_table_bytes(w.n, total) : box_table_bytes(w.n, total)) + 15) & ~(size_t)15;
+        offset += (m_providers[k]->box_table_bytes(w.n, total) + 15) & ~(size_t)15;
     }
     return offset;
 }
 
 void provider_base::stage_boxes(decode_window& w) const
 {
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        if (m_providers[k]->box_kind() < 0) continue;
-        const size_t total = w.box_total[k];
-        uint8_t*     t     = w.arena + w.box_offset[k];
-        BoxRec*      R     = (BoxRec*)t;
-        float*       bx    = (float*)(t + box_rec_bytes(w.n));
-        int32_t*     lb    = (int32_t*)(t + box_rec_bytes(w.n) + total * 16);
-        int32_t*     df    = (int32_t*)(t + box_rec_bytes(w.n) + total * 20);
-        size_t       first = 0;
-        const bool   rcnn  = m_providers[k]->box_kind() == AEON_BOX_RCNN;
-        RcnnRec*     X     = rcnn ? (RcnnRec*)(t + rcnn_ext_offset(w.n, total)) : nullptr;
-        const aeon_rcnn_out ro = rcnn ? m_providers[k]->rcnn_out() : aeon_rcnn_out{};
-        for (int i = 0; i < w.n; i++) {
-            const box_metadata& m   = w.boxes[k][i];
-            const int           cnt = (int)m.labels.size();
-            if (rcnn) {
-                if (cnt > kRcnnMaxBoxes)
-                    throw unsupported_error("localization_rcnn: more than 1024 boxes in a record, at idx " + std::to_string(i));
-                X[i] = rcnn_rec(w.params[k][i], ro.fixed_scaling_factor, ro.width, ro.height, w.rcnn_engine[i]);
-            }
-            if (const char* why = box_refusal(w.params[k][i], m.boxes.data(), cnt))
-                invalid(std::string(why) + ", at idx " + std::to_string(i));
-            R[i] = box_rec((uint32_t)first, cnt, w.params[k][i]);
-            if (cnt) {
-                std::memcpy(bx + 4 * first, m.boxes.data(), sizeof(float) * 4 * (size_t)cnt);
-                std::memcpy(lb + first, m.labels.data(), sizeof(int32_t) * (size_t)cnt);
-                std::memcpy(df + first, m.difficult.data(), sizeof(int32_t) * (size_t)cnt);
-            }
-            first += (size_t)cnt;
-        }
-    }
+    for (size_t k = 0; k < m_providers.size(); k++)
+        if (m_providers[k]->box_kind() >= 0) m_providers[k]->stage_boxes(w, k);
+}
+
+decode_window provider_base::new_window(int n) const
+{
+    decode_window w;
+    w.n = n;
+    w.params.assign(m_providers.size(), std::vector<aeon_aug_params>(n));
+    w.boxes.resize(m_providers.size());
+    for (size_t k = 0; k < m_providers.size(); k++)
+        if (m_providers[k]->box_kind() >= 0) w.boxes[k].resize(n);
+    return w;
 }
 
 std::shared_ptr<provider_base> provider_factory::create(const Json& config)
@@ -1077,14 +1063,9 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
             e.channels = cn;
             e.stride   = e.width * e.channels;
         }
-    decode_window w;
-    w.n = n;
+    decode_window w = m_provider->new_window(n);
     w.descs.assign(ne, std::vector<aeon_img_desc>(n));
-    w.params.assign(ne, std::vector<aeon_aug_params>(n));
     w.offset.assign(ne, std::vector<size_t>(n));
-    w.boxes.resize(ne);
-    for (int k = 0; k < ne; k++)
-        if (m_provider->providers()[k]->box_kind() >= 0) w.boxes[k].resize(n);
     // batch_decoder::process: the slot engine of record i draws its params (deterministic mode
     // swaps the slot engine in and out, batch_decoder.cpp:62-71).  With slot engines the draws run
     // on the pool (draw_window: aeon's in-order params exactly), and with them the extraction of the
@@ -1236,12 +1217,7 @@ void batch_decoder::draw_params(int n, const decoded_element* records, aeon_aug_
     if (n <= 0) return;
     const int ne = (int)m_provider->get_input_count();
     if (m_deterministic) grow_slot_engines(n);
-    decode_window w;
-    w.n = n;
-    w.params.assign(ne, std::vector<aeon_aug_params>(n));
-    w.boxes.resize(ne);
-    for (int k = 0; k < ne; k++)
-        if (m_provider->providers()[k]->box_kind() >= 0) w.boxes[k].resize(n);
+    decode_window w = m_provider->new_window(n);
     if (m_deterministic && !serial) {
         m_provider->draw_window(n, records, w, m_random, *m_pool);
     } else {

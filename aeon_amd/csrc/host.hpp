@@ -151,19 +151,22 @@ public:
     {
         return {{buffer_name(), shape()}};
     }
-    // box providers (boundingbox, localization_ssd): AEON_BOX_*; -1 for pixel providers.  Their element
-    // is the record's JSON metadata: extract() parses it, provide_boxes() is provide() with it (the
-    // first element of a record draws: localization_ssd make_ssd_params over the extracted boxes,
-    // boundingbox make_params), box_out() the box call's description without its buffers.
+    // box providers (boundingbox, localization_ssd, localization_rcnn): AEON_BOX_*; -1 for pixel providers.
+    // Their element is the record's JSON metadata: extract() parses it, provide_boxes() is provide() with
+    // it (the first element of a record draws: localization_ssd make_ssd_params over the extracted boxes,
+    // the others make_params).  The window's box table of provider k (box_job.hpp) takes
+    // box_table_bytes(n, total) of the arena at w.box_offset[k]; stage_boxes() writes it there and makes the
+    // host-side refusals; launch_boxes() queues the targets launch over its device copy into out[] (the
+    // provider's output buffers), and for localization_rcnn the engine states' copy back and its event.
     virtual int  box_kind() const { return -1; }
     virtual void extract(const decoded_element&, box_metadata&) const {}
     virtual void provide_boxes(const box_metadata&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
                                light_split* = nullptr) const
     {
     }
-    virtual aeon_box_out box_out() const { return aeon_box_out{}; }
-    // AEON_BOX_RCNN: the targets call's description without its buffers
-    virtual aeon_rcnn_out rcnn_out() const { return aeon_rcnn_out{}; }
+    virtual size_t box_table_bytes(int, size_t) const { return 0; }
+    virtual void   stage_boxes(decode_window&, size_t) const {}
+    virtual void   launch_boxes(aeon_hip_ctx*, decode_window&, size_t, const uint8_t*, void* const*, void*) const {}
 };
 
 class provider_base : public provider_interface {
@@ -194,6 +197,8 @@ public:
     // makes the host-side refusals: rotation, boundingbox::box::expand's precondition)
     size_t layout_boxes(decode_window& w, size_t offset) const;
     void   stage_boxes(decode_window& w) const;
+    // a window of n records for draw(): params and, for the box providers, metadata per record
+    decode_window new_window(int n) const;
 
 private:
     std::vector<std::unique_ptr<etl_provider>> m_providers;
@@ -325,7 +330,7 @@ void ctx_share_pool(aeon_hip_ctx* ctx, thread_pool* pool);
 // refusals (box_refusal) are the caller's to make while it stages.
 int box_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t total, const aeon_box_out& out,
                         void* stream);
-// aeon_hip_rcnn_targets_batch over a staged rcnn table (rcnn_job.hpp: the box table, then RcnnRec[n]);
+// aeon_hip_rcnn_targets_batch over a staged table with the rcnn extension (box_job.hpp: then RcnnRec[n]);
 // states_dev (n words, or null) receives the engines' states after the shuffles
 int rcnn_targets_staged(aeon_hip_ctx* ctx, int n, const void* dev_table, size_t total, const aeon_rcnn_out& out,
                         int shuffle, uint32_t* states_dev, void* stream);

@@ -144,8 +144,13 @@ private:
 public:
     std::vector<batch_sampler>                    batch_samplers;
     mutable std::uniform_real_distribution<float> expand_distribution{0.0f, 1.0f};
-    std::string                                   emit_constraint_type;
+    std::string                                   emit_constraint_type; // lower-cased and validated by the constructor
     float                                         emit_constraint_min_overlap = 0.0f;
+    int emit_type() const // emit_constraint_type as AEON_EMIT_*
+    {
+        const std::string& e = emit_constraint_type;
+        return e == "center" ? AEON_EMIT_CENTER : e == "min_overlap" ? AEON_EMIT_MIN_OVERLAP : AEON_EMIT_NONE;
+    }
 };
 
 // ---- geometry helpers (src/image.cpp:108-273, src/util.cpp:212-239) ---------------------------

@@ -1,9 +1,6 @@
 // rcnn_job.hpp -- what the host (stage.cpp, host.cpp) and the device (rcnn_kernels.hip) share about one
-// localization_rcnn targets launch: the limits, the per-record extension of the box table and the
-// launch description.
-//
-// Device table of a call: the box table of box_job.hpp (BoxRec[n], boxes, labels, difficult flags),
-// padded to 16 bytes, then RcnnRec[n].
+// localization_rcnn targets launch: the limits, what fills the per-record extension of the box table
+// (box_job.hpp's RcnnRec) and the launch description.
 //
 // Limits (a config or record beyond them is AEON_HIP_EUNSUPPORTED, never a wrong answer).  The kernel
 // keeps a record's state in LDS: three bits per anchor (foreground, background, sampled) and a running
@@ -24,15 +21,6 @@ constexpr int kRcnnMaxAnchors = 65536;
 constexpr int kRcnnMaxBoxes   = 1024;
 constexpr int kRcnnMaxRois    = 1024;
 
-// Per record, next to its BoxRec: transformer::transform's image scale and scaled image size
-// (etl_localization_rcnn.cpp:101-118), and the minstd_rand0 state its shuffles start from.
-struct RcnnRec {
-    float    im_scale;
-    int32_t  im_w, im_h;
-    uint32_t engine;
-};
-static_assert(sizeof(RcnnRec) == 16, "RcnnRec is read as one 16-byte load");
-
 // host: transformer::transform's first lines for one record
 int   unbiased_round(float x);                         // param_factory.cpp
 float calculate_scale(int w, int h, int ow, int oh);   // param_factory.cpp
@@ -43,15 +31,8 @@ inline RcnnRec rcnn_rec(const aeon_aug_params& p, float fixed_scaling_factor, in
     return RcnnRec{im_scale, unbiased_round(p.crop_w * im_scale), unbiased_round(p.crop_h * im_scale), engine};
 }
 
-inline size_t rcnn_ext_offset(int n, size_t total) { return (box_table_bytes(n, total) + 15) & ~(size_t)15; }
-inline size_t rcnn_table_bytes(int n, size_t total) { return rcnn_ext_offset(n, total) + (size_t)n * sizeof(RcnnRec); }
-
 struct RcnnLaunch {
-    const BoxRec*  recs;
-    const float*   boxes; // 16-byte aligned, 4 floats per box
-    const int32_t* labels;
-    const int32_t* difficult;
-    const RcnnRec* ext;
+    BoxTableDev    t;          // with the extension
     const float*   anchors;    // 16-byte aligned, 4 floats per anchor (anchor::generate, uploaded once)
     uint32_t*      states_out; // n engine states after the shuffles, or null
     int32_t        n, total_anchors, max_gt_boxes, emit_type;

@@ -194,33 +194,23 @@ __global__ __launch_bounds__(kThreads) void rcnn_targets(RcnnLaunch L)
     if (A <= 0 || A > kRcnnMaxAnchors || L.rois_per_image < 0 || L.rois_per_image > kRcnnMaxRois || L.num_fg < 0 ||
         L.num_fg > L.rois_per_image)
         return;
-    const BoxRec  r       = L.recs[rec];
-    const RcnnRec x       = L.ext[rec];
+    const BoxRec  r       = L.t.recs[rec];
+    const RcnnRec x       = L.t.ext[rec];
     const int     nchunks = (A + 63) >> 6;
     const float4* anchors = (const float4*)L.anchors;
     const float   im_w = (float)x.im_w, im_h = (float)x.im_h;
 
     // ---- 0: gt boxes ----
     if (wave == 0) {
-        const float4*  boxes   = (const float4*)L.boxes + r.first;
-        const int32_t* lab     = L.labels + r.first;
-        const int32_t* dif     = L.difficult + r.first;
+        const int32_t* lab     = L.t.labels + r.first;
+        const int32_t* dif     = L.t.difficult + r.first;
         float4*        out_box = (float4*)(L.buf[5] + (uint64_t)rec * L.stride[5]);
         int32_t*       out_cls = (int32_t*)(L.buf[7] + (uint64_t)rec * L.stride[7]);
         int32_t*       out_dif = (int32_t*)(L.buf[9] + (uint64_t)rec * L.stride[9]);
-        const int      count   = r.count < kRcnnMaxBoxes ? r.count : kRcnnMaxBoxes;
-        int            kept    = 0; // wave-uniform
-        for (int base = 0; base < count; base += 64) {
-            const int i    = base + lane;
-            bool      keep = false;
-            float4    b    = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < count) {
-                b    = boxes[i];
-                keep = transform_box(r, L.emit_type, L.emit_min_overlap, b);
-            }
-            const unsigned long long mask = __ballot(keep);
-            const int slot = kept + __popcll(mask & ((1ull << lane) - 1ull));
-            if (keep) {
+        const int      kept    = compact_boxes(
+            r, (const float4*)L.t.boxes + r.first, r.count < kRcnnMaxBoxes ? r.count : kRcnnMaxBoxes, L.emit_type,
+            L.emit_min_overlap, L.max_gt_boxes, lane,
+            [&](int slot, int i, float4 b) {
                 s_gt[slot]     = b;
                 s_garea[slot]  = (b.z - b.x + 1.0f) * (b.w - b.y + 1.0f);
                 s_colmax[slot] = 0u;
@@ -229,21 +219,18 @@ __global__ __launch_bounds__(kThreads) void rcnn_targets(RcnnLaunch L)
                     out_cls[slot] = lab[i];
                     out_dif[slot] = dif[i] != 0 ? 1 : 0;
                 }
-            }
-            kept += __popcll(mask);
-        }
-        const int filled = kept < L.max_gt_boxes ? kept : L.max_gt_boxes;
-        for (int s = filled + lane; s < L.max_gt_boxes; s += 64) {
-            out_box[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-            out_cls[s] = 0;
-            out_dif[s] = 0;
-        }
+            },
+            [&](int s) {
+                out_box[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+                out_cls[s] = 0;
+                out_dif[s] = 0;
+            });
         if (lane == 0) {
             s_K            = kept;
             int32_t* shape = (int32_t*)(L.buf[4] + (uint64_t)rec * L.stride[4]);
             shape[0]       = x.im_w;
             shape[1]       = x.im_h;
-            *(int32_t*)(L.buf[6] + (uint64_t)rec * L.stride[6]) = filled;
+            *(int32_t*)(L.buf[6] + (uint64_t)rec * L.stride[6]) = kept < L.max_gt_boxes ? kept : L.max_gt_boxes;
             *(float*)(L.buf[8] + (uint64_t)rec * L.stride[8])   = x.im_scale;
         }
     }

@@ -1,6 +1,7 @@
-"""Records, configurations and comparisons the localization_rcnn decoder tests (tests/test_hip_rcnn.py) share:
-synthetic images with random object boxes and their JSON metadata, the image and localization_ssd ETL objects
-of the regression test with its SSD augmentation, and the ssd reference over tests/box_ref.py."""
+"""Records, configurations and comparisons the decoder tests of the box providers (tests/test_hip_boxes.py,
+tests/test_hip_rcnn.py) share: synthetic images with random object boxes and their JSON metadata, the image and
+localization_ssd ETL objects with the SSD augmentation (tests/test_ssd.py draws over it too), and the ssd
+reference over tests/box_ref.py."""
 import json
 
 import numpy as np

@@ -11,7 +11,6 @@ Then the decode stage end to end: [localization_ssd, image] and [image, bounding
 against box_ref over the params make_ssd_params / make_params give on the same slot engines, with the
 image output against the oracle; pixels and boxes against each other without box_ref; the refusals."""
 import ctypes
-import json
 
 import numpy as np
 import pytest
@@ -21,7 +20,8 @@ from aeon_amd import configs as CFG
 from tests import box_cases as C
 from tests import box_ref as B
 from tests import helpers as H
-from tests.test_ssd import SSD_AUG, random_boxes
+from tests.decoder_cases import (CLASSES, IMG_ETL, SIDE, SSD_AUG, SSD_ETL, as_records, assert_outputs, box_window,
+                                 meta_json, ssd_reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -185,55 +185,6 @@ def test_box_call_refusals(ctx):
 
 
 # ---- the decode stage: [localization_ssd, image] and [image, boundingbox] -------------------------------
-CLASSES = ["cat", "dog", "bird"]
-SIDE = 128
-SSD_ETL = {"type": "localization_ssd", "height": SIDE, "width": SIDE, "max_gt_boxes": 4, "class_names": CLASSES}
-IMG_ETL = {"type": "image", "height": SIDE, "width": SIDE, "channels": 3, "output_type": "float",
-           "channel_major": True}
-
-
-def meta_json(w, h, boxes, labels, difficult):
-    objs = [{"bndbox": {"xmin": b[0], "ymin": b[1], "xmax": b[2], "ymax": b[3]}, "name": CLASSES[l],
-             "difficult": bool(d)} for b, l, d in zip(boxes, labels, difficult)]
-    return json.dumps({"object": objs, "size": {"width": w, "height": h, "depth": 3}}).encode()
-
-
-def ssd_window(n, seed):
-    """n records of 96..160 px synthetic images with 0..6 boxes each (more than max_gt_boxes)."""
-    rng = np.random.default_rng(seed)
-    recs = []
-    for i in range(n):
-        w, h = int(rng.integers(96, 161)), int(rng.integers(96, 161))
-        k = int(rng.integers(0, 7))
-        boxes = random_boxes(rng, w, h, k)
-        recs.append(dict(img=A.synthetic_image(1000 * seed + i, w, h, 3), w=w, h=h, boxes=boxes,
-                         labels=rng.integers(0, 3, k).tolist(), difficult=rng.integers(0, 2, k).tolist()))
-    return recs
-
-
-def ssd_reference(recs, f, states, aug, etl_img=IMG_ETL, ssd=SSD_ETL):
-    """The five box outputs (box_ref over make_ssd_params on the slot engines, in record order through
-    one factory, as aeon's deterministic mode draws) and the oracle's image records for the same params."""
-    params = [f.make_ssd_params(states[i:i + 1], r["w"], r["h"], ssd["width"], ssd["height"], r["boxes"])
-              for i, r in enumerate(recs)]
-    want = [B.load_ssd(r["boxes"], r["labels"], r["difficult"], p, ssd["max_gt_boxes"], ssd["width"], ssd["height"],
-                       f.emit()) for r, p in zip(recs, params)]
-    out = {k: np.stack([np.asarray(w[k]) for w in want]) for k in A.SSD_OUTPUTS}
-    out["image"] = np.stack(H.oracle_records([r["img"] for r in recs], params, CFG.out_desc_for(etl_img, aug)))
-    return out, params
-
-
-def as_records(recs):
-    return [(meta_json(r["w"], r["h"], r["boxes"], r["labels"], r["difficult"]), r["img"]) for r in recs]
-
-
-def assert_outputs(got, want, what):
-    for k, w in want.items():
-        g = np.asarray(got[k]).reshape(w.shape)
-        assert np.array_equal(g.view(np.uint32) if g.dtype.itemsize == 4 else g,
-                              w.view(np.uint32) if w.dtype.itemsize == 4 else w), (what, k)
-
-
 @pytest.mark.parametrize("lighting", [False, True])
 def test_decoder_ssd_then_image_host_outputs(lighting):
     """decode_encoded into pageable host outputs (device staging + D2H), two windows of 12 and 5 records:
@@ -244,7 +195,7 @@ def test_decoder_ssd_then_image_host_outputs(lighting):
     f, states = A.ParamFactory(aug), A.seed_slots(11, 12)
     kept = 0
     for window, n in enumerate((12, 5, 12)):
-        recs = ssd_window(n, seed=40 + window)
+        recs = box_window(n, seed=40 + window)
         want, params = ssd_reference(recs, f, states, aug)
         assert_outputs(d.decode_named(as_records(recs)), want, f"window {window}")
         kept += int(want["gt_box_count"].sum())
@@ -260,7 +211,7 @@ def test_decoder_ssd_submit_wait_device_outputs_and_batch_major_false():
     cfg = dict(batch_size=4, random_seed=23, etl=[SSD_ETL, IMG_ETL], augmentation=[SSD_AUG])
     d = A.Decoder(cfg)
     f, states = A.ParamFactory(SSD_AUG), A.seed_slots(23, 12)
-    windows = [ssd_window(12, seed=60 + k) for k in range(3)]
+    windows = [box_window(12, seed=60 + k) for k in range(3)]
     wants = [ssd_reference(w, f, states, SSD_AUG)[0] for w in windows]
     bufs = [[torch.full((12 * o["item_bytes"],), 0xFF, dtype=torch.uint8, device="cuda") for o in d.outputs]
             for _ in range(3)]
@@ -352,7 +303,7 @@ def test_decoder_image_then_boundingbox():
     bb = {"type": "boundingbox", "height": 96, "width": 96, "max_bbox_count": 3, "class_names": CLASSES}
     img_etl = dict(IMG_ETL, height=96, width=96)
     d = A.Decoder(dict(batch_size=7, random_seed=17, etl=[img_etl, bb], augmentation=[aug]))
-    recs = ssd_window(7, seed=80)
+    recs = box_window(7, seed=80)
     f, states = A.ParamFactory(aug), A.seed_slots(17, 7)
     params = [f.make_params(states[i:i + 1], r["w"], r["h"], 96, 96) for i, r in enumerate(recs)]
     out = d.decode_named([(r["img"], meta_json(r["w"], r["h"], r["boxes"], r["labels"], r["difficult"])) for r in recs])
@@ -373,7 +324,7 @@ def test_decoder_refuses_rotation_and_stays_usable():
     f, states = A.ParamFactory(aug), A.seed_slots(29, 1)
     seen = set()
     for k in range(10):
-        recs = ssd_window(1, seed=90 + k)
+        recs = box_window(1, seed=90 + k)
         want, params = ssd_reference(recs, f, states, aug)
         if params[0].angle != 0:
             with pytest.raises(A.AeonHipError) as e:
@@ -387,7 +338,7 @@ def test_decoder_refuses_rotation_and_stays_usable():
 
 def test_decoder_empty_metadata_message():
     d = A.Decoder(dict(batch_size=2, random_seed=31, etl=[SSD_ETL, IMG_ETL], augmentation=[SSD_AUG]))
-    recs = ssd_window(2, seed=99)
+    recs = box_window(2, seed=99)
     bad = as_records(recs)
     bad[1] = (b"", bad[1][1])
     with pytest.raises(A.AeonHipError) as e:

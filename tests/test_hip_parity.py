@@ -631,7 +631,7 @@ def test_16bit_errors(ctx):
 def test_ssd_expand_records(ctx):
     """make_ssd_params records (expand + batch-sampler crop + photometric, "use warping" 300x300):
     image::expand (image.cpp:276-303) runs as a pre-pass before the crop/resize job."""
-    from tests.test_ssd import SSD_AUG, random_boxes
+    from tests.decoder_cases import SSD_AUG, random_boxes
     rng = np.random.default_rng(21)
     f = A.ParamFactory(SSD_AUG)
     states = A.seed_slots(5, 24)

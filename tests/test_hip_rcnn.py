@@ -24,10 +24,11 @@ import pytest
 import aeon_amd as A
 from aeon_amd import configs as CFG
 from tests import box_cases as C
+from tests import box_ref as B
 from tests import helpers as H
 from tests import rcnn_ref as R
-from tests.rcnn_cases import (CLASSES, IMG_ETL, SIDE, SSD_AUG, SSD_ETL, as_records, assert_outputs, ssd_reference)
-from tests.rcnn_cases import box_window as ssd_window
+from tests.decoder_cases import (CLASSES, IMG_ETL, SIDE, SSD_AUG, SSD_ETL, as_records, assert_outputs, box_window,
+                                 ssd_reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -361,7 +362,7 @@ def test_decoder_threads_engine_states_through_windows(batch_major):
     cfg = dict(batch_size=5, random_seed=41, etl=[RCNN_ETL, IMG_ETL], augmentation=[RCNN_AUG], batch_major=batch_major)
     d = A.Decoder(cfg)
     f, states = A.ParamFactory(RCNN_AUG), A.seed_slots(41, 5)
-    windows = [ssd_window(5, seed=70 + k) for k in range(3)]
+    windows = [box_window(5, seed=70 + k) for k in range(3)]
     before = states.copy()
     wants = [rcnn_reference(w, f, states, RCNN_AUG)[0] for w in windows]
     assert not np.array_equal(before, states) and sum(int(w["labels_mask"].sum()) for w in wants) > 100
@@ -386,13 +387,31 @@ def test_decoder_threads_engine_states_through_windows(batch_major):
     d.close()
 
 
+def test_decoder_rcnn_and_boundingbox_tables_in_one_window():
+    """[localization_rcnn, boundingbox, image]: two box tables in one window at different arena offsets,
+    the first with the rcnn extension and its padding behind it.  The boundingbox element reuses the params
+    the rcnn element drew; the rcnn outputs and the image are the [localization_rcnn, image] reference's."""
+    bb = {"type": "boundingbox", "height": SIDE, "width": SIDE, "max_bbox_count": 4, "class_names": CLASSES}
+    d = A.Decoder(dict(batch_size=5, random_seed=43, etl=[RCNN_ETL, bb, IMG_ETL], augmentation=[RCNN_AUG]))
+    f, states = A.ParamFactory(RCNN_AUG), A.seed_slots(43, 5)
+    recs = box_window(5, seed=85)
+    want, params = rcnn_reference(recs, f, states, RCNN_AUG)
+    got = d.decode_named([(meta, meta, img) for meta, img in as_records(recs)])
+    d.close()
+    assert_rcnn_outputs(got, want, "rcnn + boundingbox")
+    want_bb = np.stack([B.load_boundingbox(r["boxes"], p, 4, emit=f.emit()) for r, p in zip(recs, params)])
+    assert got["boundingbox"].shape == (5, 4, 16)
+    assert np.array_equal(got["boundingbox"].reshape(5, -1).view(np.uint32), want_bb.view(np.uint32))
+    assert want_bb.any() and sum(len(r["boxes"]) for r in recs) % 2 == 1  # the extension follows 8 bytes of padding
+
+
 def test_decoder_seed_zero_invariants():
     """random_seed 0: the draws are not reproducible, so with an augmentation that draws nothing that
     matters (no crop, no flip) the labels are known and the sample is checked for what must hold: its
     size, sampled anchors among the labelled ones, foreground capped at num_fg, targets only there."""
     aug = {"type": "image", "crop_enable": False, "flip_enable": False}
     d = A.Decoder(dict(batch_size=4, etl=[RCNN_ETL, IMG_ETL], augmentation=[aug]))
-    recs = ssd_window(4, seed=77)
+    recs = box_window(4, seed=77)
     got = d.decode_named(as_records(recs))
     f = A.ParamFactory(aug)
     anchors, info = A.rcnn_anchors(RCNN_ETL), A.rcnn_config_info(RCNN_ETL)
@@ -421,14 +440,14 @@ def test_decoder_refusals():
     aug = {"type": "image", "crop_enable": False, "angle": [5, 5]}
     d = A.Decoder(dict(batch_size=1, random_seed=5, etl=[RCNN_ETL, IMG_ETL], augmentation=[aug]))
     with pytest.raises(A.AeonHipError) as e:
-        d.decode_named(as_records(ssd_window(1, seed=3)))
+        d.decode_named(as_records(box_window(1, seed=3)))
     assert e.value.code == A.AEON_HIP_EINVAL and "angle" in str(e.value)
     d.close()
     with pytest.raises(A.AeonHipError) as e:  # 9 * 94 * 94 anchors: above the stated 65 536
         A.Decoder(dict(batch_size=1, etl=[dict(BASE, scales=[8, 16, 32], width=1504, height=1504), IMG_ETL]))
     assert e.value.code == A.AEON_HIP_EUNSUPPORTED
     d = A.Decoder(dict(batch_size=1, random_seed=5, etl=[RCNN_ETL, IMG_ETL], augmentation=[RCNN_AUG]))
-    recs = as_records(ssd_window(1, seed=3))
+    recs = as_records(box_window(1, seed=3))
     with pytest.raises(A.AeonHipError) as e:
         d.decode_named([(b"", recs[0][1])])
     assert "received localization_rcnn data with size 0, at idx 0" in str(e.value)
@@ -442,7 +461,7 @@ def test_other_configurations_are_unchanged():
     d = A.Decoder(dict(batch_size=6, random_seed=13, etl=[IMG_ETL], augmentation=[aug]))
     f, states = A.ParamFactory(aug), A.seed_slots(13, 6)
     for k in range(2):
-        recs = ssd_window(6, seed=50 + k)
+        recs = box_window(6, seed=50 + k)
         params = [f.make_params(states[i:i + 1], r["w"], r["h"], IMG_ETL["width"], IMG_ETL["height"]) for i, r in enumerate(recs)]
         ref = np.stack(H.oracle_records([r["img"] for r in recs], params, CFG.out_desc_for(IMG_ETL, aug)))
         assert np.array_equal(d.decode_named([(r["img"],) for r in recs])["image"], ref), k
@@ -450,7 +469,7 @@ def test_other_configurations_are_unchanged():
     d = A.Decoder(dict(batch_size=1, random_seed=11, etl=[SSD_ETL, IMG_ETL], augmentation=[SSD_AUG]))
     f, states = A.ParamFactory(SSD_AUG), A.seed_slots(11, 6)
     for k in range(2):
-        recs = ssd_window(6, seed=40 + k)
+        recs = box_window(6, seed=40 + k)
         want, _ = ssd_reference(recs, f, states, SSD_AUG)
         assert_outputs(d.decode_named(as_records(recs)), want, f"ssd window {k}")
     d.close()

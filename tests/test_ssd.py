@@ -8,6 +8,7 @@ import pytest
 
 import aeon_amd as A
 from tests import helpers as H
+from tests.decoder_cases import SSD_AUG, random_boxes
 
 ALL_CONSTRAINTS = {"min_jaccard_overlap": 0.2, "max_jaccard_overlap": 0.3, "min_sample_coverage": 0.4,
                    "max_sample_coverage": 0.5, "min_object_coverage": 0.6, "max_object_coverage": 0.7}
@@ -145,26 +146,6 @@ def test_batch_sampler_random_sample_constraint(oracle):
     for i in range(20):
         v1 = float(np.float32(rng.random()))
         _check_sampler(oracle, 0.7, 0.5, ("max" if v1 > 0.9 else "min") + kinds[i % 3], v1)
-
-
-SSD_AUG = {"type": "image", "crop_enable": False, "flip_enable": True, "expand_ratio": [1.0, 4.0],
-           "expand_probability": 0.5, "brightness": [0.875, 1.125], "saturation": [0.5, 1.5],
-           "batch_samplers": [
-               {"max_sample": 1, "max_trials": 50,
-                "sampler": {"scale": [0.3, 1.0], "aspect_ratio": [0.5, 2.0]},
-                "sample_constraint": {"min_jaccard_overlap": 0.1}},
-               {"max_sample": 1, "max_trials": 50,
-                "sampler": {"scale": [0.3, 1.0], "aspect_ratio": [0.5, 2.0]},
-                "sample_constraint": {"min_object_coverage": 0.5, "max_sample_coverage": 0.9}},
-               {"max_trials": 1}]}
-
-
-def random_boxes(rng, w, h, n):
-    res = []
-    for _ in range(n):
-        x0, y0 = float(rng.integers(0, w - 1)), float(rng.integers(0, h - 1))
-        res.append((x0, y0, float(rng.integers(int(x0), w)), float(rng.integers(int(y0), h))))
-    return res
 
 
 def test_make_ssd_params_matches_oracle(oracle):

@@ -52,22 +52,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
     n = a.records
-    info = A.rcnn_config_info(CFG)
-    A_, m = int(info["total_anchors"]), info["max_gt_boxes"]
     recs = records(n, a.boxes)
     p = A.aug_params(crop_x=0, crop_y=0, crop_w=SRC_W, crop_h=SRC_H, out_w=int(SRC_W * SCALE), out_h=int(SRC_H * SCALE),
                      flip=0, expand_ratio=1.0)
     params = (A.AugParams * n)(*[p] * n)
-    strides = [16 * A_, 16 * A_, 8 * A_, 8 * A_, 8, 16 * m, 4, 4 * m, 4, 4 * m]
-    bufs = [torch.zeros(n * s, dtype=torch.uint8, device="cuda") for s in strides]
-    ptrs = [t.data_ptr() for t in bufs]
     ctx = A.Context(0)
+    prepared = A.RcnnCall(ctx, CFG, recs, params, fixed_scaling_factor=SCALE)  # the C call alone is timed
+    prepared.out.anchors_key = 1  # the context's one anchor table, named as the decoder's provider names its own
+    A_ = int(prepared.info["total_anchors"])
+    bufs = [torch.zeros(n * s, dtype=torch.uint8, device="cuda") for s in prepared.strides]
+    ptrs = [t.data_ptr() for t in bufs]
     stream = torch.cuda.current_stream()
     sid = stream.cuda_stream
     states = A.seed_slots(7, n)
-
-    prepared = A.RcnnCall(ctx, CFG, recs, params, fixed_scaling_factor=SCALE)  # the C call alone is timed
-    prepared.out.anchors_key = 1  # the context's one anchor table, named as the decoder's provider names its own
 
     def call(shuffle):
         prepared.launch(ptrs, states if shuffle else None, shuffle, sid)
