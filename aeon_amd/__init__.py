@@ -85,6 +85,11 @@ class EncodedElem(ctypes.Structure):
                 ("height", ctypes.c_int32), ("channels", ctypes.c_int32), ("stride", ctypes.c_int32)]
 
 
+class AviFrame(ctypes.Structure):
+    """aeon_avi_frame: one frame of an MJPEG AVI datum, `size` bytes at `offset` (size 0: an empty chunk)."""
+    _fields_ = [("offset", ctypes.c_uint64), ("size", ctypes.c_uint32)]
+
+
 class EncodedRecords:
     """Records marshalled once (Decoder.encoded): their aeon_encoded_elem array and the Python objects
     whose memory it points at."""
@@ -205,6 +210,10 @@ def lib():
         L.aeon_decode_png.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
                                       P(ctypes.c_int)]
         L.aeon_hip_decode_jpeg_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc), vp, vp]
+        L.aeon_avi_frames.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(AviFrame), ctypes.c_int] + [P(ctypes.c_int)] * 3
+        L.aeon_avi_last_error.restype = ctypes.c_char_p
+        L.aeon_hip_video_batch.argtypes = [vp, ctypes.c_int, P(ctypes.c_int32), P(ImgDesc), vp, P(AugParams), ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint64, vp]
         L.aeon_hip_stager_create.argtypes = [vp, ctypes.c_int, P(OutDesc), ctypes.c_int, P(vp)]
         L.aeon_hip_stager_destroy.argtypes = [vp]
         L.aeon_hip_stager_stage.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -574,6 +583,26 @@ def jpeg_host_stage(data):
     return bool(g.value), nb.value
 
 
+def avi_frames(data, cap=None):
+    """video::extractor's demux of one MJPEG AVI datum (aeon_avi_frames): (frames, width, height) with
+    frames = [(offset, size)] of the chunks' data in index order (size 0: an empty chunk, whose frame
+    repeats the previous one) and width / height from the main header.  cap: look at the first cap
+    frames only (what a provider with max_frame_count = cap does).  AeonHipError for a datum the
+    demux refuses."""
+    data = bytes(data)
+    n, w, h = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if cap is None:
+        rc = lib().aeon_avi_frames(data, len(data), None, 0, ctypes.byref(n), ctypes.byref(w), ctypes.byref(h))
+        if rc != 0:
+            raise AeonHipError(rc, lib().aeon_avi_last_error().decode())
+        cap = n.value
+    buf = (AviFrame * max(cap, 1))()
+    rc = lib().aeon_avi_frames(data, len(data), buf, cap, ctypes.byref(n), ctypes.byref(w), ctypes.byref(h))
+    if rc != 0:
+        raise AeonHipError(rc, lib().aeon_avi_last_error().decode())
+    return [(buf[i].offset, buf[i].size) for i in range(min(n.value, cap))], w.value, h.value
+
+
 PNG_BGR8, PNG_GRAY8, PNG_ANYDEPTH = 0, 1, 2
 
 
@@ -716,6 +745,24 @@ class Context:
         """depthmap transform + load (aeon src/etl_depthmap.cpp) for len(descs) records."""
         self._batch(lib().aeon_hip_depthmap_batch, descs, src_ptr, params, out, out_ptr, stream)
 
+    def video_batch(self, frame_counts, descs, src_ptr, params, max_frames, out_w, out_h, out_ptr, item_stride,
+                    stream=0):
+        """video::transformer + video::loader for len(frame_counts) clips (aeon_hip_video_batch, async on
+        stream): frame_counts = a list, or a prebuilt c_int32 array; descs = max_frames descriptors per clip,
+        row-major (a list, or a prebuilt ImgDesc array),
+        of which clip i's first frame_counts[i] are read; params[i] = clip i's AugParams.  Clip i is
+        written at out_ptr + i * item_stride as uint8 (3, max_frames, out_h, out_w), B, G, R planes, its
+        frames past frame_counts[i] zero."""
+        n = len(frame_counts)
+        fc = frame_counts if isinstance(frame_counts, ctypes.Array) else (ctypes.c_int32 * max(n, 1))(*[int(c) for c in frame_counts])
+        d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * max(len(descs), 1))(*descs)
+        p = params if isinstance(params, ctypes.Array) else (AugParams * max(n, 1))(*params)
+        if len(d) < n * max_frames or len(p) < n:
+            raise ValueError(f"{len(d)} frame descriptors / {len(p)} params for {n} clips of {max_frames} frames")
+        _check(lib().aeon_hip_video_batch(self._h, n, fc, d, ctypes.c_void_p(src_ptr), p, int(max_frames), int(out_w),
+                                          int(out_h), ctypes.c_void_p(out_ptr), int(item_stride),
+                                          ctypes.c_void_p(stream or 0)))
+
     def decode_jpeg_batch(self, files, descs, dst_ptr, stream=0):
         """image::extractor::extract of JPEG files into device memory (aeon_hip_decode_jpeg_batch):
         files = list of bytes (or a JpegFiles, marshalled once), descs[i] = where record i goes (HWC,
@@ -845,7 +892,8 @@ def _check_host(rc):
 class Decoder:
     """aeon batch_decoder over provider_factory::create(config): decode windows of records (per ETL
     element an HWC uint8 array, an encoded JPEG / PNG file, or -- boundingbox, localization_ssd and
-    localization_rcnn elements -- the JSON metadata as bytes or str) into the provider output buffers.  A provider may own
+    localization_rcnn elements -- the JSON metadata as bytes or str, a video element's MJPEG AVI file as
+    bytes, a label element's text or 4 binary bytes) into the provider output buffers.  A provider may own
     several output buffers (localization_ssd: five, localization_rcnn: ten), so records have n_inputs elements and windows
     len(outputs) buffers, in get_output_shapes() order."""
 

@@ -525,6 +525,173 @@ private:
     uint64_t           m_anchors_key = 0;
 };
 
+// video::config (etl_video.hpp:33-66): max_frame_count REQUIRED, name optional, frame an image::config;
+// one buffer {frame.channels, max_frame_count, frame.height, frame.width} of frame.output_type.
+struct video_config {
+    int64_t      max_frame_count = 0;
+    std::string  name;
+    image_config frame;
+    shape_type   shape;
+    // aeon builds image::config from js["frame"] first (etl_video.hpp:40-41): without one that is its "missing
+    // image config" runtime_error.  A clip has no pixels without its frame config, so there is nothing of it
+    // this stage could run.
+    static const Json& frame_of(const Json& js)
+    {
+        if (js.is_null()) throw std::runtime_error("missing video config in json config");
+        if (!js.has("frame") || js.at("frame").is_null())
+            throw std::runtime_error("missing image config in json config: etl type 'video' without its 'frame' is "
+                                     "outside the HIP image stage");
+        return js.at("frame");
+    }
+    explicit video_config(const Json& js) : frame(frame_of(js))
+    {
+        if (!js.has("max_frame_count")) invalid("Required Argument: 'max_frame_count' not set");
+        get_num(js, "max_frame_count", max_frame_count);
+        get_str(js, "name", name);
+        verify_config("video", {"type", "max_frame_count", "name", "frame"}, js);
+        // aeon validates nothing more.  Its loader writes three uint8 planes per frame whatever the config says
+        // (etl_video.cpp:76-107): into a one-plane item with channels 1, into a wider item with another
+        // output_type.  This stage refuses both, and a frame count it cannot launch with.
+        if (max_frame_count <= 0 || max_frame_count > 65535) invalid("invalid max_frame_count");
+        if (frame.channels != 3) invalid("video: frame 'channels' must be 3 (the loader writes three planes per frame)");
+        if (frame.shape.otype.dtype != AEON_DTYPE_U8)
+            throw unsupported_error("video: frame 'output_type' must be uint8_t (the loader writes uint8 planes)");
+        if ((uint64_t)max_frame_count * frame.height * frame.width * 3 > (uint64_t)INT32_MAX)
+            throw unsupported_error("video: a clip item above 2^31 - 1 bytes");
+        shape.shape = {frame.channels, (size_t)max_frame_count, frame.height, frame.width};
+        shape.names = {"channels", "frames", "height", "width"};
+        shape.otype = frame.shape.otype;
+    }
+};
+
+// provider::video (provider.cpp:477-517).  The param factory is built from augmentation["frame"], not from
+// the augmentation object itself (provider.cpp:483).  Per record: video::extractor's demux (avi_host.hpp) of
+// the kept frames only -- aeon decodes every frame and its transformer drops those past max_frame_count
+// (etl_video.cpp:23-41, 55-63): the same output --, params drawn from the first frame's size unless an
+// earlier element of the record drew, the frames' JPEGs decoded by the JPEG stage and the clip written by
+// aeon_hip_video_batch at post_process time.  The frame config's bgr_to_rgb, channel_major and the
+// factory's fixed_aspect_ratio / mean / stddev are parsed and ignored, as aeon's loader ignores them.
+class video_provider : public etl_provider {
+public:
+    video_provider(const Json& js, const Json& aug)
+        : m_cfg(js), m_factory(aug.has("frame") ? aug.at("frame") : Json()), m_name(create_name(m_cfg.name, "video"))
+    {
+    }
+    void provide(int, const decoded_element& in, augmentation& aug, std::minstd_rand0& random, aeon_aug_params& params,
+                 light_split* ls) const override
+    {
+        if (!aug.has) {
+            if (ls)
+                m_factory.make_params_split(random, in.width, in.height, (int)m_cfg.frame.width, (int)m_cfg.frame.height,
+                                            ls->entry_avail, &aug.image, &ls->exit_saved);
+            else
+                m_factory.make_params(random, in.width, in.height, (int)m_cfg.frame.width, (int)m_cfg.frame.height,
+                                      &aug.image);
+            aug.has = true;
+        }
+        params = aug.image;
+    }
+    int  max_frames() const override { return (int)m_cfg.max_frame_count; }
+    void extract_clip(int idx, decoded_element& e, video_clip& c) const override
+    {
+        const std::string at = ", at idx " + std::to_string(idx);
+        if (!e.data || e.size == 0) throw std::runtime_error("received encoded video with size 0" + at);
+        const int   D = max_frames();
+        int         count = 0, aw = 0, ah = 0;
+        std::string err;
+        c.frames.assign((size_t)D, aeon_avi_frame{});
+        if (avi_frames(e.data, e.size, c.frames.data(), D, &count, &aw, &ah, err) != 0) invalid(err + at);
+        c.frames.resize((size_t)std::min(count, D));
+        // every decoded frame goes through transform_single_image with the one params set, drawn for the first
+        // frame's size: a frame of another size would be cropped with a cropbox that is not its own
+        for (size_t d = 0; d < c.frames.size(); d++) {
+            if (c.frames[d].size == 0) continue; // repeats the previous frame
+            int fw = 0, fh = 0, comps = 0;
+            check(aeon_jpeg_info(e.data + c.frames[d].offset, c.frames[d].size, &fw, &fh, &comps));
+            if (d == 0) c.width = fw, c.height = fh;
+            else if (fw != c.width || fh != c.height)
+                invalid("video: frame " + std::to_string(d) + " is " + std::to_string(fw) + "x" + std::to_string(fh) +
+                        ", the first frame " + std::to_string(c.width) + "x" + std::to_string(c.height) + at);
+        }
+        e.width = c.width, e.height = c.height, e.channels = 3, e.stride = c.width * 3;
+    }
+    const param_factory& factory() const override { return m_factory; }
+    bool               is_mask() const override { return false; }
+    const shape_type&  shape() const override { return m_cfg.shape; }
+    const std::string& buffer_name() const override { return m_name; }
+    aeon_out_desc      out_desc() const override
+    {
+        aeon_out_desc o{};
+        o.dtype = AEON_DTYPE_U8, o.channels = 3, o.channel_major = 1;
+        o.item_stride = m_cfg.shape.byte_size();
+        return o;
+    }
+
+private:
+    video_config  m_cfg;
+    param_factory m_factory;
+    std::string   m_name;
+};
+
+// label::config / extractor / loader (etl_label.hpp:36-150) and provider::label (provider.cpp:190-216): shape
+// {1} of output_type (default uint32_t); the datum is 4 bytes read as a native int (binary) or text through
+// std::stoi, and the loader copies the first sizeof(output_type) bytes of that int.  With an 8-byte
+// output_type aeon copies 4 bytes past the int: refused here.
+class label_provider : public etl_provider {
+public:
+    explicit label_provider(const Json& js) : m_factory(Json())
+    {
+        std::string otype = "uint32_t", name, type;
+        get_str(js, "name", name);
+        get_bool(js, "binary", m_binary);
+        get_str(js, "type", type);
+        get_str(js, "output_type", otype);
+        if (!output_type::is_valid_type(otype)) invalid("value for 'output_type' out of range");
+        verify_config("label", {"name", "binary", "type", "output_type"}, js);
+        m_shape.shape = {1};
+        m_shape.otype = output_type(otype);
+        if (m_shape.otype.size > sizeof(int))
+            throw unsupported_error("label: an 8-byte 'output_type' (aeon's loader copies past its int)");
+        m_name = create_name(name, "label");
+    }
+    void provide(int, const decoded_element&, augmentation&, std::minstd_rand0&, aeon_aug_params&, light_split*) const override
+    {
+        throw std::logic_error("label providers draw no params");
+    }
+    size_t  label_bytes() const override { return m_shape.otype.size; }
+    int32_t extract_label(int idx, const decoded_element& e) const override
+    {
+        const std::string at = ", at idx " + std::to_string(idx);
+        if (!e.data || e.size == 0) throw std::runtime_error("received encoded image with size 0" + at);
+        if (m_binary) {
+            if (e.size != 4)
+                invalid("Only 4 byte buffers can be loaded as int32.  label_extractor::extract received " +
+                        std::to_string(e.size) + " bytes" + at);
+            int32_t v;
+            std::memcpy(&v, e.data, 4);
+            return v;
+        }
+        try {
+            return (int32_t)std::stoi(std::string((const char*)e.data, e.size));
+        } catch (const std::invalid_argument&) {
+            invalid("Cannot convert label '" + std::string((const char*)e.data, std::min<size_t>(e.size, 32)) + "' to integer" + at);
+        } catch (const std::out_of_range&) {
+            invalid("String to int conversion out of range error" + at);
+        }
+    }
+    const param_factory& factory() const override { return m_factory; }
+    bool               is_mask() const override { return false; }
+    const shape_type&  shape() const override { return m_shape; }
+    const std::string& buffer_name() const override { return m_name; }
+    aeon_out_desc      out_desc() const override { return aeon_out_desc{}; }
+
+private:
+    bool          m_binary = false;
+    shape_type    m_shape;
+    param_factory m_factory; // (none: the provider draws no params)
+    std::string   m_name;
+};
+
 } // namespace
 
 provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const Json& aug)
@@ -542,8 +709,13 @@ provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const
             if (m_has_rcnn) invalid("one localization_rcnn element per record");
             p.reset(new rcnn_provider(j, aug));
             m_has_rcnn = true;
-        } else if (type == "label" || type == "blob" || type == "video" ||
-                 type == "char_map" || type == "label_map")
+        } else if (type == "video") {
+            p.reset(new video_provider(j, aug));
+            m_has_video = true;
+        } else if (type == "label") {
+            p.reset(new label_provider(j));
+            m_has_label = true;
+        } else if (type == "blob" || type == "char_map" || type == "label_map")
             throw std::runtime_error("etl type '" + type + "' is outside the HIP image stage");
         else
             invalid("unsupported etl type '" + type + "'");
@@ -553,6 +725,13 @@ provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const
         m_providers.push_back(std::move(p));
     }
     m_out_first.push_back((int)m_output_shapes.size());
+    // A record of labels alone has no pixels, boxes or clips: the decode stage would open a device to copy a few
+    // ints.  aeon's CPU provider is the place for such a config; here label is the companion of a device element.
+    bool device_work = false;
+    for (const auto& p : m_providers) device_work = device_work || p->label_bytes() == 0;
+    if (!device_work && !m_providers.empty())
+        throw std::runtime_error("etl type 'label' on its own is outside the HIP image stage: it accompanies an image, "
+                                 "pixelmask, box or video element");
 }
 
 void provider_base::provide(int idx, const decoded_element* elems, decode_window& w,
@@ -582,9 +761,13 @@ void provider_base::draw(int idx, const decoded_element* elems, decode_window& w
             m_providers[k]->provide_boxes(m, aug, random, w.params[k][idx], ls);
             continue;
         }
+        if (m_providers[k]->label_bytes()) { // label::extractor; the provider draws no params
+            w.labels[k][idx] = m_providers[k]->extract_label(idx, e);
+            continue;
+        }
         if (!e.data || e.width <= 0 || e.height <= 0) {
             std::stringstream ss;
-            ss << "received " << (m_providers[k]->is_mask() ? "pixelmask" : "encoded image")
+            ss << "received " << (m_providers[k]->is_mask() ? "pixelmask" : m_providers[k]->max_frames() ? "encoded video" : "encoded image")
                << " with size 0, at idx " << idx;
             throw std::runtime_error(ss.str());
         }
@@ -603,7 +786,9 @@ void provider_base::draw_window(int n, const decoded_element* records, decode_wi
                                 std::vector<std::minstd_rand0>& engines, thread_pool& pool) const
 {
     const size_t ne = m_providers.size();
-    const param_factory& F = m_providers[0]->factory(); // the first element draws (aug.has after it)
+    size_t first = 0; // the first element that draws (aug.has after it): label providers draw nothing
+    while (first + 1 < ne && m_providers[first]->label_bytes()) first++;
+    const param_factory& F = m_providers[first]->factory();
     const bool               lit = F.lighting_on();
     std::vector<light_split> ls(lit ? n : 0);
     const bool               a0 = F.light_avail();
@@ -635,7 +820,7 @@ void provider_base::stage(int idx, const decoded_element* elems, decode_window& 
 {
     for (size_t k = 0; k < m_providers.size(); k++) {
         const decoded_element& e = elems[k];
-        if (e.encoded || e.metadata) continue; // decoded on the device, straight into the source arena / no pixels
+        if (e.encoded || e.no_pixels()) continue; // decoded on the device, straight into the source arena / no pixels
         const size_t row = (size_t)e.width * e.channels * e.elem_bytes;
         uint8_t*     dst = w.arena + w.offset[k][idx];
         if (e.png_mode >= 0) { // extract on this pool thread, straight into the pinned arena
@@ -668,6 +853,20 @@ void provider_base::post_process(aeon_hip_ctx* ctx, decode_window& w, const uint
             p.launch_boxes(ctx, w, k, dev_arena + w.box_offset[k], out, stream);
             continue;
         }
+        if (p.max_frames()) { // video::transformer + loader over the clip's decoded frames
+            const auto& sh = p.shape().shape; // {channels, frames, height, width}
+            check(aeon_hip_video_batch(ctx, w.n, w.clip_counts[k].data(), w.clip_descs[k].data(), dev_arena,
+                                       w.params[k].data(), (int)sh[1], (int)sh[3], (int)sh[2], out[0], p.shape().byte_size(),
+                                       stream));
+            continue;
+        }
+        if (p.label_bytes()) { // label::loader; a host output was written while staging (out[0] null)
+            if (out[0])
+                hip_check(hipMemcpyAsync(out[0], w.arena + w.label_offset[k], (size_t)w.n * p.label_bytes(),
+                                         hipMemcpyHostToDevice, (hipStream_t)stream),
+                          "hipMemcpyAsync");
+            continue;
+        }
         aeon_out_desc o = p.out_desc();
         if (p.is_mask())
             check(aeon_hip_mask_batch(ctx, w.n, w.descs[k].data(), dev_arena, w.params[k].data(), &o, out[0], stream));
@@ -692,6 +891,35 @@ size_t provider_base::layout_boxes(decode_window& w, size_t offset) const
     return offset;
 }
 
+void provider_base::extract_clips(int n, decoded_element* records, decode_window& w, thread_pool& pool) const
+{
+    const size_t ne = m_providers.size();
+    pool.run(n, [&](int i) {
+        for (size_t k = 0; k < ne; k++)
+            if (m_providers[k]->max_frames()) m_providers[k]->extract_clip(i, records[(size_t)i * ne + k], w.clips[k][i]);
+    });
+}
+
+size_t provider_base::layout_labels(decode_window& w, size_t offset) const
+{
+    w.label_offset.assign(m_providers.size(), 0);
+    for (size_t k = 0; k < m_providers.size(); k++) {
+        if (!m_providers[k]->label_bytes()) continue;
+        w.label_offset[k] = offset;
+        offset += ((size_t)w.n * m_providers[k]->label_bytes() + 15) & ~(size_t)15;
+    }
+    return offset;
+}
+
+// label::loader::load (etl_label.hpp:141-146): the first sizeof(output_type) bytes of the int
+void provider_base::stage_labels(decode_window& w) const
+{
+    for (size_t k = 0; k < m_providers.size(); k++) {
+        const size_t b = m_providers[k]->label_bytes();
+        for (int i = 0; b && i < w.n; i++) std::memcpy(w.arena + w.label_offset[k] + (size_t)i * b, &w.labels[k][i], b);
+    }
+}
+
 void provider_base::stage_boxes(decode_window& w) const
 {
     for (size_t k = 0; k < m_providers.size(); k++)
@@ -704,8 +932,13 @@ decode_window provider_base::new_window(int n) const
     w.n = n;
     w.params.assign(m_providers.size(), std::vector<aeon_aug_params>(n));
     w.boxes.resize(m_providers.size());
-    for (size_t k = 0; k < m_providers.size(); k++)
+    w.clips.resize(m_providers.size());
+    w.labels.resize(m_providers.size());
+    for (size_t k = 0; k < m_providers.size(); k++) {
         if (m_providers[k]->box_kind() >= 0) w.boxes[k].resize(n);
+        if (m_providers[k]->max_frames()) w.clips[k].resize(n);
+        if (m_providers[k]->label_bytes()) w.labels[k].resize(n);
+    }
     return w;
 }
 
@@ -1066,6 +1299,12 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     decode_window w = m_provider->new_window(n);
     w.descs.assign(ne, std::vector<aeon_img_desc>(n));
     w.offset.assign(ne, std::vector<size_t>(n));
+    // video::extractor of the video elements (the AVI demux and the kept frames' JPEG headers), on the pool:
+    // the draws below need the first frame's size
+    if (m_provider->has_video()) {
+        phase_range r("aeon.demux");
+        m_provider->extract_clips(n, records.data(), w, *m_pool);
+    }
     // batch_decoder::process: the slot engine of record i draws its params (deterministic mode
     // swaps the slot engine in and out, batch_decoder.cpp:62-71).  With slot engines the draws run
     // on the pool (draw_window: aeon's in-order params exactly), and with them the extraction of the
@@ -1104,12 +1343,31 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     }
     // source arena: the box tables and the decoded elements first (staged + one H2D), then the
     // device-decoded JPEGs
-    size_t staged = m_provider->layout_boxes(w, 0), total = staged;
+    size_t staged = m_provider->layout_labels(w, m_provider->layout_boxes(w, 0)), total = staged;
+    w.clip_descs.resize(ne), w.clip_counts.resize(ne);
+    for (int k = 0; k < ne; k++)
+        if (const int D = m_provider->providers()[k]->max_frames())
+            w.clip_descs[k].assign((size_t)n * D, aeon_img_desc{}), w.clip_counts[k].assign(n, 0);
     for (int pass = 0; pass < 2; pass++)
         for (int i = 0; i < n; i++)
             for (int k = 0; k < ne; k++) {
                 const decoded_element& e = records[(size_t)i * ne + k];
-                if (e.encoded != (pass == 1) || e.metadata) continue;
+                if (e.video && pass == 1) {
+                    // one source-arena slot per distinct decoded frame of the clip; an empty chunk's frame is the
+                    // previous frame's slot again (cap_mjpeg_decoder.cpp:138-141)
+                    const video_clip& c = w.clips[k][i];
+                    aeon_img_desc*    row = &w.clip_descs[k][(size_t)i * m_provider->providers()[k]->max_frames()];
+                    for (size_t d = 0; d < c.frames.size(); d++) {
+                        if (c.frames[d].size == 0) {
+                            row[d] = row[d - 1]; // (the demux refuses an empty first frame)
+                            continue;
+                        }
+                        row[d] = aeon_img_desc{total, c.width, c.height, c.width * 3, 3, 0, 0};
+                        total += ((size_t)c.width * c.height * 3 + 15) & ~(size_t)15;
+                    }
+                    w.clip_counts[k][i] = (int32_t)c.frames.size();
+                }
+                if (e.encoded != (pass == 1) || e.no_pixels()) continue;
                 const size_t b = (size_t)std::max(e.width, 0) * std::max(e.height, 0) * std::max(e.channels, 0) *
                                  e.elem_bytes;
                 w.offset[k][i] = total;
@@ -1132,6 +1390,7 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
         {
             phase_range r("aeon.stage");
             m_provider->stage_boxes(w);
+            m_provider->stage_labels(w);
             m_pool->run(n, [&](int i) { m_provider->stage(i, records.data() + (size_t)i * ne, w); });
         }
         phase_range r("aeon.h2d_enqueue");
@@ -1147,9 +1406,22 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
             if (!e.encoded) continue;
             files.push_back(e.data), sizes.push_back(e.size), descs.push_back(w.descs[k][i]);
         }
-        if (!files.empty())
-            check(aeon_hip_decode_jpeg_batch(m_ctx, (int)files.size(), files.data(), sizes.data(), descs.data(),
-                                             ws.dev_src, stream));
+        // a video element's distinct non-empty frames: each a JPEG file of its own (imdecode COLOR: 3 channels)
+        if (const int D = m_provider->providers()[k]->max_frames())
+            for (int i = 0; i < n; i++) {
+                const decoded_element& e = records[(size_t)i * ne + k];
+                const video_clip&      c = w.clips[k][i];
+                for (size_t d = 0; d < c.frames.size(); d++)
+                    if (c.frames[d].size)
+                        files.push_back(e.data + c.frames[d].offset), sizes.push_back(c.frames[d].size),
+                            descs.push_back(w.clip_descs[k][(size_t)i * D + d]);
+            }
+        // (a window of clips holds many more files than a window of images: calls of a JPEG window's size, so the
+        // stage's two staging sets stay at the size the image path sizes them to)
+        constexpr size_t kJpegCallFiles = 512;
+        for (size_t f = 0; f < files.size(); f += kJpegCallFiles)
+            check(aeon_hip_decode_jpeg_batch(m_ctx, (int)std::min(kJpegCallFiles, files.size() - f), files.data() + f,
+                                             sizes.data() + f, descs.data() + f, ws.dev_src, stream));
     }
     // outputs[] follow get_output_shapes(): a provider may own several buffers (localization_ssd: five)
     const auto& oshapes = m_provider->get_output_shapes();
@@ -1158,8 +1430,17 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     std::vector<bool>  copy_out(no, false); // staged on the device, then one D2H into outputs[k]
     ws.dev_out.resize(no, nullptr), ws.dev_out_cap.resize(no, 0);
     ws.dev_tmp.resize(no, nullptr), ws.dev_tmp_cap.resize(no, 0);
+    // a label provider's host output is written here and now (no device round trip): its outs[] stays null
+    std::vector<bool> host_label(no, false);
+    for (int k = 0; k < ne && !on_device; k++)
+        if (const size_t b = m_provider->providers()[k]->label_bytes()) {
+            const int o = m_provider->output_first(k);
+            host_label[o] = true;
+            for (int i = 0; i < n; i++) std::memcpy((uint8_t*)outputs[o] + (size_t)i * b, &w.labels[k][i], b);
+        }
     for (int k = 0; k < no; k++) {
         const size_t bytes = (size_t)n * oshapes[k].second.byte_size();
+        if (host_label[k]) continue;
         if (on_device) outs[k] = outputs[k];
         else if (void* v = zero_copy_view(outputs[k])) outs[k] = v;
         else {
@@ -1185,11 +1466,13 @@ void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, v
     } else {
         std::vector<void*> tmp(no);
         for (int k = 0; k < no; k++) {
+            if (host_label[k]) continue; // (one element per item: its transpose is itself)
             grow_dev(ws.dev_tmp[k], ws.dev_tmp_cap[k], (size_t)n * oshapes[k].second.byte_size());
             tmp[k] = ws.dev_tmp[k];
         }
         m_provider->post_process(m_ctx, w, ws.dev_src, tmp.data(), stream);
         for (int k = 0; k < no; k++) {
+            if (host_label[k]) continue;
             const shape_type& sh    = oshapes[k].second;
             const size_t      esize = sh.otype.size;
             const size_t      item  = sh.byte_size();
@@ -1340,6 +1623,15 @@ std::vector<aeon_hip::decoded_element> to_elements(aeon_decoder* d, int n, const
             r.metadata = true, r.size = e.size;
             continue;
         }
+        // an AVI datum / a label's bytes: data / size (an empty one is refused per record, with aeon's message)
+        if (d->d->provider().providers()[i % ne]->max_frames()) {
+            r.video = true, r.size = e.size;
+            continue;
+        }
+        if (d->d->provider().providers()[i % ne]->label_bytes()) {
+            r.label = true, r.size = e.size;
+            continue;
+        }
         if (e.width > 0) {
             r.width = e.width, r.height = e.height, r.channels = e.channels;
             r.stride = e.stride ? e.stride : e.width * e.channels;
@@ -1409,9 +1701,9 @@ int aeon_decoder_decode(aeon_decoder* d, int n, const aeon_record_elem* elems, v
 {
     return host_guarded([&] {
         if (!d || (n > 0 && (!elems || !outputs))) throw std::invalid_argument("null argument");
-        if (d->d->provider().has_boxes())
+        if (d->d->provider().has_sized())
             throw std::invalid_argument("aeon_record_elem carries no byte size for the metadata of a boundingbox / "
-                                        "localization_ssd element: use aeon_decoder_decode_encoded");
+                                        "localization_ssd element, a video or a label datum: use aeon_decoder_decode_encoded");
         const int ne = (int)d->d->provider().get_input_count();
         std::vector<aeon_hip::decoded_element> recs((size_t)n * ne);
         for (size_t i = 0; i < recs.size(); i++)
@@ -1427,9 +1719,10 @@ int aeon_decoder_draw_params(aeon_decoder* d, int n, const aeon_record_elem* ele
 {
     return host_guarded([&] {
         if (!d || (n > 0 && (!elems || !params))) throw std::invalid_argument("null argument");
-        if (d->d->provider().has_boxes())
+        if (d->d->provider().has_sized())
             throw std::invalid_argument("aeon_record_elem carries no byte size for the metadata of a boundingbox / "
-                                        "localization_ssd element: the draws of such a config need the records");
+                                        "localization_ssd element, a video or a label datum: the draws of such a config need "
+                                        "the records");
         const int ne = (int)d->d->provider().get_input_count();
         std::vector<aeon_hip::decoded_element> recs((size_t)n * ne);
         for (size_t i = 0; i < recs.size(); i++)

@@ -8,6 +8,8 @@
 //   provider::boundingbox    src/provider.cpp:395-439          (etl type "boundingbox")
 //   provider::localization::ssd src/provider.cpp:289-346       (etl type "localization_ssd")
 //   provider::localization::rcnn src/provider.cpp:222-287      (etl type "localization_rcnn")
+//   provider::video          src/provider.cpp:477-517          (etl type "video": an MJPEG AVI datum)
+//   provider::label          src/provider.cpp:190-216          (etl type "label")
 //   image::config            src/etl_image.hpp:56-96, etl_image.cpp:25-65
 //   batch_decoder            src/batch_decoder.cpp:24-99        (thread pool + deterministic slots)
 //   thread_pool              src/thread_pool.hpp:82-175         (dynamic atomic task counter)
@@ -32,6 +34,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/aeon_hip.h"
+#include "avi_host.hpp"
 #include "box_host.hpp"
 #include "json.hpp"
 #include "param_factory.hpp"
@@ -75,7 +78,19 @@ struct decoded_element {
     bool           encoded = false; // JPEG file: decoded on the device (jpeg_host.cpp)
     int            png_mode   = -1; // PNG file: AEON_PNG_* decode on the host while staging
     bool           metadata   = false; // JSON text of a box provider (data / size), no pixels
+    bool           video      = false; // MJPEG AVI datum of a video provider (data / size): width / height are
+                                       // filled in from its first frame by the demux
+    bool           label      = false; // the datum of a label provider (data / size), no pixels
     int            elem_bytes = 1;  // bytes per sample (2: a 16-bit mask / depth map)
+    bool           no_pixels() const { return metadata || video || label; } // nothing to stage as it stands
+};
+
+// One record of a video provider after video::extractor's demux (avi_host.hpp): the kept frames
+// (the first min(frames of the file, max_frame_count)) and the first frame's JPEG size, which every
+// other non-empty kept frame must have.
+struct video_clip {
+    std::vector<aeon_avi_frame> frames;
+    int                         width = 0, height = 0;
 };
 
 // Per-window staging shared by the providers (filled concurrently by the pool threads).
@@ -98,6 +113,16 @@ struct decode_window {
     uint32_t*                                 rcnn_states_host = nullptr;
     hipEvent_t                                rcnn_states_done = nullptr;
     bool                                      rcnn_states_queued = false; // the copy and its event are on the stream
+    // video providers: the records' demuxed clips; per clip max_frame_count frame descriptors into the source
+    // arena (one slot per distinct decoded frame: an empty chunk repeats the previous frame's) and the number of
+    // kept frames
+    std::vector<std::vector<video_clip>>      clips;       // [provider][record]
+    std::vector<std::vector<aeon_img_desc>>   clip_descs;  // [provider][record * max_frame_count + frame]
+    std::vector<std::vector<int32_t>>         clip_counts; // [provider][record]
+    // label providers: the records' values, and where the provider's output items (n values of its output
+    // type) are staged in the arena for a device output
+    std::vector<std::vector<int32_t>>         labels;       // [provider][record]
+    std::vector<size_t>                       label_offset; // [provider]
 };
 
 // augmentation shared by the ETL providers of one record (provider.cpp:109-119)
@@ -167,6 +192,15 @@ public:
     virtual size_t box_table_bytes(int, size_t) const { return 0; }
     virtual void   stage_boxes(decode_window&, size_t) const {}
     virtual void   launch_boxes(aeon_hip_ctx*, decode_window&, size_t, const uint8_t*, void* const*, void*) const {}
+    // video providers: max_frame_count (0 for every other provider).  Their element is the whole AVI datum:
+    // extract_clip() is video::extractor for record idx -- the demux, the kept frames' JPEG headers, the
+    // element's width / height set to the first frame's -- after which provide() draws like an image's.
+    virtual int  max_frames() const { return 0; }
+    virtual void extract_clip(int, decoded_element&, video_clip&) const {}
+    // label providers: bytes of the output type (0 for every other provider); extract_label() is
+    // label::extractor for record idx.  They draw no params.
+    virtual size_t  label_bytes() const { return 0; }
+    virtual int32_t extract_label(int, const decoded_element&) const { return 0; }
 };
 
 class provider_base : public provider_interface {
@@ -192,6 +226,16 @@ public:
     int  output_first(size_t k) const { return m_out_first[k]; }
     bool has_boxes() const { return m_has_boxes; }
     bool has_rcnn() const { return m_has_rcnn; }
+    bool has_video() const { return m_has_video; }
+    // some element is a datum with a byte size (box metadata, an AVI file, a label): what aeon_record_elem
+    // cannot carry
+    bool has_sized() const { return m_has_boxes || m_has_video || m_has_label; }
+    // video::extractor of every video element of the window, on the pool (before the draws, which need the
+    // first frame's size)
+    void extract_clips(int n, decoded_element* records, decode_window& w, thread_pool& pool) const;
+    // the label providers' output items after `offset` of the arena, and written there
+    size_t layout_labels(decode_window& w, size_t offset) const;
+    void   stage_labels(decode_window& w) const;
     // the box tables of the window's box providers: their size after the window's pixels at `offset`
     // of the arena (layout_boxes), and the tables themselves written there (stage_boxes, which also
     // makes the host-side refusals: rotation, boundingbox::box::expand's precondition)
@@ -203,7 +247,7 @@ public:
 private:
     std::vector<std::unique_ptr<etl_provider>> m_providers;
     std::vector<int>                           m_out_first; // size providers + 1
-    bool                                       m_has_boxes = false, m_has_rcnn = false;
+    bool                                       m_has_boxes = false, m_has_rcnn = false, m_has_video = false, m_has_label = false;
 };
 
 struct provider_factory {

@@ -94,8 +94,11 @@ AEON_HD inline int photo_flags(const aeon_aug_params& p)
 }
 
 // Loader geometry of the output buffer (image::loader, src/etl_image.cpp:246-341).
+// `plane` > 0 overrides the plane stride (elements): video::loader (src/etl_video.cpp:76-107) lays a
+// clip out channel x frame x height x width, so a frame's planes lie max_frame_count frames apart.
 struct OutGeom {
     int32_t fixed_aspect_ratio, canvas_w, canvas_h;
+    int32_t plane = 0;
 };
 
 // The record goes through image::expand (etl_image.cpp:155-159: expand_ratio > 1), a pre-pass.
@@ -132,7 +135,7 @@ AEON_HD inline void plan_direct(const aeon_img_desc& d, uint64_t src_base, const
     // image::loader::load (etl_image.cpp:258-306): planes of the record's own size, or with
     // fixed_aspect_ratio the record at the top-left of the (zeroed) config-sized canvas
     J.out_pitch = o.fixed_aspect_ratio ? o.canvas_w : p.out_w;
-    J.out_plane = o.fixed_aspect_ratio ? o.canvas_w * o.canvas_h : p.out_w * p.out_h;
+    J.out_plane = o.plane > 0 ? o.plane : o.fixed_aspect_ratio ? o.canvas_w * o.canvas_h : p.out_w * p.out_h;
     if (!is_mask) {
         const int photo = photo_flags(p);
         if (photo & PHOTO_BS) plan_bs(J, p.brightness, p.saturation);

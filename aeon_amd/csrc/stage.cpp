@@ -27,6 +27,7 @@
 #include "json.hpp"
 #include "param_factory.hpp"
 #include "plan_record.hpp"
+#include "video_job.hpp"
 
 namespace aeon_hip {
 hipError_t launch_tiles(int km, int rm, bool tail, bool photo, const LaunchArgs& a, int grid, hipStream_t stream,
@@ -51,6 +52,7 @@ hipError_t launch_split(bool tail, int occ, const LaunchArgs& a, const SplitArgs
 hipError_t split_lds_limit(int bytes);
 hipError_t launch_box_targets(const BoxLaunch& L, hipStream_t stream);
 hipError_t launch_rcnn_targets(const RcnnLaunch& L, hipStream_t stream);
+hipError_t launch_clip_pad(const PadRegion* regions, int n_regions, uint64_t max_bytes, hipStream_t stream);
 hipError_t split_occupancy(bool tail, int occ, const LaunchArgs& a, int* blocks);
 hipError_t launch_resize_generic(const ResizeJob* jobs, const uint8_t* table, int n_jobs, int max_tiles, int TR, int CW,
                                  int NR, int xs, int amax, int cn_max, int SW, const float* lut, int bgr, int chm,
@@ -397,7 +399,21 @@ void validate_record(const aeon_img_desc& d, const aeon_aug_params& p, const aeo
     if (!is_mask && (p.n_lighting != 0 && p.n_lighting != 3)) fail(AEON_HIP_EINVAL, "lighting needs 3 values");
 }
 
-OutGeom out_geom(const aeon_out_desc& o) { return OutGeom{o.fixed_aspect_ratio, o.canvas_w, o.canvas_h}; }
+// Where a call's records go when not to out_dev + i * item_stride as planes of their own size: the video
+// call's frames (run_video), frame d of a clip at its item + d * H * W with planes D * H * W apart.
+struct ItemMap {
+    const uint64_t* item;  // record i's output address
+    int32_t         plane; // plane stride (elements)
+};
+uint64_t item_of(const ItemMap* im, const void* out_dev, const aeon_out_desc& o, int i)
+{
+    return im ? im->item[i] : (uint64_t)out_dev + (uint64_t)i * o.item_stride;
+}
+
+OutGeom out_geom(const aeon_out_desc& o, const ItemMap* im = nullptr)
+{
+    return OutGeom{o.fixed_aspect_ratio, o.canvas_w, o.canvas_h, im ? im->plane : 0};
+}
 
 // The cv::resize of a (sw x sh -> dw x dh) resize with interpolation `interp` when the tile kernel
 // has no mode for it: a resize_generic method (CUBIC, LANCZOS4, INTER_AREA but its exact 2x box), or
@@ -690,12 +706,12 @@ ResizeJob resize_job(const AugJob& J, int method, int isx, int isy)
 void plan_image(const aeon_img_desc& d, const void* src_base, const aeon_aug_params& p,
                 const aeon_out_desc& o, uint8_t* out_item, bool is_mask, std::vector<RotJob>& rot,
                 std::vector<ExpandJob>& exp, GrPlan& gr_short, LaunchPlan& pre, GrPlan& gr_main, LaunchPlan& pre2,
-                LaunchPlan& pass1, LaunchPlan& main, size_t& scratch_bytes)
+                LaunchPlan& pass1, LaunchPlan& main, size_t& scratch_bytes, const ItemMap* im = nullptr)
 {
     validate_record(d, p, o, is_mask);
     const int cn = d.channels;
     AugJob    J;
-    plan_direct(d, (uint64_t)src_base, p, out_geom(o), (uint64_t)out_item, is_mask, J);
+    plan_direct(d, (uint64_t)src_base, p, out_geom(o, im), (uint64_t)out_item, is_mask, J);
     if (p.angle != 0) {
         // image::rotate into scratch (interpolated for images, nearest + border 0 for pixel
         // masks, etl_pixel_mask.cpp:72-74); everything after reads the rotated record
@@ -1437,7 +1453,7 @@ bool plan_split(const aeon_hip_ctx* ctx, const std::vector<J_>& geo, LaunchPlan&
 template <typename Phase>
 bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* src_base,
                 const aeon_aug_params* params, const aeon_out_desc& od, void* out_dev, hipStream_t stream,
-                bool is_mask, Phase&& phase)
+                bool is_mask, Phase&& phase, const ItemMap* im = nullptr)
 {
     const OutView        ov = out_view(od);
     const aeon_out_desc& o  = ov.ko; // what the kernels write
@@ -1447,7 +1463,7 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
     if (jobs.size() < (size_t)n) jobs.resize(n);
     int  key = -1, max_h = 0;
     bool vec_ok = !o.fixed_aspect_ratio;
-    const OutGeom og = out_geom(o);
+    const OutGeom og = out_geom(o, im);
     for (int i = 0; i < n; i++) {
         const aeon_img_desc&   d = descs[i];
         const aeon_aug_params& p = params[i];
@@ -1457,14 +1473,15 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
         if (!is_mask && p.interp > AEON_INTERP_NEAREST) return false; // CUBIC / AREA / LANCZOS4 (plan_image)
         validate_record(d, p, o, is_mask);
         AugJob& J = jobs[i];
-        plan_direct(d, (uint64_t)src_base, p, og, (uint64_t)out_dev + (uint64_t)i * o.item_stride, is_mask, J);
+        const uint64_t item = item_of(im, out_dev, o, i);
+        plan_direct(d, (uint64_t)src_base, p, og, item, is_mask, J);
         const int photo = J.photo, mode = J.mode; // (plan_direct: the cv::resize dispatch, photometric flags)
         if ((photo & PHOTO_CONTRAST) || (photo && mode == RESIZE_AREA2X)) return false;
         const bool tail = mode == RESIZE_LINEAR && J.xv < p.out_w * d.channels;
         const int  k    = mode * 4 + (tail ? 2 : 0) + (photo ? 1 : 0);
         if (key < 0) key = k;
         else if (k != key) return false;
-        if ((((uint64_t)out_dev + (uint64_t)i * o.item_stride) & 15) != 0 || (p.out_w & 3) != 0) vec_ok = false;
+        if ((item & 15) != 0 || (p.out_w & 3) != 0) vec_ok = false;
         JobGeom& g = geo[i];
         g.mode = mode, g.cn = d.channels, g.crop_w = p.crop_w, g.crop_h = p.crop_h;
         g.win_w = g.dst_w = p.out_w, g.win_h = g.dst_h = p.out_h, g.photo = photo, g.stats_slot = -1;
@@ -1561,13 +1578,15 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
 template <typename Phase>
 bool run_records(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* src_base,
                  const aeon_aug_params* params, const aeon_out_desc& od, void* out_dev, hipStream_t stream,
-                 bool is_mask, Phase&& phase)
+                 bool is_mask, Phase&& phase, const ItemMap* im = nullptr)
 {
     if (is_mask || n <= 0 || !ctx->records) return false;
     const OutView        ov = out_view(od);
     const aeon_out_desc& o  = ov.ko;
     if (o.dtype != AEON_DTYPE_F32 || !o.channel_major || o.fixed_aspect_ratio || o.channels != 3) return false;
     if ((((uint64_t)out_dev) & 15) != 0 || (o.item_stride & 15) != 0) return false;
+    for (int i = 0; im && i < n; i++)
+        if ((im->item[i] & 15) != 0) return false;
     const int W = params[0].out_w, H = params[0].out_h;
     int       nph = rec_phases(W, H);
     if (ctx->rec_phases > 0 && W / 4 * ctx->rec_phases <= 1024 && (H + ctx->rec_phases - 1) / ctx->rec_phases <= kRecRows)
@@ -1602,12 +1621,11 @@ bool run_records(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const voi
     const float* d_lut = resident_lut(ctx, od, false);
     ensure_ring(ctx, (size_t)n * sizeof(AugJob), 16, 32);
     AugJob*       jt   = (AugJob*)s.host;
-    const OutGeom og   = out_geom(o);
+    const OutGeom og   = out_geom(o, im);
     bool          fast = true;
     double        bytes = 0;
     for (int i = 0; i < n; i++) {
-        plan_direct(descs[i], (uint64_t)src_base, params[i], og, (uint64_t)out_dev + (uint64_t)i * o.item_stride, false,
-                    jt[i]);
+        plan_direct(descs[i], (uint64_t)src_base, params[i], og, item_of(im, out_dev, o, i), false, jt[i]);
         if ((jt[i].photo & PHOTO_BS) && jt[i].bs_kind != BS_FIXPT) fast = false;
         // algorithmic bytes: the crop read once + the float32 output written once
         bytes += (double)params[i].crop_w * params[i].crop_h * 3 + (double)W * H * 3 * 4;
@@ -1659,7 +1677,7 @@ struct MaskSet {
 
 int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* src_base,
               const aeon_aug_params* params, const aeon_out_desc* out, void* out_dev, void* stream_,
-              bool is_mask, const MaskSet* ms = nullptr)
+              bool is_mask, const MaskSet* ms = nullptr, const ItemMap* im = nullptr)
 {
     if (!ctx || n < 0 || (n > 0 && (!descs || !params || !out || !out_dev || !src_base)))
         fail(AEON_HIP_EINVAL, "null argument");
@@ -1700,9 +1718,9 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     HIP_OK(hipSetDevice(ctx->device));
     phase(0);
     // (a pair call goes through the planner: its masks join the images' launch)
-    if (!ms && ctx->direct && run_direct(ctx, n, descs, src_base, params, od, out_dev, stream, is_mask, phase))
+    if (!ms && ctx->direct && run_direct(ctx, n, descs, src_base, params, od, out_dev, stream, is_mask, phase, im))
         return 0;
-    if (!ms && run_records(ctx, n, descs, src_base, params, od, out_dev, stream, is_mask, phase)) return 0;
+    if (!ms && run_records(ctx, n, descs, src_base, params, od, out_dev, stream, is_mask, phase, im)) return 0;
 
     LaunchPlan             pre_all, pre2_all, pass1_all, main_all;
     GrPlan                 gr_short, gr_main;
@@ -1711,7 +1729,7 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     std::vector<Mask16Job> m16;
     size_t     scratch_bytes = 0;
     for (int i = 0; i < n; i++) {
-        uint8_t* item = (uint8_t*)out_dev + (size_t)i * o.item_stride;
+        uint8_t* item = (uint8_t*)item_of(im, out_dev, o, i);
         // pixel masks without rotation (and every 16-bit record): the NEAREST gather pass
         const bool gather = descs[i].elem_bytes == 2 ||
                             (is_mask && descs[i].channels == 1 && o.channels == 1 && params[i].angle == 0 &&
@@ -1719,7 +1737,7 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
         if (gather) plan_mask16(descs[i], src_base, params[i], o, item, is_mask, m16, rot, scratch_bytes);
         else if (descs[i].elem_bytes == 0 || descs[i].elem_bytes == 1)
             plan_image(descs[i], src_base, params[i], o, item, is_mask, rot, exp, gr_short, pre_all, gr_main, pre2_all,
-                       pass1_all, main_all, scratch_bytes);
+                       pass1_all, main_all, scratch_bytes, im);
         else fail(AEON_HIP_EINVAL, "elem_bytes must be 1 (CV_8U) or 2 (CV_16U)");
     }
     for (int i = 0; ms && i < n; i++) // the pair call's masks: the gather pass's jobs
@@ -2004,6 +2022,85 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     phase(6);
     release_slot(ctx, slot, stream);
     phase(7);
+    return 0;
+}
+
+// ---- video ---------------------------------------------------------------------------------------
+// aeon_hip_video_batch: video::transformer + video::loader (src/etl_video.cpp:49-107).  Every kept frame
+// is one record of a run_batch call with its clip's params -- so every pass of the image path takes
+// clips as it takes images -- writing uint8 planes, no channel swap, at item + d * H * W with the planes
+// D * H * W apart (ItemMap); the pad frames of the short clips are one clip_pad launch behind it.
+int run_video(aeon_hip_ctx* ctx, int n, const int32_t* frame_counts, const aeon_img_desc* descs, const void* src_base,
+              const aeon_aug_params* params, int D, int out_w, int out_h, void* out_dev, uint64_t item_stride,
+              void* stream_)
+{
+    if (!ctx || n < 0 || (n > 0 && (!frame_counts || !descs || !params || !out_dev || !src_base)))
+        fail(AEON_HIP_EINVAL, "null argument");
+    if (n == 0) return 0;
+    if (D <= 0 || out_w <= 0 || out_h <= 0) fail(AEON_HIP_EINVAL, "video: invalid max_frame_count or frame size");
+    const uint64_t hw = (uint64_t)out_w * (uint64_t)out_h;
+    if (hw > INT32_MAX || 3 * (uint64_t)D * hw > (uint64_t)INT32_MAX)
+        fail(AEON_HIP_EUNSUPPORTED, "video: a clip item above 2^31 - 1 bytes");
+    const uint64_t item_bytes = 3 * (uint64_t)D * hw;
+    if (item_stride < item_bytes) fail(AEON_HIP_EINVAL, "video: output item does not fit item_stride");
+    uint64_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (frame_counts[i] < 0 || frame_counts[i] > D)
+            fail(AEON_HIP_EINVAL, "video: frame count of clip " + std::to_string(i) + " outside [0, max_frame_count]");
+        if (params[i].out_w != out_w || params[i].out_h != out_h)
+            fail(AEON_HIP_EINVAL, "video: output_size of clip " + std::to_string(i) + " differs from the frame size");
+        total += (uint64_t)frame_counts[i];
+    }
+    // (run_batch's own limit, with the clip in the message: a job table of n * D entries)
+    if (total > 65535) fail(AEON_HIP_EINVAL, "video: at most 65535 frames per call");
+    // (kept between calls: a C3D window's 2,048 frames make these ~300 KB, which allocated per call come
+    // from mmap and cost their page faults again each time)
+    static thread_local std::vector<aeon_img_desc>   fd;
+    static thread_local std::vector<aeon_aug_params> fp;
+    static thread_local std::vector<uint64_t>        items;
+    static thread_local std::vector<PadRegion>       pads;
+    fd.clear(), fp.clear(), items.clear(), pads.clear();
+    fd.reserve(total), fp.reserve(total), items.reserve(total);
+    uint64_t max_pad = 0;
+    for (int i = 0; i < n; i++) {
+        const uint64_t item = (uint64_t)out_dev + (uint64_t)i * item_stride;
+        const int      fc   = frame_counts[i];
+        for (int d = 0; d < fc; d++) {
+            const aeon_img_desc& f = descs[(size_t)i * D + d];
+            // imdecode(ANYDEPTH | COLOR): three channels, also for grayscale files (cap_mjpeg_decoder.cpp:140)
+            if (f.channels != 3 || (f.elem_bytes != 0 && f.elem_bytes != 1))
+                fail(AEON_HIP_EINVAL, "video: frames are 3-channel 8-bit records");
+            fd.push_back(f), fp.push_back(params[i]), items.push_back(item + (uint64_t)d * hw);
+        }
+        if (fc < D) { // the pad frames of one plane are contiguous
+            const uint64_t bytes = (uint64_t)(D - fc) * hw;
+            for (int c = 0; c < 3; c++) pads.push_back(PadRegion{item + ((uint64_t)c * D + (uint64_t)fc) * hw, bytes});
+            max_pad = std::max(max_pad, bytes);
+        }
+    }
+    if (total) {
+        aeon_out_desc o{};
+        o.dtype = AEON_DTYPE_U8, o.channels = 3, o.channel_major = 1;
+        o.item_stride = item_stride; // (validate_record: a frame fits its clip's item)
+        const ItemMap im{items.data(), (int32_t)((uint64_t)D * hw)};
+        run_batch(ctx, (int)total, fd.data(), src_base, fp.data(), &o, out_dev, stream_, false, nullptr, &im);
+    }
+    if (pads.empty()) return 0; // no clip is short: no launch
+    hipStream_t                 stream = (hipStream_t)stream_;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_OK(hipSetDevice(ctx->device));
+    int   slot;
+    Slot& s = take_slot(ctx, stream, slot);
+    const size_t tbytes = pads.size() * sizeof(PadRegion);
+    ensure_ring(ctx, tbytes, 0, 0);
+    std::memcpy(s.host, pads.data(), tbytes);
+    // the table goes to the slot's device copy first, as the planner's job tables do (run_batch): read from the
+    // pinned slot by every work item, its ~4,600 16-byte PCIe reads held the C3D half-short window's launch
+    // at 62 us for 19 MB of zeros
+    if (tbytes > kUploadKernelMax) HIP_OK(hipMemcpyAsync(s.dev, s.host, tbytes, hipMemcpyHostToDevice, stream));
+    else HIP_OK(launch_upload_table(s.host_dev, s.dev, tbytes, stream));
+    HIP_OK(launch_clip_pad((const PadRegion*)s.dev, (int)pads.size(), max_pad, stream));
+    release_slot(ctx, slot, stream);
     return 0;
 }
 
@@ -2505,6 +2602,16 @@ int aeon_hip_depthmap_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs
         if (out && out->fixed_aspect_ratio)
             fail(AEON_HIP_EINVAL, "depthmap::loader has no fixed_aspect_ratio canvas (etl_depthmap.cpp:98-134)");
         return run_batch(ctx, n, descs, src_base, params, out, out_dev, stream, true);
+    });
+}
+
+int aeon_hip_video_batch(aeon_hip_ctx* ctx, int n, const int32_t* frame_counts, const aeon_img_desc* descs,
+                         const void* src_base, const aeon_aug_params* params, int max_frames, int out_w, int out_h,
+                         void* out_dev, uint64_t item_stride, void* stream)
+{
+    return guarded([&] {
+        return run_video(ctx, n, frame_counts, descs, src_base, params, max_frames, out_w, out_h, out_dev, item_stride,
+                         stream);
     });
 }
 

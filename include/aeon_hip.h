@@ -191,6 +191,42 @@ int aeon_jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_
 int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
                                const aeon_img_desc* descs, void* dst_base, void* stream);
 
+/* ---- video: provider::video (src/provider.cpp:477-517, src/etl_video.{hpp,cpp}) ------------------
+ * aeon_avi_frames: video::extractor's demux (MotionJpegCapture, src/cap_mjpeg_decoder.cpp:132-227 over
+ * AviMjpegStream, src/avi.cpp:145-379) of one MJPEG AVI datum.  The frames are the idx1 entries of the
+ * first vids/MJPG stream whose chunk lies inside movi, over every AVI / AVIX list of the datum; frame k
+ * is the `size` bytes at data + `offset` (the chunk's own size; size 0: an empty chunk, for which aeon
+ * repeats the previous frame).  *count receives the number of frames, of which the first min(*count, cap)
+ * are written to frames and are the only ones whose chunk headers are read (cap 0: the count alone);
+ * *width / *height (may be NULL): the main header's dwWidth / dwHeight.  Host only, no context.
+ * AEON_HIP_EINVAL, message in aeon_avi_last_error(), where aeon would dereference null or read past the
+ * datum: not a RIFF AVI file; no MJPG video stream; the index flag (0x10) clear, no idx1 after movi or no
+ * frame in it ("Not a valid AVI file type", aeon's message); a kept frame's chunk that runs past the
+ * datum; an empty first frame. */
+typedef struct aeon_avi_frame {
+    uint64_t offset; /* of the chunk's data from the start of the datum */
+    uint32_t size;   /* the chunk's size as written (no RIFF even-padding) */
+} aeon_avi_frame;
+int aeon_avi_frames(const void* data, size_t size, aeon_avi_frame* frames, int cap, int* count, int* width,
+                    int* height);
+const char* aeon_avi_last_error(void);
+
+/* video::transformer + video::loader (src/etl_video.cpp:49-107) for n clips of at most max_frames (D)
+ * decoded frames each: clip i's first frame_counts[i] <= D frames are descs[i*D ..] (row-major by clip;
+ * the rest of a row is not read; a repeated frame is a desc with the earlier frame's offset), every one
+ * through transform_single_image with params[i], written as raw uint8 planes in source channel order
+ * (B, G, R), channel x frame x height x width: frame d of channel c at
+ * out_dev + i*item_stride + (c*D + d)*out_h*out_w.  Frames frame_counts[i] .. D-1 of every channel are
+ * zero-filled (aeon appends all-zero frames).  No bgr_to_rgb, no standardization, no type conversion: the
+ * loader does none.  Frames are 3-channel; params[i].out_w / out_h must equal out_w / out_h and
+ * item_stride be at least 3*D*out_h*out_w, else AEON_HIP_EINVAL.  The frames run as n*D-at-most records
+ * of one aeon_hip_augment_batch-like call (every pass of it: pre-passes, contrast, the resize methods)
+ * followed by one zero-fill launch when some clip is short.  Asynchronous on `stream` like the other
+ * batch calls. */
+int aeon_hip_video_batch(aeon_hip_ctx* ctx, int n, const int32_t* frame_counts, const aeon_img_desc* descs,
+                         const void* src_base, const aeon_aug_params* params, int max_frames, int out_w, int out_h,
+                         void* out_dev, uint64_t item_stride, void* stream);
+
 /* Wait for `stream` and check the device error word of the calls made on it (each stream has its own
  * word, so a window's check never reads or clears what another stream's kernels set):
  * AEON_HIP_EDEVICE (the word cleared) when a kernel flagged an inconsistency -- an LDS footprint the host sized too small, a dynamic-tail counter
@@ -397,7 +433,7 @@ int aeon_cropbox_max_proportional(float in_w, float in_h, float out_w, float out
 /* ---- decode stage: provider_factory + batch_decoder (host C++ above the kernels) --------------
  * aeon_decoder = batch_decoder (src/batch_decoder.cpp:24-99) over provider_factory::create
  * (src/provider_factory.cpp:24-51) with "image" / "pixelmask" / "boundingbox" / "localization_ssd" /
- * "localization_rcnn" ETL providers.  config_json is the
+ * "localization_rcnn" / "video" / "label" ETL providers.  config_json is the
  * aeon loader configuration ({"batch_size", "random_seed", "node_id", "cpu_list", "etl": [...],
  * "augmentation": [...]}, src/loader.hpp:50-109; unknown keys are rejected like verify_config).
  * Records arrive decoded (image::extractor::extract stays with the caller).
@@ -417,7 +453,28 @@ int aeon_cropbox_max_proportional(float in_w, float in_h, float out_w, float out
  * With random_seed != 0 the engines' states after the shuffles come back with the window and are the
  * slot engines of the next one, as aeon's: a later window waits for that small copy alone before it
  * draws.  With random_seed 0 each record's shuffle engine is seeded by one further draw of the window's
- * engine. */
+ * engine.
+ * video (provider::video, src/provider.cpp:477-517; one buffer {3, max_frame_count, height, width} uint8, B, G, R
+ * planes, channel x frame x height x width): {"type": "video", "max_frame_count" (required), "name", "frame": an
+ * image config}; frame.channels other than 3 is AEON_HIP_EINVAL and a frame.output_type other than uint8_t
+ * AEON_HIP_EUNSUPPORTED (aeon's loader writes three uint8 planes per frame whatever they say); the frame config's
+ * other members are parsed and ignored, as aeon's loader ignores them.  Its element is the whole MJPEG AVI datum,
+ * an aeon_encoded_elem with width == 0.  The param factory is built from augmentation[0]["frame"], not from
+ * augmentation[0] (provider.cpp:483).  Per record: the demux (aeon_avi_frames) of the first max_frame_count frames
+ * -- aeon decodes every frame and drops the later ones: the same output --, params from the first frame's size
+ * unless an earlier element drew, the kept non-empty frames through the JPEG stage (at most 512 files a call),
+ * then aeon_hip_video_batch.  A kept frame of another size than the first, a datum the demux refuses: AEON_HIP_EINVAL
+ * naming the record; an empty datum: "received encoded video with size 0, at idx N".
+ * label (provider::label, src/provider.cpp:190-216; one buffer {1} of output_type, default uint32_t):
+ * {"type": "label", "binary", "name", "output_type"}; the datum is 4 bytes read as a native int (binary) or text
+ * through std::stoi; the first sizeof(output_type) bytes of the int are the item.  A text that is no integer or out
+ * of int's range and a binary datum that is not 4 bytes are AEON_HIP_EINVAL naming the record; an 8-byte output_type
+ * (aeon copies past the int) is AEON_HIP_EUNSUPPORTED.  Host outputs are written directly, device outputs staged in
+ * the window's pinned arena and copied on its stream.  The provider draws no params.  A config of label
+ * elements alone has nothing for the device and is refused ("outside the HIP image stage"), as is a video element
+ * without its "frame" (aeon's "missing image config in json config").
+ * aeon_decoder_decode and aeon_decoder_draw_params refuse a config with a video or a label element as they refuse
+ * the box ones: aeon_record_elem carries no byte size. */
 typedef struct aeon_decoder aeon_decoder;
 
 /* One decoded element of a record: HWC uint8 (BGR) pixels in host memory. */
@@ -446,7 +503,8 @@ int aeon_decoder_draw_params(aeon_decoder* d, int n, const aeon_record_elem* ele
                              int serial);
 /* A record element as aeon's encoded_record holds it (src/buffer_batch.hpp:45-152): an encoded
  * JPEG file (width == 0: data/size, decoded by the JPEG stage with the provider's channel count;
- * for a boundingbox / localization_ssd provider the JSON metadata text),
+ * for a boundingbox / localization_ssd provider the JSON metadata text, for a video provider the AVI file,
+ * for a label provider the label's bytes),
  * or -- width > 0 -- decoded HWC uint8 pixels as in aeon_record_elem (pixel masks must be). */
 typedef struct aeon_encoded_elem {
     const void* data;
