@@ -176,13 +176,26 @@ std::string create_name(const std::string& name, const std::string& base)
     return name.empty() ? base : name + "." + base;
 }
 
-// provider::image (provider.cpp:145-184): make_params when the record has none yet,
-// transform_single_image + image::loader::load on the GPU at post_process time.
-class image_provider : public etl_provider {
+std::string empty_element(const char* what, int idx)
+{
+    return std::string("received ") + what + " with size 0, at idx " + std::to_string(idx);
+}
+
+// provider::image (provider.cpp:145-184): make_params when the record has none yet, transform_single_image +
+// image::loader::load on the GPU at post_process time; and provider::pixelmask (provider.cpp:353-393), which
+// shares the record's image params, resamples with nearest neighbour and neither standardizes nor swaps channels.
+class pixel_provider : public etl_provider {
 public:
-    image_provider(const Json& js, const Json& aug)
-        : m_cfg(js), m_factory(aug), m_name(create_name(m_cfg.name, "image"))
+    pixel_provider(const Json& js, const Json& aug, bool mask)
+        : m_cfg(js), m_factory(aug), m_mask(mask), m_name(create_name(m_cfg.name, mask ? "pixelmask" : "image"))
     {
+        m_out.dtype         = m_cfg.shape.otype.dtype;
+        m_out.channels      = (int)m_cfg.channels;
+        m_out.channel_major = m_cfg.channel_major;
+        m_out.item_stride   = m_cfg.shape.byte_size();
+        m_out.fixed_aspect_ratio = m_factory.fixed_aspect_ratio;
+        m_out.canvas_w = (int)m_cfg.width, m_out.canvas_h = (int)m_cfg.height;
+        if (mask) return;
         // image::loader ctor (etl_image.cpp:204-244)
         const auto& mean = m_factory.mean;
         const auto& std_ = m_factory.stddev;
@@ -192,86 +205,100 @@ public:
             if (mean.size() != m_cfg.channels || std_.size() != m_cfg.channels)
                 invalid("Size of 'mean' and 'stddev' must be equal to number of channels or empty.");
         }
+        m_out.bgr_to_rgb = m_cfg.bgr_to_rgb;
+        m_out.has_mean   = !mean.empty();
+        for (size_t i = 0; i < mean.size() && i < 3; i++) m_out.mean[i] = mean[i], m_out.stddev[i] = std_[i];
     }
-    void provide(int, const decoded_element& in, augmentation& aug, std::minstd_rand0& random,
-                 aeon_aug_params& params, light_split* ls) const override
+    std::vector<std::pair<std::string, shape_type>> output_shapes() const override { return {{m_name, m_cfg.shape}}; }
+    const param_factory* factory() const override { return &m_factory; }
+    const aeon_out_desc* pixel_out(bool mask) const override { return mask == m_mask ? &m_out : nullptr; }
+    void from_abi(const aeon_encoded_elem& in, int idx, decoded_element& e) const override
     {
-        if (!aug.has) {
-            if (ls)
-                m_factory.make_params_split(random, in.width, in.height, (int)m_cfg.width, (int)m_cfg.height,
-                                            ls->entry_avail, &aug.image, &ls->exit_saved);
-            else
-                m_factory.make_params(random, in.width, in.height, (int)m_cfg.width, (int)m_cfg.height, &aug.image);
-            aug.has = true;
+        if (in.width > 0) {
+            e.width = in.width, e.height = in.height, e.channels = in.channels;
+            e.stride = in.stride ? in.stride : in.width * in.channels;
+        } else {
+            if (!in.data || !in.size) throw std::runtime_error(empty_element("encoded image", idx));
+            e.encoded = true, e.size = in.size;
         }
-        params = aug.image;
     }
-    const param_factory& factory() const override { return m_factory; }
-    bool               is_mask() const override { return false; }
-    const shape_type&  shape() const override { return m_cfg.shape; }
-    const std::string& buffer_name() const override { return m_name; }
-    aeon_out_desc      out_desc() const override
+    std::unique_ptr<window_part> new_part(int n) const override
     {
-        aeon_out_desc o{};
-        o.dtype         = m_cfg.shape.otype.dtype;
-        o.channels      = (int)m_cfg.channels;
-        o.channel_major = m_cfg.channel_major;
-        o.bgr_to_rgb    = m_cfg.bgr_to_rgb;
-        o.has_mean      = !m_factory.mean.empty();
-        for (size_t i = 0; i < m_factory.mean.size() && i < 3; i++)
-            o.mean[i] = m_factory.mean[i], o.stddev[i] = m_factory.stddev[i];
-        o.item_stride = m_cfg.shape.byte_size();
-        o.fixed_aspect_ratio = m_factory.fixed_aspect_ratio;
-        o.canvas_w = (int)m_cfg.width, o.canvas_h = (int)m_cfg.height;
-        return o;
+        std::unique_ptr<window_part> p(new window_part);
+        p->descs.resize(n);
+        return p;
+    }
+    // image::extractor::extract of an encoded element: the file's header gives the decoded size; it is decoded
+    // with the provider's channel count (CV_LOAD_IMAGE_COLOR / GRAYSCALE for images, CV_LOAD_IMAGE_ANYDEPTH
+    // for pixel masks).  PNG files are decoded on the host pool while staging (png_host.cpp), JPEG files on
+    // the device.
+    void inspect(window_part&, int idx, decoded_element& e) const override
+    {
+        static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+        const int            cn         = m_out.channels;
+        if (e.encoded && e.size >= 8 && std::memcmp(e.data, kPngSig, 8) == 0) {
+            int depth = 0, ctype = 0;
+            check(aeon_png_info(e.data, e.size, &e.width, &e.height, &depth, &ctype));
+            e.encoded    = false;
+            e.png_mode   = m_mask ? AEON_PNG_ANYDEPTH : (cn == 3 ? AEON_PNG_BGR8 : AEON_PNG_GRAY8);
+            e.channels   = m_mask ? 1 : cn;
+            e.elem_bytes = (m_mask && depth == 16 && ctype != 3) ? 2 : 1;
+            e.stride     = e.width * e.channels * e.elem_bytes;
+        } else if (e.encoded) {
+            if (m_mask)
+                throw std::runtime_error("encoded pixel masks are decoded from PNG files only (JPEG masks: pass the "
+                                         "decoded mask)");
+            int comps = 0;
+            check(aeon_jpeg_info(e.data, e.size, &e.width, &e.height, &comps));
+            e.channels = cn;
+            e.stride   = e.width * e.channels;
+        }
+        if (!e.data || e.width <= 0 || e.height <= 0)
+            throw std::runtime_error(empty_element(m_mask ? "pixelmask" : "encoded image", idx));
+    }
+    void layout_record(window_part& part, arena_region r, int idx, const decoded_element& e, size_t& offset,
+                       jpeg_list& jpegs) const override
+    {
+        if (r != (e.encoded ? arena_region::device_decoded : arena_region::staged)) return;
+        const size_t b = (size_t)std::max(e.width, 0) * std::max(e.height, 0) * std::max(e.channels, 0) * e.elem_bytes;
+        part.descs[idx] = aeon_img_desc{offset, e.width, e.height, e.width * e.channels * e.elem_bytes, e.channels,
+                                        e.elem_bytes == 2 ? 2 : 0, 0};
+        if (e.encoded) jpegs.add(e.data, e.size, part.descs[idx]);
+        offset += arena_align(b);
+    }
+    void stage_record(const decode_window& w, size_t k, int idx, const decoded_element& e) const override
+    {
+        if (e.encoded) return; // decoded on the device, straight into the source arena
+        const size_t row = (size_t)e.width * e.channels * e.elem_bytes;
+        uint8_t*     dst = w.arena + w.parts[k]->descs[idx].offset;
+        if (e.png_mode >= 0) { // extract on this pool thread, straight into the pinned arena
+            check(aeon_decode_png(e.data, e.size, e.png_mode, dst, row, nullptr));
+        } else if ((size_t)e.stride == row) {
+            std::memcpy(dst, e.data, row * e.height);
+        } else {
+            for (int y = 0; y < e.height; y++) std::memcpy(dst + y * row, e.data + (size_t)y * e.stride, row);
+        }
+    }
+    void launch(aeon_hip_ctx* ctx, const decode_window& w, size_t k, const uint8_t* dev_arena, void* const* out,
+                void* stream) const override
+    {
+        const auto batch = m_mask ? aeon_hip_mask_batch : aeon_hip_augment_batch;
+        check(batch(ctx, w.n, w.parts[k]->descs.data(), dev_arena, w.params[k].data(), &m_out, out[0], stream));
+    }
+
+protected:
+    bool draw_over(const window_part&, int, const decoded_element& e, draw_source& s) const override
+    {
+        s = draw_source{e.width, e.height, (int)m_cfg.width, (int)m_cfg.height};
+        return true;
     }
 
 private:
     image_config  m_cfg;
     param_factory m_factory;
+    bool          m_mask;
     std::string   m_name;
-};
-
-// provider::pixelmask (provider.cpp:353-393): shares the record's image params.
-class pixelmask_provider : public etl_provider {
-public:
-    pixelmask_provider(const Json& js, const Json& aug)
-        : m_cfg(js), m_factory(aug), m_name(create_name(m_cfg.name, "pixelmask"))
-    {
-    }
-    void provide(int, const decoded_element& in, augmentation& aug, std::minstd_rand0& random,
-                 aeon_aug_params& params, light_split* ls) const override
-    {
-        if (!aug.has) {
-            if (ls)
-                m_factory.make_params_split(random, in.width, in.height, (int)m_cfg.width, (int)m_cfg.height,
-                                            ls->entry_avail, &aug.image, &ls->exit_saved);
-            else
-                m_factory.make_params(random, in.width, in.height, (int)m_cfg.width, (int)m_cfg.height, &aug.image);
-            aug.has = true;
-        }
-        params = aug.image;
-    }
-    const param_factory& factory() const override { return m_factory; }
-    bool               is_mask() const override { return true; }
-    const shape_type&  shape() const override { return m_cfg.shape; }
-    const std::string& buffer_name() const override { return m_name; }
-    aeon_out_desc      out_desc() const override
-    {
-        aeon_out_desc o{};
-        o.dtype         = m_cfg.shape.otype.dtype;
-        o.channels      = (int)m_cfg.channels;
-        o.channel_major = m_cfg.channel_major;
-        o.item_stride   = m_cfg.shape.byte_size();
-        o.fixed_aspect_ratio = m_factory.fixed_aspect_ratio;
-        o.canvas_w = (int)m_cfg.width, o.canvas_h = (int)m_cfg.height;
-        return o;
-    }
-
-private:
-    image_config  m_cfg;
-    param_factory m_factory;
-    std::string   m_name;
+    aeon_out_desc m_out{};
 };
 
 // boundingbox::config (etl_boundingbox.cpp:27-49, etl_boundingbox.hpp) and localization::ssd::config
@@ -335,50 +362,52 @@ struct box_config {
     }
 };
 
-// What the box providers share: their element is the record's JSON metadata (extract), the first element of a
-// record draws (provide_boxes: make_params over the metadata's image size unless a provider draws otherwise),
-// and the transform + load run in the window's targets launch over the provider's box table (box_job.hpp),
-// staged in the arena with the pixels.
+// What the box providers share: their element is the record's JSON metadata (inspect extracts it), the draw is
+// make_params over the metadata's image size unless a provider draws otherwise, and the transform + load run in
+// the window's targets launch over the provider's box table, staged in the arena with the pixels.
 class box_provider_base : public etl_provider {
 public:
-    void provide(int, const decoded_element&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
-                 light_split*) const override
-    {
-        throw std::logic_error("box providers take their element through provide_boxes");
-    }
-    void extract(const decoded_element& in, box_metadata& m) const override
-    {
-        box_extract(m_label_map, in.data, in.size, m);
-    }
-    void provide_boxes(const box_metadata& m, augmentation& aug, std::minstd_rand0& random, aeon_aug_params& params,
-                       light_split* ls) const override
-    {
-        if (!aug.has) {
-            draw(m, random, aug.image, ls);
-            aug.has = true;
-        }
-        params = aug.image;
-    }
-    const param_factory& factory() const override { return m_factory; }
-    bool               is_mask() const override { return false; }
-    const shape_type&  shape() const override { return m_shapes[0].second; }
-    const std::string& buffer_name() const override { return m_shapes[0].first; }
-    aeon_out_desc      out_desc() const override { return aeon_out_desc{}; }
     std::vector<std::pair<std::string, shape_type>> output_shapes() const override { return m_shapes; }
-    size_t box_table_bytes(int n, size_t total) const override { return aeon_hip::box_table_bytes(n, total, m_ext); }
-    void   stage_boxes(decode_window& w, size_t k) const override
+    const param_factory* factory() const override { return &m_factory; }
+    void from_abi(const aeon_encoded_elem& in, int, decoded_element& e) const override { e.size = in.size; }
+    std::unique_ptr<window_part> new_part(int n) const override
     {
-        const BoxTableHost t(w.arena + w.box_offset[k], w.n, w.box_total[k], m_ext);
+        std::unique_ptr<box_part> p(new box_part);
+        p->boxes.resize(n);
+        return p;
+    }
+    void inspect(window_part& part, int idx, decoded_element& e) const override
+    {
+        if (!e.data || e.size == 0) throw std::runtime_error(empty_element(m_what, idx));
+        box_extract(m_label_map, e.data, e.size, static_cast<box_part&>(part).boxes[idx]);
+    }
+    void layout_window(window_part& part, arena_region r, int n, size_t& offset) const override
+    {
+        if (r != arena_region::box_tables) return;
+        box_part& b = static_cast<box_part&>(part);
+        b.total     = 0;
+        for (const box_metadata& m : b.boxes) b.total += m.labels.size();
+        if (b.total > ((size_t)1 << 26)) invalid("box table too large");
+        b.offset = offset;
+        offset += arena_align(box_table_bytes(n, b.total, m_ext));
+    }
+    // the table, and the host-side refusals (rotation, boundingbox::box::expand's precondition)
+    void stage_window(const decode_window& w, size_t k) const override
+    {
+        const box_part&    b = static_cast<const box_part&>(*w.parts[k]);
+        const BoxTableHost t(w.arena + b.offset, w.n, b.total, m_ext);
         size_t             first = 0;
         for (int i = 0; i < w.n; i++) {
-            stage_record(t, i, first, w.boxes[k][i], w.params[k][i], w);
-            first += w.boxes[k][i].labels.size();
+            stage_box_record(t, i, first, b, w.params[k][i]);
+            first += b.boxes[i].labels.size();
         }
     }
 
 protected:
-    box_provider_base(const Json& aug, size_t width, size_t height, const std::vector<std::string>& class_names, bool ext)
-        : m_factory(aug), m_width((int)width), m_height((int)height), m_label_map(box_label_map(class_names)), m_ext(ext)
+    box_provider_base(const Json& aug, size_t width, size_t height, const std::vector<std::string>& class_names, bool ext,
+                      const char* what)
+        : m_factory(aug), m_width((int)width), m_height((int)height), m_label_map(box_label_map(class_names)), m_ext(ext),
+          m_what(what)
     {
     }
     void add_output(const std::string& name, const char* base, std::vector<size_t> shape, const std::string& type)
@@ -388,16 +417,17 @@ protected:
         st.otype = output_type(type);
         m_shapes.emplace_back(create_name(name, base), st);
     }
-    virtual void draw(const box_metadata& m, std::minstd_rand0& random, aeon_aug_params& p, light_split* ls) const
+    bool draw_over(const window_part& part, int idx, const decoded_element&, draw_source& s) const override
     {
-        if (ls) m_factory.make_params_split(random, m.width, m.height, m_width, m_height, ls->entry_avail, &p, &ls->exit_saved);
-        else m_factory.make_params(random, m.width, m.height, m_width, m_height, &p);
+        const box_metadata& m = static_cast<const box_part&>(part).boxes[idx];
+        s = draw_source{m.width, m.height, m_width, m_height};
+        return true;
     }
     // record i of the window, whose boxes start at `first` of the table's: refused, or written into t
-    virtual void stage_record(const BoxTableHost& t, int i, size_t first, const box_metadata& m, const aeon_aug_params& p,
-                              const decode_window&) const
+    virtual void stage_box_record(const BoxTableHost& t, int i, size_t first, const box_part& b, const aeon_aug_params& p) const
     {
-        const int cnt = (int)m.labels.size();
+        const box_metadata& m   = b.boxes[i];
+        const int           cnt = (int)m.labels.size();
         if (const char* why = box_refusal(p, m.boxes.data(), cnt)) invalid(std::string(why) + ", at idx " + std::to_string(i));
         t.recs[i] = box_rec((uint32_t)first, cnt, p);
         if (cnt) {
@@ -409,7 +439,8 @@ protected:
     param_factory                                   m_factory;
     int                                             m_width, m_height; // the config's: what the params are drawn for
     std::unordered_map<std::string, int>            m_label_map;
-    bool                                            m_ext; // the table carries the rcnn extension
+    bool                                            m_ext;  // the table carries the rcnn extension
+    const char*                                     m_what; // the element, as the empty-element refusal names it
     std::vector<std::pair<std::string, shape_type>> m_shapes;
 };
 
@@ -418,32 +449,34 @@ protected:
 class box_provider : public box_provider_base {
 public:
     box_provider(const Json& js, const Json& aug, int kind) : box_provider(box_config(js, kind), aug) {}
-    void draw(const box_metadata& m, std::minstd_rand0& random, aeon_aug_params& p, light_split* ls) const override
+    void launch(aeon_hip_ctx* ctx, const decode_window& w, size_t k, const uint8_t* dev_arena, void* const* out,
+                void* stream) const override
     {
-        if (m_cfg.kind != AEON_BOX_SSD) return box_provider_base::draw(m, random, p, ls);
-        const int nb = (int)m.labels.size();
-        if (ls)
-            m_factory.make_ssd_params_split(random, m.width, m.height, m_width, m_height, m.boxes.data(), nb, ls->entry_avail,
-                                            &p, &ls->exit_saved);
-        else
-            m_factory.make_ssd_params(random, m.width, m.height, m_width, m_height, m.boxes.data(), nb, &p);
-    }
-    int  box_kind() const override { return m_cfg.kind; }
-    void launch_boxes(aeon_hip_ctx* ctx, decode_window& w, size_t k, const uint8_t* dev_table, void* const* out,
-                      void* stream) const override
-    {
-        aeon_box_out o{};
+        const box_part& b = static_cast<const box_part&>(*w.parts[k]);
+        aeon_box_out    o{};
         o.kind      = m_cfg.kind;
         o.max_boxes = (int)m_cfg.max_boxes;
         o.out_w = m_width, o.out_h = m_height;
         o.emit_type = m_factory.emit_type(), o.emit_min_overlap = m_factory.emit_constraint_min_overlap;
         for (size_t i = 0; i < m_shapes.size(); i++) o.item_stride[i] = m_shapes[i].second.byte_size(), o.buf[i] = out[i];
-        check(box_targets_staged(ctx, w.n, dev_table, w.box_total[k], o, stream));
+        check(box_targets_staged(ctx, w.n, dev_arena + b.offset, b.total, o, stream));
+    }
+
+protected:
+    bool draw_over(const window_part& part, int idx, const decoded_element& e, draw_source& s) const override
+    {
+        box_provider_base::draw_over(part, idx, e, s);
+        if (m_cfg.kind != AEON_BOX_SSD) return true;
+        const box_metadata& m = static_cast<const box_part&>(part).boxes[idx];
+        s.boxes = m.boxes.data(), s.nboxes = (int)m.labels.size();
+        return true;
     }
 
 private:
     box_provider(box_config cfg, const Json& aug)
-        : box_provider_base(aug, cfg.width, cfg.height, cfg.class_names, false), m_cfg(std::move(cfg))
+        : box_provider_base(aug, cfg.width, cfg.height, cfg.class_names, false,
+                            cfg.kind == AEON_BOX_SSD ? "localization_ssd data" : "boundingbox"),
+          m_cfg(std::move(cfg))
     {
         static const char* const ssd_names[5] = {"image_shape", "gt_boxes", "gt_box_count", "gt_class_count",
                                                  "difficult_flag"};
@@ -462,19 +495,23 @@ private:
 class rcnn_provider : public box_provider_base {
 public:
     rcnn_provider(const Json& js, const Json& aug) : rcnn_provider(rcnn_config(js), aug) {}
-    int  box_kind() const override { return AEON_BOX_RCNN; }
-    void stage_record(const BoxTableHost& t, int i, size_t first, const box_metadata& m, const aeon_aug_params& p,
-                      const decode_window& w) const override
+    void take_engines(window_part& part, std::vector<uint32_t>&& words, engine_states* end) const override
     {
-        if (m.labels.size() > (size_t)kRcnnMaxBoxes)
-            throw unsupported_error("localization_rcnn: more than 1024 boxes in a record, at idx " + std::to_string(i));
-        t.ext[i] = rcnn_rec(p, m_factory.fixed_scaling_factor, m_width, m_height, w.rcnn_engine[i]);
-        box_provider_base::stage_record(t, i, first, m, p, w);
+        box_part& b = static_cast<box_part&>(part);
+        b.engines = std::move(words), b.end = end;
     }
-    void launch_boxes(aeon_hip_ctx* ctx, decode_window& w, size_t k, const uint8_t* dev_table, void* const* out,
-                      void* stream) const override
+    void stage_box_record(const BoxTableHost& t, int i, size_t first, const box_part& b, const aeon_aug_params& p) const override
     {
-        aeon_rcnn_out o{};
+        if (b.boxes[i].labels.size() > (size_t)kRcnnMaxBoxes)
+            throw unsupported_error("localization_rcnn: more than 1024 boxes in a record, at idx " + std::to_string(i));
+        t.ext[i] = rcnn_rec(p, m_factory.fixed_scaling_factor, m_width, m_height, b.engines[i]);
+        box_provider_base::stage_box_record(t, i, first, b, p);
+    }
+    void launch(aeon_hip_ctx* ctx, const decode_window& w, size_t k, const uint8_t* dev_arena, void* const* out,
+                void* stream) const override
+    {
+        const box_part& b = static_cast<const box_part&>(*w.parts[k]);
+        aeon_rcnn_out   o{};
         o.total_anchors  = (int32_t)m_cfg.total_anchors();
         o.max_gt_boxes   = (int32_t)m_cfg.max_gt_boxes;
         o.rois_per_image = (int32_t)m_cfg.rois_per_image;
@@ -486,19 +523,20 @@ public:
         o.anchors              = m_anchors.data();
         o.anchors_key          = m_anchors_key;
         for (size_t i = 0; i < m_shapes.size(); i++) o.item_stride[i] = m_shapes[i].second.byte_size(), o.buf[i] = out[i];
-        check(rcnn_targets_staged(ctx, w.n, dev_table, w.box_total[k], o, 1, w.rcnn_states_dev, stream));
-        if (w.rcnn_states_dev) { // the engines' end states, right behind the kernel
-            hip_check(hipMemcpyAsync(w.rcnn_states_host, w.rcnn_states_dev, (size_t)w.n * sizeof(uint32_t),
-                                     hipMemcpyDeviceToHost, (hipStream_t)stream),
+        engine_states* end = b.end && b.end->dev ? b.end : nullptr;
+        check(rcnn_targets_staged(ctx, w.n, dev_arena + b.offset, b.total, o, 1, end ? end->dev : nullptr, stream));
+        if (end) { // the engines' end states, right behind the kernel
+            hip_check(hipMemcpyAsync(end->host, end->dev, (size_t)w.n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                     (hipStream_t)stream),
                       "hipMemcpyAsync");
-            hip_check(hipEventRecord(w.rcnn_states_done, (hipStream_t)stream), "hipEventRecord");
-            w.rcnn_states_queued = true;
+            hip_check(hipEventRecord(end->done, (hipStream_t)stream), "hipEventRecord");
+            end->queued = true;
         }
     }
 
 private:
     rcnn_provider(rcnn_config cfg, const Json& aug)
-        : box_provider_base(aug, cfg.width, cfg.height, cfg.class_names, true), m_cfg(std::move(cfg))
+        : box_provider_base(aug, cfg.width, cfg.height, cfg.class_names, true, "localization_rcnn data"), m_cfg(std::move(cfg))
     {
         if (m_cfg.total_anchors() > kRcnnMaxAnchors)
             throw unsupported_error("localization_rcnn: total_anchors " + std::to_string(m_cfg.total_anchors()) +
@@ -577,26 +615,23 @@ public:
         : m_cfg(js), m_factory(aug.has("frame") ? aug.at("frame") : Json()), m_name(create_name(m_cfg.name, "video"))
     {
     }
-    void provide(int, const decoded_element& in, augmentation& aug, std::minstd_rand0& random, aeon_aug_params& params,
-                 light_split* ls) const override
+    std::vector<std::pair<std::string, shape_type>> output_shapes() const override { return {{m_name, m_cfg.shape}}; }
+    const param_factory* factory() const override { return &m_factory; }
+    void from_abi(const aeon_encoded_elem& in, int, decoded_element& e) const override { e.size = in.size; }
+    std::unique_ptr<window_part> new_part(int n) const override
     {
-        if (!aug.has) {
-            if (ls)
-                m_factory.make_params_split(random, in.width, in.height, (int)m_cfg.frame.width, (int)m_cfg.frame.height,
-                                            ls->entry_avail, &aug.image, &ls->exit_saved);
-            else
-                m_factory.make_params(random, in.width, in.height, (int)m_cfg.frame.width, (int)m_cfg.frame.height,
-                                      &aug.image);
-            aug.has = true;
-        }
-        params = aug.image;
+        std::unique_ptr<video_part> p(new video_part);
+        p->clips.resize(n), p->counts.assign(n, 0);
+        p->descs.assign((size_t)n * m_cfg.max_frame_count, aeon_img_desc{});
+        return p;
     }
-    int  max_frames() const override { return (int)m_cfg.max_frame_count; }
-    void extract_clip(int idx, decoded_element& e, video_clip& c) const override
+    // video::extractor: the demux, the kept frames' JPEG headers, the element's size set to the first frame's
+    void inspect(window_part& part, int idx, decoded_element& e) const override
     {
+        video_clip&       c  = static_cast<video_part&>(part).clips[idx];
         const std::string at = ", at idx " + std::to_string(idx);
         if (!e.data || e.size == 0) throw std::runtime_error("received encoded video with size 0" + at);
-        const int   D = max_frames();
+        const int   D = (int)m_cfg.max_frame_count;
         int         count = 0, aw = 0, ah = 0;
         std::string err;
         c.frames.assign((size_t)D, aeon_avi_frame{});
@@ -614,17 +649,43 @@ public:
                         ", the first frame " + std::to_string(c.width) + "x" + std::to_string(c.height) + at);
         }
         e.width = c.width, e.height = c.height, e.channels = 3, e.stride = c.width * 3;
+        if (e.width <= 0 || e.height <= 0) throw std::runtime_error("received encoded video with size 0" + at);
     }
-    const param_factory& factory() const override { return m_factory; }
-    bool               is_mask() const override { return false; }
-    const shape_type&  shape() const override { return m_cfg.shape; }
-    const std::string& buffer_name() const override { return m_name; }
-    aeon_out_desc      out_desc() const override
+    // one source-arena slot per distinct non-empty frame of the clip, each a JPEG file of its own (imdecode COLOR:
+    // 3 channels); an empty chunk's frame is the previous frame's slot again (cap_mjpeg_decoder.cpp:138-141)
+    void layout_record(window_part& part, arena_region r, int idx, const decoded_element& e, size_t& offset,
+                       jpeg_list& jpegs) const override
     {
-        aeon_out_desc o{};
-        o.dtype = AEON_DTYPE_U8, o.channels = 3, o.channel_major = 1;
-        o.item_stride = m_cfg.shape.byte_size();
-        return o;
+        if (r != arena_region::device_decoded) return;
+        video_part&       v   = static_cast<video_part&>(part);
+        const video_clip& c   = v.clips[idx];
+        aeon_img_desc*    row = &v.descs[(size_t)idx * m_cfg.max_frame_count];
+        for (size_t d = 0; d < c.frames.size(); d++) {
+            if (c.frames[d].size == 0) {
+                row[d] = row[d - 1]; // (the demux refuses an empty first frame)
+                continue;
+            }
+            row[d] = aeon_img_desc{offset, c.width, c.height, c.width * 3, 3, 0, 0};
+            jpegs.add(e.data + c.frames[d].offset, c.frames[d].size, row[d]);
+            offset += arena_align((size_t)c.width * c.height * 3);
+        }
+        v.counts[idx] = (int32_t)c.frames.size();
+    }
+    // video::transformer + loader over the clip's decoded frames
+    void launch(aeon_hip_ctx* ctx, const decode_window& w, size_t k, const uint8_t* dev_arena, void* const* out,
+                void* stream) const override
+    {
+        const video_part& v = static_cast<const video_part&>(*w.parts[k]);
+        check(aeon_hip_video_batch(ctx, w.n, v.counts.data(), v.descs.data(), dev_arena, w.params[k].data(),
+                                   (int)m_cfg.max_frame_count, (int)m_cfg.frame.width, (int)m_cfg.frame.height, out[0],
+                                   m_cfg.shape.byte_size(), stream));
+    }
+
+protected:
+    bool draw_over(const window_part&, int, const decoded_element& e, draw_source& s) const override
+    {
+        s = draw_source{e.width, e.height, (int)m_cfg.frame.width, (int)m_cfg.frame.height};
+        return true;
     }
 
 private:
@@ -636,10 +697,10 @@ private:
 // label::config / extractor / loader (etl_label.hpp:36-150) and provider::label (provider.cpp:190-216): shape
 // {1} of output_type (default uint32_t); the datum is 4 bytes read as a native int (binary) or text through
 // std::stoi, and the loader copies the first sizeof(output_type) bytes of that int.  With an 8-byte
-// output_type aeon copies 4 bytes past the int: refused here.
+// output_type aeon copies 4 bytes past the int: refused here.  The provider draws no params.
 class label_provider : public etl_provider {
 public:
-    explicit label_provider(const Json& js) : m_factory(Json())
+    explicit label_provider(const Json& js)
     {
         std::string otype = "uint32_t", name, type;
         get_str(js, "name", name);
@@ -654,125 +715,157 @@ public:
             throw unsupported_error("label: an 8-byte 'output_type' (aeon's loader copies past its int)");
         m_name = create_name(name, "label");
     }
-    void provide(int, const decoded_element&, augmentation&, std::minstd_rand0&, aeon_aug_params&, light_split*) const override
+    std::vector<std::pair<std::string, shape_type>> output_shapes() const override { return {{m_name, m_shape}}; }
+    const param_factory* factory() const override { return nullptr; }
+    void from_abi(const aeon_encoded_elem& in, int, decoded_element& e) const override { e.size = in.size; }
+    std::unique_ptr<window_part> new_part(int n) const override
     {
-        throw std::logic_error("label providers draw no params");
+        std::unique_ptr<label_part> p(new label_part);
+        p->values.resize(n);
+        return p;
     }
-    size_t  label_bytes() const override { return m_shape.otype.size; }
-    int32_t extract_label(int idx, const decoded_element& e) const override
+    // label::extractor
+    void inspect(window_part& part, int idx, decoded_element& e) const override
     {
+        int32_t&          v  = static_cast<label_part&>(part).values[idx];
         const std::string at = ", at idx " + std::to_string(idx);
         if (!e.data || e.size == 0) throw std::runtime_error("received encoded image with size 0" + at);
         if (m_binary) {
             if (e.size != 4)
                 invalid("Only 4 byte buffers can be loaded as int32.  label_extractor::extract received " +
                         std::to_string(e.size) + " bytes" + at);
-            int32_t v;
             std::memcpy(&v, e.data, 4);
-            return v;
+            return;
         }
         try {
-            return (int32_t)std::stoi(std::string((const char*)e.data, e.size));
+            v = (int32_t)std::stoi(std::string((const char*)e.data, e.size));
         } catch (const std::invalid_argument&) {
             invalid("Cannot convert label '" + std::string((const char*)e.data, std::min<size_t>(e.size, 32)) + "' to integer" + at);
         } catch (const std::out_of_range&) {
             invalid("String to int conversion out of range error" + at);
         }
     }
-    const param_factory& factory() const override { return m_factory; }
-    bool               is_mask() const override { return false; }
-    const shape_type&  shape() const override { return m_shape; }
-    const std::string& buffer_name() const override { return m_name; }
-    aeon_out_desc      out_desc() const override { return aeon_out_desc{}; }
+    void layout_window(window_part& part, arena_region r, int n, size_t& offset) const override
+    {
+        if (r != arena_region::label_items) return;
+        static_cast<label_part&>(part).offset = offset;
+        offset += arena_align((size_t)n * m_shape.otype.size);
+    }
+    void stage_window(const decode_window& w, size_t k) const override
+    {
+        const label_part& l = static_cast<const label_part&>(*w.parts[k]);
+        host_output(l, w.n, w.arena + l.offset);
+    }
+    void launch(aeon_hip_ctx*, const decode_window& w, size_t k, const uint8_t*, void* const* out, void* stream) const override
+    {
+        if (!out[0]) return; // a host output: written by host_output
+        const label_part& l = static_cast<const label_part&>(*w.parts[k]);
+        hip_check(hipMemcpyAsync(out[0], w.arena + l.offset, (size_t)w.n * m_shape.otype.size, hipMemcpyHostToDevice,
+                                 (hipStream_t)stream),
+                  "hipMemcpyAsync");
+    }
+    // label::loader::load (etl_label.hpp:141-146): the first sizeof(output_type) bytes of the int
+    bool host_output(const window_part& part, int n, void* out) const override
+    {
+        const size_t b = m_shape.otype.size;
+        for (int i = 0; i < n; i++) std::memcpy((uint8_t*)out + (size_t)i * b, &static_cast<const label_part&>(part).values[i], b);
+        return true;
+    }
+
+protected:
+    bool draw_over(const window_part&, int, const decoded_element&, draw_source&) const override { return false; }
 
 private:
-    bool          m_binary = false;
-    shape_type    m_shape;
-    param_factory m_factory; // (none: the provider draws no params)
-    std::string   m_name;
+    bool        m_binary = false;
+    shape_type  m_shape;
+    std::string m_name;
 };
 
 } // namespace
 
+// The first element of a record that draws makes the record's params (localization_ssd: make_ssd_params over
+// the extracted boxes, the others make_params); every later element copies them.
+void etl_provider::draw(const window_part& part, int idx, const decoded_element& e, augmentation& aug,
+                        std::minstd_rand0& random, aeon_aug_params& params, light_split* ls) const
+{
+    draw_source s;
+    if (!draw_over(part, idx, e, s)) return;
+    if (!aug.has) {
+        const param_factory& f = *factory();
+        aeon_aug_params*     p = &aug.image;
+        if (s.nboxes >= 0 && ls)
+            f.make_ssd_params_split(random, s.in_w, s.in_h, s.out_w, s.out_h, s.boxes, s.nboxes, ls->entry_avail, p, &ls->exit_saved);
+        else if (s.nboxes >= 0) f.make_ssd_params(random, s.in_w, s.in_h, s.out_w, s.out_h, s.boxes, s.nboxes, p);
+        else if (ls) f.make_params_split(random, s.in_w, s.in_h, s.out_w, s.out_h, ls->entry_avail, p, &ls->exit_saved);
+        else f.make_params(random, s.in_w, s.in_h, s.out_w, s.out_h, p);
+        aug.has = true;
+    }
+    params = aug.image;
+}
+
 provider_base::provider_base(const Json& js, const std::vector<Json>& etl, const Json& aug)
     : provider_interface(js, etl.size())
 {
+    bool device_work = false;
     for (const Json& j : etl) {
         std::string type;
         without_type(j, type);
         std::unique_ptr<etl_provider> p;
-        if (type == "image") p.reset(new image_provider(j, aug));
-        else if (type == "pixelmask") p.reset(new pixelmask_provider(j, aug));
+        if (type == "image") p.reset(new pixel_provider(j, aug, false));
+        else if (type == "pixelmask") p.reset(new pixel_provider(j, aug, true));
         else if (type == "boundingbox") p.reset(new box_provider(j, aug, AEON_BOX_BOUNDINGBOX));
         else if (type == "localization_ssd") p.reset(new box_provider(j, aug, AEON_BOX_SSD));
         else if (type == "localization_rcnn") {
-            if (m_has_rcnn) invalid("one localization_rcnn element per record");
+            if (m_shuffler >= 0) invalid("one localization_rcnn element per record");
             p.reset(new rcnn_provider(j, aug));
-            m_has_rcnn = true;
-        } else if (type == "video") {
-            p.reset(new video_provider(j, aug));
-            m_has_video = true;
-        } else if (type == "label") {
-            p.reset(new label_provider(j));
-            m_has_label = true;
-        } else if (type == "blob" || type == "char_map" || type == "label_map")
+            m_shuffler = (int)m_providers.size();
+        } else if (type == "video") p.reset(new video_provider(j, aug));
+        else if (type == "label") p.reset(new label_provider(j));
+        else if (type == "blob" || type == "char_map" || type == "label_map")
             throw std::runtime_error("etl type '" + type + "' is outside the HIP image stage");
         else
             invalid("unsupported etl type '" + type + "'");
         m_out_first.push_back((int)m_output_shapes.size());
         for (auto& s : p->output_shapes()) m_output_shapes.push_back(std::move(s));
-        m_has_boxes = m_has_boxes || p->box_kind() >= 0;
+        m_has_sized = m_has_sized || (type != "image" && type != "pixelmask");
+        device_work = device_work || type != "label";
         m_providers.push_back(std::move(p));
     }
     m_out_first.push_back((int)m_output_shapes.size());
     // A record of labels alone has no pixels, boxes or clips: the decode stage would open a device to copy a few
     // ints.  aeon's CPU provider is the place for such a config; here label is the companion of a device element.
-    bool device_work = false;
-    for (const auto& p : m_providers) device_work = device_work || p->label_bytes() == 0;
     if (!device_work && !m_providers.empty())
         throw std::runtime_error("etl type 'label' on its own is outside the HIP image stage: it accompanies an image, "
                                  "pixelmask, box or video element");
 }
 
-void provider_base::provide(int idx, const decoded_element* elems, decode_window& w,
-                            std::minstd_rand0& random) const
+decode_window provider_base::new_window(int n) const
 {
-    draw(idx, elems, w, random);
-    stage(idx, elems, w);
+    decode_window w;
+    w.n = n;
+    w.params.assign(m_providers.size(), std::vector<aeon_aug_params>(n));
+    for (const auto& p : m_providers) w.parts.push_back(p->new_part(n));
+    return w;
+}
+
+void provider_base::inspect_window(int n, decoded_element* records, decode_window& w, thread_pool& pool) const
+{
+    const size_t ne = m_providers.size();
+    // tasks of consecutive records, about eight per worker: a record's inspection may be a clip's demux or a
+    // null check, and a task per record cost a 1,024-record window of decoded images 200 us of task hand-out
+    const int chunk = std::max(1, n / (8 * pool.size()));
+    pool.run((n + chunk - 1) / chunk, [&](int t) {
+        for (int i = t * chunk; i < std::min(n, (t + 1) * chunk); i++)
+            for (size_t k = 0; k < ne; k++) m_providers[k]->inspect(*w.parts[k], i, records[(size_t)i * ne + k]);
+    });
 }
 
 void provider_base::draw(int idx, const decoded_element* elems, decode_window& w, std::minstd_rand0& random,
                          light_split* ls) const
 {
     augmentation aug;
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        const decoded_element& e = elems[k];
-        if (m_providers[k]->box_kind() >= 0) { // metadata: extract, then the record's (shared) params
-            if (!e.data || e.size == 0) {
-                std::stringstream ss;
-                const int kind = m_providers[k]->box_kind();
-                ss << "received "
-                   << (kind == AEON_BOX_SSD ? "localization_ssd data" : kind == AEON_BOX_RCNN ? "localization_rcnn data" : "boundingbox")
-                   << " with size 0, at idx " << idx;
-                throw std::runtime_error(ss.str());
-            }
-            box_metadata& m = w.boxes[k][idx];
-            m_providers[k]->extract(e, m);
-            m_providers[k]->provide_boxes(m, aug, random, w.params[k][idx], ls);
-            continue;
-        }
-        if (m_providers[k]->label_bytes()) { // label::extractor; the provider draws no params
-            w.labels[k][idx] = m_providers[k]->extract_label(idx, e);
-            continue;
-        }
-        if (!e.data || e.width <= 0 || e.height <= 0) {
-            std::stringstream ss;
-            ss << "received " << (m_providers[k]->is_mask() ? "pixelmask" : m_providers[k]->max_frames() ? "encoded video" : "encoded image")
-               << " with size 0, at idx " << idx;
-            throw std::runtime_error(ss.str());
-        }
-        m_providers[k]->provide(idx, e, aug, random, w.params[k][idx], ls);
-    }
+    for (size_t k = 0; k < m_providers.size(); k++)
+        m_providers[k]->draw(*w.parts[k], idx, elems[k], aug, random, w.params[k][idx], ls);
 }
 
 // aeon runs provide() -- make_params included -- on its pool threads (batch_decoder.cpp:62-71); with
@@ -787,8 +880,8 @@ void provider_base::draw_window(int n, const decoded_element* records, decode_wi
 {
     const size_t ne = m_providers.size();
     size_t first = 0; // the first element that draws (aug.has after it): label providers draw nothing
-    while (first + 1 < ne && m_providers[first]->label_bytes()) first++;
-    const param_factory& F = m_providers[first]->factory();
+    while (first + 1 < ne && !m_providers[first]->factory()) first++;
+    const param_factory& F = *m_providers[first]->factory();
     const bool               lit = F.lighting_on();
     std::vector<light_split> ls(lit ? n : 0);
     const bool               a0 = F.light_avail();
@@ -816,130 +909,45 @@ void provider_base::draw_window(int n, const decoded_element* records, decode_wi
     F.set_light_state(!ls[n - 1].entry_avail, cached);
 }
 
-void provider_base::stage(int idx, const decoded_element* elems, decode_window& w) const
-{
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        const decoded_element& e = elems[k];
-        if (e.encoded || e.no_pixels()) continue; // decoded on the device, straight into the source arena / no pixels
-        const size_t row = (size_t)e.width * e.channels * e.elem_bytes;
-        uint8_t*     dst = w.arena + w.offset[k][idx];
-        if (e.png_mode >= 0) { // extract on this pool thread, straight into the pinned arena
-            check(aeon_decode_png(e.data, e.size, e.png_mode, dst, row, nullptr));
-        } else if ((size_t)e.stride == row) {
-            std::memcpy(dst, e.data, row * e.height);
-        } else {
-            for (int y = 0; y < e.height; y++) std::memcpy(dst + y * row, e.data + (size_t)y * e.stride, row);
-        }
-    }
-}
-
-void provider_base::post_process(aeon_hip_ctx* ctx, decode_window& w, const uint8_t* dev_arena,
-                                 void* const* outputs, void* stream) const
-{
-    // image + pixelmask with the same params per record (provider.cpp:365-393): one pair call, whose
-    // masks run inside the image launch
-    if (m_providers.size() == 2 && m_providers[0]->box_kind() < 0 && !m_providers[0]->is_mask() &&
-        m_providers[1]->is_mask() && w.n > 0 &&
-        std::memcmp(w.params[0].data(), w.params[1].data(), (size_t)w.n * sizeof(aeon_aug_params)) == 0) {
-        aeon_out_desc io = m_providers[0]->out_desc(), mo = m_providers[1]->out_desc();
-        check(aeon_hip_augment_pair_batch(ctx, w.n, w.descs[0].data(), dev_arena, w.descs[1].data(), dev_arena,
-                                          w.params[0].data(), &io, outputs[0], &mo, outputs[1], stream));
-        return;
-    }
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        const etl_provider& p = *m_providers[k];
-        void* const*        out = outputs + m_out_first[k];
-        if (p.box_kind() >= 0) { // the window's box launch, over the table staged with the pixels
-            p.launch_boxes(ctx, w, k, dev_arena + w.box_offset[k], out, stream);
-            continue;
-        }
-        if (p.max_frames()) { // video::transformer + loader over the clip's decoded frames
-            const auto& sh = p.shape().shape; // {channels, frames, height, width}
-            check(aeon_hip_video_batch(ctx, w.n, w.clip_counts[k].data(), w.clip_descs[k].data(), dev_arena,
-                                       w.params[k].data(), (int)sh[1], (int)sh[3], (int)sh[2], out[0], p.shape().byte_size(),
-                                       stream));
-            continue;
-        }
-        if (p.label_bytes()) { // label::loader; a host output was written while staging (out[0] null)
-            if (out[0])
-                hip_check(hipMemcpyAsync(out[0], w.arena + w.label_offset[k], (size_t)w.n * p.label_bytes(),
-                                         hipMemcpyHostToDevice, (hipStream_t)stream),
-                          "hipMemcpyAsync");
-            continue;
-        }
-        aeon_out_desc o = p.out_desc();
-        if (p.is_mask())
-            check(aeon_hip_mask_batch(ctx, w.n, w.descs[k].data(), dev_arena, w.params[k].data(), &o, out[0], stream));
-        else
-            check(aeon_hip_augment_batch(ctx, w.n, w.descs[k].data(), dev_arena, w.params[k].data(), &o, out[0], stream));
-    }
-}
-
-size_t provider_base::layout_boxes(decode_window& w, size_t offset) const
-{
-    w.box_offset.assign(m_providers.size(), 0);
-    w.box_total.assign(m_providers.size(), 0);
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        if (m_providers[k]->box_kind() < 0) continue;
-        size_t total = 0;
-        for (int i = 0; i < w.n; i++) total += w.boxes[k][i].labels.size();
-        if (total > ((size_t)1 << 26)) invalid("box table too large");
-        w.box_offset[k] = offset;
-        w.box_total[k]  = total;
-        offset += (m_providers[k]->box_table_bytes(w.n, total) + 15) & ~(size_t)15;
-    }
-    return offset;
-}
-
-void provider_base::extract_clips(int n, decoded_element* records, decode_window& w, thread_pool& pool) const
+void provider_base::layout(window_plan& p) const
 {
     const size_t ne = m_providers.size();
-    pool.run(n, [&](int i) {
-        for (size_t k = 0; k < ne; k++)
-            if (m_providers[k]->max_frames()) m_providers[k]->extract_clip(i, records[(size_t)i * ne + k], w.clips[k][i]);
+    size_t       offset = 0;
+    p.jpegs.assign(ne, jpeg_list{});
+    for (arena_region r : {arena_region::box_tables, arena_region::label_items})
+        for (size_t k = 0; k < ne; k++) m_providers[k]->layout_window(*p.w.parts[k], r, p.w.n, offset);
+    for (arena_region r : {arena_region::staged, arena_region::device_decoded}) {
+        for (int i = 0; i < p.w.n; i++)
+            for (size_t k = 0; k < ne; k++)
+                m_providers[k]->layout_record(*p.w.parts[k], r, i, p.records[(size_t)i * ne + k], offset, p.jpegs[k]);
+        if (r == arena_region::staged) p.staged = offset;
+    }
+    p.total = std::max<size_t>(offset, 16);
+}
+
+void provider_base::stage(const window_plan& p, thread_pool& pool) const
+{
+    const size_t ne = m_providers.size();
+    for (size_t k = 0; k < ne; k++) m_providers[k]->stage_window(p.w, k);
+    pool.run(p.w.n, [&](int i) {
+        for (size_t k = 0; k < ne; k++) m_providers[k]->stage_record(p.w, k, i, p.records[(size_t)i * ne + k]);
     });
 }
 
-size_t provider_base::layout_labels(decode_window& w, size_t offset) const
+void provider_base::post_process(aeon_hip_ctx* ctx, const decode_window& w, const uint8_t* dev_arena, void* const* outputs,
+                                 void* stream) const
 {
-    w.label_offset.assign(m_providers.size(), 0);
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        if (!m_providers[k]->label_bytes()) continue;
-        w.label_offset[k] = offset;
-        offset += ((size_t)w.n * m_providers[k]->label_bytes() + 15) & ~(size_t)15;
+    // image + pixelmask with the same params per record (provider.cpp:365-393): one pair call, whose
+    // masks run inside the image launch
+    const aeon_out_desc *io = nullptr, *mo = nullptr;
+    if (m_providers.size() == 2 && (io = m_providers[0]->pixel_out(false)) && (mo = m_providers[1]->pixel_out(true)) &&
+        w.n > 0 && std::memcmp(w.params[0].data(), w.params[1].data(), (size_t)w.n * sizeof(aeon_aug_params)) == 0) {
+        check(aeon_hip_augment_pair_batch(ctx, w.n, w.parts[0]->descs.data(), dev_arena, w.parts[1]->descs.data(), dev_arena,
+                                          w.params[0].data(), io, outputs[0], mo, outputs[1], stream));
+        return;
     }
-    return offset;
-}
-
-// label::loader::load (etl_label.hpp:141-146): the first sizeof(output_type) bytes of the int
-void provider_base::stage_labels(decode_window& w) const
-{
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        const size_t b = m_providers[k]->label_bytes();
-        for (int i = 0; b && i < w.n; i++) std::memcpy(w.arena + w.label_offset[k] + (size_t)i * b, &w.labels[k][i], b);
-    }
-}
-
-void provider_base::stage_boxes(decode_window& w) const
-{
     for (size_t k = 0; k < m_providers.size(); k++)
-        if (m_providers[k]->box_kind() >= 0) m_providers[k]->stage_boxes(w, k);
-}
-
-decode_window provider_base::new_window(int n) const
-{
-    decode_window w;
-    w.n = n;
-    w.params.assign(m_providers.size(), std::vector<aeon_aug_params>(n));
-    w.boxes.resize(m_providers.size());
-    w.clips.resize(m_providers.size());
-    w.labels.resize(m_providers.size());
-    for (size_t k = 0; k < m_providers.size(); k++) {
-        if (m_providers[k]->box_kind() >= 0) w.boxes[k].resize(n);
-        if (m_providers[k]->max_frames()) w.clips[k].resize(n);
-        if (m_providers[k]->label_bytes()) w.labels[k].resize(n);
-    }
-    return w;
+        m_providers[k]->launch(ctx, w, k, dev_arena, outputs + m_out_first[k], stream);
 }
 
 std::shared_ptr<provider_base> provider_factory::create(const Json& config)
@@ -1257,257 +1265,204 @@ void grow_dev(uint8_t*& p, size_t& cap, size_t bytes)
 
 // One decode window on `stream` using window slot ws (whose previous window has completed):
 // batch_decoder::filler (batch_decoder.cpp:73-99) with the per-record body split into
-//   host:   JPEG headers -> make_params (record order: aeon's deterministic draw order) ->
-//           decoded pixels staged into pinned memory on the pool -> JPEG entropy decode
-//   device: H2D of the staged pixels -> JPEG IDCT/colour into the source arena -> augmentation
-//           kernels (post_process) -> [batch transpose] -> host outputs: stored there directly
-//           when pinned (zero_copy_view), else staged on the device + one D2H
+//   plan:          inspect (headers, demux, metadata) -> make_params (aeon's deterministic draw order) ->
+//                  the arena layout; host only
+//   stage_sources: staged bytes into pinned memory on the pool -> one H2D -> JPEG entropy decode and
+//                  IDCT/colour into the source arena
+//   route_outputs: device outputs in place, pinned host outputs through zero_copy_view, others staged
+//   launch:        the providers' kernels (post_process) -> [batch transpose] -> D2H of staged outputs
 void batch_decoder::enqueue(window_slot& ws, int n, const decoded_element* in, void* const* outputs, bool on_device,
                             hipStream_t stream)
 {
-    const int ne = (int)m_provider->get_input_count();
-    // image::extractor::extract of encoded elements: the frame header gives the decoded size; the
-    // record is decoded with the provider's channel count (CV_LOAD_IMAGE_COLOR / GRAYSCALE)
-    // (CV_LOAD_IMAGE_COLOR / GRAYSCALE for images, CV_LOAD_IMAGE_ANYDEPTH for pixel masks).  PNG
-    // files are decoded on the host pool while staging (png_host.cpp), JPEG files on the device.
-    std::vector<decoded_element> records(in, in + (size_t)n * ne);
-    static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-    for (int i = 0; i < n; i++)
-        for (int k = 0; k < ne; k++) {
-            decoded_element& e = records[(size_t)i * ne + k];
-            if (!e.encoded) continue;
-            const bool mask = m_provider->providers()[k]->is_mask();
-            const int  cn   = m_provider->providers()[k]->out_desc().channels;
-            if (e.size >= 8 && std::memcmp(e.data, kPngSig, 8) == 0) {
-                int depth = 0, ctype = 0;
-                check(aeon_png_info(e.data, e.size, &e.width, &e.height, &depth, &ctype));
-                e.encoded    = false;
-                e.png_mode   = mask ? AEON_PNG_ANYDEPTH : (cn == 3 ? AEON_PNG_BGR8 : AEON_PNG_GRAY8);
-                e.channels   = mask ? 1 : cn;
-                e.elem_bytes = (mask && depth == 16 && ctype != 3) ? 2 : 1;
-                e.stride     = e.width * e.channels * e.elem_bytes;
-                continue;
-            }
-            if (mask)
-                throw std::runtime_error("encoded pixel masks are decoded from PNG files only (JPEG masks: pass the "
-                                         "decoded mask)");
-            int comps = 0;
-            check(aeon_jpeg_info(e.data, e.size, &e.width, &e.height, &comps));
-            e.channels = cn;
-            e.stride   = e.width * e.channels;
-        }
-    decode_window w = m_provider->new_window(n);
-    w.descs.assign(ne, std::vector<aeon_img_desc>(n));
-    w.offset.assign(ne, std::vector<size_t>(n));
-    // video::extractor of the video elements (the AVI demux and the kept frames' JPEG headers), on the pool:
-    // the draws below need the first frame's size
-    if (m_provider->has_video()) {
-        phase_range r("aeon.demux");
-        m_provider->extract_clips(n, records.data(), w, *m_pool);
-    }
-    // batch_decoder::process: the slot engine of record i draws its params (deterministic mode
-    // swaps the slot engine in and out, batch_decoder.cpp:62-71).  With slot engines the draws run
-    // on the pool (draw_window: aeon's in-order params exactly), and with them the extraction of the
-    // box providers' metadata, which make_ssd_params draws over.
-    const bool rcnn = m_provider->has_rcnn();
-    {
-        phase_range r("aeon.draw");
-        if (rcnn) w.rcnn_engine.resize(n);
-        if (m_deterministic) {
-            // aeon's shuffles draw from the slot engine after make_params and leave it advanced
-            // (batch_decoder.cpp:62-71): an earlier window's end states first, then this window's draws
-            if (rcnn) adopt_states();
-            m_provider->draw_window(n, records.data(), w, m_random, *m_pool);
-            for (int i = 0; rcnn && i < n; i++) w.rcnn_engine[i] = minstd_state(m_random[i]);
-        } else { // one engine for the window: in record order
-            // (aeon's result depends on its thread scheduling here; a record's shuffle engine is seeded by
-            // one further draw of the window's engine)
-            for (int i = 0; i < n; i++) {
-                m_provider->draw(i, records.data() + (size_t)i * ne, w, m_local_random);
-                if (rcnn) w.rcnn_engine[i] = (uint32_t)m_local_random();
-            }
-        }
-    }
-    if (rcnn && m_deterministic) {
-        if ((size_t)n > ws.states_cap) {
-            if (ws.states_dev) hip_check(hipFree(ws.states_dev), "hipFree");
-            if (ws.states_host) hip_check(hipHostFree(ws.states_host), "hipHostFree");
-            ws.states_dev = ws.states_host = nullptr, ws.states_cap = 0;
-            hip_check(hipMalloc((void**)&ws.states_dev, (size_t)n * sizeof(uint32_t)), "hipMalloc");
-            hip_check(hipHostMalloc((void**)&ws.states_host, (size_t)n * sizeof(uint32_t), hipHostMallocDefault),
-                      "hipHostMalloc");
-            ws.states_cap = (size_t)n;
-        }
-        if (!ws.states_done) hip_check(hipEventCreateWithFlags(&ws.states_done, hipEventDisableTiming), "hipEventCreate");
-        w.rcnn_states_dev = ws.states_dev, w.rcnn_states_host = ws.states_host, w.rcnn_states_done = ws.states_done;
-    }
-    // source arena: the box tables and the decoded elements first (staged + one H2D), then the
-    // device-decoded JPEGs
-    size_t staged = m_provider->layout_labels(w, m_provider->layout_boxes(w, 0)), total = staged;
-    w.clip_descs.resize(ne), w.clip_counts.resize(ne);
-    for (int k = 0; k < ne; k++)
-        if (const int D = m_provider->providers()[k]->max_frames())
-            w.clip_descs[k].assign((size_t)n * D, aeon_img_desc{}), w.clip_counts[k].assign(n, 0);
-    for (int pass = 0; pass < 2; pass++)
-        for (int i = 0; i < n; i++)
-            for (int k = 0; k < ne; k++) {
-                const decoded_element& e = records[(size_t)i * ne + k];
-                if (e.video && pass == 1) {
-                    // one source-arena slot per distinct decoded frame of the clip; an empty chunk's frame is the
-                    // previous frame's slot again (cap_mjpeg_decoder.cpp:138-141)
-                    const video_clip& c = w.clips[k][i];
-                    aeon_img_desc*    row = &w.clip_descs[k][(size_t)i * m_provider->providers()[k]->max_frames()];
-                    for (size_t d = 0; d < c.frames.size(); d++) {
-                        if (c.frames[d].size == 0) {
-                            row[d] = row[d - 1]; // (the demux refuses an empty first frame)
-                            continue;
-                        }
-                        row[d] = aeon_img_desc{total, c.width, c.height, c.width * 3, 3, 0, 0};
-                        total += ((size_t)c.width * c.height * 3 + 15) & ~(size_t)15;
-                    }
-                    w.clip_counts[k][i] = (int32_t)c.frames.size();
-                }
-                if (e.encoded != (pass == 1) || e.no_pixels()) continue;
-                const size_t b = (size_t)std::max(e.width, 0) * std::max(e.height, 0) * std::max(e.channels, 0) *
-                                 e.elem_bytes;
-                w.offset[k][i] = total;
-                w.descs[k][i]  = aeon_img_desc{total, e.width, e.height, e.width * e.channels * e.elem_bytes, e.channels,
-                                              e.elem_bytes == 2 ? 2 : 0, 0};
-                total += (b + 15) & ~(size_t)15;
-                if (pass == 0) staged = total;
-            }
-    total = std::max<size_t>(total, 16);
-    if (staged > ws.pinned_cap) {
-        if (ws.pinned) hip_check(hipHostFree(ws.pinned), "hipHostFree");
-        ws.pinned = nullptr;
-        hip_check(hipHostMalloc((void**)&ws.pinned, staged, hipHostMallocDefault), "hipHostMalloc");
-        ws.pinned_cap = staged;
-    }
-    grow_dev(ws.dev_src, ws.dev_src_cap, total);
-    w.arena = ws.pinned;
-    // the pool threads stage the pixels into the pinned arena, next to the window's box tables
-    if (staged) {
-        {
-            phase_range r("aeon.stage");
-            m_provider->stage_boxes(w);
-            m_provider->stage_labels(w);
-            m_pool->run(n, [&](int i) { m_provider->stage(i, records.data() + (size_t)i * ne, w); });
-        }
-        phase_range r("aeon.h2d_enqueue");
-        hip_check(hipMemcpyAsync(ws.dev_src, ws.pinned, staged, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
-    }
-    for (int k = 0; k < ne; k++) {
-        phase_range r("aeon.jpeg");
-        std::vector<const void*> files;
-        std::vector<size_t>      sizes;
-        std::vector<aeon_img_desc> descs;
-        for (int i = 0; i < n; i++) {
-            const decoded_element& e = records[(size_t)i * ne + k];
-            if (!e.encoded) continue;
-            files.push_back(e.data), sizes.push_back(e.size), descs.push_back(w.descs[k][i]);
-        }
-        // a video element's distinct non-empty frames: each a JPEG file of its own (imdecode COLOR: 3 channels)
-        if (const int D = m_provider->providers()[k]->max_frames())
-            for (int i = 0; i < n; i++) {
-                const decoded_element& e = records[(size_t)i * ne + k];
-                const video_clip&      c = w.clips[k][i];
-                for (size_t d = 0; d < c.frames.size(); d++)
-                    if (c.frames[d].size)
-                        files.push_back(e.data + c.frames[d].offset), sizes.push_back(c.frames[d].size),
-                            descs.push_back(w.clip_descs[k][(size_t)i * D + d]);
-            }
-        // (a window of clips holds many more files than a window of images: calls of a JPEG window's size, so the
-        // stage's two staging sets stay at the size the image path sizes them to)
-        constexpr size_t kJpegCallFiles = 512;
-        for (size_t f = 0; f < files.size(); f += kJpegCallFiles)
-            check(aeon_hip_decode_jpeg_batch(m_ctx, (int)std::min(kJpegCallFiles, files.size() - f), files.data() + f,
-                                             sizes.data() + f, descs.data() + f, ws.dev_src, stream));
-    }
-    // outputs[] follow get_output_shapes(): a provider may own several buffers (localization_ssd: five)
-    const auto& oshapes = m_provider->get_output_shapes();
-    const int   no      = (int)oshapes.size();
-    std::vector<void*> outs(no);
-    std::vector<bool>  copy_out(no, false); // staged on the device, then one D2H into outputs[k]
-    ws.dev_out.resize(no, nullptr), ws.dev_out_cap.resize(no, 0);
-    ws.dev_tmp.resize(no, nullptr), ws.dev_tmp_cap.resize(no, 0);
-    // a label provider's host output is written here and now (no device round trip): its outs[] stays null
-    std::vector<bool> host_label(no, false);
-    for (int k = 0; k < ne && !on_device; k++)
-        if (const size_t b = m_provider->providers()[k]->label_bytes()) {
-            const int o = m_provider->output_first(k);
-            host_label[o] = true;
-            for (int i = 0; i < n; i++) std::memcpy((uint8_t*)outputs[o] + (size_t)i * b, &w.labels[k][i], b);
-        }
-    for (int k = 0; k < no; k++) {
-        const size_t bytes = (size_t)n * oshapes[k].second.byte_size();
-        if (host_label[k]) continue;
-        if (on_device) outs[k] = outputs[k];
-        else if (void* v = zero_copy_view(outputs[k])) outs[k] = v;
-        else {
-            grow_dev(ws.dev_out[k], ws.dev_out_cap[k], bytes);
-            outs[k]     = ws.dev_out[k];
-            copy_out[k] = true;
-        }
-    }
-    phase_range launch("aeon.launch");
+    // aeon's shuffles draw from the slot engine after make_params and leave it advanced
+    // (batch_decoder.cpp:62-71): an earlier window's end states first, then this window's draws
+    if (m_deterministic) adopt_states();
+    window_plan   p = plan(n, in);
+    engine_states end;
     // once post_process has queued the engine states' copy and its event, the next window adopts them,
     // whatever happens to the rest of this one
     struct adopt_later {
         batch_decoder& d;
-        decode_window& w;
+        engine_states& end;
         window_slot&   ws;
+        int            n;
         ~adopt_later()
         {
-            if (w.rcnn_states_queued) d.m_states_from = &ws, d.m_states_n = w.n;
+            if (end.queued) d.m_states_from = &ws, d.m_states_n = n;
         }
-    } adopt_guard{*this, w, ws};
+    } adopt_guard{*this, end, ws, n};
+    if (m_provider->shuffles()) {
+        if (m_deterministic) slot_states(ws, n, end);
+        m_provider->take_engines(p.w, std::move(p.engines), &end);
+    }
+    stage_sources(ws, p, stream);
+    const routed_outputs r = route_outputs(ws, p.w, outputs, on_device);
+    launch(ws, p.w, r, outputs, stream);
+}
+
+// The draw phase of a window, host only.  Every element goes through its provider's inspect on the pool; then
+// batch_decoder::process: the slot engine of record i draws its params (deterministic mode swaps the slot
+// engine in and out, batch_decoder.cpp:62-71).  With slot engines the draws run on the pool (draw_window:
+// aeon's in-order params exactly) unless serial asks for the in-order loop.  A record of a provider that
+// shuffles gets its engine word: the slot engine's state after the draw, or -- with the one engine of
+// non-deterministic mode, where aeon's result depends on its thread scheduling -- one further draw of it.
+void batch_decoder::draw(window_plan& p, int n, const decoded_element* in, bool serial)
+{
+    const int ne = (int)m_provider->get_input_count();
+    if (m_deterministic) grow_slot_engines(n);
+    p.records.assign(in, in + (size_t)n * ne);
+    p.w = m_provider->new_window(n);
+    {
+        phase_range r("aeon.inspect");
+        m_provider->inspect_window(n, p.records.data(), p.w, *m_pool);
+    }
+    phase_range r("aeon.draw");
+    const bool  words = m_provider->shuffles();
+    if (words) p.engines.resize(n);
+    if (m_deterministic && !serial) {
+        m_provider->draw_window(n, p.records.data(), p.w, m_random, *m_pool);
+        for (int i = 0; words && i < n; i++) p.engines[i] = minstd_state(m_random[i]);
+        return;
+    }
+    for (int i = 0; i < n; i++) {
+        std::minstd_rand0& random = m_deterministic ? m_random[i] : m_local_random;
+        m_provider->draw(i, p.records.data() + (size_t)i * ne, p.w, random);
+        if (words) p.engines[i] = m_deterministic ? minstd_state(random) : (uint32_t)random();
+    }
+}
+
+window_plan batch_decoder::plan(int n, const decoded_element* records)
+{
+    window_plan p;
+    draw(p, n, records, false);
+    m_provider->layout(p);
+    return p;
+}
+
+void batch_decoder::draw_params(int n, const decoded_element* records, aeon_aug_params* params, bool serial)
+{
+    if (n <= 0) return;
+    window_plan p;
+    draw(p, n, records, serial);
+    std::copy(p.w.params[0].begin(), p.w.params[0].end(), params);
+}
+
+// localization_rcnn, deterministic mode: the slot's buffers for the window's engine end states
+void batch_decoder::slot_states(window_slot& ws, int n, engine_states& end)
+{
+    if ((size_t)n > ws.states_cap) {
+        if (ws.states_dev) hip_check(hipFree(ws.states_dev), "hipFree");
+        if (ws.states_host) hip_check(hipHostFree(ws.states_host), "hipHostFree");
+        ws.states_dev = ws.states_host = nullptr, ws.states_cap = 0;
+        hip_check(hipMalloc((void**)&ws.states_dev, (size_t)n * sizeof(uint32_t)), "hipMalloc");
+        hip_check(hipHostMalloc((void**)&ws.states_host, (size_t)n * sizeof(uint32_t), hipHostMallocDefault),
+                  "hipHostMalloc");
+        ws.states_cap = (size_t)n;
+    }
+    if (!ws.states_done) hip_check(hipEventCreateWithFlags(&ws.states_done, hipEventDisableTiming), "hipEventCreate");
+    end.dev = ws.states_dev, end.host = ws.states_host, end.done = ws.states_done;
+}
+
+// The source arena: what the plan staged (box tables, label items, decoded elements) written into the slot's
+// pinned memory and copied H2D in one piece, then the JPEG files decoded on the device behind it.
+void batch_decoder::stage_sources(window_slot& ws, window_plan& p, hipStream_t stream)
+{
+    if (p.staged > ws.pinned_cap) {
+        if (ws.pinned) hip_check(hipHostFree(ws.pinned), "hipHostFree");
+        ws.pinned = nullptr;
+        hip_check(hipHostMalloc((void**)&ws.pinned, p.staged, hipHostMallocDefault), "hipHostMalloc");
+        ws.pinned_cap = p.staged;
+    }
+    grow_dev(ws.dev_src, ws.dev_src_cap, p.total);
+    p.w.arena = ws.pinned;
+    if (p.staged) {
+        {
+            phase_range r("aeon.stage");
+            m_provider->stage(p, *m_pool);
+        }
+        phase_range r("aeon.h2d_enqueue");
+        hip_check(hipMemcpyAsync(ws.dev_src, ws.pinned, p.staged, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+    }
+    // (a window of clips holds many more files than a window of images: calls of a JPEG window's size, so the
+    // stage's two staging sets stay at the size the image path sizes them to)
+    constexpr size_t kJpegCallFiles = 512;
+    for (const jpeg_list& j : p.jpegs) {
+        phase_range r("aeon.jpeg");
+        for (size_t f = 0; f < j.files.size(); f += kJpegCallFiles)
+            check(aeon_hip_decode_jpeg_batch(m_ctx, (int)std::min(kJpegCallFiles, j.files.size() - f), j.files.data() + f,
+                                             j.sizes.data() + f, j.descs.data() + f, ws.dev_src, stream));
+    }
+}
+
+// outputs[] follow get_output_shapes() (a provider may own several buffers: localization_ssd five).  A device
+// output is written in place; a pinned host output through its device view (zero_copy_view); any other host
+// output is staged in the slot's device buffer and copied D2H; a provider that needs no device has written
+// its host output here and now (a label: no device round trip), and its dev[] stays null.
+batch_decoder::routed_outputs batch_decoder::route_outputs(window_slot& ws, const decode_window& w, void* const* outputs,
+                                                           bool on_device)
+{
+    const auto&    oshapes = m_provider->get_output_shapes();
+    const int      no      = (int)oshapes.size();
+    routed_outputs r{std::vector<void*>(no), std::vector<bool>(no, false), std::vector<bool>(no, false)};
+    ws.dev_out.resize(no, nullptr), ws.dev_out_cap.resize(no, 0);
+    for (size_t k = 0; k < m_provider->providers().size() && !on_device; k++) {
+        const int o  = m_provider->output_first(k);
+        r.on_host[o] = m_provider->providers()[k]->host_output(*w.parts[k], w.n, outputs[o]);
+    }
+    for (int k = 0; k < no; k++) {
+        if (r.on_host[k]) continue;
+        if (on_device) r.dev[k] = outputs[k];
+        else if (void* v = zero_copy_view(outputs[k])) r.dev[k] = v;
+        else {
+            grow_dev(ws.dev_out[k], ws.dev_out_cap[k], (size_t)w.n * oshapes[k].second.byte_size());
+            r.dev[k]      = ws.dev_out[k];
+            r.copy_out[k] = true;
+        }
+    }
+    return r;
+}
+
+// The providers' device work into the routed outputs -- through dev_tmp and a transpose per batch for
+// batch_major=false --, the D2H of the staged host outputs, and the window's completion event.
+void batch_decoder::launch(window_slot& ws, const decode_window& w, const routed_outputs& r, void* const* outputs,
+                           hipStream_t stream)
+{
+    const auto& oshapes = m_provider->get_output_shapes();
+    const int   no = (int)oshapes.size(), n = w.n;
+    phase_range range("aeon.launch");
     if (m_batch_major) {
-        m_provider->post_process(m_ctx, w, ws.dev_src, outs.data(), stream);
+        m_provider->post_process(m_ctx, w, ws.dev_src, r.dev.data(), stream);
     } else {
+        ws.dev_tmp.resize(no, nullptr), ws.dev_tmp_cap.resize(no, 0);
         std::vector<void*> tmp(no);
         for (int k = 0; k < no; k++) {
-            if (host_label[k]) continue; // (one element per item: its transpose is itself)
+            if (r.on_host[k]) continue; // (one element per item: its transpose is itself)
             grow_dev(ws.dev_tmp[k], ws.dev_tmp_cap[k], (size_t)n * oshapes[k].second.byte_size());
             tmp[k] = ws.dev_tmp[k];
         }
         m_provider->post_process(m_ctx, w, ws.dev_src, tmp.data(), stream);
         for (int k = 0; k < no; k++) {
-            if (host_label[k]) continue;
+            if (r.on_host[k]) continue;
             const shape_type& sh    = oshapes[k].second;
             const size_t      esize = sh.otype.size;
             const size_t      item  = sh.byte_size();
             for (int b = 0; b < n / m_batch_size; b++) {
                 const size_t off = (size_t)b * m_batch_size * item;
-                check(aeon_hip_transpose_batch(m_ctx, (uint8_t*)tmp[k] + off, (uint8_t*)outs[k] + off,
+                check(aeon_hip_transpose_batch(m_ctx, (uint8_t*)tmp[k] + off, (uint8_t*)r.dev[k] + off,
                                                m_batch_size, (int64_t)(item / esize), (int)esize, stream));
             }
         }
     }
     for (int k = 0; k < no; k++)
-        if (copy_out[k]) {
+        if (r.copy_out[k]) {
             phase_range d2h("aeon.d2h_enqueue");
-            hip_check(hipMemcpyAsync(outputs[k], outs[k], (size_t)n * oshapes[k].second.byte_size(),
+            hip_check(hipMemcpyAsync(outputs[k], r.dev[k], (size_t)n * oshapes[k].second.byte_size(),
                                      hipMemcpyDeviceToHost, stream),
                       "hipMemcpyAsync");
         }
     if (!ws.done) hip_check(hipEventCreateWithFlags(&ws.done, hipEventDisableTiming), "hipEventCreate");
     hip_check(hipEventRecord(ws.done, stream), "hipEventRecord");
     ws.pending = true;
-}
-
-void batch_decoder::draw_params(int n, const decoded_element* records, aeon_aug_params* params, bool serial)
-{
-    if (n <= 0) return;
-    const int ne = (int)m_provider->get_input_count();
-    if (m_deterministic) grow_slot_engines(n);
-    decode_window w = m_provider->new_window(n);
-    if (m_deterministic && !serial) {
-        m_provider->draw_window(n, records, w, m_random, *m_pool);
-    } else {
-        for (int i = 0; i < n; i++)
-            m_provider->draw(i, records + (size_t)i * ne, w, m_deterministic ? m_random[i] : m_local_random);
-    }
-    std::copy(w.params[0].begin(), w.params[0].end(), params);
 }
 
 void batch_decoder::decode(int n, const decoded_element* records, void* const* outputs, bool on_device, void* stream_)
@@ -1608,39 +1563,27 @@ int host_guarded(F&& f)
         return AEON_HIP_ERUNTIME;
     }
 }
-} // namespace
 
-namespace {
 std::vector<aeon_hip::decoded_element> to_elements(aeon_decoder* d, int n, const aeon_encoded_elem* elems)
 {
     const int ne = (int)d->d->provider().get_input_count();
     std::vector<aeon_hip::decoded_element> recs((size_t)n * ne);
+    // (a datum -- JSON metadata, an AVI file, a label's bytes -- is data / size: an empty one is refused per
+    // record by its provider's inspect, with aeon's message)
     for (size_t i = 0; i < recs.size(); i++) {
-        const aeon_encoded_elem& e = elems[i];
-        aeon_hip::decoded_element& r = recs[i];
-        r.data = (const uint8_t*)e.data;
-        if (d->d->provider().providers()[i % ne]->box_kind() >= 0) { // JSON metadata: data / size
-            r.metadata = true, r.size = e.size;
-            continue;
-        }
-        // an AVI datum / a label's bytes: data / size (an empty one is refused per record, with aeon's message)
-        if (d->d->provider().providers()[i % ne]->max_frames()) {
-            r.video = true, r.size = e.size;
-            continue;
-        }
-        if (d->d->provider().providers()[i % ne]->label_bytes()) {
-            r.label = true, r.size = e.size;
-            continue;
-        }
-        if (e.width > 0) {
-            r.width = e.width, r.height = e.height, r.channels = e.channels;
-            r.stride = e.stride ? e.stride : e.width * e.channels;
-        } else {
-            if (!e.data || !e.size) throw std::runtime_error("received encoded image with size 0, at idx " +
-                                                             std::to_string(i / ne));
-            r.encoded = true, r.size = e.size;
-        }
+        recs[i].data = (const uint8_t*)elems[i].data;
+        d->d->provider().providers()[i % ne]->from_abi(elems[i], (int)(i / ne), recs[i]);
     }
+    return recs;
+}
+
+// decoded pixels as aeon_record_elem carries them
+std::vector<aeon_hip::decoded_element> to_elements(aeon_decoder* d, int n, const aeon_record_elem* elems)
+{
+    std::vector<aeon_hip::decoded_element> recs((size_t)n * d->d->provider().get_input_count());
+    for (size_t i = 0; i < recs.size(); i++)
+        recs[i] = aeon_hip::decoded_element{(const uint8_t*)elems[i].data, elems[i].width, elems[i].height, elems[i].channels,
+                                            elems[i].stride ? elems[i].stride : elems[i].width * elems[i].channels};
     return recs;
 }
 } // namespace
@@ -1704,12 +1647,7 @@ int aeon_decoder_decode(aeon_decoder* d, int n, const aeon_record_elem* elems, v
         if (d->d->provider().has_sized())
             throw std::invalid_argument("aeon_record_elem carries no byte size for the metadata of a boundingbox / "
                                         "localization_ssd element, a video or a label datum: use aeon_decoder_decode_encoded");
-        const int ne = (int)d->d->provider().get_input_count();
-        std::vector<aeon_hip::decoded_element> recs((size_t)n * ne);
-        for (size_t i = 0; i < recs.size(); i++)
-            recs[i] = aeon_hip::decoded_element{(const uint8_t*)elems[i].data, elems[i].width, elems[i].height,
-                                                elems[i].channels,
-                                                elems[i].stride ? elems[i].stride : elems[i].width * elems[i].channels};
+        auto recs = to_elements(d, n, elems);
         d->d->decode(n, recs.data(), outputs, outputs_on_device != 0, stream);
     });
 }
@@ -1723,12 +1661,7 @@ int aeon_decoder_draw_params(aeon_decoder* d, int n, const aeon_record_elem* ele
             throw std::invalid_argument("aeon_record_elem carries no byte size for the metadata of a boundingbox / "
                                         "localization_ssd element, a video or a label datum: the draws of such a config need "
                                         "the records");
-        const int ne = (int)d->d->provider().get_input_count();
-        std::vector<aeon_hip::decoded_element> recs((size_t)n * ne);
-        for (size_t i = 0; i < recs.size(); i++)
-            recs[i] = aeon_hip::decoded_element{(const uint8_t*)elems[i].data, elems[i].width, elems[i].height,
-                                                elems[i].channels,
-                                                elems[i].stride ? elems[i].stride : elems[i].width * elems[i].channels};
+        auto recs = to_elements(d, n, elems);
         d->d->draw_params(n, recs.data(), params, serial != 0);
     });
 }

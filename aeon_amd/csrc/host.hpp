@@ -70,59 +70,89 @@ struct image_config {
 };
 
 // An element of a record: an encoded JPEG file (size > 0; width/height/channels filled in from
-// its header by the decoder) or decoded HWC uint8 pixels (what image::extractor::extract returns).
+// its header by its provider's inspect step), decoded HWC uint8 pixels (what image::extractor::extract
+// returns), or the datum of a box, video or label provider (data / size: JSON metadata, an MJPEG AVI
+// file whose width / height the demux fills in from its first frame, a label's bytes).
 struct decoded_element {
     const uint8_t* data = nullptr;
     int            width = 0, height = 0, channels = 0, stride = 0;
     size_t         size    = 0;     // encoded bytes
     bool           encoded = false; // JPEG file: decoded on the device (jpeg_host.cpp)
     int            png_mode   = -1; // PNG file: AEON_PNG_* decode on the host while staging
-    bool           metadata   = false; // JSON text of a box provider (data / size), no pixels
-    bool           video      = false; // MJPEG AVI datum of a video provider (data / size): width / height are
-                                       // filled in from its first frame by the demux
-    bool           label      = false; // the datum of a label provider (data / size), no pixels
     int            elem_bytes = 1;  // bytes per sample (2: a 16-bit mask / depth map)
-    bool           no_pixels() const { return metadata || video || label; } // nothing to stage as it stands
 };
 
-// One record of a video provider after video::extractor's demux (avi_host.hpp): the kept frames
-// (the first min(frames of the file, max_frame_count)) and the first frame's JPEG size, which every
-// other non-empty kept frame must have.
-struct video_clip {
-    std::vector<aeon_avi_frame> frames;
-    int                         width = 0, height = 0;
+// What one provider keeps of a window's n records (etl_provider::new_part): the source descriptors into the
+// arena -- one per record of a pixel provider, max_frame_count per record of a video provider -- and, in the
+// provider's own subclass, its metadata, values, offsets and counts.
+struct window_part {
+    virtual ~window_part() = default;
+    std::vector<aeon_img_desc> descs;
 };
 
 // Per-window staging shared by the providers (filled concurrently by the pool threads).
 struct decode_window {
     int                                       n = 0;
-    std::vector<std::vector<aeon_img_desc>>   descs;  // [provider][record]
     std::vector<std::vector<aeon_aug_params>> params; // [provider][record]
-    std::vector<std::vector<size_t>>          offset; // [provider][record] in the pinned arena
+    std::vector<std::unique_ptr<window_part>> parts;  // [provider]
     uint8_t*                                  arena = nullptr;
-    // box providers: the records' extracted metadata, and where the provider's box table (BoxRec per
-    // record, then boxes, labels, difficult flags; box_job.hpp) lies in the arena
-    std::vector<std::vector<box_metadata>>    boxes;      // [provider][record]
-    std::vector<size_t>                       box_offset; // [provider]
-    std::vector<size_t>                       box_total;  // [provider] boxes of the window
-    // localization_rcnn: the minstd_rand0 state record i's shuffles start from (its engine after the params
-    // draw); in deterministic mode the states after the shuffles are copied from rcnn_states_dev to
-    // rcnn_states_host right behind the targets kernel, and rcnn_states_done is recorded after the copy
-    std::vector<uint32_t>                     rcnn_engine; // [record]
-    uint32_t*                                 rcnn_states_dev  = nullptr;
-    uint32_t*                                 rcnn_states_host = nullptr;
-    hipEvent_t                                rcnn_states_done = nullptr;
-    bool                                      rcnn_states_queued = false; // the copy and its event are on the stream
-    // video providers: the records' demuxed clips; per clip max_frame_count frame descriptors into the source
-    // arena (one slot per distinct decoded frame: an empty chunk repeats the previous frame's) and the number of
-    // kept frames
-    std::vector<std::vector<video_clip>>      clips;       // [provider][record]
-    std::vector<std::vector<aeon_img_desc>>   clip_descs;  // [provider][record * max_frame_count + frame]
-    std::vector<std::vector<int32_t>>         clip_counts; // [provider][record]
-    // label providers: the records' values, and where the provider's output items (n values of its output
-    // type) are staged in the arena for a device output
-    std::vector<std::vector<int32_t>>         labels;       // [provider][record]
-    std::vector<size_t>                       label_offset; // [provider]
+};
+
+// The source arena of a window, in this order, every claim 16-byte aligned: the box tables (provider order),
+// the label items (provider order), the staged elements (record-major, provider-minor) -- up to here it is
+// pinned host memory copied H2D in one piece --, then the device-decoded slots (record-major, provider-minor;
+// a clip's frame slots at its element's position).
+enum class arena_region { box_tables, label_items, staged, device_decoded };
+inline size_t arena_align(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// The JPEG files one provider wants decoded into the device-decoded region, with their destinations
+struct jpeg_list {
+    std::vector<const void*>   files;
+    std::vector<size_t>        sizes;
+    std::vector<aeon_img_desc> descs;
+    void add(const void* file, size_t size, const aeon_img_desc& d) { files.push_back(file), sizes.push_back(size), descs.push_back(d); }
+};
+
+// Where the engines' states after a localization_rcnn window's device shuffles go (deterministic mode; dev
+// null: not wanted): the device words, their pinned host copy, the event recorded behind the copy, and whether
+// the copy and the event are on the stream.
+struct engine_states {
+    uint32_t*  dev = nullptr, *host = nullptr;
+    hipEvent_t done   = nullptr;
+    bool       queued = false;
+};
+
+// A box provider's part of a window: the records' extracted metadata, where the provider's box table (BoxRec
+// per record, then boxes, labels, difficult flags; box_job.hpp) lies in the arena and how many boxes it
+// holds.  localization_rcnn: the minstd_rand0 state record i's shuffles start from, and where the states after
+// the shuffles go (copied back right behind the targets kernel).
+struct box_part : window_part {
+    std::vector<box_metadata> boxes;
+    size_t                    offset = 0, total = 0;
+    std::vector<uint32_t>     engines;
+    engine_states*            end = nullptr;
+};
+
+// One record of a video provider after video::extractor's demux (avi_host.hpp): the kept frames (the first
+// min(frames of the file, max_frame_count)) and the first frame's size, which every other non-empty kept
+// frame must have.
+struct video_clip {
+    std::vector<aeon_avi_frame> frames;
+    int                         width = 0, height = 0;
+};
+
+// A video provider's part of a window: the records' demuxed clips and the number of kept frames; descs holds
+// max_frame_count frame descriptors per clip (one arena slot per distinct decoded frame).
+struct video_part : window_part {
+    std::vector<video_clip> clips;
+    std::vector<int32_t>    counts;
+};
+
+// A label provider's part of a window: the records' values, and where the provider's output items (n values of
+// its output type) are staged in the arena for a device output.
+struct label_part : window_part {
+    std::vector<int32_t> values;
+    size_t               offset = 0;
 };
 
 // augmentation shared by the ETL providers of one record (provider.cpp:109-119)
@@ -158,96 +188,116 @@ struct light_split {
     float exit_saved  = 0.f;
 };
 
-// One ETL element provider of the HIP stage (provider::image / provider::pixelmask).
+// What a record's params are drawn over (etl_provider::draw): the source size and the target size;
+// nboxes >= 0 asks for make_ssd_params over the record's boxes.
+struct draw_source {
+    int          in_w = 0, in_h = 0, out_w = 0, out_h = 0;
+    const float* boxes  = nullptr;
+    int          nboxes = -1;
+};
+
+// One ETL element provider of the HIP stage: image, pixelmask, boundingbox, localization_ssd,
+// localization_rcnn, video or label.  Its virtuals are the steps of a decode window, in the order they run;
+// part is the provider's own new_part() of that window, e its element of record idx.
 class etl_provider {
 public:
     virtual ~etl_provider() = default;
-    // host half of provide(): params for record idx (shared through aug) + its descriptor; with ls,
-    // the record is drawn out of order (provider_base::draw_window)
-    virtual void provide(int idx, const decoded_element& in, augmentation& aug, std::minstd_rand0& random,
-                         aeon_aug_params& params, light_split* ls = nullptr) const = 0;
-    virtual const param_factory& factory() const = 0;
-    virtual bool               is_mask() const = 0;
-    virtual const shape_type&  shape() const = 0;
-    virtual const std::string& buffer_name() const = 0;
-    virtual aeon_out_desc      out_desc() const = 0;
-    // the provider's output buffers in aeon's get_output_shapes() order (one for pixel providers)
-    virtual std::vector<std::pair<std::string, shape_type>> output_shapes() const
-    {
-        return {{buffer_name(), shape()}};
-    }
-    // box providers (boundingbox, localization_ssd, localization_rcnn): AEON_BOX_*; -1 for pixel providers.
-    // Their element is the record's JSON metadata: extract() parses it, provide_boxes() is provide() with
-    // it (the first element of a record draws: localization_ssd make_ssd_params over the extracted boxes,
-    // the others make_params).  The window's box table of provider k (box_job.hpp) takes
-    // box_table_bytes(n, total) of the arena at w.box_offset[k]; stage_boxes() writes it there and makes the
-    // host-side refusals; launch_boxes() queues the targets launch over its device copy into out[] (the
-    // provider's output buffers), and for localization_rcnn the engine states' copy back and its event.
-    virtual int  box_kind() const { return -1; }
-    virtual void extract(const decoded_element&, box_metadata&) const {}
-    virtual void provide_boxes(const box_metadata&, augmentation&, std::minstd_rand0&, aeon_aug_params&,
-                               light_split* = nullptr) const
+    // the provider's output buffers in aeon's get_output_shapes() order
+    virtual std::vector<std::pair<std::string, shape_type>> output_shapes() const = 0;
+    // the factory the provider's draws go through; null for a provider that draws nothing (label)
+    virtual const param_factory* factory() const = 0;
+    // the element as the C ABI hands it over (the byte size of a datum; decoded pixels or an encoded file)
+    virtual void from_abi(const aeon_encoded_elem& in, int idx, decoded_element& e) const = 0;
+    virtual std::unique_ptr<window_part> new_part(int n) const = 0;
+    // inspect (on the pool): refuses an empty element and reads what the draw and the layout need -- the PNG /
+    // JPEG header, the AVI demux and the kept frames' headers, the JSON metadata, the label's int
+    virtual void inspect(window_part& part, int idx, decoded_element& e) const = 0;
+    // draw: the record's params through the shared augmentation (the first element of a record draws, the
+    // others copy); with ls, the record is drawn out of order (provider_base::draw_window)
+    void draw(const window_part& part, int idx, const decoded_element& e, augmentation& aug, std::minstd_rand0& random,
+              aeon_aug_params& params, light_split* ls) const;
+    // layout: the provider claims its bytes of region r from the running offset and records its descriptors,
+    // per window (box table, label items) or per record (pixels, device-decoded slots); the JPEG files it wants
+    // decoded go into jpegs with their destinations
+    virtual void layout_window(window_part&, arena_region, int /*n*/, size_t& /*offset*/) const {}
+    virtual void layout_record(window_part&, arena_region, int /*idx*/, const decoded_element&, size_t& /*offset*/,
+                               jpeg_list&) const
     {
     }
-    virtual size_t box_table_bytes(int, size_t) const { return 0; }
-    virtual void   stage_boxes(decode_window&, size_t) const {}
-    virtual void   launch_boxes(aeon_hip_ctx*, decode_window&, size_t, const uint8_t*, void* const*, void*) const {}
-    // video providers: max_frame_count (0 for every other provider).  Their element is the whole AVI datum:
-    // extract_clip() is video::extractor for record idx -- the demux, the kept frames' JPEG headers, the
-    // element's width / height set to the first frame's -- after which provide() draws like an image's.
-    virtual int  max_frames() const { return 0; }
-    virtual void extract_clip(int, decoded_element&, video_clip&) const {}
-    // label providers: bytes of the output type (0 for every other provider); extract_label() is
-    // label::extractor for record idx.  They draw no params.
-    virtual size_t  label_bytes() const { return 0; }
-    virtual int32_t extract_label(int, const decoded_element&) const { return 0; }
+    // stage: the provider's staged bytes into the pinned arena, per window (the box table, with its host-side
+    // refusals; the label items) or per record on the pool (pixels, the PNG decode)
+    virtual void stage_window(const decode_window&, size_t /*k*/) const {}
+    virtual void stage_record(const decode_window&, size_t /*k*/, int /*idx*/, const decoded_element&) const {}
+    // launch: the provider's device work over the arena's device copy into out[] (its output buffers)
+    virtual void launch(aeon_hip_ctx* ctx, const decode_window& w, size_t k, const uint8_t* dev_arena, void* const* out,
+                        void* stream) const = 0;
+    // host output: a provider that needs no device writes its n items into the host buffer and returns true
+    virtual bool host_output(const window_part&, int /*n*/, void* /*out*/) const { return false; }
+    // A provider whose device work shuffles (localization_rcnn) is handed the engine word each record's
+    // shuffles start from and where the engines' end states go (the decoder's: they cross windows).
+    virtual void take_engines(window_part&, std::vector<uint32_t>&&, engine_states*) const {}
+    // the image + pixelmask pair call's one question: the output descriptor of a plain image (mask false) /
+    // of a pixel mask (mask true), null for anything else
+    virtual const aeon_out_desc* pixel_out(bool /*mask*/) const { return nullptr; }
+
+protected:
+    // what idx's draw is made over; false: the provider draws nothing
+    virtual bool draw_over(const window_part& part, int idx, const decoded_element& e, draw_source& s) const = 0;
+};
+
+// What batch_decoder::plan makes of a window on the host alone: the inspected elements, the drawn window, its
+// arena layout (staged bytes are copied H2D, total includes the device-decoded slots), the JPEG files per
+// provider, and the records' shuffle engine words (empty unless a provider shuffles).
+struct window_plan {
+    std::vector<decoded_element> records;
+    decode_window                w;
+    size_t                       staged = 0, total = 0;
+    std::vector<jpeg_list>       jpegs; // [provider]
+    std::vector<uint32_t>        engines;
 };
 
 class provider_base : public provider_interface {
 public:
     provider_base(const Json& js, const std::vector<Json>& etl, const Json& augmentation);
+    // a window of n records: params and one part per provider
+    decode_window new_window(int n) const;
+    // every element of the window through its provider's inspect, on the pool
+    void inspect_window(int n, decoded_element* records, decode_window& w, thread_pool& pool) const;
     // record idx of the window: params for every ETL element from one shared augmentation
-    // (provider_base::provide, provider.cpp:109-119), then its pixels into the pinned arena
-    void provide(int idx, const decoded_element* elems, decode_window& w, std::minstd_rand0& random) const;
+    // (provider_base::provide, provider.cpp:109-119)
     void draw(int idx, const decoded_element* elems, decode_window& w, std::minstd_rand0& random,
               light_split* ls = nullptr) const;
     // draw() for every record of a window with its own engine (deterministic mode), on the pool:
     // the same params as the in-order loop (the lighting cache hand-off is fixed up afterwards)
     void draw_window(int n, const decoded_element* records, decode_window& w, std::vector<std::minstd_rand0>& engines,
                      thread_pool& pool) const;
-    void stage(int idx, const decoded_element* elems, decode_window& w) const;
+    // the arena layout of an inspected, drawn window: p.staged, p.total, p.jpegs and the parts' descriptors
+    void layout(window_plan& p) const;
+    // the window's tables and items into the arena, then its records' pixels on the pool
+    void stage(const window_plan& p, thread_pool& pool) const;
     // aeon's vestigial post_process hook, used as the per-window GPU flush: outputs[k] receives
     // n items of provider k (device pointers if on_device, else host memory)
-    void post_process(aeon_hip_ctx* ctx, decode_window& w, const uint8_t* dev_arena, void* const* outputs,
+    void post_process(aeon_hip_ctx* ctx, const decode_window& w, const uint8_t* dev_arena, void* const* outputs,
                       void* stream) const;
     const std::vector<std::unique_ptr<etl_provider>>& providers() const { return m_providers; }
     // outputs[] of the decoder calls follow get_output_shapes(): provider k's buffers are
     // output_first(k) .. output_first(k + 1) - 1
     int  output_first(size_t k) const { return m_out_first[k]; }
-    bool has_boxes() const { return m_has_boxes; }
-    bool has_rcnn() const { return m_has_rcnn; }
-    bool has_video() const { return m_has_video; }
     // some element is a datum with a byte size (box metadata, an AVI file, a label): what aeon_record_elem
     // cannot carry
-    bool has_sized() const { return m_has_boxes || m_has_video || m_has_label; }
-    // video::extractor of every video element of the window, on the pool (before the draws, which need the
-    // first frame's size)
-    void extract_clips(int n, decoded_element* records, decode_window& w, thread_pool& pool) const;
-    // the label providers' output items after `offset` of the arena, and written there
-    size_t layout_labels(decode_window& w, size_t offset) const;
-    void   stage_labels(decode_window& w) const;
-    // the box tables of the window's box providers: their size after the window's pixels at `offset`
-    // of the arena (layout_boxes), and the tables themselves written there (stage_boxes, which also
-    // makes the host-side refusals: rotation, boundingbox::box::expand's precondition)
-    size_t layout_boxes(decode_window& w, size_t offset) const;
-    void   stage_boxes(decode_window& w) const;
-    // a window of n records for draw(): params and, for the box providers, metadata per record
-    decode_window new_window(int n) const;
+    bool has_sized() const { return m_has_sized; }
+    // a provider's device work shuffles: every record needs an engine word (take_engines hands them over)
+    bool shuffles() const { return m_shuffler >= 0; }
+    void take_engines(decode_window& w, std::vector<uint32_t>&& words, engine_states* end) const
+    {
+        m_providers[m_shuffler]->take_engines(*w.parts[m_shuffler], std::move(words), end);
+    }
 
 private:
     std::vector<std::unique_ptr<etl_provider>> m_providers;
     std::vector<int>                           m_out_first; // size providers + 1
-    bool                                       m_has_boxes = false, m_has_rcnn = false, m_has_video = false, m_has_label = false;
+    bool                                       m_has_sized = false;
+    int                                        m_shuffler  = -1; // the localization_rcnn provider
 };
 
 struct provider_factory {
@@ -308,6 +358,9 @@ public:
     // the draw phase of one window alone (host only): params[i] = record i's (first element's)
     // params; serial = the in-order loop instead of draw_window
     void draw_params(int n, const decoded_element* records, aeon_aug_params* params, bool serial);
+    // the host half of one window alone -- inspect, draw and the arena layout --: no device call, no window
+    // slot; what decode() and submit() go on to stage and launch
+    window_plan plan(int n, const decoded_element* records);
     int  outstanding() const { return (int)m_queue.size(); }
     provider_base& provider() { return *m_provider; }
     thread_pool&   pool() { return *m_pool; }
@@ -334,8 +387,20 @@ private:
     void adopt_states();
     window_slot*                   m_states_from = nullptr; // window whose end states are not adopted yet
     int                            m_states_n    = 0;
+    // where each output buffer's device work writes (null: the provider wrote its host output itself, on_host),
+    // and which are staged on the device and then copied D2H into outputs[k]
+    struct routed_outputs {
+        std::vector<void*> dev;
+        std::vector<bool>  copy_out, on_host;
+    };
+    // one window through slot ws: plan -> stage_sources -> route_outputs -> launch
     void enqueue(window_slot& ws, int n, const decoded_element* records, void* const* outputs, bool on_device,
                  hipStream_t stream);
+    void draw(window_plan& p, int n, const decoded_element* records, bool serial);
+    void slot_states(window_slot& ws, int n, engine_states& end);
+    void stage_sources(window_slot& ws, window_plan& p, hipStream_t stream);
+    routed_outputs route_outputs(window_slot& ws, const decode_window& w, void* const* outputs, bool on_device);
+    void launch(window_slot& ws, const decode_window& w, const routed_outputs& r, void* const* outputs, hipStream_t stream);
     void                           grow_slot_engines(int n);
     std::shared_ptr<provider_base> m_provider;
     int                            m_batch_size = 1;

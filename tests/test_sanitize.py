@@ -159,7 +159,8 @@ HOST_TSAN = os.path.join(ROOT, "aeon_amd", "csrc", "build_sanitize", "host_drive
 def _host_driver(target, exe, env_extra):
     """tests/sanitize/host_driver.cpp over host.cpp + stager.cpp with the HIP runtime stubbed
     (tests/sanitize/hip_stubs.cpp): loader configs, the pinned thread_pool, window draws on the pool
-    against serial draws over odd and even windows, a failing window, concurrent stager stages."""
+    against serial draws over odd and even windows, a failing window, concurrent stager stages, and the host
+    half of a decode window (batch_decoder::plan) for every provider kind against the arena's layout rule."""
     if not os.path.exists("/opt/rocm/llvm/bin/clang++"):
         pytest.skip("no clang with sanitizer runtimes")
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "aeon_amd", "csrc"), target])
@@ -176,6 +177,7 @@ def test_host_layer_under_asan_ubsan():
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     assert len(lines) >= 20 and all("\tok" in l for l in lines), r.stdout
+    assert sum(l.startswith("plan_") for l in lines) == 7, r.stdout
 
 
 def test_host_layer_under_tsan():
@@ -185,3 +187,4 @@ def test_host_layer_under_tsan():
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert "ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
     assert len(lines) >= 20 and all("\tok" in l for l in lines), r.stdout
+    assert sum(l.startswith("plan_") for l in lines) == 7, r.stdout
