@@ -1,6 +1,7 @@
-// stage.cpp -- host side of the HIP augmentation stage: per-record planning (the host-side
-// arithmetic aeon does per record before touching pixels), the per-GPU context with its
-// pinned/device staging ring, kernel launches and the extern "C" boundary (include/aeon_hip.h).
+// stage.cpp -- device side of the HIP augmentation stage's host code: the per-GPU context with its
+// pinned/device staging ring, kernel launches and the extern "C" boundary (include/aeon_hip.h).  The
+// image path's per-record planning and table layout are plan.cpp's (host arithmetic only); run_batch
+// acts on the CallPlan it returns.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,7 +15,6 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/aeon_hip.h"
@@ -26,6 +26,7 @@
 #include "mask16.hpp"
 #include "json.hpp"
 #include "param_factory.hpp"
+#include "plan.hpp"
 #include "plan_record.hpp"
 #include "video_job.hpp"
 
@@ -77,12 +78,6 @@ namespace {
 
 thread_local std::string g_err;
 
-struct aeon_error : std::runtime_error {
-    int code;
-    aeon_error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-[[noreturn]] void fail(int code, const std::string& msg) { throw aeon_error(code, msg); }
-
 // The device error word's bits (kernels atomicOr them; aeon_hip_synchronize reports and clears).
 std::string device_error_text(int err)
 {
@@ -109,16 +104,6 @@ std::string device_error_text(int err)
         if (e_ != hipSuccess) fail(AEON_HIP_ERUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-constexpr int kMaxLds        = 160 * 1024;
-// launch-shape constants (compile-time overrides only for tuning builds, tools/build_variants.sh)
-#ifndef AEON_HIP_STAGE_BUDGET_KB
-#define AEON_HIP_STAGE_BUDGET_KB 48
-#endif
-#ifndef AEON_HIP_FIXED_THREADS
-#define AEON_HIP_FIXED_THREADS 0
-#endif
-constexpr int kStageBudget   = AEON_HIP_STAGE_BUDGET_KB * 1024; // preferred LDS bytes of the staging buffer
-constexpr int kStageBudgetHi = 140 * 1024;  // fallback for very wide crops
 #ifndef AEON_HIP_UPLOAD_KERNEL_MAX_KB
 #define AEON_HIP_UPLOAD_KERNEL_MAX_KB 128
 #endif
@@ -168,714 +153,6 @@ void build_lut(const aeon_out_desc& o, float* lut, bool u8_map = false)
             lut[c * 256 + x] = o.stddev[oc] != 0 ? (float)((double)t2 * (1. / o.stddev[oc])) : t2;
         }
     }
-}
-
-// What the launch planner needs to know of a job (the fields share AugJob's names, so the
-// templates below take either).
-struct JobGeom {
-    int32_t mode, cn, crop_w, crop_h, win_w, win_h, dst_w, dst_h, photo, stats_slot;
-    double  scale_x, scale_y;
-};
-
-// source-footprint bounds used to size the LDS staging area
-template <typename J_>
-int stage_cols(const J_& J)
-{
-    switch (J.mode) {
-    // +1: the second tap column is staged even where its weight is 0
-    case RESIZE_LINEAR: return std::min(J.crop_w + 1, (int)std::ceil((J.win_w - 1) * J.scale_x) + 4);
-    case RESIZE_NEAREST: return std::min(J.crop_w, (int)std::ceil((J.win_w - 1) * J.scale_x) + 3);
-    case RESIZE_AREA2X: return 2 * J.win_w;
-    default: return J.win_w;
-    }
-}
-template <typename J_>
-int stage_rows_for(const J_& J, int tr)
-{
-    int rows = std::min(tr, J.win_h);
-    switch (J.mode) {
-    case RESIZE_LINEAR: return std::min(J.crop_h, (int)std::ceil((rows - 1) * J.scale_y) + 3);
-    case RESIZE_NEAREST: return std::min(J.crop_h, (int)std::ceil((rows - 1) * J.scale_y) + 2);
-    case RESIZE_AREA2X: return 2 * rows;
-    default: return rows;
-    }
-}
-
-struct LaunchPlan {
-    int                 rm = RESIZE_LINEAR;
-    bool                photo = false;
-    bool                tail  = false; // LINEAR jobs with OpenCV scalar-tail columns
-    size_t              blob_off = 0;     // byte offset of this group's jobs in the slot blob
-    std::vector<AugJob> jobs;
-    int                 tr = 1, stage_bytes = 0, max_win_w = 0, max_tiles = 0;
-    int                 lds = 0, threads = kBlockMax;
-    bool                vec_ok = true;
-    bool                has_hue = false, has_contrast = false;
-    bool                rtab    = false; // final f32 launch with contrast / lighting: per-record LDS table
-    bool                split   = false; // launched as augment_split (shape set by plan_split)
-    SplitArgs           sa{};
-
-    // launch shape for this->jobs (unless plan_split set it), and each job's tile count
-    void finalize()
-    {
-        if (jobs.empty()) return;
-        if (!split) shape(jobs);
-        max_tiles = 0;
-        for (AugJob& J : jobs) {
-            J.tiles   = (J.win_h + tr - 1) / tr;
-            max_tiles = std::max(max_tiles, J.tiles);
-        }
-    }
-
-    // workgroup size, rows per tile, LDS staging size for a set of jobs (AugJob or JobGeom)
-    template <typename J_>
-    void shape(const std::vector<J_>& jobs)
-    {
-        int ww = 0;
-        for (const J_& J : jobs) ww = std::max(ww, J.win_w);
-        max_win_w = std::max(ww, 1);
-        // workgroup = 256..512 lanes holding whole 4-pixel column groups (fewest idle lanes;
-        // ties go to the larger group), row phases = lanes / column groups
-        const int gpr = (max_win_w + 3) / 4;
-        const int ncg = std::min(gpr, kBlockMax);
-        threads       = kBlockMax;
-        int best_idle = kBlockMax;
-        for (int nt = kBlockMin; nt <= kBlockMax; nt += 64) {
-            const int idle = nt - (nt / ncg) * ncg;
-            // idle / nt <= best_idle / threads
-            if ((long)idle * threads <= (long)best_idle * nt) threads = nt, best_idle = idle;
-        }
-        // contrast pass 2 (photometric over the u8 intermediate, no resize): full workgroups
-        // beat the fewest-idle-lanes choice (C3: 140 vs 158 us at 512 vs 448 lanes)
-        if (rm == RESIZE_COPY && photo) threads = kBlockMax;
-        if (AEON_HIP_FIXED_THREADS) threads = AEON_HIP_FIXED_THREADS;
-        const int nph = threads / ncg;
-        // one staging buffer and four rows per lane (a multiple of the row phases): the CU's other
-        // workgroups cover a tile's staging latency.  Measured on C2/C3 against two buffers
-        // (the next tile's loads in flight during the current tile's compute) at two rows per
-        // lane: 42 vs 45 us (C2), 152/291 vs 186/370 us (C3 pass 2 / pass 1) -- the second
-        // buffer costs occupancy and halves the rows per tile (rejected).
-        // (development: AEON_HIP_TILE_ROWS caps the rows per tile instead)
-        static const int tr_env = std::getenv("AEON_HIP_TILE_ROWS") ? std::atoi(std::getenv("AEON_HIP_TILE_ROWS")) : 0;
-        const int        tr_cap = std::min(64, std::max(1, tr_env > 0 ? tr_env : 4 * nph));
-        int       budget = kStageBudget;
-        bool hue = false, contrast = false;
-        for (const J_& J : jobs) {
-            hue |= (J.photo & PHOTO_HUE) != 0;
-            contrast |= (J.photo & PHOTO_CONTRAST) != 0 && J.stats_slot >= 0;
-        }
-        has_hue = hue, has_contrast = contrast;
-        for (int pass = 0; pass < 2; pass++) {
-            for (int t = tr_cap; t >= 1; t--) {
-                // staged rows, each in whole DMA instructions (stage_bytes_for)
-                long by = 0;
-                for (const J_& J : jobs) by = std::max(by, stage_bytes_for(J.cn, stage_rows_for(J, t), stage_cols(J)));
-                by = (by + 1023) / 1024 * 1024;
-                if (by <= budget || (t == 1 && pass == 1)) {
-                    tr = t, stage_bytes = (int)by;
-                    goto chosen;
-                }
-            }
-            budget = kStageBudgetHi;
-        }
-    chosen:
-        lds = lds_layout(max_win_w, tr, stage_bytes, photo && hue, rtab).total;
-        if (lds > kMaxLds)
-            fail(AEON_HIP_EUNSUPPORTED, "source crop too wide for LDS-staged row bands (" + std::to_string(lds) +
-                                            " bytes)");
-    }
-};
-
-// Geometry + constants of one image-provider record (transform_single_image).
-// image::rotate (src/image.cpp:53-75): cv::getRotationMatrix2D(Point2i(cols/2, rows/2), angle, 1)
-// inverted the way cv::warpAffine does without WARP_INVERSE_MAP (OpenCV 2.4 imgwarp.cpp); double
-// arithmetic on the host, as aeon's.
-void rotation_inverse_map(int w, int h, int angle, double M[6])
-{
-    const float  cx = (float)(w / 2), cy = (float)(h / 2); // Point2i -> Point2f
-    const double a  = (double)angle * (3.1415926535897932384626433832795 / 180);
-    const double alpha = std::cos(a) * 1.0, beta = std::sin(a) * 1.0;
-    M[0] = alpha, M[1] = beta, M[2] = (1 - alpha) * cx - beta * cy;
-    M[3] = -beta, M[4] = alpha, M[5] = beta * cx + (1 - alpha) * cy;
-    double D = M[0] * M[4] - M[1] * M[3];
-    D        = D != 0 ? 1. / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11;
-    M[1] *= -D;
-    M[3] *= -D;
-    M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5];
-    const double b2 = -M[3] * M[2] - M[4] * M[5];
-    M[2] = b1, M[5] = b2;
-}
-
-// A single-channel pixel-mask / depth-map record, 16-bit (CV_16U, ANYDEPTH) or rotation-free
-// 8-bit: crop -> INTER_NEAREST -> flip -> convertTo (etl_pixel_mask.cpp:65-92,
-// etl_depthmap.cpp:65-96, image.cpp:176-212), one gather pass (mask16_kernels.hip).
-void rotation_inverse_map(int w, int h, int angle, double M[6]);
-
-void plan_mask16(const aeon_img_desc& d, const void* src_base, const aeon_aug_params& p, const aeon_out_desc& o,
-                 uint8_t* out_item, bool is_mask, std::vector<Mask16Job>& m16, std::vector<RotJob>& rot,
-                 size_t& scratch_bytes)
-{
-    const int eb = d.elem_bytes == 2 ? 2 : 1;
-    if (!is_mask) fail(AEON_HIP_EUNSUPPORTED, "16-bit sources are implemented for pixel masks / depth maps only");
-    if (d.channels != 1 || o.channels != 1) fail(AEON_HIP_EINVAL, "16-bit masks must have one channel");
-    if (d.width <= 0 || d.height <= 0 || d.stride < d.width * eb || (eb == 2 && ((d.stride & 1) || (d.offset & 1))))
-        fail(AEON_HIP_EINVAL, eb == 2 ? "invalid 16-bit source image descriptor" : "invalid source image descriptor");
-    if (p.out_w <= 0 || p.out_h <= 0) fail(AEON_HIP_EINVAL, "invalid output size");
-    const size_t elem = out_elem_bytes(o.dtype);
-    if ((size_t)p.out_w * p.out_h * elem > o.item_stride) fail(AEON_HIP_EINVAL, "output item does not fit item_stride");
-    if (o.fixed_aspect_ratio && (p.out_w > o.canvas_w || p.out_h > o.canvas_h))
-        fail(AEON_HIP_EINVAL, "fixed_aspect_ratio: output_size larger than the image canvas");
-    if (p.crop_x < 0 || p.crop_y < 0 || p.crop_w <= 0 || p.crop_h <= 0 || p.crop_x + p.crop_w > d.width ||
-        p.crop_y + p.crop_h > d.height)
-        fail(AEON_HIP_EINVAL, "cropbox outside image");
-    Mask16Job M{};
-    M.scale_x    = 1. / ((double)p.out_w / p.crop_w);
-    M.scale_y    = 1. / ((double)p.out_h / p.crop_h);
-    M.src_ptr    = (uint64_t)((const uint8_t*)src_base + d.offset);
-    M.out_ptr    = (uint64_t)out_item;
-    M.src_stride = d.stride;
-    M.crop_x = p.crop_x, M.crop_y = p.crop_y, M.crop_w = p.crop_w, M.crop_h = p.crop_h;
-    M.out_w = p.out_w, M.out_h = p.out_h;
-    M.out_pitch = o.fixed_aspect_ratio ? o.canvas_w : p.out_w;
-    M.flip      = p.flip ? 1 : 0;
-    M.dtype     = o.dtype;
-    M.src_elem  = eb;
-    if (p.angle != 0) {
-        // image::rotate(..., interpolate = false, border 0) (etl_pixel_mask.cpp:72-74,
-        // etl_depthmap.cpp:72-73): nearest moves whole elements, so a 16-bit record rotates as a
-        // 2-byte-per-pixel one; the gather pass then reads the rotated copy in the slot scratch
-        // only the cropbox window of the rotated record is produced (the gather reads nothing else)
-        RotJob R{};
-        rotation_inverse_map(d.width, d.height, p.angle, R.M);
-        R.src_ptr = M.src_ptr;
-        R.w = d.width, R.h = d.height, R.stride = d.stride, R.cn = eb;
-        R.interp      = AEON_INTERP_NEAREST;
-        R.ox = p.crop_x, R.oy = p.crop_y, R.ow = p.crop_w, R.oh = p.crop_h;
-        size_t off    = (scratch_bytes + 15) & ~(size_t)15;
-        scratch_bytes = off + (size_t)R.ow * R.oh * eb + 16;
-        R.out_ptr     = off; // relocated to the slot's scratch by the caller
-        R.angle       = p.angle;
-        rot.push_back(R);
-        M.src_ptr     = off;
-        M.src_scratch = 1;
-        M.src_stride  = R.ow * eb;
-        M.crop_x = M.crop_y = 0;
-    }
-    m16.push_back(M);
-}
-
-// Checks of one 8-bit record aeon's transformer would throw on (or that this stage refuses).
-void validate_record(const aeon_img_desc& d, const aeon_aug_params& p, const aeon_out_desc& o, bool is_mask)
-{
-    const int cn = d.channels;
-    if (cn != 1 && cn != 3) fail(AEON_HIP_EINVAL, "channels must be 1 or 3");
-    if (cn != o.channels) fail(AEON_HIP_EINVAL, "decoded channels do not match the output config");
-    if (d.width <= 0 || d.height <= 0 || d.stride < d.width * cn)
-        fail(AEON_HIP_EINVAL, "invalid source image descriptor");
-    const int interp = is_mask ? AEON_INTERP_NEAREST : p.interp;
-    if (interp < AEON_INTERP_LINEAR || interp > AEON_INTERP_LANCZOS4) fail(AEON_HIP_EINVAL, "unknown interpolation");
-    if (p.out_w <= 0 || p.out_h <= 0) fail(AEON_HIP_EINVAL, "invalid output size");
-    const size_t elem = out_elem_bytes(o.dtype);
-    if ((size_t)p.out_w * p.out_h * cn * elem > o.item_stride)
-        fail(AEON_HIP_EINVAL, "output item does not fit item_stride");
-    if (o.fixed_aspect_ratio && (p.out_w > o.canvas_w || p.out_h > o.canvas_h))
-        fail(AEON_HIP_EINVAL, "fixed_aspect_ratio: output_size larger than the image canvas");
-    int base_w = d.width, base_h = d.height;
-    if (!is_mask && expands(p)) { // image::expand throws on a record that does not fit the canvas
-        if (p.expand_x < 0 || p.expand_y < 0 || p.expand_x + d.width > p.expand_w || p.expand_y + d.height > p.expand_h)
-            fail(AEON_HIP_EINVAL, "Invalid parameters to expand image");
-        base_w = p.expand_w, base_h = p.expand_h;
-    }
-    if (!is_mask && p.resize_short_size > 0) get_resized_short_size(base_w, base_h, p.resize_short_size, &base_w, &base_h);
-    if (p.crop_x < 0 || p.crop_y < 0 || p.crop_w <= 0 || p.crop_h <= 0 || p.crop_x + p.crop_w > base_w ||
-        p.crop_y + p.crop_h > base_h)
-        fail(AEON_HIP_EINVAL, (is_mask || p.resize_short_size <= 0) && !(!is_mask && expands(p))
-                                  ? "cropbox outside image"
-                                  : "cropbox outside the expanded / resize_short image");
-    if (!is_mask && photo_flags(p) && cn != 3) fail(AEON_HIP_EINVAL, "photometric augmentation needs a 3-channel image");
-    if (!is_mask && (p.n_lighting != 0 && p.n_lighting != 3)) fail(AEON_HIP_EINVAL, "lighting needs 3 values");
-}
-
-// Where a call's records go when not to out_dev + i * item_stride as planes of their own size: the video
-// call's frames (run_video), frame d of a clip at its item + d * H * W with planes D * H * W apart.
-struct ItemMap {
-    const uint64_t* item;  // record i's output address
-    int32_t         plane; // plane stride (elements)
-};
-uint64_t item_of(const ItemMap* im, const void* out_dev, const aeon_out_desc& o, int i)
-{
-    return im ? im->item[i] : (uint64_t)out_dev + (uint64_t)i * o.item_stride;
-}
-
-OutGeom out_geom(const aeon_out_desc& o, const ItemMap* im = nullptr)
-{
-    return OutGeom{o.fixed_aspect_ratio, o.canvas_w, o.canvas_h, im ? im->plane : 0};
-}
-
-// The cv::resize of a (sw x sh -> dw x dh) resize with interpolation `interp` when the tile kernel
-// has no mode for it: a resize_generic method (CUBIC, LANCZOS4, INTER_AREA but its exact 2x box), or
-// -1 -- LINEAR / NEAREST, any identity (every method reproduces the source at scale 1) and INTER_AREA's
-// 2x fast path (RESIZE_AREA2X, the same (a+b+c+d+2)>>2).  OpenCV 2.4.9 cv::resize's dispatch.
-int generic_method(int sw, int sh, int dw, int dh, int interp, int cn, int* isx, int* isy)
-{
-    if (interp != AEON_INTERP_CUBIC && interp != AEON_INTERP_AREA && interp != AEON_INTERP_LANCZOS4) return -1;
-    if (sw == dw && sh == dh) return -1;
-    if (interp == AEON_INTERP_CUBIC) return GR_CUBIC;
-    if (interp == AEON_INTERP_LANCZOS4) return GR_LANCZOS4;
-    const double sx = 1. / ((double)dw / sw), sy = 1. / ((double)dh / sh);
-    if (sx < 1 || sy < 1) return GR_LINEAR_AREA; // an upscaled axis: bilinear over area-mode coefficients
-    const int ix = cv_round(sx), iy = cv_round(sy);
-    if (std::fabs(sx - ix) < DBL_EPSILON && std::fabs(sy - iy) < DBL_EPSILON) {
-        if (ix == 2 && iy == 2 && (cn == 1 || cn == 3)) return -1;
-        *isx = ix, *isy = iy;
-        return GR_AREA_FAST;
-    }
-    return GR_AREA;
-}
-
-// The host half of interpolateLanczos4 (OpenCV 2.4.9 imgwarp.cpp) for destinations [d0, d0 + n) of an
-// ssize -> dsize axis (x: the anchor clamped as cv::resize does for columns; y: raw, the rows clipped
-// per tap on use): the anchor, the fraction and the double sin / cos of the C library as OpenCV's --
-// the one part a device could not reproduce bit for bit.  The coefficients are finished on the device
-// (lanczos4_taps, resize_kernels.hip).
-void lanczos4_inputs(int ssize, double scale, int d0, int n, bool clamp, LzIn* out)
-{
-    const double kPi = 3.1415926535897932384626433832795;
-    for (int d = d0; d < d0 + n; d++) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int   s = (int)std::floor(f);
-        f -= (float)s;
-        if (clamp && s < 0) f = 0, s = 0;
-        if (clamp && s >= ssize - 1) f = 0, s = ssize - 1;
-        LzIn L{0.0, 0.0, f, s};
-        if (!(f < FLT_EPSILON)) {
-            // sin / cos of a function of the float f alone: memoised per thread.  A batch's fractions are
-            // few (integer crop sizes over a common output size: multiples of 1 / (2 * size), rounded to
-            // float), so a 256-record LANCZOS4 call computes a few thousand pairs instead of 115 K (the
-            // host side was the C2:LANCZOS4 step's bound).  Same libm calls on the same doubles: the
-            // same bits.
-            struct Entry {
-                uint32_t key; // float bits + 1 (0: empty)
-                double   s, c;
-            };
-            static thread_local std::vector<Entry> memo(1 << 14);
-            uint32_t bits;
-            std::memcpy(&bits, &f, 4);
-            Entry& e = memo[(bits * 2654435761u) >> 18];
-            if (e.key != bits + 1) {
-                const double y0 = -(f + 3) * kPi * 0.25;
-                e               = Entry{bits + 1, std::sin(y0), std::cos(y0)};
-            }
-            L.s0 = e.s, L.c0 = e.c;
-        }
-        out[d - d0] = L;
-    }
-}
-
-// One resize_generic launch: its jobs, the Lanczos tap tables, and the tile shape every job of it
-// shares (rows x columns of a tile sized so the taps and the horizontal sums fit 64 KiB of LDS).
-struct GrPlan {
-    std::vector<ResizeJob> jobs;
-    size_t                 off = 0, lz_off = 0, taps_off = 0; // byte offsets in the call's table
-    // One launch per method class (finalize sorts the jobs so each class is contiguous): the
-    // fixed-K methods as resize_sep bands, the rest (INTER_AREA's float taps, integer boxes, jobs
-    // whose bands do not fit) as resize_generic tiles.
-    struct Sub {
-        int  first = 0, count = 0;
-        int  TR = 16, CW = 128, NR = 1, xs = 3, amax = 1, cn_max = 1, max_tiles = 0, SW = 4;
-        int  sep = 0;           // K of resize_sep, or 0: resize_generic
-        bool area = false;      // resize_sep's INTER_AREA form (resizeArea_ jobs, sep = their most taps)
-        bool any_final = false; // some job writes the loader's output itself (its LUT in the launch's LDS)
-    };
-    std::vector<Sub> subs;
-    double bytes = 0; // algorithmic: the source region read once + the window written
-
-    size_t n_taps = 0;     // Lanczos4 taps reserved by add(), their inputs computed by fill_taps()
-    size_t n_taps_max = 0; // ... and what the jobs would need with no axis shared (the ring's sizing bound)
-    // One tap array per distinct axis (source size, scale, first destination index, count, column clamp):
-    // a batch of random crops over one output size repeats them (C2: ~76 crop widths, ~76 heights for 512
-    // axes of 256 records), and equal inputs give equal taps.
-    struct LzAxis {
-        int      ssize, d0, n, clamp;
-        uint64_t scale_bits;
-        bool     operator==(const LzAxis& o) const
-        {
-            return ssize == o.ssize && d0 == o.d0 && n == o.n && clamp == o.clamp && scale_bits == o.scale_bits;
-        }
-    };
-    struct LzAxisHash {
-        size_t operator()(const LzAxis& a) const
-        {
-            uint64_t h = a.scale_bits * 0x9E3779B97F4A7C15ull;
-            for (int v : {a.ssize, a.d0, a.n, a.clamp}) h = (h ^ (uint32_t)v) * 0x100000001B3ull;
-            return (size_t)h;
-        }
-    };
-    std::unordered_map<LzAxis, size_t, LzAxisHash> lz_index; // axis -> its first tap
-    std::vector<std::pair<LzAxis, size_t>>          lz_axes;  // (axis, first tap), in reservation order
-    int32_t axis_taps(int ssize, double scale, int d0, int n, bool clamp)
-    {
-        LzAxis a{ssize, d0, n, clamp ? 1 : 0, 0};
-        std::memcpy(&a.scale_bits, &scale, 8);
-        auto it = lz_index.find(a);
-        if (it == lz_index.end()) {
-            it = lz_index.emplace(a, n_taps).first;
-            lz_axes.emplace_back(a, n_taps);
-            n_taps += n;
-        }
-        return (int32_t)(it->second * sizeof(GrTap));
-    }
-
-    void add(ResizeJob R)
-    {
-        if (R.method == GR_LANCZOS4) { // byte offsets, relative until the table is laid out
-            n_taps_max += (size_t)R.win_w + R.win_h;
-            R.coef_x = axis_taps(R.crop_w, R.scale_x, R.win_x, R.win_w, true);
-            R.coef_y = axis_taps(R.crop_h, R.scale_y, R.win_y, R.win_h, false);
-        }
-        jobs.push_back(R);
-    }
-    // The Lanczos4 tap inputs (a sin and a cos per destination column and row), on `pool` when there
-    // are enough jobs to pay for it; the device turns them into the taps (the whole taps computed here
-    // cost ~75 us per 224x224 record of libm, divisions and rounding: ~1.1 ms per 256-record call on
-    // 14 threads, and the LANCZOS4 step was host-bound).
-    // They go straight into the call's pinned table (`lz`: n_taps entries; a per-call vector of ~2.8 MB
-    // and its copy into the table cost page faults under 14 writers and ~0.1 ms of memcpy).
-    void fill_taps(thread_pool* pool, LzIn* lz) const
-    {
-        auto one = [&](int i) {
-            const LzAxis& a = lz_axes[i].first;
-            double        scale;
-            std::memcpy(&scale, &a.scale_bits, 8);
-            lanczos4_inputs(a.ssize, scale, a.d0, a.n, a.clamp != 0, lz + lz_axes[i].second);
-        };
-        if (pool && n_taps > 4096) pool->run((int)lz_axes.size(), one);
-        else for (int i = 0; i < (int)lz_axes.size(); i++) one(i);
-    }
-    static int ksize(int m) { return m == GR_CUBIC ? 4 : (m == GR_LANCZOS4 ? 8 : 2); }
-    static int sep_k(int m) { return m == GR_CUBIC ? 4 : m == GR_LANCZOS4 ? 8 : m == GR_LINEAR_AREA ? 2 : 0; }
-    // launch classes: the fixed-K methods by K, resizeArea_ jobs, the rest
-    static int cls(int m) { return sep_k(m) ? sep_k(m) : m == GR_AREA ? 50 : 99; }
-    // rows of H a tile of `tr` output rows needs at most (jobs [f, f + n))
-    int rows_for(int f, int n, int tr) const
-    {
-        int nr = 1;
-        for (int i = f; i < f + n; i++) {
-            const ResizeJob& R = jobs[i];
-            if (R.method == GR_AREA) nr = std::max(nr, (int)std::ceil(tr * R.scale_y) + 3);
-            else if (R.method != GR_AREA_FAST) nr = std::max(nr, (int)std::ceil((tr - 1) * R.scale_y) + ksize(R.method) + 2);
-        }
-        return nr;
-    }
-    // staged source bytes per row a tile of `cw` output columns needs at most (a multiple of 4)
-    int bytes_for(int f, int n, int cw) const
-    {
-        int sw = 4;
-        for (int i = f; i < f + n; i++) {
-            const ResizeJob& R = jobs[i];
-            int              cols = 1;
-            if (R.method == GR_AREA) cols = (int)std::ceil(cw * R.scale_x) + 4;
-            else if (R.method != GR_AREA_FAST) cols = (int)std::ceil((cw - 1) * R.scale_x) + ksize(R.method) + 2;
-            sw = std::max(sw, (std::min(cols, R.crop_w) * R.cn + 3) / 4 * 4);
-        }
-        return sw;
-    }
-    // the launch shape of jobs [f, f + n): resize_sep when they are one fixed-K class of one channel
-    // count and a band fits, else resize_generic
-    Sub shape(int f, int n) const
-    {
-        Sub u;
-        u.first = f, u.count = n;
-        for (int i = f; i < f + n; i++) u.any_final = u.any_final || jobs[i].final_out;
-        const size_t lut_lds = u.any_final ? 768 * 4 : 0;
-        int          K = 2, ww = 1;
-        for (int i = f; i < f + n; i++) {
-            const ResizeJob& R = jobs[i];
-            K = std::max(K, ksize(R.method));
-            if (R.method == GR_AREA) u.amax = std::max(u.amax, (int)std::ceil(std::max(R.scale_x, R.scale_y)) + 3);
-            u.cn_max = std::max(u.cn_max, R.cn);
-            ww       = std::max(ww, R.win_w);
-        }
-        // resize_sep: bands of up to 32 rows x the window's width (at most 256 lanes of 4 bytes); resizeArea_
-        // jobs as its INTER_AREA form, K = their most taps per destination index (floor(scale) + 2)
-        int               ka      = 0;
-        static const bool no_area = std::getenv("AEON_HIP_AREA_SEP") && std::atoi(std::getenv("AEON_HIP_AREA_SEP")) == 0;
-        if (jobs[f].method == GR_AREA && !no_area) { // (development: AEON_HIP_AREA_SEP=0, resize_generic)
-            double smax = 1;
-            for (int i = f; i < f + n; i++) smax = std::max({smax, jobs[i].scale_x, jobs[i].scale_y});
-            const int taps = (int)std::floor(smax) + 2;
-            ka             = taps <= 4 ? 4 : taps <= 8 ? 8 : 0;
-        }
-        const int sk  = ka ? ka : sep_k(jobs[f].method);
-        const int xs  = (ka ? 2 : 1) + sk;
-        bool      one = sk != 0;
-        for (int i = f; i < f + n; i++) one = one && jobs[i].method == jobs[f].method && jobs[i].cn == u.cn_max;
-        if (one) {
-            static const int tr0 = std::getenv("AEON_HIP_SEP_TR") ? std::atoi(std::getenv("AEON_HIP_SEP_TR")) : 16;
-            // a band's lanes (at most 256): 4 bytes of a u8 window row each, or 4 pixels of one channel of a
-            // final_out job each -- cn * ceil(cw / 4) lanes, so 340 columns for 3 channels, not 341
-            int cw = std::min({ww, 1024 / u.cn_max, 4 * (256 / u.cn_max)}), tr = std::max(4, std::min(64, tr0));
-            // staged rows: whole 16-byte blocks (resize_sep), hence up to 30 bytes more per row, and 32
-            // bytes of room for the replicated borders (resize_kernels.hip kSepPadL)
-            auto sw = [&] { return (bytes_for(f, n, cw) + 30 + 15) / 16 * 16 + 32; };
-            auto l  = [&] {
-                return ((size_t)(cw + tr) * xs * 4 + 15) / 16 * 16 + (size_t)rows_for(f, n, tr) * sw() + lut_lds;
-            };
-            while (l() > kSepLds && tr > 4) tr /= 2;
-            if (l() <= kSepLds) {
-                u.sep = sk, u.area = ka != 0, u.TR = tr, u.CW = cw, u.NR = rows_for(f, n, tr), u.SW = sw(), u.xs = xs;
-                return u;
-            }
-        }
-        u.xs = std::max(1 + K, 2 + u.amax);
-        u.CW = std::min(128, ww);
-        u.TR = 16;
-        // with the source rows staged in LDS (SW > 0) when they fit at 16 x 128 tiles, else without
-        bool staged = true;
-        auto lds    = [&] {
-            return ((size_t)u.CW * u.xs + (size_t)u.TR * u.xs + (size_t)rows_for(f, n, u.TR) * u.CW * u.cn_max) * 4 +
-                   (staged ? (size_t)rows_for(f, n, u.TR) * bytes_for(f, n, u.CW) : 0) + lut_lds;
-        };
-        staged = lds() <= kGenericLds;
-        while (lds() > kGenericLds && u.TR > 1) u.TR--;
-        while (lds() > kGenericLds && u.CW > 8) u.CW /= 2;
-        if (lds() > kGenericLds) fail(AEON_HIP_EUNSUPPORTED, "resize scale too large for the generic resize's LDS tiles");
-        u.NR = rows_for(f, n, u.TR);
-        u.SW = staged ? bytes_for(f, n, u.CW) : 0;
-        return u;
-    }
-    void finalize()
-    {
-        subs.clear();
-        bytes = 0;
-        if (jobs.empty()) return;
-        // the classes contiguous: resize_sep's by K, resizeArea_'s, then the other generic methods
-        std::stable_sort(jobs.begin(), jobs.end(), [](const ResizeJob& a, const ResizeJob& b) { return cls(a.method) < cls(b.method); });
-        for (int f = 0; f < (int)jobs.size();) {
-            int e = f + 1;
-            while (e < (int)jobs.size() && cls(jobs[e].method) == cls(jobs[f].method)) e++;
-            subs.push_back(shape(f, e - f));
-            f = e;
-        }
-        for (Sub& u : subs) {
-            u.max_tiles = 0;
-            for (int i = u.first; i < u.first + u.count; i++) {
-                ResizeJob& R = jobs[i];
-                R.tiles_x    = (R.win_w + u.CW - 1) / u.CW;
-                R.tiles      = R.tiles_x * ((R.win_h + u.TR - 1) / u.TR);
-                u.max_tiles  = std::max(u.max_tiles, R.tiles);
-                bytes += (double)R.crop_w * R.crop_h * R.cn * ((double)R.win_w / R.dst_w) * ((double)R.win_h / R.dst_h) +
-                         (double)R.win_w * R.win_h * R.cn * (R.final_out ? 4 : 1);
-            }
-        }
-    }
-    static constexpr size_t kGenericLds = 64 * 1024;
-    static constexpr size_t kSepLds     = 40 * 1024; // (four bands per CU)
-};
-
-// A resize of the (cropped, padded) region of J's source to its window, into scratch at `off`.
-// (development: AEON_HIP_IDENTITY_SEP=0 keeps identity resizes on the tile kernel)
-bool no_identity_sep()
-{
-    static const bool v = std::getenv("AEON_HIP_IDENTITY_SEP") && std::atoi(std::getenv("AEON_HIP_IDENTITY_SEP")) == 0;
-    return v;
-}
-
-ResizeJob resize_job(const AugJob& J, int method, int isx, int isy)
-{
-    ResizeJob R{};
-    R.scale_x = J.scale_x, R.scale_y = J.scale_y;
-    R.inv_x = (double)J.dst_w / J.crop_w, R.inv_y = (double)J.dst_h / J.crop_h;
-    R.src_ptr = J.src_ptr, R.src_scratch = J.src_scratch;
-    R.src_stride = J.src_stride, R.cn = J.cn;
-    R.crop_x = J.crop_x, R.crop_y = J.crop_y, R.crop_w = J.crop_w, R.crop_h = J.crop_h;
-    R.shift_x = J.shift_x, R.shift_y = J.shift_y, R.padded = J.padded;
-    R.dst_w = J.dst_w, R.dst_h = J.dst_h;
-    R.win_x = J.win_x, R.win_y = J.win_y, R.win_w = J.win_w, R.win_h = J.win_h;
-    R.method = method, R.isx = isx, R.isy = isy;
-    return R;
-}
-
-// Launch order: rot (image::rotate) -> exp (image::expand) -> gr_short / pre (resize_short, generic
-// or tile) -> gr_main (CUBIC / LANCZOS4 / AREA resize of the crop) -> pre2 (2x-area resize ahead of
-// photometric stages) -> pass1 (contrast statistics) -> main; each reads only what an earlier group
-// wrote.
-void plan_image(const aeon_img_desc& d, const void* src_base, const aeon_aug_params& p,
-                const aeon_out_desc& o, uint8_t* out_item, bool is_mask, std::vector<RotJob>& rot,
-                std::vector<ExpandJob>& exp, GrPlan& gr_short, LaunchPlan& pre, GrPlan& gr_main, LaunchPlan& pre2,
-                LaunchPlan& pass1, LaunchPlan& main, size_t& scratch_bytes, const ItemMap* im = nullptr)
-{
-    validate_record(d, p, o, is_mask);
-    const int cn = d.channels;
-    AugJob    J;
-    plan_direct(d, (uint64_t)src_base, p, out_geom(o, im), (uint64_t)out_item, is_mask, J);
-    if (p.angle != 0) {
-        // image::rotate into scratch (interpolated for images, nearest + border 0 for pixel
-        // masks, etl_pixel_mask.cpp:72-74); everything after reads the rotated record
-        // Only the cropbox window is produced when nothing before the crop needs the whole rotated
-        // record (no expand canvas, no resize_short of it); the job then crops it at (0, 0).
-        RotJob R{};
-        rotation_inverse_map(d.width, d.height, p.angle, R.M);
-        R.src_ptr = J.src_ptr;
-        R.w = d.width, R.h = d.height, R.stride = d.stride, R.cn = cn;
-        R.interp = is_mask ? AEON_INTERP_NEAREST : AEON_INTERP_LINEAR;
-        const bool window = is_mask || (!expands(p) && p.resize_short_size <= 0);
-        R.ox = window ? p.crop_x : 0, R.oy = window ? p.crop_y : 0;
-        R.ow = window ? p.crop_w : d.width, R.oh = window ? p.crop_h : d.height;
-        size_t off    = (scratch_bytes + 15) & ~(size_t)15;
-        scratch_bytes = off + (size_t)R.ow * R.oh * cn + 16;
-        R.out_ptr     = off; // relocated to the slot's scratch by the caller
-        R.angle       = p.angle;
-        rot.push_back(R);
-        J.src_ptr     = off;
-        J.src_scratch = 1;
-        J.src_w = R.ow, J.src_h = R.oh;
-        J.src_bytes   = (uint64_t)R.ow * R.oh * cn;
-        J.src_stride  = R.ow * cn;
-        J.crop_x -= R.ox, J.crop_y -= R.oy;
-    }
-    if (!is_mask && expands(p)) {
-        // image::expand (image.cpp:276-303) into scratch: a zeroed expand_w x expand_h canvas with the
-        // (rotated) record at (expand_x, expand_y); everything after reads the canvas
-        ExpandJob E{};
-        E.src_ptr     = J.src_ptr;
-        E.src_scratch = J.src_scratch;
-        E.w = J.src_w, E.h = J.src_h, E.stride = J.src_stride, E.cn = cn;
-        E.ew = p.expand_w, E.eh = p.expand_h, E.ox = p.expand_x, E.oy = p.expand_y;
-        size_t off    = (scratch_bytes + 15) & ~(size_t)15;
-        scratch_bytes = off + (size_t)E.ew * E.eh * cn + 16;
-        E.out_ptr     = off; // relocated to the slot's scratch by the caller
-        exp.push_back(E);
-        J.src_ptr     = off;
-        J.src_scratch = 1;
-        J.src_bytes   = (uint64_t)E.ew * E.eh * cn;
-        J.src_w = E.ew, J.src_h = E.eh, J.src_stride = E.ew * cn;
-    }
-    if (!is_mask && p.resize_short_size > 0) {
-        // image::resize_short (image.cpp:118-127) into a device scratch, cropbox window only
-        const int bw = J.src_w, bh = J.src_h; // the (rotated, expanded) record
-        int       rw, rh;
-        get_resized_short_size(bw, bh, p.resize_short_size, &rw, &rh);
-        AugJob P = J;
-        P.photo   = 0;
-        P.flip    = 0;
-        P.shift_x = P.shift_y = P.padded = 0;
-        P.crop_x = 0, P.crop_y = 0, P.crop_w = bw, P.crop_h = bh;
-        P.mode    = choose_mode(bw, bh, rw, rh, p.interp, cn);
-        P.scale_x = 1. / ((double)rw / bw);
-        P.scale_y = 1. / ((double)rh / bh);
-        P.dst_w = rw, P.dst_h = rh;
-        P.win_x = p.crop_x, P.win_y = p.crop_y, P.win_w = p.crop_w, P.win_h = p.crop_h;
-        P.xv      = simd_boundary(rw * cn);
-        size_t off = (scratch_bytes + 15) & ~(size_t)15;
-        scratch_bytes = off + (size_t)p.crop_w * p.crop_h * cn + 16;
-        P.out_ptr = off; // relocated to the slot's scratch by the caller
-        int       isx = 0, isy = 0;
-        const int gm  = generic_method(bw, bh, rw, rh, p.interp, cn, &isx, &isy);
-        if (gm >= 0) {
-            ResizeJob R   = resize_job(P, gm, isx, isy);
-            R.out_ptr     = off;
-            R.out_scratch = 1;
-            gr_short.add(R);
-        } else {
-            pre.jobs.push_back(P);
-        }
-        J.src_ptr = off; // likewise
-        J.src_bytes  = (uint64_t)p.crop_w * p.crop_h * cn;
-        J.src_w = p.crop_w, J.src_h = p.crop_h, J.src_stride = p.crop_w * cn;
-        J.crop_x = 0, J.crop_y = 0;
-        J.src_scratch = 1; // relocated to the slot's scratch by the caller
-    }
-    int       isx = 0, isy = 0;
-    int       gm  = is_mask ? -1 : generic_method(J.crop_w, J.crop_h, J.dst_w, J.dst_h, p.interp, cn, &isx, &isy);
-    const bool final_ok = J.photo == 0 && o.dtype == AEON_DTYPE_F32 && !o.fixed_aspect_ratio && (cn == 1 || cn == 3) &&
-                          o.channels == cn;
-    // An identity resize (cv::resize copies) of a CUBIC / LANCZOS4 / INTER_AREA call with no photometric
-    // stage and f32 output: through the call's resize class with identity taps -- (0, 2048, 0, 0), the
-    // fraction-0 Lanczos row, the bilinear emulation's (2048, 0), each reproducing the byte exactly -- so
-    // the call launches no tile kernel for its few uncropped records (an 8.5 us launch per C2:<method>
-    // step: one tile's latency).
-    if (gm < 0 && !is_mask && final_ok && J.crop_w == J.dst_w && J.crop_h == J.dst_h &&
-        (p.interp == AEON_INTERP_CUBIC || p.interp == AEON_INTERP_LANCZOS4 || p.interp == AEON_INTERP_AREA) && !no_identity_sep())
-        gm = p.interp == AEON_INTERP_CUBIC ? GR_CUBIC : p.interp == AEON_INTERP_LANCZOS4 ? GR_LANCZOS4 : GR_LINEAR_AREA;
-    if (gm >= 0 && gm != GR_AREA_FAST && final_ok) {
-        // no photometric stage and f32 output: the resize pass is the last one -- it flips,
-        // standardizes through the LUT and stores the loader's layout itself (no u8 window in scratch,
-        // no copy pass)
-        ResizeJob R = resize_job(J, gm, isx, isy);
-        R.out_ptr   = J.out_ptr;
-        R.final_out = 1, R.flip = J.flip, R.out_pitch = J.out_pitch, R.out_plane = J.out_plane;
-        gr_main.add(R);
-        return;
-    }
-    if (gm >= 0) {
-        // CUBIC / LANCZOS4 / INTER_AREA resize of the (padded) crop into scratch (resize_kernels.hip),
-        // then the photometric stages, flip and the loader as a copy pass over it
-        ResizeJob R   = resize_job(J, gm, isx, isy);
-        size_t    off = (scratch_bytes + 15) & ~(size_t)15;
-        scratch_bytes = off + (size_t)J.win_w * J.win_h * cn + 16;
-        R.out_ptr     = off; // relocated to the slot's scratch by the caller
-        R.out_scratch = 1;
-        gr_main.add(R);
-        J.src_ptr     = off;
-        J.src_scratch = 1;
-        J.src_bytes   = (uint64_t)J.win_w * J.win_h * cn;
-        J.src_w = J.win_w, J.src_h = J.win_h, J.src_stride = J.win_w * cn;
-        J.crop_x = J.crop_y = 0, J.crop_w = J.win_w, J.crop_h = J.win_h;
-        J.shift_x = J.shift_y = J.padded = 0;
-        J.mode    = RESIZE_COPY;
-        J.scale_x = J.scale_y = 1.0;
-        J.xv      = simd_boundary(J.win_w * cn);
-    }
-    const int photo = J.photo;
-    if (photo && J.mode == RESIZE_AREA2X) {
-        // 2x-area resize first (resize-only pre-pass into scratch, unflipped), then the
-        // photometric stages as a copy pass over it
-        AugJob P      = J;
-        P.photo       = 0;
-        P.flip        = 0;
-        size_t off    = (scratch_bytes + 15) & ~(size_t)15;
-        scratch_bytes = off + (size_t)J.win_w * J.win_h * 3 + 16;
-        P.out_ptr     = off; // relocated to the slot's scratch by the caller
-        pre2.jobs.push_back(P);
-        J.src_ptr     = off;
-        J.src_scratch = 1;
-        J.src_bytes   = (uint64_t)J.win_w * J.win_h * 3;
-        J.src_w = J.win_w, J.src_h = J.win_h, J.src_stride = J.win_w * 3;
-        J.crop_x = J.crop_y = 0, J.crop_w = J.win_w, J.crop_h = J.win_h;
-        J.shift_x = J.shift_y = J.padded = 0;
-        J.mode    = RESIZE_COPY;
-        J.scale_x = J.scale_y = 1.0;
-        J.xv      = simd_boundary(J.win_w * 3);
-    }
-    if (photo & PHOTO_CONTRAST) {
-        // contrast needs the mean of the post-hue image: pass 1 writes that image (HWC
-        // uint8, unflipped) and its exact per-chunk sums; pass 2 (this job) reads it back
-        AugJob P1     = J;
-        P1.flip       = 0;
-        P1.photo      = photo & (PHOTO_BS | PHOTO_HUE | PHOTO_CONTRAST);
-        P1.stats_slot = (int)pass1.jobs.size();
-        size_t off    = (scratch_bytes + 15) & ~(size_t)15;
-        scratch_bytes = off + (size_t)J.win_w * J.win_h * 3 + 16;
-        P1.out_ptr    = off; // relocated to the slot's scratch by the caller
-        pass1.jobs.push_back(P1);
-        J.stats_slot  = P1.stats_slot;
-        J.src_ptr     = off;
-        J.src_scratch = 1;
-        J.src_bytes   = (uint64_t)J.win_w * J.win_h * 3;
-        J.src_w = J.win_w, J.src_h = J.win_h, J.src_stride = J.win_w * 3;
-        J.crop_x = J.crop_y = 0, J.crop_w = J.win_w, J.crop_h = J.win_h;
-        J.shift_x = J.shift_y = J.padded = 0;
-        J.mode    = RESIZE_COPY;
-        J.scale_x = J.scale_y = 1.0;
-        J.xv      = simd_boundary(J.win_w * 3);
-        J.photo   = photo & (PHOTO_CONTRAST | PHOTO_LIGHTING);
-    }
-    if ((J.out_ptr & 15) != 0 || (J.win_w & 3) != 0 || o.fixed_aspect_ratio) main.vec_ok = false;
-    main.jobs.push_back(J);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -946,6 +223,7 @@ struct aeon_hip_ctx {
     std::vector<JobGeom> geoms;              // reused per call
     std::vector<AugJob>  direct_jobs;        // (run_direct) the call's jobs before they go into the slot
     std::vector<int>     direct_order;       // (run_direct) their table order: largest crop first
+    CallPlan             plan;               // (run_batch) the call's plan
     JpegState*           jpeg = nullptr;     // JPEG decode stage (pool, staging ring), on first use
     thread_pool*         host_pool = nullptr; // the owning decoder's pool (ctx_share_pool), for the JPEG stage
     // localization_rcnn: the anchor table of the last config seen stays resident (uploaded once), and the
@@ -1213,22 +491,9 @@ const float* resident_lut(aeon_hip_ctx* ctx, const aeon_out_desc& o, bool u8_map
     return dev;
 }
 
-// Algorithmic bytes of one launch: the resampled u8 source footprint plus
-// the bytes written (KM_STATS / KM_RAW write an HWC uint8 intermediate).
-template <typename J_>
-double launch_bytes(const std::vector<J_>& jobs, int mode, size_t out_elem)
+SplitKnobs split_knobs(const aeon_hip_ctx* ctx, bool allowed)
 {
-    double b = 0;
-    for (const J_& J : jobs) {
-        double rd = (double)J.crop_w * J.crop_h * J.cn;
-        if (J.mode == RESIZE_LINEAR || J.mode == RESIZE_NEAREST) {
-            // a window of the resize target reads only its share of the source
-            rd *= ((double)J.win_w / J.dst_w) * ((double)J.win_h / J.dst_h);
-        }
-        double wr = (double)J.win_w * J.win_h * J.cn * (mode == KM_FINAL ? out_elem : 1);
-        b += rd + wr;
-    }
-    return b;
+    return SplitKnobs{ctx->split && allowed, ctx->split_helpers, ctx->split_rpl, ctx->split_occ};
 }
 
 // Persistent grid: as many workgroups as the CUs hold at once, never more than the tiles.
@@ -1292,6 +557,32 @@ void timed_launch(aeon_hip_ctx* ctx, int mode, const LaunchPlan& P, const Launch
     if (timed) ctx->timers.push_back(t);
 }
 
+// Per-launch timing events on one call in timing_every (each event pair costs GPU time between launches).
+bool take_timing(aeon_hip_ctx* ctx)
+{
+    return ctx->timing && (ctx->timing_calls++ % ctx->timing_every) == ctx->timing_every - 1;
+}
+
+// A final launch: as augment_split with shape `sa` (plan_split), or (null) as augment_tiles.
+void launch_final(aeon_hip_ctx* ctx, const LaunchPlan& P, const SplitArgs* sa, const LaunchArgs& a, hipStream_t stream,
+                  double bytes, bool timed)
+{
+    if (!sa) return timed_launch(ctx, KM_FINAL, P, a, stream, bytes, timed);
+    KernelTimer t{};
+    if (timed) t = take_timer(ctx, KM_FINAL, bytes);
+    const int grid = std::min(a.total_tiles, sa->occ * ctx->n_cu); // sa->occ workgroups per CU (the LDS request holds it)
+    HIP_OK(launch_split(P.tail, sa->occ, a, *sa, grid, stream, timed ? t.start : nullptr, timed ? t.stop : nullptr));
+    if (timed) ctx->timers.push_back(t);
+}
+
+// fixed_aspect_ratio: std::fill_n of each item's canvas, its whole byte size as declared (etl_image.cpp:263)
+void clear_canvases(const aeon_out_desc& od, void* out_dev, int n, hipStream_t stream)
+{
+    if (od.fixed_aspect_ratio)
+        HIP_OK(hipMemset2DAsync(out_dev, od.item_stride, 0,
+                                (size_t)od.canvas_w * od.canvas_h * od.channels * out_elem_bytes(od.dtype), n, stream));
+}
+
 // The next ring slot for a call on `stream`, once the kernels that last used it are done.
 Slot& take_slot(aeon_hip_ctx* ctx, hipStream_t stream, int& index)
 {
@@ -1314,25 +605,6 @@ void release_slot(aeon_hip_ctx* ctx, int index, hipStream_t stream)
     ctx->open_stream = stream;
     if ((int)ctx->open_slots.size() >= ctx->done_every) close_slots(ctx);
     ctx->host_calls++;
-}
-
-// The loader side of a launch: ko = what the kernels write (fixed_aspect_ratio writes its uint8
-// canvas whatever the declared type, u8_map = standardized through the LUT); double output
-// standardizes in the kernel with the declared mean / stddev by source channel.
-struct OutView {
-    aeon_out_desc ko;
-    bool          u8_map = false;
-};
-OutView out_view(const aeon_out_desc& o)
-{
-    OutView v;
-    v.ko = o;
-    if (o.fixed_aspect_ratio && o.dtype != AEON_DTYPE_U8) {
-        v.ko.dtype    = AEON_DTYPE_U8;
-        v.ko.has_mean = 0;
-        v.u8_map      = o.has_mean != 0;
-    }
-    return v;
 }
 
 // The device error word of the calls on `stream`: each stream its own (so that aeon_hip_synchronize of
@@ -1403,46 +675,6 @@ LaunchArgs launch_args(aeon_hip_ctx* ctx, const Slot& s, const uint8_t* table, c
     return a;
 }
 
-// augment_split's shape for a direct call's records (all 3-channel, INTER_LINEAR, one window width W,
-// W % 4 == 0): nwc compute waves of nph row phases x W/4 column groups plus ctx->split_helpers staging
-// waves in one workgroup of <= 1,024 lanes, rows_per_tile = nph * rpl, two staging buffers.  The LDS
-// request is held above half a CU's 160 KB so that the grid's n_cu workgroups land one per CU.  False:
-// no such shape (the caller keeps augment_tiles).
-template <typename J_>
-bool plan_split(const aeon_hip_ctx* ctx, const std::vector<J_>& geo, LaunchPlan& P, SplitArgs& sa)
-{
-    if (geo.empty()) return false;
-    const int W = geo[0].win_w;
-    if (W <= 0 || (W & 3) != 0) return false;
-    for (const J_& g : geo)
-        if (g.cn != 3 || g.win_w != W || g.mode != RESIZE_LINEAR) return false;
-    const int gpr = W / 4, nh = ctx->split_helpers;
-    int       nph = 0, nwc = 0;
-    for (int p = 32; p >= 1; p--) {
-        const int w = (p * gpr + 63) / 64;
-        if (w + nh <= 16) {
-            nph = p, nwc = w;
-            break;
-        }
-    }
-    if (nph == 0) return false;
-    const int rpl = std::max(1, std::min(ctx->split_rpl, kSplitTRMax / nph));
-    const int tr  = nph * rpl;
-    long      by  = 0;
-    for (const J_& g : geo) by = std::max(by, stage_bytes_for(3, stage_rows_for(g, tr), stage_cols(g)));
-    by             = (by + 1023) / 1024 * 1024;
-    const int lds  = split_lds_layout(W, (int)by).total;
-    const int occ  = ctx->split_occ == 2 && !P.tail && lds <= kMaxLds / 2 ? 2 : 1; // (the TAIL form spills at 64 VGPRs)
-    if (lds > kMaxLds) return false;
-    P.tr          = tr;
-    P.stage_bytes = (int)by;
-    P.max_win_w   = W;
-    P.threads     = (nwc + nh) * 64;
-    P.lds         = occ == 2 ? lds : std::max(lds, kMaxLds / 2 + 1024);
-    sa.nwc = nwc, sa.nph = nph, sa.rpl = rpl, sa.win_w = W, sa.occ = occ;
-    return true;
-}
-
 // Direct call (the common case: C2, C5's image, every record transformed straight from its source in
 // one launch group): one launch and nothing else on the stream.  The host checks the records, sizes
 // the launch from their geometry and writes each record's AugJob (plan_direct) into the slot's
@@ -1498,7 +730,7 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
     // helper waves, split_kernels.hip); else augment_tiles' shape
     SplitArgs  sa{};
     const bool split = ctx->split && !P.photo && P.rm == RESIZE_LINEAR && o.dtype == AEON_DTYPE_F32 && o.channel_major &&
-                       vec_ok && !ov.u8_map && !o.fixed_aspect_ratio && plan_split(ctx, geo, P, sa);
+                       vec_ok && !ov.u8_map && !o.fixed_aspect_ratio && plan_split(split_knobs(ctx, true), geo, P, sa);
     if (!split) P.shape(geo);
     P.max_tiles = (max_h + P.tr - 1) / P.tr;
     // every tile reads its job over PCIe: past ~512 KB of such reads per launch the multi-pass path's
@@ -1543,10 +775,8 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
         std::memcpy(dstt + i * stride, &J, stride);
     }
     phase(4);
-    const bool timed = ctx->timing && (ctx->timing_calls++ % ctx->timing_every) == ctx->timing_every - 1;
-    if (o.fixed_aspect_ratio) // std::fill_n of each item's canvas, its whole byte size (etl_image.cpp:263)
-        HIP_OK(hipMemset2DAsync(out_dev, o.item_stride, 0,
-                                (size_t)o.canvas_w * o.canvas_h * o.channels * out_elem_bytes(od.dtype), n, stream));
+    const bool timed = take_timing(ctx);
+    clear_canvases(od, out_dev, n, stream);
     const uint8_t* vt = vram ? publish_written(s, tbytes) : nullptr;
     phase(5);
     LaunchArgs     a  = launch_args(ctx, s, vt ? vt : s.host_dev, P, n, o, d_lut, 1, ov.u8_map);
@@ -1554,15 +784,7 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
     a.jobs_host       = 1; // (read-through loads: pinned host memory, or the uncached HBM copy)
     // (the algorithmic bytes only for a timed launch: a pass over the records the call does not need)
     const double lbytes = timed ? launch_bytes(geo, KM_FINAL, out_elem_bytes(o.dtype)) : 0;
-    if (split) {
-        KernelTimer t{};
-        if (timed) t = take_timer(ctx, KM_FINAL, lbytes);
-        const int grid = std::min(a.total_tiles, sa.occ * ctx->n_cu); // sa.occ workgroups per CU (the LDS request holds it)
-        HIP_OK(launch_split(P.tail, sa.occ, a, sa, grid, stream, timed ? t.start : nullptr, timed ? t.stop : nullptr));
-        if (timed) ctx->timers.push_back(t);
-    } else {
-        timed_launch(ctx, KM_FINAL, P, a, stream, lbytes, timed);
-    }
+    launch_final(ctx, P, split ? &sa : nullptr, a, stream, lbytes, timed);
     phase(6);
     release_slot(ctx, slot, stream);
     phase(7);
@@ -1655,7 +877,7 @@ bool run_records(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const voi
 #endif
     const RecArgs r{n, nph, W, H, ((H + nph - 1) / nph + kRecTileRows - 1) / kRecTileRows};
     const int     grid  = std::min(n, ctx->n_cu); // one workgroup per CU (LDS, 14-16 waves at <= 128 VGPRs)
-    const bool    timed = ctx->timing && (ctx->timing_calls++ % ctx->timing_every) == ctx->timing_every - 1;
+    const bool    timed = take_timing(ctx);
     KernelTimer   t{};
     if (timed) t = take_timer(ctx, KM_FINAL, bytes);
     HIP_OK(launch_contrast_records(fast, split, a, r, grid, stream, timed ? t.start : nullptr, timed ? t.stop : nullptr));
@@ -1666,14 +888,92 @@ bool run_records(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const voi
     return true;
 }
 
-// The masks of an image + mask call (aeon_hip_augment_pair_batch): 8-bit single-channel records
-// without rotation into uint8 items, sharing the images' params.
-struct MaskSet {
-    const aeon_img_desc* descs;
-    const void*          src_base;
-    aeon_out_desc        out;
-    void*                out_dev;
+// A pair call whose images are one final tile launch: the masks' row blocks go into that launch (its
+// workgroups take them after their tiles, augment_kernels.hip mask_blocks) -- no gather launch.
+// into = that launch's group (null: the gather launch), then nearest_staged's geometry inside it.
+struct MaskFuse {
+    const LaunchPlan* into = nullptr;
+    int               rows = 0, pitch = 0, slots = 0, base = 0, lds = 0;
 };
+MaskFuse fuse_masks(const CallPlan& plan)
+{
+    MaskFuse f;
+    if (plan.m16.empty() || !plan.rot.empty() || !plan.exp.empty() || !plan.gr_short.jobs.empty() || !plan.gr_main.jobs.empty())
+        return f;
+    int groups = 0;
+    for (const LaunchPlan& P : plan.tiles)
+        if (!P.jobs.empty()) groups++, f.into = &P;
+#ifndef AEON_HIP_FUSED_MASK_ROWS
+#define AEON_HIP_FUSED_MASK_ROWS 64
+#endif
+    f.rows = std::min(mask16_rows(plan.m16_max_w, plan.m16_max_seg), AEON_HIP_FUSED_MASK_ROWS);
+    if (groups != 1 || f.into < plan.tiles + CallPlan::kMain || f.rows < 1 || f.into->has_contrast || f.into->split) return MaskFuse{};
+    const LaunchPlan& P = *f.into;
+    f.pitch = mask16_pitch(plan.m16_max_seg);
+    f.slots = std::max(1, std::min(plan.m16_max_slots, f.rows));
+    f.base  = lds_layout(P.max_win_w, P.tr, P.stage_bytes, P.photo && P.has_hue, P.rtab).stage;
+    f.lds   = std::max(P.lds, f.base + kMaskBlockHdrBytes + f.slots * f.pitch);
+    return f.lds > kMaxLds ? MaskFuse{} : f;
+}
+
+// Job-table transport: where the call's kernels read the table that plan.write left in the pinned slot.
+// Tables up to kUploadKernelMax go up by a small kernel on the launch
+// stream that reads the pinned slot over PCIe (kernel-to-kernel order, no cross-queue wait:
+// 43.5 vs 44.2 us per C2 step against an SDMA copy + event, which costs a ~6.6 us dispatch gap);
+// larger ones by SDMA on copy_stream, which overlaps the previous call's kernels while the
+// upload kernel would read PCIe at ~34 GB/s (C3, 512 KB: 347 vs 357 us per step).
+// A call of pixel-mask gather jobs only (C5's masks): the gather reads its few jobs (one per
+// workgroup) from the pinned slot itself, no upload launch ahead of it.
+// (A pair call's tables go up together by the upload kernel, and its gather launch reads the device
+// copy: C5 93-94 us per step against 96-98 for the image and mask calls, whose gather reads the
+// pinned slot -- 4.5 us more kernel time -- and 97-98 for the masks first on the pinned slot while
+// SDMA uploads the images' table; tools/c5_ab.sh)
+const uint8_t* transport_table(aeon_hip_ctx* ctx, Slot& s, const CallPlan& plan, hipStream_t stream)
+{
+    // the tables in HBM written by the host (no upload launch) unless a LANCZOS4 tap table is among
+    // them (read per output pixel: the cached device copy)
+    const bool     vram_ok = plan.gr_short.n_taps == 0 && plan.gr_main.n_taps == 0;
+    const uint8_t* vt      = vram_ok ? publish_table(ctx, s, plan.blob) : nullptr;
+    const uint8_t* table   = vt ? vt : plan.mask_only ? s.host_dev : s.dev;
+    if (plan.mask_only || vt) {
+    } else if (plan.blob > kUploadKernelMax) {
+        HIP_OK(hipMemcpyAsync(s.dev, s.host, plan.blob, hipMemcpyHostToDevice, ctx->copy_stream));
+        HIP_OK(hipEventRecord(s.copied, ctx->copy_stream));
+        HIP_OK(hipStreamWaitEvent(stream, s.copied, 0));
+    } else {
+        HIP_OK(launch_upload_table(s.host_dev, s.dev, plan.blob, stream));
+    }
+    for (const GrPlan* g : {&plan.gr_short, &plan.gr_main}) // the Lanczos4 taps from their host-computed inputs
+        if (g->n_taps)
+            HIP_OK(launch_lanczos4_taps((const LzIn*)(table + g->lz_off), (GrTap*)(table + g->taps_off), (int)g->n_taps,
+                                        stream));
+    return table;
+}
+
+// The launches of one GrPlan: resize_sep bands or resize_generic tiles per method class.
+void launch_generic(aeon_hip_ctx* ctx, const GrPlan& g, const uint8_t* table, const aeon_out_desc& o, const float* d_lut,
+                    hipStream_t stream, bool timed)
+{
+    if (g.jobs.empty()) return;
+    KernelTimer t{};
+    if (timed) t = take_timer(ctx, KM_RAW, g.bytes);
+    if (timed) HIP_OK(hipEventRecord(t.start, stream));
+    const int gbgr = o.bgr_to_rgb && o.channels == 3, gchm = o.channel_major;
+    for (const GrPlan::Sub& u : g.subs) {
+        const ResizeJob* gj   = (const ResizeJob*)(table + g.off) + u.first;
+        const float*     glut = u.any_final ? d_lut : nullptr;
+        if (u.sep)
+            HIP_OK(launch_resize_sep(u.sep, u.area, gj, table, u.count, u.max_tiles, u.TR, u.CW, u.NR, u.SW, u.cn_max, glut, gbgr,
+                                     gchm, ctx->call_error, stream));
+        else
+            HIP_OK(launch_resize_generic(gj, table, u.count, u.max_tiles, u.TR, u.CW, u.NR, u.xs, u.amax, u.cn_max, u.SW,
+                                         glut, gbgr, gchm, ctx->call_error, stream));
+    }
+    if (timed) {
+        HIP_OK(hipEventRecord(t.stop, stream));
+        ctx->timers.push_back(t);
+    }
+}
 
 int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* src_base,
               const aeon_aug_params* params, const aeon_out_desc* out, void* out_dev, void* stream_,
@@ -1722,121 +1022,13 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
         return 0;
     if (!ms && run_records(ctx, n, descs, src_base, params, od, out_dev, stream, is_mask, phase, im)) return 0;
 
-    LaunchPlan             pre_all, pre2_all, pass1_all, main_all;
-    GrPlan                 gr_short, gr_main;
-    std::vector<RotJob>    rot;
-    std::vector<ExpandJob> exp;
-    std::vector<Mask16Job> m16;
-    size_t     scratch_bytes = 0;
-    for (int i = 0; i < n; i++) {
-        uint8_t* item = (uint8_t*)item_of(im, out_dev, o, i);
-        // pixel masks without rotation (and every 16-bit record): the NEAREST gather pass
-        const bool gather = descs[i].elem_bytes == 2 ||
-                            (is_mask && descs[i].channels == 1 && o.channels == 1 && params[i].angle == 0 &&
-                             (descs[i].elem_bytes == 0 || descs[i].elem_bytes == 1));
-        if (gather) plan_mask16(descs[i], src_base, params[i], o, item, is_mask, m16, rot, scratch_bytes);
-        else if (descs[i].elem_bytes == 0 || descs[i].elem_bytes == 1)
-            plan_image(descs[i], src_base, params[i], o, item, is_mask, rot, exp, gr_short, pre_all, gr_main, pre2_all,
-                       pass1_all, main_all, scratch_bytes, im);
-        else fail(AEON_HIP_EINVAL, "elem_bytes must be 1 (CV_8U) or 2 (CV_16U)");
-    }
-    for (int i = 0; ms && i < n; i++) // the pair call's masks: the gather pass's jobs
-        plan_mask16(ms->descs[i], ms->src_base, params[i], ms->out, (uint8_t*)ms->out_dev + (size_t)i * ms->out.item_stride,
-                    true, m16, rot, scratch_bytes);
-
+    CallPlan& plan = ctx->plan;
+    plan.clear();
+    plan.add_records(n, descs, src_base, params, o, out_dev, is_mask, ms, im);
     phase(1);
-    // one launch per (resize mode, photometric) group: the kernels are specialised on both
-    // one launch per (resize mode, scalar tail, photometric) group: the kernels are specialised
-    // on all three
-    auto has_tail = [](const AugJob& J) { return J.mode == RESIZE_LINEAR && J.xv < J.dst_w * J.cn; };
-    std::vector<LaunchPlan> pre(8), pre2(8), pass1(8), main(16);
-    for (int g = 0; g < 8; g++) {
-        pre[g].rm = pre2[g].rm = pass1[g].rm = g >> 1;
-        pre[g].tail = pre2[g].tail = pass1[g].tail = (g & 1) != 0;
-        pass1[g].photo = true;
-    }
-    for (int g = 0; g < 16; g++) main[g].rm = g >> 2, main[g].tail = (g & 2) != 0, main[g].photo = (g & 1) != 0;
-    for (const AugJob& J : pre_all.jobs) pre[J.mode * 2 + has_tail(J)].jobs.push_back(J);
-    for (const AugJob& J : pre2_all.jobs) pre2[J.mode * 2 + has_tail(J)].jobs.push_back(J);
-    for (const AugJob& J : pass1_all.jobs) pass1[J.mode * 2 + has_tail(J)].jobs.push_back(J);
-    for (const AugJob& J : main_all.jobs) main[J.mode * 4 + has_tail(J) * 2 + (J.photo ? 1 : 0)].jobs.push_back(J);
-    const size_t     rot_off   = 0;
-    const size_t     m16_off   = rot_off + rot.size() * sizeof(RotJob);
-    const size_t     exp_off   = m16_off + m16.size() * sizeof(Mask16Job);
-    size_t           blob      = exp_off + exp.size() * sizeof(ExpandJob);
-    for (GrPlan* g : {&gr_short, &gr_main}) { // jobs, then their Lanczos taps (offsets made absolute)
-        if (g->jobs.empty()) continue;
-        if (g->n_taps > 4096 && !ctx->plan_pool) ctx->plan_pool.reset(new thread_pool(thread_affinity_map("")));
-        g->finalize();
-        blob        = (blob + 15) & ~(size_t)15;
-        g->off      = blob;
-        blob += g->jobs.size() * sizeof(ResizeJob);
-        g->lz_off = blob;
-        blob += g->n_taps * sizeof(LzIn);
-    }
-    blob = (blob + 15) & ~(size_t)15;
-    int              exp_max_px = 0;
-    for (const ExpandJob& E : exp) exp_max_px = std::max(exp_max_px, E.ew * E.eh);
-    int              m16_max_h = 0, m16_max_w = 0, m16_max_seg = 0;
-    double           m16_bytes = 0; // algorithmic: crop read once + output written once
-    for (const Mask16Job& M : m16) {
-        m16_max_h = std::max(m16_max_h, M.out_h), m16_max_w = std::max(m16_max_w, M.out_w);
-        m16_max_seg = std::max(m16_max_seg, M.crop_w * M.src_elem);
-        m16_bytes += (double)M.crop_w * M.crop_h * M.src_elem + (double)M.out_w * M.out_h * out_elem_bytes(M.dtype);
-    }
-    // distinct source rows of any block of the gather pass: the kernel's own row map
-    // (sy = min(floor(y * ify), crop_h - 1), monotonic in y), evaluated at each block's ends
-    int m16_max_slots = 1;
-    if (!m16.empty()) {
-        const int srows = mask16_rows(m16_max_w, m16_max_seg);
-        for (const Mask16Job& M : m16)
-            for (int y0 = 0; y0 < M.out_h; y0 += srows) {
-                const auto sy = [&](int y) { return std::min((int)std::floor(y * M.scale_y), M.crop_h - 1); };
-                const int  y1 = std::min(y0 + srows, M.out_h) - 1;
-                m16_max_slots = std::max(m16_max_slots, std::min(y1 - y0 + 1, sy(y1) - sy(y0) + 1));
-            }
-    }
-    int              rot_max_tiles = 0, rot_words = 0, rot_cn = rot.empty() ? 0 : rot[0].cn; // (rotate_tiles)
-    for (size_t r = 0; r < rot.size(); r++) {
-        const RotJob& R = rot[r];
-        if (R.cn != rot_cn) rot_cn = 0;
-        rot_max_tiles   = std::max(rot_max_tiles, ((R.ow + 63) / 64) * ((R.oh + 31) / 32));
-        rot_words       = std::max(rot_words, rot_box_words(R.angle));
-    }
-    std::vector<int> slot_tiles(pass1_all.jobs.size(), 0);
-    int              partial_stride = 1;
-    for (auto* v : {&pre, &pre2, &pass1, &main})
-        for (LaunchPlan& P : *v) {
-            if (P.jobs.empty()) continue;
-            P.vec_ok = main_all.vec_ok;
-            P.rtab   = v == &main && P.photo && o.dtype == AEON_DTYPE_F32;
-            // final non-photometric INTER_LINEAR float32 CHW launches (C5's images): augment_split
-            P.split = v == &main && ctx->split && !P.photo && P.rm == RESIZE_LINEAR && o.dtype == AEON_DTYPE_F32 &&
-                      o.channel_major && P.vec_ok && !ov.u8_map && !o.fixed_aspect_ratio && !(ms && ctx->fuse_masks) &&
-                      plan_split(ctx, P.jobs, P, P.sa);
-            P.finalize();
-            P.blob_off = blob;
-            blob += P.jobs.size() * sizeof(AugJob);
-            if (v == &pass1)
-                for (const AugJob& J : P.jobs) {
-                    slot_tiles[J.stats_slot] = J.tiles;
-                    partial_stride           = std::max(partial_stride, J.tiles * 8); // (tile, wave) sums
-                }
-            if (v == &main)
-                for (AugJob& J : P.jobs)
-                    if (J.stats_slot >= 0) J.stats_tiles = slot_tiles[J.stats_slot];
-        }
-    const size_t partial_words = std::max<size_t>(4, pass1_all.jobs.size() * partial_stride * 4);
-    // the Lanczos4 taps the device builds: after everything the host writes (not uploaded)
-    size_t table_cap = (blob + 15) & ~(size_t)15;
-    for (GrPlan* g : {&gr_short, &gr_main}) {
-        if (g->n_taps == 0) continue;
-        g->taps_off = table_cap;
-        table_cap += ((g->n_taps * sizeof(GrTap)) + 15) & ~(size_t)15;
-        for (ResizeJob& R : g->jobs)
-            if (R.method == GR_LANCZOS4) R.coef_x += (int32_t)g->taps_off, R.coef_y += (int32_t)g->taps_off;
-    }
-
+    plan.finalize(o, ov.u8_map, split_knobs(ctx, !(ms && ctx->fuse_masks)));
+    if (std::max(plan.gr_short.n_taps, plan.gr_main.n_taps) > 4096 && !ctx->plan_pool)
+        ctx->plan_pool.reset(new thread_pool(thread_affinity_map("")));
     phase(2);
     int   slot;
     Slot& s = take_slot(ctx, stream, slot);
@@ -1844,181 +1036,65 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     const float* d_lut = resident_lut(ctx, od, ov.u8_map);
     // job tables, contrast sums and shifts: one capacity for every slot of the ring (a call never
     // allocates unless it needs more than any call before it); scratch per slot, on demand
-    // (sized for the Lanczos4 taps with no axis shared: the shared count varies from call to call, and a
-    // ring growth inside a loader's steady state costs ~10-20 ms of allocations)
-    size_t ring_need = table_cap;
-    for (GrPlan* g : {&gr_short, &gr_main})
-        ring_need += (g->n_taps_max - g->n_taps) * (sizeof(LzIn) + sizeof(GrTap)) + 32;
-    ensure_ring(ctx, ring_need, partial_words * 4, std::max<size_t>(1, pass1_all.jobs.size()) * 4 * sizeof(double));
-    if (scratch_bytes > s.scratch_cap) grow(s.scratch, s.scratch_cap, scratch_bytes + scratch_bytes / 4, false); // (slack as ensure_ring)
-    for (RotJob& R : rot) R.out_ptr += (uint64_t)s.scratch;
-    for (Mask16Job& M : m16)
-        if (M.src_scratch) M.src_ptr += (uint64_t)s.scratch;
-    for (ExpandJob& E : exp) {
-        E.out_ptr += (uint64_t)s.scratch;
-        if (E.src_scratch) E.src_ptr += (uint64_t)s.scratch;
-    }
-    if (!exp.empty()) std::memcpy(s.host + exp_off, exp.data(), exp.size() * sizeof(ExpandJob));
-    for (GrPlan* g : {&gr_short, &gr_main}) {
-        if (g->jobs.empty()) continue;
-        for (ResizeJob& R : g->jobs) {
-            if (R.src_scratch) R.src_ptr += (uint64_t)s.scratch;
-            if (R.out_scratch) R.out_ptr += (uint64_t)s.scratch;
-        }
-        std::memcpy(s.host + g->off, g->jobs.data(), g->jobs.size() * sizeof(ResizeJob));
-        if (g->n_taps) g->fill_taps(ctx->plan_pool.get(), (LzIn*)(s.host + g->lz_off));
-    }
-    if (!rot.empty()) std::memcpy(s.host + rot_off, rot.data(), rot.size() * sizeof(RotJob));
-    if (!m16.empty()) std::memcpy(s.host + m16_off, m16.data(), m16.size() * sizeof(Mask16Job));
-    for (auto* v : {&pre, &pre2, &pass1, &main})
-        for (LaunchPlan& P : *v) {
-            for (AugJob& J : P.jobs) { // relocate scratch references
-                if (v != &main) J.out_ptr += (uint64_t)s.scratch;
-                if (J.src_scratch) J.src_ptr += (uint64_t)s.scratch;
-            }
-            if (!P.jobs.empty()) std::memcpy(s.host + P.blob_off, P.jobs.data(), P.jobs.size() * sizeof(AugJob));
-        }
+    ensure_ring(ctx, plan.ring_need, plan.partial_words * 4, std::max(1, plan.n_stats) * 4 * sizeof(double));
+    if (plan.scratch_bytes > s.scratch_cap) // (slack as ensure_ring)
+        grow(s.scratch, s.scratch_cap, plan.scratch_bytes + plan.scratch_bytes / 4, false);
+    plan.write(s.host, (uint64_t)s.scratch, [&](int k, const std::function<void(int)>& f) { ctx->plan_pool->run(k, f); });
     phase(4);
-    // Job-table transport: tables up to kUploadKernelMax go up by a small kernel on the launch
-    // stream that reads the pinned slot over PCIe (kernel-to-kernel order, no cross-queue wait:
-    // 43.5 vs 44.2 us per C2 step against an SDMA copy + event, which costs a ~6.6 us dispatch gap);
-    // larger ones by SDMA on copy_stream, which overlaps the previous call's kernels while the
-    // upload kernel would read PCIe at ~34 GB/s (C3, 512 KB: 347 vs 357 us per step).
-    // A call of pixel-mask gather jobs only (C5's masks): the gather reads its few jobs (one per
-    // workgroup) from the pinned slot itself, no upload launch ahead of it.
-    bool mask_only = !m16.empty() && rot.empty() && exp.empty() && gr_short.jobs.empty() && gr_main.jobs.empty();
-    for (auto* v : {&pre, &pre2, &pass1, &main})
-        for (LaunchPlan& P : *v) mask_only = mask_only && P.jobs.empty();
-    // the tables in HBM written by the host (no upload launch) unless a LANCZOS4 tap table is among
-    // them (read per output pixel: the cached device copy)
-    const bool     vram_ok = gr_short.n_taps == 0 && gr_main.n_taps == 0;
-    const uint8_t* vt      = vram_ok ? publish_table(ctx, s, blob) : nullptr;
-    const uint8_t* table   = vt ? vt : mask_only ? s.host_dev : s.dev;
-    // timing events on one call in timing_every (each event pair costs GPU time between launches)
-    const bool timed = ctx->timing && (ctx->timing_calls++ % ctx->timing_every) == ctx->timing_every - 1;
-    auto launch_masks = [&](const uint8_t* tbl) { // the gather pass, its jobs at tbl + m16_off
-        KernelTimer t{};
-        if (timed) t = take_timer(ctx, KM_FINAL, m16_bytes);
-        HIP_OK(launch_nearest((const Mask16Job*)(tbl + m16_off), (int)m16.size(), m16_max_h, m16_max_w, m16_max_seg,
-                              m16_max_slots, stream, timed ? t.start : nullptr, timed ? t.stop : nullptr));
-        if (timed) ctx->timers.push_back(t);
-    };
-    // (A pair call's tables go up together by the upload kernel, and its gather launch reads the device
-    // copy: C5 93-94 us per step against 96-98 for the image and mask calls, whose gather reads the
-    // pinned slot -- 4.5 us more kernel time -- and 97-98 for the masks first on the pinned slot while
-    // SDMA uploads the images' table; tools/c5_ab.sh)
-    if (mask_only || vt) {
-    } else if (blob > kUploadKernelMax) {
-        HIP_OK(hipMemcpyAsync(s.dev, s.host, blob, hipMemcpyHostToDevice, ctx->copy_stream));
-        HIP_OK(hipEventRecord(s.copied, ctx->copy_stream));
-        HIP_OK(hipStreamWaitEvent(stream, s.copied, 0));
-    } else {
-        HIP_OK(launch_upload_table(s.host_dev, s.dev, blob, stream));
-    }
-    for (GrPlan* g : {&gr_short, &gr_main}) // the Lanczos4 taps from their host-computed inputs
-        if (g->n_taps)
-            HIP_OK(launch_lanczos4_taps((const LzIn*)(table + g->lz_off), (GrTap*)(table + g->taps_off), (int)g->n_taps,
-                                        stream));
+    const uint8_t* table = transport_table(ctx, s, plan, stream);
+    const bool     timed = take_timing(ctx);
     phase(5);
 
-    auto args = [&](const LaunchPlan& L) {
-        return launch_args(ctx, s, table, L, (int)L.jobs.size(), o, d_lut, partial_stride, ov.u8_map);
-    };
-    const size_t oelem = out_elem_bytes(o.dtype);
-    if (o.fixed_aspect_ratio) // std::fill_n of each item's canvas, its whole byte size (etl_image.cpp:263)
-        HIP_OK(hipMemset2DAsync(out_dev, o.item_stride, 0,
-                                (size_t)o.canvas_w * o.canvas_h * o.channels * out_elem_bytes(od.dtype), n, stream));
-    if (!rot.empty()) // image::rotate pre-pass first: the gather and tile passes read its output
-        HIP_OK(launch_rotate((const RotJob*)(table + rot_off), (int)rot.size(), rot_max_tiles, rot_words, rot_cn, ctx->call_error,
-                             stream));
-    if (!exp.empty()) // then image::expand (etl_image.cpp:155-159)
-        HIP_OK(launch_expand((const ExpandJob*)(table + exp_off), (int)exp.size(), exp_max_px, stream));
-    // A pair call whose images are one tile launch: the masks' row blocks go into that launch (its
-    // workgroups take them after their tiles, augment_kernels.hip mask_blocks) -- no gather launch.
-    LaunchPlan* fused = nullptr;
-    LaunchArgs  fused_masks{};
-    if (ms && ctx->fuse_masks && !m16.empty() && rot.empty() && exp.empty() && gr_short.jobs.empty() && gr_main.jobs.empty()) {
-        int groups = 0;
-        for (auto* v : {&pre, &pre2, &pass1, &main})
-            for (LaunchPlan& P : *v)
-                if (!P.jobs.empty()) groups++, fused = &P;
-#ifndef AEON_HIP_FUSED_MASK_ROWS
-#define AEON_HIP_FUSED_MASK_ROWS 64
-#endif
-        const int srows = std::min(mask16_rows(m16_max_w, m16_max_seg), AEON_HIP_FUSED_MASK_ROWS);
-        bool in_main = false;
-        for (LaunchPlan& P : main) in_main |= fused == &P;
-        if (groups == 1 && in_main && srows >= 1 && !fused->has_contrast && !fused->split) {
-            const int pitch = mask16_pitch(m16_max_seg);
-            const int slots = std::max(1, std::min(m16_max_slots, srows));
-            const int base  = lds_layout(fused->max_win_w, fused->tr, fused->stage_bytes, fused->photo && fused->has_hue,
-                                         fused->rtab).stage;
-            const int need  = base + kMaskBlockHdrBytes + slots * pitch;
-            fused_masks.mjobs    = (const Mask16Job*)(table + m16_off);
-            fused_masks.m_ctr    = ctx->d_tail + aeon_hip_ctx::kSlots + slot;
-            fused_masks.m_bpj    = (m16_max_h + srows - 1) / srows;
-            fused_masks.m_blocks = (int)m16.size() * fused_masks.m_bpj;
-            fused_masks.m_rows = srows, fused_masks.m_pitch = pitch, fused_masks.m_perm = 1, fused_masks.m_slots = slots;
-            fused_masks.m_lds    = base;
-            fused_masks.lds_bytes = std::max(fused->lds, need);
-            if (fused_masks.lds_bytes > kMaxLds) fused = nullptr;
-        } else {
-            fused = nullptr;
-        }
+    clear_canvases(od, out_dev, n, stream);
+    if (!plan.rot.empty()) { // image::rotate pre-pass first: the gather and tile passes read its output
+        int words = 0;       // (the launch's LDS source box, rotate_kernels.hip)
+        for (const RotJob& R : plan.rot) words = std::max(words, rot_box_words(R.angle));
+        HIP_OK(launch_rotate((const RotJob*)(table + plan.rot_off), (int)plan.rot.size(), plan.rot_max_tiles, words, plan.rot_cn,
+                             ctx->call_error, stream));
     }
-    if (!m16.empty() && !fused) launch_masks(table);
-    auto generic = [&](const GrPlan& g) {
-        if (g.jobs.empty()) return;
+    if (!plan.exp.empty()) // then image::expand (etl_image.cpp:155-159)
+        HIP_OK(launch_expand((const ExpandJob*)(table + plan.exp_off), (int)plan.exp.size(), plan.exp_max_px, stream));
+    const MaskFuse mf = ms && ctx->fuse_masks ? fuse_masks(plan) : MaskFuse{};
+    if (!plan.m16.empty() && !mf.into) { // the gather pass
         KernelTimer t{};
-        if (timed) t = take_timer(ctx, KM_RAW, g.bytes);
-        if (timed) HIP_OK(hipEventRecord(t.start, stream));
-        const int gbgr = o.bgr_to_rgb && o.channels == 3, gchm = o.channel_major;
-        for (const GrPlan::Sub& u : g.subs) {
-            const ResizeJob* gj   = (const ResizeJob*)(table + g.off) + u.first;
-            const float*     glut = u.any_final ? d_lut : nullptr;
-            if (u.sep)
-                HIP_OK(launch_resize_sep(u.sep, u.area, gj, table, u.count, u.max_tiles, u.TR, u.CW, u.NR, u.SW, u.cn_max, glut, gbgr,
-                                         gchm, ctx->call_error, stream));
-            else
-                HIP_OK(launch_resize_generic(gj, table, u.count, u.max_tiles, u.TR, u.CW, u.NR, u.xs, u.amax, u.cn_max, u.SW,
-                                             glut, gbgr, gchm, ctx->call_error, stream));
-        }
-        if (timed) {
-            HIP_OK(hipEventRecord(t.stop, stream));
-            ctx->timers.push_back(t);
+        if (timed) t = take_timer(ctx, KM_FINAL, plan.m16_bytes);
+        HIP_OK(launch_nearest((const Mask16Job*)(table + plan.m16_off), (int)plan.m16.size(), plan.m16_max_h, plan.m16_max_w,
+                              plan.m16_max_seg, plan.m16_max_slots, stream, timed ? t.start : nullptr, timed ? t.stop : nullptr));
+        if (timed) ctx->timers.push_back(t);
+    }
+    const size_t oelem = out_elem_bytes(o.dtype);
+    const auto   args  = [&](const LaunchPlan& L) {
+        return launch_args(ctx, s, table, L, (int)L.jobs.size(), o, d_lut, plan.partial_stride, ov.u8_map);
+    };
+    const auto pass = [&](int first, int end, int km) { // the tile launches of one pass
+        for (int g = first; g < end; g++) {
+            const LaunchPlan& P = plan.tiles[g];
+            if (P.jobs.empty()) continue;
+            double bytes = launch_bytes(P.jobs, km, km == KM_RAW ? 1 : oelem);
+            if (km != KM_FINAL) {
+                timed_launch(ctx, km, P, args(P), stream, bytes, timed);
+                continue;
+            }
+            if (P.has_contrast) HIP_OK(launch_contrast_reduce(args(P), (int)P.jobs.size(), stream));
+            LaunchArgs a = args(P);
+            if (&P == mf.into) {
+                a.mjobs    = (const Mask16Job*)(table + plan.m16_off);
+                a.m_ctr    = ctx->d_tail + aeon_hip_ctx::kSlots + slot;
+                a.m_bpj    = (plan.m16_max_h + mf.rows - 1) / mf.rows;
+                a.m_blocks = (int)plan.m16.size() * a.m_bpj;
+                a.m_rows = mf.rows, a.m_pitch = mf.pitch, a.m_perm = 1, a.m_slots = mf.slots, a.m_lds = mf.base;
+                a.lds_bytes = mf.lds;
+                bytes += plan.m16_bytes;
+            }
+            launch_final(ctx, P, P.split ? &P.sa : nullptr, a, stream, bytes, timed);
         }
     };
-    generic(gr_short);
-    for (LaunchPlan& P : pre)
-        if (!P.jobs.empty()) timed_launch(ctx, KM_RAW, P, args(P), stream, launch_bytes(P.jobs, KM_RAW, 1), timed);
-    generic(gr_main);
-    for (LaunchPlan& P : pre2)
-        if (!P.jobs.empty()) timed_launch(ctx, KM_RAW, P, args(P), stream, launch_bytes(P.jobs, KM_RAW, 1), timed);
-    for (LaunchPlan& P : pass1)
-        if (!P.jobs.empty())
-            timed_launch(ctx, KM_STATS, P, args(P), stream, launch_bytes(P.jobs, KM_STATS, oelem), timed);
-    for (LaunchPlan& P : main) {
-        if (P.jobs.empty()) continue;
-        if (P.has_contrast) HIP_OK(launch_contrast_reduce(args(P), (int)P.jobs.size(), stream));
-        LaunchArgs a     = args(P);
-        double     bytes = launch_bytes(P.jobs, KM_FINAL, oelem);
-        if (&P == fused) {
-            a.mjobs = fused_masks.mjobs, a.m_ctr = fused_masks.m_ctr, a.m_blocks = fused_masks.m_blocks;
-            a.m_bpj = fused_masks.m_bpj, a.m_rows = fused_masks.m_rows, a.m_pitch = fused_masks.m_pitch;
-            a.m_perm = fused_masks.m_perm, a.m_slots = fused_masks.m_slots, a.m_lds = fused_masks.m_lds;
-            a.lds_bytes = fused_masks.lds_bytes;
-            bytes += m16_bytes;
-        }
-        if (P.split) {
-            KernelTimer t{};
-            if (timed) t = take_timer(ctx, KM_FINAL, bytes);
-            HIP_OK(launch_split(P.tail, P.sa.occ, a, P.sa, std::min(a.total_tiles, P.sa.occ * ctx->n_cu), stream,
-                                timed ? t.start : nullptr, timed ? t.stop : nullptr));
-            if (timed) ctx->timers.push_back(t);
-        } else {
-            timed_launch(ctx, KM_FINAL, P, a, stream, bytes, timed);
-        }
-    }
+    launch_generic(ctx, plan.gr_short, table, o, d_lut, stream, timed);
+    pass(CallPlan::kPre, CallPlan::kPre2, KM_RAW);
+    launch_generic(ctx, plan.gr_main, table, o, d_lut, stream, timed);
+    pass(CallPlan::kPre2, CallPlan::kPass1, KM_RAW);
+    pass(CallPlan::kPass1, CallPlan::kMain, KM_STATS);
+    pass(CallPlan::kMain, CallPlan::kGroups, KM_FINAL);
     phase(6);
     release_slot(ctx, slot, stream);
     phase(7);
