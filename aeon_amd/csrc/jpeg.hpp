@@ -10,9 +10,11 @@
 // of block counts and DC differences and a final decode that writes every block's coefficients.
 // Progressive and multi-scan files are entropy-decoded on the host pool into the sparse stream (per
 // 8x8 block a 64-bit zigzag mask of its non-zero coefficients plus those values, int16).  Everything
-// per pixel -- dequantisation, the ISLOW IDCT, fancy upsampling and the YCbCr -> BGR conversion --
-// runs on the GPU, which writes the decoded HWC records straight into the device source arena the
-// augmentation kernels read.
+// per pixel -- dequantisation, the ISLOW IDCT, fancy upsampling and the colour conversion (YCbCr -> BGR
+// in jpeg_color; CMYK, YCCK and RGB sources in jpeg_color4) -- runs on the GPU, which writes the
+// decoded HWC records straight into the device source arena the augmentation kernels read.  A file
+// has one, three or four components; its source colour space (libjpeg's default_decompress_parms) is
+// decided on the host and carried in JpegImage.cs.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -44,23 +46,39 @@ struct alignas(16) JpegBlock {
     uint32_t pad_;
 };
 
+constexpr int kJpegMaxComp = 4; // components of a frame (a 2-component frame is refused)
+
+// Source colour space of a file (jdapimin.c default_decompress_parms: component count, JFIF / Adobe
+// APP14 markers, component ids), decided by the parser so the kernels branch on no marker data.
+enum JpegColorSpace : int32_t {
+    CS_GRAY = 0,
+    CS_YCC  = 1, // YCbCr
+    CS_RGB  = 2, // 3 components, Adobe transform 0 or ids 'R','G','B'
+    CS_CMYK = 3, // 4 components, Adobe transform 0 or no Adobe marker
+    CS_YCCK = 4, // 4 components, any other Adobe transform
+};
+
 // One file of a decode call, as the kernels see it (device addresses).
 struct alignas(16) JpegImage {
-    uint64_t blocks[3]; // JpegBlock[bh][bw] per component
-    uint64_t values;    // int16 coefficient values (sparse stream: host-decoded files)
-    uint64_t dvals[3];  // GPU-decoded files: 64 int16 per block (zigzag order, the mask's bits valid), else 0
-    uint64_t planes[3]; // IDCT output per component: (bw*8) x (bh*8) uint8, row pitch bw*8
-    uint64_t out;       // decoded record: HWC uint8 (BGR or gray), out_stride bytes per row
-    int32_t  W, H, ncomp, out_cn, out_stride, hmax, vmax, pad_;
-    int32_t  bw[3], bh[3], dw[3], dh[3], hs[3], vs[3];
-    int32_t  up[3];     // JpegUpsample of each component (host-chosen: no divisions per pixel)
-    int32_t  hf[3], vf[3]; // hmax / hs, vmax / vs
-    int32_t  pad2_;
-    uint16_t q[3][64];  // quantisation table of each component, natural order
-    uint16_t pad3_[4];
-    uint16_t qz[3][64]; // the same in zigzag order (the dense path of jpeg_idct: 16-byte loads)
+    uint64_t blocks[kJpegMaxComp]; // JpegBlock[bh][bw] per component
+    uint64_t values;               // int16 coefficient values (sparse stream: host-decoded files)
+    uint64_t dvals[kJpegMaxComp];  // GPU-decoded files: 64 int16 per block (zigzag order, the mask's bits valid), else 0
+    uint64_t planes[kJpegMaxComp]; // IDCT output per component: (bw*8) x (bh*8) uint8, row pitch bw*8
+    uint64_t out;                  // decoded record: HWC uint8 (BGR or gray), out_stride bytes per row
+    int32_t  W, H, ncomp, out_cn, out_stride, hmax, vmax;
+    int32_t  cs;                   // JpegColorSpace
+    int32_t  bw[kJpegMaxComp], bh[kJpegMaxComp], dw[kJpegMaxComp], dh[kJpegMaxComp], hs[kJpegMaxComp], vs[kJpegMaxComp];
+    int32_t  up[kJpegMaxComp];     // JpegUpsample of each component (host-chosen: no divisions per pixel)
+    int32_t  hf[kJpegMaxComp], vf[kJpegMaxComp]; // hmax / hs, vmax / vs
+    uint16_t q[kJpegMaxComp][64];  // quantisation table of each component, natural order
+    uint16_t qz[kJpegMaxComp][64]; // the same in zigzag order (the dense path of jpeg_idct: 16-byte loads)
 };
 static_assert(offsetof(JpegImage, qz) % 16 == 0, "JpegImage.qz: 16-byte rows");
+static_assert(sizeof(JpegImage) % 16 == 0, "JpegImage: 16-byte aligned array elements");
+
+// Components whose planes a decode to `out_cn` channels needs: a gray record of a YCbCr file is its
+// luma plane alone; gray from RGB, CMYK or YCCK takes every component.
+inline int jpeg_planes_needed(int cs, int ncomp, int out_cn) { return out_cn == 1 && cs <= CS_YCC ? 1 : ncomp; }
 
 // jdsample.c's upsampler of a component, chosen per file on the host.
 enum JpegUpsample : int32_t {
@@ -115,7 +133,11 @@ struct alignas(16) JpegHuffSub {
     uint64_t st, en;
     int32_t  cnt[4]; // blocks started, DC difference sums of components 0..2
     int32_t  ex[4];  // exclusive prefix of cnt over the file's subsequences
+    int32_t  cnt3;   // DC difference sum of component 3 (four-component files)
+    int32_t  ex3;    // its exclusive prefix
+    int32_t  pad_[2];
 };
+static_assert(sizeof(JpegHuffSub) == 64, "JpegHuffSub: 16-byte aligned");
 
 // One GPU-decoded file (device addresses).
 struct alignas(16) JpegHuffFile {
@@ -124,16 +146,18 @@ struct alignas(16) JpegHuffFile {
     uint64_t sub_seg;   // int32 per subsequence: its segment
     uint64_t tabs;      // JpegHuffTab[kJpegHuffSlots]: the scan's DC tables in slots 0-1, AC in 2-3
     uint64_t subs;      // JpegHuffSub[nsub] (device scratch)
-    uint64_t blocks[3]; // JpegBlock[bh][bw] per frame component (zeroed before the launch)
-    uint64_t dvals[3];  // 64 int16 per block per frame component
+    uint64_t blocks[kJpegMaxComp]; // JpegBlock[bh][bw] per frame component (zeroed before the launch)
+    uint64_t dvals[kJpegMaxComp];  // 64 int16 per block per frame component
     uint64_t blk_tab[2]; // byte c (c < kHuffMaxBpm) = MCU block c: frame component | x << 2 | y << 4 |
                          // its DC table slot << 6 | (its AC table slot - 2) << 7
     int32_t  nseg, nsub, restart, n_mcu; // restart: MCUs per segment (n_mcu without DRI)
     int32_t  bpm, mcux, ncomp;           // a non-interleaved (grayscale) scan: bpm 1, mcux = blocks per row
     int32_t  truncated; // first segment whose data ends with the file, not a marker (reading past it is an error); -1: none
-    int32_t  bw[3], hs[3], vs[3], sub_bits; // sub_bits: the file's subsequence length
-    int32_t  data_words, pad_[3];           // the data's 32-bit words (padding included)
+    int32_t  bw[kJpegMaxComp], hs[kJpegMaxComp], vs[kJpegMaxComp];
+    int32_t  sub_bits;   // the file's subsequence length
+    int32_t  data_words; // the data's 32-bit words (padding included)
 };
+static_assert(sizeof(JpegHuffFile) % 16 == 0, "JpegHuffFile: 16-byte aligned array elements");
 
 // Device error word bit of a GPU-decoded file whose entropy-coded data is corrupt or truncated.
 constexpr int kJpegCorruptBit = 256;

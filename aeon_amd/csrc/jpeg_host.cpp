@@ -5,8 +5,10 @@
 // Follows libjpeg's Huffman decoders (ITU T.81 F.2 / G.1.2: DHT/DQT/DRI/SOF0-2/SOS, interleaved and
 // non-interleaved scans, restart intervals, 0xFF00 stuffing; progressive files through spectral
 // selection and successive approximation, jdphuff.c), which is what cv::imdecode runs under aeon's
-// image::extractor::extract (src/etl_image.cpp:83-99).  Arithmetic-coded, lossless, 12-bit and
-// 4-component (CMYK / Adobe RGB) files are refused with AEON_HIP_EUNSUPPORTED.
+// image::extractor::extract (src/etl_image.cpp:83-99).  Files of one, three or four components are
+// decoded; the source colour space (YCbCr, RGB, CMYK, YCCK) follows jdapimin.c's
+// default_decompress_parms (decide_colorspace).  Arithmetic-coded, lossless, 12-bit and 2-component
+// files are refused with AEON_HIP_EUNSUPPORTED.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,7 +28,7 @@
 
 namespace aeon_hip {
 hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                       int color_lds, hipStream_t stream);
+                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, hipStream_t stream);
 int        jpeg_huff_stage_cap(int lanes);
 hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, int stage_bytes, int32_t* error,
                             hipStream_t stream);
@@ -204,7 +206,10 @@ struct Comp {
 struct Frame {
     int      W = 0, H = 0, ncomp = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
     bool     progressive = false; // SOF2
-    Comp     c[3];
+    bool     jfif = false, adobe = false; // JFIF APP0 / Adobe APP14 seen
+    int      adobe_transform = 0;
+    int      cs = CS_YCC; // JpegColorSpace (decide_colorspace, once every marker is read)
+    Comp     c[kJpegMaxComp];
     uint16_t q[4][64];
     bool     qset[4] = {false, false, false, false};
 };
@@ -261,6 +266,28 @@ struct Arena {
 
 uint16_t be16(const uint8_t* p) { return (uint16_t)((p[0] << 8) | p[1]); }
 
+// JFIF APP0 / Adobe APP14 (jdmarker.c examine_app0 / examine_app14); s: the segment's data, len: its
+// length field.
+void app_segment(Frame& f, int m, const uint8_t* s, int len)
+{
+    if (m == 0xE0 && len >= 16 && std::memcmp(s, "JFIF\0", 5) == 0) f.jfif = true;
+    if (m == 0xEE && len >= 14 && std::memcmp(s, "Adobe", 5) == 0) f.adobe = true, f.adobe_transform = s[11];
+}
+
+// jdapimin.c default_decompress_parms: the file's source colour space.
+void decide_colorspace(Frame& f)
+{
+    if (f.ncomp == 1) {
+        f.cs = CS_GRAY;
+    } else if (f.ncomp == 3) {
+        if (f.jfif) f.cs = CS_YCC;
+        else if (f.adobe) f.cs = f.adobe_transform == 0 ? CS_RGB : CS_YCC;
+        else f.cs = f.c[0].id == 'R' && f.c[1].id == 'G' && f.c[2].id == 'B' ? CS_RGB : CS_YCC;
+    } else {
+        f.cs = f.adobe && f.adobe_transform != 0 ? CS_YCCK : CS_CMYK;
+    }
+}
+
 // Parse markers up to the frame header (SOF): size, components, sampling.
 void parse_frame(const uint8_t* d, size_t size, Frame& f, const uint8_t** after)
 {
@@ -288,7 +315,7 @@ void parse_frame(const uint8_t* d, size_t size, Frame& f, const uint8_t** after)
             // (libjpeg would allocate whatever the header asks for; a bound keeps a corrupt header
             // from reserving gigabytes of coefficient staging)
             if ((int64_t)f.W * f.H > ((int64_t)1 << 28)) unsupported("images above 2^28 pixels");
-            if (f.ncomp != 1 && f.ncomp != 3) unsupported("only 1- and 3-component images are supported");
+            if (f.ncomp != 1 && f.ncomp != 3 && f.ncomp != 4) unsupported("only 1-, 3- and 4-component images are supported");
             if (len < 8 + 3 * f.ncomp) bad("bad frame header");
             for (int k = 0; k < f.ncomp; k++) {
                 Comp& c = f.c[k];
@@ -390,10 +417,10 @@ struct ProgScan {
 }
 
 void decode_progressive_scan(Bits& br, const Frame& f, const int* sc, int ns, const ProgScan& S, const Huffman* dc,
-                             const Huffman* ac, int restart, int16_t* const coef_of[3])
+                             const Huffman* ac, int restart, int16_t* const coef_of[kJpegMaxComp])
 {
     const int p1 = 1 << S.Al, m1 = -p1;
-    int       pred[3] = {0, 0, 0};
+    int       pred[kJpegMaxComp] = {0, 0, 0, 0};
     int       eobrun  = 0;
     // block (bx, by) of scan component i
     auto dc_block = [&](int i, int16_t* blk) {
@@ -465,7 +492,7 @@ void decode_progressive_scan(Bits& br, const Frame& f, const int* sc, int ns, co
     };
     int done = 0, left = restart;
     auto at_restart = [&]() {
-        if (restart && done && left == 0) br.restart(), pred[0] = pred[1] = pred[2] = 0, eobrun = 0, left = restart;
+        if (restart && done && left == 0) br.restart(), pred[0] = pred[1] = pred[2] = pred[3] = 0, eobrun = 0, left = restart;
     };
     if (ns == 1) { // non-interleaved: the component's own block grid
         const Comp& c  = f.c[sc[0]];
@@ -493,7 +520,8 @@ void decode_progressive_scan(Bits& br, const Frame& f, const int* sc, int ns, co
         }
 }
 
-void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_off[3], size_t* val_off, bool luma_only)
+void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_off[kJpegMaxComp], size_t* val_off,
+                 bool luma_only)
 {
     const uint8_t* p = nullptr;
     parse_frame(d, size, f, &p);
@@ -501,8 +529,7 @@ void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_o
     // re-walk the tables defined before the frame (DQT / DHT / DRI may precede SOF)
     Huffman dc[4], ac[4];
     int     restart = 0;
-    bool    adobe_rgb = false;
-    size_t  nblocks   = 0;
+    size_t  nblocks = 0;
     for (int k = 0; k < f.ncomp; k++) nblocks += (size_t)f.c[k].bw * f.c[k].bh;
     // block records (zeroed: blocks a non-interleaved scan never codes stay empty), then values
     for (int k = 0; k < f.ncomp; k++) {
@@ -514,7 +541,7 @@ void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_o
     uint8_t* vbase = a.reserve(nblocks * 64 * sizeof(int16_t));
     *val_off       = (size_t)(vbase - a.host.data());
     uint32_t nvals = 0;
-    int16_t* coef_of[3] = {nullptr, nullptr, nullptr};
+    int16_t* coef_of[kJpegMaxComp] = {nullptr, nullptr, nullptr, nullptr};
     if (f.progressive) { // scans refine a dense coefficient image; the sparse records come at the end
         a.coef.assign(nblocks * 64, 0);
         size_t o = 0;
@@ -544,8 +571,8 @@ void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_o
         } else if (m == 0xDD) {
             if (len < 4) bad("bad restart interval segment");
             restart = be16(s);
-        } else if (m == 0xEE) {
-            if (len >= 14 && std::memcmp(s, "Adobe", 5) == 0 && s[11] == 0) adobe_rgb = true;
+        } else {
+            app_segment(f, m, s, len);
         }
     };
     {
@@ -591,7 +618,7 @@ void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_o
         const uint8_t* s  = p + 2;
         const int      ns = s[0];
         if (ns < 1 || ns > f.ncomp || len != 6 + 2 * ns) bad("bad scan header");
-        int sc[3];
+        int sc[kJpegMaxComp];
         for (int i = 0; i < ns; i++) {
             const int cid = s[1 + 2 * i], t = s[2 + 2 * i];
             int       k   = 0;
@@ -656,12 +683,12 @@ void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_o
                     done++, left--;
                 }
         } else {
-            int pred[3] = {0, 0, 0};
+            int pred[kJpegMaxComp] = {0, 0, 0, 0};
             for (int my = 0; my < f.mcuy; my++)
                 for (int mx = 0; mx < f.mcux; mx++) {
                     if (restart && done && left == 0) {
                         br.restart();
-                        pred[0] = pred[1] = pred[2] = 0;
+                        pred[0] = pred[1] = pred[2] = pred[3] = 0;
                         left = restart;
                     }
                     for (int i = 0; i < ns; i++) {
@@ -686,7 +713,7 @@ void decode_file(const uint8_t* d, size_t size, Frame& f, Arena& a, size_t blk_o
         p = br.p;
         while (p + 1 < end && !(p[0] == 0xFF && p[1] != 0 && !(p[1] >= 0xD0 && p[1] <= 0xD7))) p++;
     }
-    if (adobe_rgb && f.ncomp == 3) unsupported("RGB (Adobe transform 0) JPEGs");
+    decide_colorspace(f);
     if (f.progressive) { // the dense coefficients as the sparse stream the kernels read
         int16_t* vals = (int16_t*)(a.host.data() + *val_off);
         for (int k = 0; k < f.ncomp; k++) {
@@ -742,7 +769,6 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
     JpegHuffTab    dct[4], act[4];
     bool           dset[4] = {false, false, false, false}, aset[4] = {false, false, false, false};
     int            restart = 0;
-    bool           adobe_rgb = false;
     auto segment = [&](int m, const uint8_t* s, int len) {
         const uint8_t* e = s + len - 2;
         if (m == 0xC4) {
@@ -771,8 +797,8 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
         } else if (m == 0xDD) {
             if (len < 4) bad("bad restart interval segment");
             restart = be16(s);
-        } else if (m == 0xEE) {
-            if (len >= 14 && std::memcmp(s, "Adobe", 5) == 0 && s[11] == 0) adobe_rgb = true;
+        } else {
+            app_segment(f, m, s, len);
         }
     };
     { // tables before SOF
@@ -790,7 +816,7 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
         }
     }
     // markers up to the scan
-    int sc[3] = {0, 0, 0}, ns = 0;
+    int sc[kJpegMaxComp] = {0, 0, 0, 0}, ns = 0;
     for (;;) {
         while (p < end && *p != 0xFF) p++;
         while (p < end && *p == 0xFF) p++;
@@ -838,7 +864,7 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
     }
     // the decoder's table slots: the scan's distinct DC tables in slots 0-1, its AC tables in 2-3 (a
     // scan naming more than two of either -- extended-sequential files may -- goes to the host decoder)
-    int dslot[3] = {0, 0, 0}, aslot[3] = {0, 0, 0}, dids[2] = {-1, -1}, aids[2] = {-1, -1};
+    int dslot[kJpegMaxComp] = {0, 0, 0, 0}, aslot[kJpegMaxComp] = {0, 0, 0, 0}, dids[2] = {-1, -1}, aids[2] = {-1, -1};
     for (int i = 0; i < ns; i++) {
         const int td = f.c[sc[i]].td, ta = f.c[sc[i]].ta;
         int       d = 0, q = 0;
@@ -927,10 +953,10 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
             return false;
         }
         if ((m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) bad("second frame header");
-        if (m == 0xEE) segment(m, p + 2, len);
+        app_segment(f, m, p + 2, len);
         p += len;
     }
-    if (adobe_rgb && f.ncomp == 3) unsupported("RGB (Adobe transform 0) JPEGs");
+    decide_colorspace(f);
     // segments: the ones past the scan's restart intervals are ignored, missing ones are empty;
     // subsequences: the data spread over the workgroup's lanes, within [kHuffSubMin, kHuffSubMax] bits
     // (longer when the segments' rounding up would give a lane more than one)
@@ -1096,7 +1122,8 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     for (auto& a : arenas) a.used = 0;
     std::vector<Frame>   frames(n);
     std::vector<int>     owner(n);
-    std::vector<size_t>  blk(3 * (size_t)n), val(n);
+    constexpr size_t     NC = kJpegMaxComp;
+    std::vector<size_t>  blk(NC * (size_t)n), val(n);
     std::vector<GpuScan> gs(n);
     std::vector<char>    on_gpu(n, 0);
     S->pool->run_indexed(n, [&](int i, int w) {
@@ -1109,7 +1136,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
                 on_gpu[i] = 1;
             } else {
                 frames[i] = Frame();
-                decode_file(b, sizes[i], frames[i], arenas[w], &blk[3 * (size_t)i], &val[i], d.channels == 1);
+                decode_file(b, sizes[i], frames[i], arenas[w], &blk[NC * (size_t)i], &val[i], d.channels == 1);
             }
             owner[i] = w;
             if (frames[i].W != d.width || frames[i].H != d.height)
@@ -1125,31 +1152,32 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     // work buffer (device only): [block records of the GPU-decoded files][their dense coefficients]
     // [their subsequence scratch]
     std::vector<JpegChunk> chunks;
-    std::vector<JpegRows>  rows;
+    std::vector<JpegRows>  rows, rows4; // bands of YCbCr / gray files (jpeg_color), of the others (jpeg_color4)
     // colour band height: kJpegRowsPerWg, or AEON_HIP_JPEG_BAND (tests: 1, 2, ... rows per workgroup
     // take the colour kernels' band-edge cases)
     int band_max = kJpegRowsPerWg;
     if (const char* e = std::getenv("AEON_HIP_JPEG_BAND"))
         if (std::atoi(e) >= 1) band_max = std::min(std::atoi(e), 64);
     size_t                 plane_bytes = 0;
-    std::vector<size_t>    plane_off(3 * (size_t)n, 0);
-    int                    color_lds = 0, n_gpu = 0;
+    std::vector<size_t>    plane_off(NC * (size_t)n, 0);
+    int                    color_lds = 0, color4_lds = 0, n_gpu = 0;
     size_t                 rec_bytes = 0, coef_bytes = 0, sub_bytes = 0;
-    std::vector<size_t>    wrec(3 * (size_t)n, 0), wcoef(3 * (size_t)n, 0), wsub(n, 0);
+    std::vector<size_t>    wrec(NC * (size_t)n, 0), wcoef(NC * (size_t)n, 0), wsub(n, 0);
     for (int i = 0; i < n; i++) {
         const Frame& f  = frames[i];
-        const int    nc = descs[i].channels == 1 ? 1 : f.ncomp; // grayscale output needs Y only
+        const int    nc = jpeg_planes_needed(f.cs, f.ncomp, descs[i].channels); // gray from YCbCr needs Y only
+        const bool   ycc = f.cs <= CS_YCC;
         if (on_gpu[i]) {
             n_gpu++;
             for (int k = 0; k < f.ncomp; k++) {
                 const size_t nb = (size_t)f.c[k].bw * f.c[k].bh;
-                wrec[3 * (size_t)i + k] = rec_bytes, rec_bytes += (nb * sizeof(JpegBlock) + 255) & ~(size_t)255;
-                wcoef[3 * (size_t)i + k] = coef_bytes, coef_bytes += (nb * 64 * sizeof(int16_t) + 255) & ~(size_t)255;
+                wrec[NC * (size_t)i + k] = rec_bytes, rec_bytes += (nb * sizeof(JpegBlock) + 255) & ~(size_t)255;
+                wcoef[NC * (size_t)i + k] = coef_bytes, coef_bytes += (nb * 64 * sizeof(int16_t) + 255) & ~(size_t)255;
             }
             wsub[i] = sub_bytes, sub_bytes += (size_t)gs[i].nsub * sizeof(JpegHuffSub);
         }
         for (int k = 0; k < nc; k++) {
-            plane_off[3 * (size_t)i + k] = plane_bytes;
+            plane_off[NC * (size_t)i + k] = plane_bytes;
             plane_bytes += ((size_t)f.c[k].bw * 8 * f.c[k].bh * 8 + 255) & ~(size_t)255;
             const int nb = f.c[k].bw * f.c[k].bh;
             for (int b = 0; b < nb; b += kJpegIdctBlocks) chunks.push_back({i, k, b, std::min(kJpegIdctBlocks, nb - b)});
@@ -1166,14 +1194,15 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
             if (lds <= kJpegColorLds || band == 1) break;
         }
         if (lds > kJpegColorLds) unsupported("image too wide for the colour pass's LDS rows");
-        color_lds = std::max(color_lds, lds);
-        for (int y = 0; y < f.H; y += band) rows.push_back({i, y, std::min(band, f.H - y), 0});
+        (ycc ? color_lds : color4_lds) = std::max(ycc ? color_lds : color4_lds, lds);
+        for (int y = 0; y < f.H; y += band) (ycc ? rows : rows4).push_back({i, y, std::min(band, f.H - y), 0});
     }
     const size_t img_bytes = (size_t)n * sizeof(JpegImage);
     const size_t huf_off   = (img_bytes + 255) & ~(size_t)255;
     const size_t chk_off   = huf_off + (((size_t)n_gpu * sizeof(JpegHuffFile) + 255) & ~(size_t)255);
     const size_t row_off   = chk_off + ((chunks.size() * sizeof(JpegChunk) + 255) & ~(size_t)255);
-    size_t       total     = row_off + ((rows.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
+    const size_t row4_off  = row_off + ((rows.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
+    size_t       total     = row4_off + ((rows4.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
     const size_t head = total; // descriptors and lists: staged in st.pinned; the arenas go up from their own
     std::vector<size_t> arena_off(arenas.size());
     for (size_t w = 0; w < arenas.size(); w++) {
@@ -1216,12 +1245,12 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         const uint64_t base = dev + arena_off[owner[i]];
         for (int k = 0; k < f.ncomp; k++) {
             if (on_gpu[i]) {
-                J.blocks[k] = work + wrec[3 * (size_t)i + k];
-                J.dvals[k]  = work + coef_off + wcoef[3 * (size_t)i + k];
+                J.blocks[k] = work + wrec[NC * (size_t)i + k];
+                J.dvals[k]  = work + coef_off + wcoef[NC * (size_t)i + k];
             } else {
-                J.blocks[k] = base + blk[3 * (size_t)i + k];
+                J.blocks[k] = base + blk[NC * (size_t)i + k];
             }
-            J.planes[k] = (uint64_t)st.planes + plane_off[3 * (size_t)i + k];
+            J.planes[k] = (uint64_t)st.planes + plane_off[NC * (size_t)i + k];
             J.bw[k] = f.c[k].bw, J.bh[k] = f.c[k].bh, J.dw[k] = f.c[k].dw, J.dh[k] = f.c[k].dh;
             J.hs[k] = f.c[k].h, J.vs[k] = f.c[k].v;
             J.hf[k] = f.hmax / f.c[k].h, J.vf[k] = f.vmax / f.c[k].v;
@@ -1232,7 +1261,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         J.values     = on_gpu[i] ? 0 : base + val[i];
         J.out        = (uint64_t)dst_base + descs[i].offset;
         J.W          = f.W, J.H = f.H, J.ncomp = f.ncomp, J.out_cn = descs[i].channels, J.out_stride = descs[i].stride;
-        J.hmax       = f.hmax, J.vmax = f.vmax;
+        J.hmax       = f.hmax, J.vmax = f.vmax, J.cs = f.cs;
         if (!on_gpu[i]) continue;
         const GpuScan& g = gs[i];
         JpegHuffFile&  H = hf[hpos[i]];
@@ -1255,6 +1284,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     }
     if (!chunks.empty()) std::memcpy(st.pinned + chk_off, chunks.data(), chunks.size() * sizeof(JpegChunk));
     if (!rows.empty()) std::memcpy(st.pinned + row_off, rows.data(), rows.size() * sizeof(JpegRows));
+    if (!rows4.empty()) std::memcpy(st.pinned + row4_off, rows4.data(), rows4.size() * sizeof(JpegRows));
     mark(3);
     // (round 4 copied the arenas into st.pinned on the pool first: ~0.5 ms per 512 files)
     auto h2d = [&](hipStream_t on) {
@@ -1280,7 +1310,8 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         hip_ok(launch_jpeg_huff((const JpegHuffFile*)(st.dev + huf_off), n_gpu, S->huff_lanes, huff_stage, error, stream),
                "JPEG Huffman kernel");
     hip_ok(launch_jpeg((const JpegImage*)st.dev, (const JpegChunk*)(st.dev + chk_off), (int)chunks.size(),
-                       (const JpegRows*)(st.dev + row_off), (int)rows.size(), color_lds, stream),
+                       (const JpegRows*)(st.dev + row_off), (int)rows.size(), color_lds,
+                       (const JpegRows*)(st.dev + row4_off), (int)rows4.size(), color4_lds, stream),
            "JPEG kernels");
     if (stop) hip_ok(hipEventRecord(stop, stream), "hipEventRecord");
     hip_ok(hipEventRecord(st.done, stream), "hipEventRecord");
@@ -1309,7 +1340,7 @@ void jpeg_entropy_only(const void* data, size_t size, int* w, int* h, int* ncomp
 {
     Frame  f;
     Arena  a;
-    size_t blk_off[3] = {0, 0, 0}, val_off = 0;
+    size_t blk_off[kJpegMaxComp] = {0, 0, 0, 0}, val_off = 0;
     decode_file((const uint8_t*)data, size, f, a, blk_off, &val_off, false);
     uint64_t  hv = 1469598103934665603ull;
     auto      mix = [&](uint64_t x) {
@@ -1339,7 +1370,7 @@ void jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* s
     GpuScan g;
     *gpu_entropy = prepare_gpu((const uint8_t*)data, size, f, a, g, kHuffLanes) ? 1 : 0;
     if (!*gpu_entropy) {
-        size_t blk_off[3] = {0, 0, 0}, val_off = 0;
+        size_t blk_off[kJpegMaxComp] = {0, 0, 0, 0}, val_off = 0;
         f = Frame(), a.used = 0;
         decode_file((const uint8_t*)data, size, f, a, blk_off, &val_off, false);
     }
@@ -1358,8 +1389,8 @@ int jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, i
     Arena   a;
     GpuScan g;
     if (!prepare_gpu((const uint8_t*)data, size, f, a, g, lanes)) return 0;
-    std::vector<JpegBlock>   recs[3];
-    std::vector<int16_t>     coef[3];
+    std::vector<JpegBlock>   recs[kJpegMaxComp];
+    std::vector<int16_t>     coef[kJpegMaxComp];
     std::vector<JpegHuffSub> subs(g.nsub);
     JpegHuffFile             F;
     std::memset(&F, 0, sizeof(F));
@@ -1384,9 +1415,11 @@ int jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, i
     huff::pass_guess(*T, F, subs.data(), 0, 1);
     int r = 0;
     while (huff::pass_compare(F, subs.data(), 0, 1)) huff::pass_rewalk(*T, F, subs.data(), 0, 1), r++;
-    int32_t acc[4] = {0, 0, 0, 0};
-    for (auto& s : subs)
+    int32_t acc[4] = {0, 0, 0, 0}, acc3 = 0;
+    for (auto& s : subs) {
         for (int i = 0; i < 4; i++) s.ex[i] = acc[i], acc[i] += s.cnt[i];
+        s.ex3 = acc3, acc3 += s.cnt3;
+    }
     if (!huff::pass_write(*T, F, subs.data(), 0, 1)) return -1;
     uint64_t hv  = 1469598103934665603ull;
     auto     mix = [&](uint64_t x) {

@@ -47,28 +47,42 @@ __shared__ int                probe_k;
     } while (0)
 #endif
 
+using huff::Sums;
+
 struct Scan {
     int4 wsum[1024 / 64];
     int4 carry;
+    int  wsum3[1024 / 64]; // component 3's DC sums (Sums::b)
+    int  carry3;
 };
+
+__device__ __forceinline__ void add(Sums& v, const Sums& o)
+{
+    v.a.x += o.a.x, v.a.y += o.a.y, v.a.z += o.a.z, v.a.w += o.a.w, v.b += o.b;
+}
+__device__ __forceinline__ Sums minus(const Sums& s, const Sums& v)
+{
+    return Sums{make_int4(s.a.x - v.a.x, s.a.y - v.a.y, s.a.z - v.a.z, s.a.w - v.a.w), s.b - v.b};
+}
 
 // Inclusive scan of v over the workgroup's LANES lanes, plus the running carry of earlier chunks.
 template <int LANES>
-__device__ int4 wg_scan(Scan& X, int4 v)
+__device__ Sums wg_scan(Scan& X, Sums v)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(v.x, o), y = __shfl_up(v.y, o), z = __shfl_up(v.z, o), w = __shfl_up(v.w, o);
-        if (lane >= o) v.x += x, v.y += y, v.z += z, v.w += w;
+        const Sums u{make_int4(__shfl_up(v.a.x, o), __shfl_up(v.a.y, o), __shfl_up(v.a.z, o), __shfl_up(v.a.w, o)),
+                     __shfl_up(v.b, o)};
+        if (lane >= o) add(v, u);
     }
-    if (lane == 63) X.wsum[wave] = v;
+    if (lane == 63) X.wsum[wave] = v.a, X.wsum3[wave] = v.b;
     __syncthreads();
-    int4 off = X.carry;
-    for (int i = 0; i < wave; i++) off.x += X.wsum[i].x, off.y += X.wsum[i].y, off.z += X.wsum[i].z, off.w += X.wsum[i].w;
-    v.x += off.x, v.y += off.y, v.z += off.z, v.w += off.w;
+    Sums off{X.carry, X.carry3};
+    for (int i = 0; i < wave; i++) add(off, Sums{X.wsum[i], X.wsum3[i]});
+    add(v, off);
     __syncthreads();
-    if (threadIdx.x == LANES - 1) X.carry = v;
+    if (threadIdx.x == LANES - 1) X.carry = v.a, X.carry3 = v.b;
     return v;
 }
 
@@ -93,10 +107,13 @@ __device__ __forceinline__ void decode_strided(const huff::Tables& T, Scan& X, c
     // 3. exclusive prefix of (blocks, DC differences) over the file's subsequences
     for (int base = 0; base < nsub; base += LANES) {
         const int  j = base + tid;
-        const int4 v = j < nsub ? make_int4(subs[j].cnt[0], subs[j].cnt[1], subs[j].cnt[2], subs[j].cnt[3])
-                                : make_int4(0, 0, 0, 0);
-        const int4 s = wg_scan<LANES>(X, v);
-        if (j < nsub) subs[j].ex[0] = s.x - v.x, subs[j].ex[1] = s.y - v.y, subs[j].ex[2] = s.z - v.z, subs[j].ex[3] = s.w - v.w;
+        const Sums v = j < nsub ? Sums{make_int4(subs[j].cnt[0], subs[j].cnt[1], subs[j].cnt[2], subs[j].cnt[3]), subs[j].cnt3}
+                                : huff::sums_zero();
+        const Sums s = wg_scan<LANES>(X, v);
+        if (j < nsub) {
+            const Sums e = minus(s, v);
+            subs[j].ex[0] = e.a.x, subs[j].ex[1] = e.a.y, subs[j].ex[2] = e.a.z, subs[j].ex[3] = e.a.w, subs[j].ex3 = e.b;
+        }
         __syncthreads();
     }
     // 4. the final decode: coefficients and masks
@@ -110,7 +127,8 @@ struct LaneStates {
     uint64_t en[LANES];
     uint2    se[LANES];
     int4     ex[LANES];
-    int      todo[LANES];
+    int      ex3[LANES]; // component 3's part of the counts (Sums::b)
+    uint16_t todo[LANES];
     int      wave_n[LANES / 64];
 };
 
@@ -137,6 +155,7 @@ __device__ __forceinline__ void decode_lanes(const huff::Tables& T, Scan& X, Lan
     uint64_t   st    = huff::pack_state(p0, 0, 0);
     L.se[tid]        = make_uint2((uint32_t)stop, S.end_bit);
     L.ex[tid]        = make_int4(0, 0, 0, 0);
+    L.ex3[tid]       = 0;
     HUFF_STAMP("start", nsub);
     // a walk of subsequence j from state s (bounds from L.se): its end state and counts into L
     auto walk_sync = [&](int j, uint64_t s0) __attribute__((always_inline)) {
@@ -144,17 +163,17 @@ __device__ __forceinline__ void decode_lanes(const huff::Tables& T, Scan& X, Lan
         const uint2      se = L.se[j];
         const JpegHuffSeg Sj{0, se.y, 0, 0};
         auto             b   = huff::bits_from(words, Sj, (int)(uint32_t)s0);
-        int4             cnt = make_int4(0, 0, 0, 0);
+        Sums             cnt = huff::sums_zero();
         huff::walk_sync(T, F, b, c, k, (int)se.x, cnt);
         L.en[j] = huff::pack_state(b.p, c, k);
-        L.ex[j] = cnt;
+        L.ex[j] = cnt.a, L.ex3[j] = cnt.b;
     };
     // 1. the guessed start, kHuffLeadBits ahead (the segment's last subsequence ends nobody's start)
     if (have) {
-        int4     cnt;
+        Sums     cnt;
         uint64_t en;
         huff::guess_walk(T, F, S, huff::bits_from(words, S, huff::guess_from(S, p0)), p0, !last, st, en, cnt);
-        if (!last) L.en[tid] = en, L.ex[tid] = cnt;
+        if (!last) L.en[tid] = en, L.ex[tid] = cnt.a, L.ex3[tid] = cnt.b;
     }
     // 2. Jacobi rounds
     for (int round = 0;; round++) {
@@ -175,7 +194,7 @@ __device__ __forceinline__ void decode_lanes(const huff::Tables& T, Scan& X, Lan
             rank += w < wave ? n : 0;
             total += n;
         }
-        if (dirty) L.todo[rank] = tid;
+        if (dirty) L.todo[rank] = (uint16_t)tid;
         __syncthreads();
         int      j  = 0;
         uint64_t s0 = 0;
@@ -184,21 +203,20 @@ __device__ __forceinline__ void decode_lanes(const huff::Tables& T, Scan& X, Lan
         if (tid < total) walk_sync(j, s0);
     }
     // 3. exclusive prefix (one chunk: nsub <= LANES)
-    const int4 cnt = L.ex[tid];
-    const int4 s   = wg_scan<LANES>(X, cnt);
+    const Sums cnt{L.ex[tid], L.ex3[tid]};
+    const Sums ex = minus(wg_scan<LANES>(X, cnt), cnt);
     __syncthreads();
-    L.ex[tid] = make_int4(s.x - cnt.x, s.y - cnt.y, s.z - cnt.z, s.w - cnt.w);
+    L.ex[tid] = ex.a, L.ex3[tid] = ex.b;
     __syncthreads();
     HUFF_STAMP("scanned", 0);
     if (!have) return;
     // 4. the final decode
-    const int4 e0 = L.ex[S.first_sub], e1 = L.ex[tid];
+    const Sums e0{L.ex[S.first_sub], L.ex3[S.first_sub]};
     const int  per_seg = F.restart * F.bpm, total = F.n_mcu * F.bpm;
     int        c = (int)(st >> 32) & 0xff, k = (int)(st >> 40) & 0xff;
     huff::Out  o;
-    o.blk     = sg * per_seg + (e1.x - e0.x) - (k > 0);
+    huff::out_from(o, e0, ex, sg * per_seg, k);
     o.blk_end = min(sg * per_seg + per_seg, total);
-    o.pred0 = e1.y - e0.y, o.pred1 = e1.z - e0.z, o.pred2 = e1.w - e0.w;
     o.trunc = F.truncated >= 0 && sg >= F.truncated;
     if (o.blk < sg * per_seg) return;
     const int mcu = o.blk / F.bpm;
@@ -233,7 +251,7 @@ __global__ __launch_bounds__(LANES) void jpeg_huff(const JpegHuffFile* __restric
 #endif
     HUFF_STAMP("enter", F.data_words);
     huff::tables_codes(T, F, tid, LANES);
-    if (tid == 0) X.carry = make_int4(0, 0, 0, 0);
+    if (tid == 0) X.carry = make_int4(0, 0, 0, 0), X.carry3 = 0;
     __syncthreads();
     HUFF_STAMP("codes", 0);
     huff::tables_fast(T, F, tid, LANES);

@@ -49,12 +49,15 @@ struct Tables {
 };
 
 HUFF_FN int imin(int a, int b) { return a < b ? a : b; }
-// v[comp] of three per-component values as arithmetic: a select chain over locals can become a
+// v[comp] of the per-component values as arithmetic: a select chain over locals can become a
 // stack lookup table (scratch memory) on the device
-HUFF_FN int pick3(int comp, int a, int b, int c) { return a + (comp >= 1) * (b - a) + (comp >= 2) * (c - b); }
-HUFF_FN uint64_t pick3(int comp, uint64_t a, uint64_t b, uint64_t c)
+HUFF_FN int pick4(int comp, int a, int b, int c, int d)
 {
-    return a + (uint64_t)(comp >= 1) * (b - a) + (uint64_t)(comp >= 2) * (c - b);
+    return a + (comp >= 1) * (b - a) + (comp >= 2) * (c - b) + (comp >= 3) * (d - c);
+}
+HUFF_FN uint64_t pick4(int comp, uint64_t a, uint64_t b, uint64_t c, uint64_t d)
+{
+    return a + (uint64_t)(comp >= 1) * (b - a) + (uint64_t)(comp >= 2) * (c - b) + (uint64_t)(comp >= 3) * (d - c);
 }
 HUFF_FN int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
@@ -234,7 +237,7 @@ HUFF_FN uint64_t pack_state(int p, int c, int k) { return (uint32_t)p | ((uint64
 struct Out {
     int blk, blk_end; // current block (scan order), the segment's end
     int mx, my;       // MCU of the current block
-    int pred0, pred1, pred2;
+    int pred0, pred1, pred2, pred3;
     int trunc; // reading past the segment's data is an error
 };
 
@@ -264,6 +267,14 @@ HUFF_FN uint32_t long_entry(const Tables& T, int t, uint64_t buf, bool& ok)
     return kSym | (uint32_t)l | ((uint32_t)(sym >> 4) << 5) | ((uint32_t)(sym & 15) << 16);
 }
 
+// The running sums of a walk, and of the prefix over a file's subsequences: blocks started (a.x) and
+// the DC differences of components 0..2 (a.y, a.z, a.w) and 3 (b).
+struct Sums {
+    int4 a;
+    int  b;
+};
+HUFF_FN Sums sums_zero() { return Sums{make_int4(0, 0, 0, 0), 0}; }
+
 // The MCU's block table in registers (F lives in device memory: a lane-dependent index into it would
 // be a memory round trip at every block end).
 struct BlkTab {
@@ -284,11 +295,13 @@ struct BlkTab {
 // than the lookahead and a DC difference whose bits exceed it.  AC value bits are skipped, not
 // decoded.  (A guessed start can meet no-code bit patterns and DC sizes above 15: fixed continuations.)
 template <typename B>
-HUFF_FN void walk_sync(const Tables& T, const JpegHuffFile& F, B& b, int& c, int& k, int stop, int4& cnt)
+HUFF_FN void walk_sync(const Tables& T, const JpegHuffFile& F, B& b, int& c, int& k, int stop, Sums& sums)
 {
     const BlkTab bt{F.blk_tab[0], F.blk_tab[1]};
     const int    bpm  = F.bpm;
     int          comp = bt.comp(c);
+    int4         cnt  = sums.a;
+    int          cnt3 = sums.b;
     while (b.p < stop) {
         if constexpr (WordsInMemory<decltype(b.w)>::value) b.fill();
         else b.fill_always();
@@ -313,6 +326,7 @@ HUFF_FN void walk_sync(const Tables& T, const JpegHuffFile& F, B& b, int& c, int
         cnt.y += comp == 0 ? vd : 0;
         cnt.z += comp == 1 ? vd : 0;
         cnt.w += comp == 2 ? vd : 0;
+        cnt3 += comp == 3 ? vd : 0;
         const int dk = kind == kEob ? 64 : (kind == kZrl ? 16 : (int)((e >> 5) & 15) + 1);
         k            = dc ? 1 : k + dk;
         const bool end = k >= 64;
@@ -320,6 +334,7 @@ HUFF_FN void walk_sync(const Tables& T, const JpegHuffFile& F, B& b, int& c, int
         c              = end ? (c + 1 == bpm ? 0 : c + 1) : c;
         comp           = bt.comp(c);
     }
+    sums.a = cnt, sums.b = cnt3;
 }
 
 // The final walk from an exact state: every block's coefficients into its dense slots and its mask
@@ -331,10 +346,11 @@ template <typename B>
 HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, int& k, int stop, bool last, Out& o)
 {
     const BlkTab          bt{F.blk_tab[0], F.blk_tab[1]};
-    const int             bw0 = F.bw[0], bw1 = F.bw[1], bw2 = F.bw[2], hs0 = F.hs[0], hs1 = F.hs[1], hs2 = F.hs[2];
-    const int             vs0 = F.vs[0], vs1 = F.vs[1], vs2 = F.vs[2], bpm = F.bpm, mcux = F.mcux;
-    const uint64_t        dv0 = F.dvals[0], dv1 = F.dvals[1], dv2 = F.dvals[2];
-    const uint64_t        bk0 = F.blocks[0], bk1 = F.blocks[1], bk2 = F.blocks[2];
+    const int             bw0 = F.bw[0], bw1 = F.bw[1], bw2 = F.bw[2], bw3 = F.bw[3];
+    const int             hs0 = F.hs[0], hs1 = F.hs[1], hs2 = F.hs[2], hs3 = F.hs[3];
+    const int             vs0 = F.vs[0], vs1 = F.vs[1], vs2 = F.vs[2], vs3 = F.vs[3], bpm = F.bpm, mcux = F.mcux;
+    const uint64_t        dv0 = F.dvals[0], dv1 = F.dvals[1], dv2 = F.dvals[2], dv3 = F.dvals[3];
+    const uint64_t        bk0 = F.blocks[0], bk1 = F.blocks[1], bk2 = F.blocks[2], bk3 = F.blocks[3];
     int                   comp = bt.comp(c);
     uint64_t              mask = 0;
     HUFF_GLOBAL int16_t*  coef = nullptr;
@@ -342,10 +358,11 @@ HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, in
     bool                  own  = k == 0; // the current block started in this walk
     auto open = [&]() {                  // locate the current block in its component plane
         const int    by = bt.byte(c), x = (by >> 2) & 3, y = (by >> 4) & 3;
-        const int    bw = pick3(comp, bw0, bw1, bw2), hs = pick3(comp, hs0, hs1, hs2), vs = pick3(comp, vs0, vs1, vs2);
+        const int    bw = pick4(comp, bw0, bw1, bw2, bw3), hs = pick4(comp, hs0, hs1, hs2, hs3);
+        const int    vs = pick4(comp, vs0, vs1, vs2, vs3);
         const size_t idx = (size_t)(o.my * vs + y) * bw + o.mx * hs + x;
-        coef = gmem<int16_t>(pick3(comp, dv0, dv1, dv2)) + idx * 64;
-        mrec = gmem<uint64_t>(pick3(comp, bk0, bk1, bk2)) + idx * 2;
+        coef = gmem<int16_t>(pick4(comp, dv0, dv1, dv2, dv3)) + idx * 64;
+        mrec = gmem<uint64_t>(pick4(comp, bk0, bk1, bk2, bk3)) + idx * 2;
     };
     if (o.blk < o.blk_end) open();
     while (o.blk < o.blk_end && (last || b.p < stop)) {
@@ -366,10 +383,11 @@ HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, in
         b.skip(used + z);
         if (o.trunc && b.p > b.end) return false; // past the end of the file's data
         if (k == 0) { // DC difference
-            const int pr = pick3(comp, o.pred0, o.pred1, o.pred2) + v;
+            const int pr = pick4(comp, o.pred0, o.pred1, o.pred2, o.pred3) + v;
             o.pred0 = comp == 0 ? pr : o.pred0;
             o.pred1 = comp == 1 ? pr : o.pred1;
             o.pred2 = comp == 2 ? pr : o.pred2;
+            o.pred3 = comp == 3 ? pr : o.pred3;
             const int16_t dc = (int16_t)pr;
             if (dc) coef[0] = dc;
             mask = dc ? 1 : 0;
@@ -403,14 +421,21 @@ HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, in
 
 
 template <typename S>
-HUFF_FN void set_cnt(S& s, int4 v)
+HUFF_FN void set_cnt(S& s, const Sums& v)
 {
-    s.cnt[0] = v.x, s.cnt[1] = v.y, s.cnt[2] = v.z, s.cnt[3] = v.w;
+    s.cnt[0] = v.a.x, s.cnt[1] = v.a.y, s.cnt[2] = v.a.z, s.cnt[3] = v.a.w, s.cnt3 = v.b;
 }
 template <typename S>
-HUFF_FN int4 get_ex(const S& s)
+HUFF_FN Sums get_ex(const S& s)
 {
-    return make_int4(s.ex[0], s.ex[1], s.ex[2], s.ex[3]);
+    return Sums{make_int4(s.ex[0], s.ex[1], s.ex[2], s.ex[3]), s.ex3};
+}
+// The first block and the DC predictors of a final walk from the exclusive sums of its subsequence
+// (e1) and of its segment's first one (e0).
+HUFF_FN void out_from(Out& o, const Sums& e0, const Sums& e1, int seg_first_blk, int k)
+{
+    o.blk   = seg_first_blk + (e1.a.x - e0.a.x) - (k > 0);
+    o.pred0 = e1.a.y - e0.a.y, o.pred1 = e1.a.z - e0.a.z, o.pred2 = e1.a.w - e0.a.w, o.pred3 = e1.b - e0.b;
 }
 
 // The phases below take the file's subsequence states `subs` (F.subs in device memory, or an LDS
@@ -426,13 +451,13 @@ HUFF_FN int guess_from(const JpegHuffSeg& S, int p) { return p - kHuffLeadBits <
 // end: en and the counts of its own bits.
 template <typename B>
 HUFF_FN void guess_walk(const Tables& T, const JpegHuffFile& F, const JpegHuffSeg& S, B b, int p, bool ends,
-                        uint64_t& st, uint64_t& en, int4& cnt)
+                        uint64_t& st, uint64_t& en, Sums& cnt)
 {
     int  c = 0, k = 0;
-    int4 lead = make_int4(0, 0, 0, 0);
+    Sums lead = sums_zero();
     walk_sync(T, F, b, c, k, p, lead);
     st  = pack_state(b.p, c, k);
-    cnt = make_int4(0, 0, 0, 0);
+    cnt = sums_zero();
     en  = 0;
     if (ends) {
         walk_sync(T, F, b, c, k, p + F.sub_bits, cnt);
@@ -449,7 +474,7 @@ HUFF_FN void pass_guess(const Tables& T, const JpegHuffFile& F, SP subs, int j0,
     for (int j = j0; j < F.nsub; j += dj) {
         const JpegHuffSeg S = segs[sseg[j]];
         const int         i = j - S.first_sub, p = (int)S.start_bit + i * F.sub_bits;
-        int4              cnt = make_int4(0, 0, 0, 0);
+        Sums              cnt = sums_zero();
         uint64_t          st, en = 0;
         guess_walk(T, F, S, bits_at(F, S, guess_from(S, p)), p, i + 1 < S.nsub, st, en, cnt);
         subs[j].st = st;
@@ -490,7 +515,7 @@ HUFF_FN void pass_rewalk(const Tables& T, const JpegHuffFile& F, SP subs, int j0
         const uint64_t    st = subs[j].st;
         const int         p = (int)(uint32_t)st, stop = (int)S.start_bit + (j - S.first_sub + 1) * F.sub_bits;
         int               c = (int)(st >> 32) & 0xff, k = (int)(st >> 40) & 0xff;
-        int4              cnt = make_int4(0, 0, 0, 0);
+        Sums              cnt = sums_zero();
         Bits              b   = bits_at(F, S, p);
         walk_sync(T, F, b, c, k, stop, cnt);
         subs[j].en = pack_state(b.p, c, k);
@@ -511,13 +536,12 @@ HUFF_FN bool pass_write(const Tables& T, const JpegHuffFile& F, SP subs, int j0,
         const int         sg = sseg[j];
         const JpegHuffSeg S  = segs[sg];
         const int         i  = j - S.first_sub;
-        const int4        e0 = get_ex(subs[S.first_sub]), e1 = get_ex(subs[j]);
+        const Sums        e0 = get_ex(subs[S.first_sub]), e1 = get_ex(subs[j]);
         const uint64_t    st = subs[j].st;
         int               c = (int)(st >> 32) & 0xff, k = (int)(st >> 40) & 0xff;
         Out               o;
-        o.blk     = sg * per_seg + (e1.x - e0.x) - (k > 0);
+        out_from(o, e0, e1, sg * per_seg, k);
         o.blk_end = imin(sg * per_seg + per_seg, total);
-        o.pred0 = e1.y - e0.y, o.pred1 = e1.z - e0.z, o.pred2 = e1.w - e0.w;
         o.trunc = F.truncated >= 0 && sg >= F.truncated;
         if (o.blk < sg * per_seg) continue; // (a continuation with no block before it cannot be exact)
         const int mcu = o.blk / F.bpm;

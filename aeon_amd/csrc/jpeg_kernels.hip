@@ -14,6 +14,10 @@
 // replicated at the edges as jdmainct.c does; box replication for the other ratios and for
 // components narrower than 3 samples), then jdcolor.c ycc_rgb_convert (16-bit fixed point) and the
 // BGR store of the decoded record into the augmentation stage's source arena.
+// jpeg_color4: the bands of CMYK, YCCK and RGB files (JpegImage.cs), which jpeg_color never sees: up
+// to four staged planes, each through its own upsampler, then jdcolor.c ycck_cmyk_convert (YCCK),
+// OpenCV's CMYK -> BGR / gray (grfmt_jpeg / utils.cpp icvCvt_CMYK2BGR_8u_C4C3R, icvCvt_CMYK2Gray_8u_C4C1R)
+// or, for RGB files, the channel swap / libjpeg-turbo's rgb_gray_convert.
 #include <hip/hip_runtime.h>
 
 #include "jpeg.hpp"
@@ -482,19 +486,109 @@ __global__ __launch_bounds__(256) void jpeg_color(const JpegImage* __restrict__ 
     color_rows(I, cv, R.y0, R.rows);
 }
 
+// ---- CMYK, YCCK and RGB sources ------------------------------------------------------------------
+// One pixel from its upsampled samples s0..s3 (C M Y K, Y Cb Cr K or R G B -): packed B | G << 8 |
+// R << 16, or the gray value when cn == 1.
+__device__ __forceinline__ uint32_t convert4(int cs, int cn, int s0, int s1, int s2, int s3)
+{
+    if (cs == CS_RGB) {
+        // jccolor.c rgb_gray_convert: FIX(0.299), FIX(0.587), FIX(0.114) at 16 bits
+        if (cn == 1) return (uint32_t)((s0 * 19595 + s1 * 38470 + s2 * 7471 + 32768) >> 16);
+        return (uint32_t)s2 | (uint32_t)s1 << 8 | (uint32_t)s0 << 16;
+    }
+    int c = s0, m = s1, y = s2;
+    if (cs == CS_YCCK) { // jdcolor.c ycck_cmyk_convert: 255 - the YCbCr path's R, G, B; K unchanged
+        const int cb = s1 - 128, cr = s2 - 128;
+        c = min(max(255 - (s0 + ((91881 * cr + 32768) >> 16)), 0), 255);
+        m = min(max(255 - (s0 + ((-22554 * cb + 32768 + -46802 * cr) >> 16)), 0), 255);
+        y = min(max(255 - (s0 + ((116130 * cb + 32768) >> 16)), 0), 255);
+    }
+    const int k = s3;
+    c = k - (((255 - c) * k) >> 8);
+    m = k - (((255 - m) * k) >> 8);
+    y = k - (((255 - y) * k) >> 8);
+    if (cn == 1) return (uint32_t)((y * 1868 + m * 9617 + c * 4899 + 8192) >> 14);
+    return (uint32_t)y | (uint32_t)m << 8 | (uint32_t)c << 16;
+}
+
+// A workgroup per band of output rows of a CMYK, YCCK or RGB file: every component's plane rows the
+// band reads staged in LDS as jpeg_color stages them (jpeg_stage_rows bounds them), then one lane per
+// 4 consecutive pixels with color_rows' stores.
+__global__ __launch_bounds__(256) void jpeg_color4(const JpegImage* __restrict__ imgs, const JpegRows* __restrict__ rows)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_b[];
+    const JpegRows   R  = rows[blockIdx.x];
+    const JpegImage& I  = imgs[R.img];
+    const int        nc = I.ncomp, y0 = R.y0, y1 = R.y0 + R.rows - 1;
+    CompView         cv[kJpegMaxComp];
+    int              off = 0;
+#pragma unroll
+    for (int k = 0; k < kJpegMaxComp; k++) {
+        CompView& c = cv[k];
+        if (k >= nc) { // (an RGB file has no fourth plane: never sampled)
+            c = cv[0];
+            continue;
+        }
+        int hi;
+        comp_rows(I, k, y0, y1, c, hi);
+        c.P = lds_b + off;
+        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)c.lo * c.pw);
+        uint2*       dst = (uint2*)(lds_b + off);
+        const int    n8  = (hi - c.lo + 1) * c.pw / 8;
+        for (int e = threadIdx.x; e < n8; e += blockDim.x) dst[e] = src[e];
+        off += (hi - c.lo + 1) * c.pw;
+    }
+    __syncthreads();
+    const int W = I.W, cn = I.out_cn, cs = I.cs, stride = I.out_stride;
+    const gp<uint8_t> out = gaddr<uint8_t>(I.out);
+    const int groups = (W + 3) >> 2;
+    for (int q = threadIdx.x; q < groups * R.rows; q += blockDim.x) {
+        const int y = y0 + q / groups, x0 = (q % groups) * 4;
+        uint32_t  p[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int x  = min(x0 + e, W - 1);
+            const int s0 = upsampled(cv[0], x, y), s1 = upsampled(cv[1], x, y), s2 = upsampled(cv[2], x, y);
+            const int s3 = nc == 4 ? upsampled(cv[3], x, y) : 0;
+            p[e] = convert4(cs, cn, s0, s1, s2, s3);
+        }
+        const gp<uint8_t> o = out + (size_t)y * stride + (size_t)x0 * cn;
+        if (x0 + 3 < W && ((uintptr_t)o & 3) == 0) {
+            if (cn == 1) {
+                *(gp<uint32_t>)o = p[0] | p[1] << 8 | p[2] << 16 | p[3] << 24;
+            } else {
+                const gp<uint32_t> d = (gp<uint32_t>)o;
+                d[0] = p[0] | p[1] << 24;
+                d[1] = p[1] >> 8 | p[2] << 16;
+                d[2] = p[2] >> 16 | p[3] << 8;
+            }
+        } else {
+            for (int e = 0; e < 4 && x0 + e < W; e++)
+                for (int c = 0; c < cn; c++) o[e * cn + c] = (uint8_t)(p[e] >> (8 * c));
+        }
+    }
+}
+
+// A colour kernel's launch: past 64 KB of dynamic LDS the kernel's limit is raised first.
+template <typename K>
+static hipError_t launch_color(K kernel, const JpegImage* imgs, const JpegRows* rows, int n_rows, int lds, hipStream_t stream)
+{
+    if (n_rows <= 0) return hipSuccess;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(n_rows), dim3(256), (size_t)lds, stream, imgs, rows);
+    return hipSuccess;
+}
+
 hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                       int color_lds, hipStream_t stream)
+                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, hipStream_t stream)
 {
     if (n_chunks > 0) hipLaunchKernelGGL(jpeg_idct, dim3(n_chunks), dim3(kJpegIdctLanes), 0, stream, imgs, chunks);
-    if (n_rows > 0) {
-        if (color_lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute((const void*)jpeg_color, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     color_lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(jpeg_color, dim3(n_rows), dim3(256), (size_t)color_lds, stream, imgs, rows);
-    }
-    return hipGetLastError();
+    hipError_t e = launch_color(jpeg_color, imgs, rows, n_rows, color_lds, stream);
+    if (e == hipSuccess) e = launch_color(jpeg_color4, imgs, rows4, n_rows4, color4_lds, stream);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 } // namespace aeon_hip

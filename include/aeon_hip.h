@@ -28,7 +28,7 @@ extern "C" {
 #define AEON_HIP_OK 0
 #define AEON_HIP_EINVAL -1     /* invalid argument / configuration (aeon: std::invalid_argument) */
 #define AEON_HIP_ERUNTIME -2   /* HIP runtime failure (aeon: std::runtime_error) */
-#define AEON_HIP_EUNSUPPORTED -3 /* input this build refuses (e.g. arithmetic-coded / 12-bit JPEG, CMYK) */
+#define AEON_HIP_EUNSUPPORTED -3 /* input this build refuses (e.g. arithmetic-coded / 12-bit / 2-component JPEG) */
 #define AEON_HIP_EDEVICE -4    /* a kernel reported an inconsistency in its device error word */
 
 /* output element types (aeon output_type -> cv type, src/typemap.hpp:43-52); the loader converts the
@@ -179,15 +179,18 @@ int aeon_jpeg_entropy_decode(const void* data, size_t size, int* width, int* hei
  * stages for the H2D.  For timing the host side of the stage per file. */
 int aeon_jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* staged_bytes);
 /* cv::imdecode(CV_LOAD_IMAGE_COLOR / GRAYSCALE) of n JPEG files (baseline / extended sequential /
- * progressive Huffman, 8-bit, 1 or 3 components) as libjpeg decodes them (ISLOW IDCT, fancy upsampling),
- * into device memory: record i as HWC uint8 (BGR if descs[i].channels == 3, the Y component if 1)
+ * progressive Huffman, 8-bit, 1, 3 or 4 components) as libjpeg decodes them (ISLOW IDCT, fancy upsampling),
+ * into device memory: record i as HWC uint8 (BGR if descs[i].channels == 3, gray if 1: the Y component of a YCbCr file)
  * at dst_base + descs[i].offset with descs[i].stride bytes per row; descs[i].width/height must be
  * the file's (aeon_jpeg_info).  Headers are parsed on the context's host pool; sequential files with
  * one scan of every component are Huffman-decoded on the GPU (their unstuffed entropy-coded bytes go
  * up), the others on the pool (their sparse coefficients go up), all in one H2D; the Huffman, IDCT /
  * upsampling / colour conversion kernels run on `stream`.  Corrupt entropy-coded data of a
  * GPU-decoded file is reported by aeon_hip_synchronize (AEON_HIP_EDEVICE).  The files may be released when the call returns; dst must stay valid until the stream
- * reaches the work.  Arithmetic-coded / lossless / 12-bit / CMYK files: AEON_HIP_EUNSUPPORTED. */
+ * reaches the work.  Files of one, three or four components are taken: YCbCr and gray, and CMYK /
+ * YCCK / Adobe-RGB files, which decode to what cv::imdecode gives for them (libjpeg's samples through
+ * OpenCV's CMYK -> BGR / gray; aeon_jpeg_info reports 4 components, the record is still 3 channels or
+ * 1).  Arithmetic-coded / lossless / 12-bit / 2-component files: AEON_HIP_EUNSUPPORTED. */
 int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
                                const aeon_img_desc* descs, void* dst_base, void* stream);
 
