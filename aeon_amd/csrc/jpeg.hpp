@@ -86,7 +86,7 @@ enum JpegUpsample : int32_t {
     UP_H2V1 = 1, // h2v1_fancy_upsample
     UP_H1V2 = 2, // h1v2_fancy_upsample (libjpeg-turbo)
     UP_H2V2 = 3, // h2v2_fancy_upsample
-    UP_BOX  = 4, // h2v1 / h2v2 / int_upsample box replication (other ratios, components < 3 samples wide)
+    UP_BOX  = 4, // h2v1 / h2v2 / int_upsample box replication (other ratios, h2v1 / h2v2 components < 3 samples wide)
 };
 
 // IDCT work item: blocks [first, first + count) of component `comp` of image `img`.
@@ -168,14 +168,15 @@ constexpr int kJpegIdctBlocks = kJpegIdctLanes / 8 * kJpegIdctUnroll; // blocks 
 constexpr int kJpegRowsPerWg = 32;  // output rows per colour workgroup (fewer when the staged rows outgrow LDS)
 constexpr int kJpegColorLds  = 160 * 1024; // most LDS a colour workgroup stages
 
-// jdsample.c's choice for a component (h / v expansion factors, dw samples per row): fancy
-// upsampling needs 3+ samples per row.
+// jdsample.c's choice for a component (h / v expansion factors, dw samples per row): the fancy
+// upsamplers that filter along a row (h2v1, h2v2) need 3+ samples per row; h1v2_fancy_upsample filters
+// down the columns only and is taken at any width.
 inline int jpeg_upsample_mode(int hf, int vf, int dw)
 {
     const bool fancy = dw > 2;
     if (hf == 1 && vf == 1) return UP_FULL;
     if (hf == 2 && vf == 1 && fancy) return UP_H2V1;
-    if (hf == 1 && vf == 2 && fancy) return UP_H1V2;
+    if (hf == 1 && vf == 2) return UP_H1V2;
     if (hf == 2 && vf == 2 && fancy) return UP_H2V2;
     return UP_BOX;
 }

@@ -11,8 +11,11 @@
 //   * jidctint.c jpeg_idct_islow (LL&M, CONST_BITS 13, PASS1_BITS 2) with the post-IDCT
 //     range-limit table of jdmaster.c prepare_range_limit_table (x & 1023 wrap);
 //   * jdsample.c: h2v1 / h2v2 / h1v2 fancy upsampling (triangle filters, context rows
-//     replicated at the image edges as jdmainct.c does), box replication otherwise;
-//   * jdcolor.c ycc_rgb_convert (SCALEBITS 16 fixed point tables); grayscale output = Y.
+//     replicated at the image edges as jdmainct.c does; h2v1 and h2v2 only for components of 3+
+//     samples a row, h1v2 at any width), box replication otherwise; fractional ratios refused;
+//   * jdcolor.c ycc_rgb_convert (SCALEBITS 16 fixed point tables); grayscale output = Y;
+//   * four components (CMYK, or YCCK through jdcolor.c ycck_cmyk_convert) with OpenCV 2.4's CMYK -> BGR /
+//     gray formulas, as tests/jpeg_cmyk_ref.py states them.
 // Pinned by Pillow's libjpeg-turbo decodes of aeon's own JPEG fixtures (test/test_data/
 // img_2112_70.jpg, flowers.jpg) and of JPEGs Pillow encodes (tests/golden/make_jpeg_fixtures.py).
 #include <stdint.h>
@@ -299,7 +302,7 @@ struct Decoder {
                 if (u8() != 8) bad("only 8-bit precision");
                 H = u16(), W = u16();
                 int n = u8();
-                if (W <= 0 || H <= 0 || (n != 1 && n != 3)) bad("unsupported frame");
+                if (W <= 0 || H <= 0 || (n != 1 && n != 3 && n != 4)) bad("unsupported frame");
                 comps.resize(n);
                 for (auto& c : comps) {
                     c.id = u8();
@@ -308,6 +311,9 @@ struct Decoder {
                     if (c.h < 1 || c.h > 4 || c.v < 1 || c.v > 4 || c.tq > 3) bad("bad component");
                     hmax = std::max(hmax, c.h), vmax = std::max(vmax, c.v);
                 }
+                // jdsample.c jinit_upsampler: JERR_FRACT_SAMPLE_NOTIMPL
+                for (auto& c : comps)
+                    if (hmax % c.h || vmax % c.v) bad("fractional sampling factors");
                 mcux = (W + 8 * hmax - 1) / (8 * hmax);
                 mcuy = (H + 8 * vmax - 1) / (8 * vmax);
                 for (auto& c : comps) {
@@ -438,7 +444,7 @@ std::vector<uint8_t> upsample(const std::vector<uint8_t>& pl, int pw, const Comp
 {
     const int hf = hmax / c.h, vf = vmax / c.v;
     std::vector<uint8_t> out((size_t)W * H);
-    const bool fancy = c.dw > 2;
+    const bool fancy = c.dw > 2; // (h2v1 and h2v2 only: jinit_upsampler takes h1v2_fancy_upsample at any width)
     auto at = [&](int x, int y) { return (int)pl[(size_t)y * pw + x]; };
     if (hf == 1 && vf == 1) {
         for (int y = 0; y < H; y++)
@@ -463,7 +469,7 @@ std::vector<uint8_t> upsample(const std::vector<uint8_t>& pl, int pw, const Comp
         for (int y = 0; y < H; y++) h2v1_row([&](int i) { return at(i, y); }, &out[(size_t)y * W]);
         return out;
     }
-    if (hf == 1 && vf == 2 && fancy) { // libjpeg-turbo h1v2_fancy_upsample
+    if (hf == 1 && vf == 2) { // libjpeg-turbo h1v2_fancy_upsample
         for (int y = 0; y < H; y++) {
             const int r = y / 2, v = y & 1;
             const int nb = v == 0 ? std::max(r - 1, 0) : std::min(r + 1, c.dh - 1);
@@ -528,7 +534,9 @@ int orc_jpeg_decode(const uint8_t* data, size_t size, int channels, uint8_t* out
         d.parse();
         const int W = d.W, H = d.H;
         std::vector<std::vector<uint8_t>> full;
-        const int ncomp = channels == 1 ? 1 : (int)d.comps.size();
+        // gray from a grayscale or YCbCr file is its (upsampled) first component; from CMYK / YCCK all four
+        const int ncomp = channels == 1 && d.comps.size() != 4 ? 1 : (int)d.comps.size();
+        const bool ycck = d.adobe && d.adobe_transform != 0; // jdapimin.c default_decompress_parms
         for (int k = 0; k < ncomp; k++) {
             Comp&                c  = d.comps[k];
             const int            pw = c.bw * 8;
@@ -541,7 +549,21 @@ int orc_jpeg_decode(const uint8_t* data, size_t size, int channels, uint8_t* out
         for (int y = 0; y < H; y++)
             for (int x = 0; x < W; x++) {
                 const size_t i = (size_t)y * W + x;
-                if (channels == 1) {
+                if (ncomp == 4) {
+                    // jdcolor.c ycck_cmyk_convert, then OpenCV 2.4's icvCvt_CMYK2BGR_8u_C4C3R /
+                    // icvCvt_CMYK2Gray_8u_C4C1R on libjpeg's samples (tests/jpeg_cmyk_ref.py)
+                    int c = full[0][i], m = full[1][i], ye = full[2][i];
+                    const int k = full[3][i];
+                    if (ycck) {
+                        const int Y = c, cb = m - 128, cr = ye - 128;
+                        c  = clamp255(255 - (Y + (int)((91881L * cr + 32768) >> 16)));
+                        m  = clamp255(255 - (Y + (int)((-22554L * cb + 32768 + -46802L * cr) >> 16)));
+                        ye = clamp255(255 - (Y + (int)((116130L * cb + 32768) >> 16)));
+                    }
+                    c = k - (((255 - c) * k) >> 8), m = k - (((255 - m) * k) >> 8), ye = k - (((255 - ye) * k) >> 8);
+                    if (channels == 1) out[i] = (uint8_t)((ye * 1868 + m * 9617 + c * 4899 + 8192) >> 14);
+                    else out[3 * i] = (uint8_t)ye, out[3 * i + 1] = (uint8_t)m, out[3 * i + 2] = (uint8_t)c;
+                } else if (channels == 1) {
                     out[i] = full[0][i];
                 } else if (ncomp == 1) {
                     out[3 * i] = out[3 * i + 1] = out[3 * i + 2] = full[0][i];

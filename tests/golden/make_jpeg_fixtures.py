@@ -16,6 +16,10 @@ Fixtures: aeon's own test/test_data/img_2112_70.jpg and flowers.jpg (4:2:0 basel
 Pillow encodes from seeded smooth-noise images: 4:4:4 / 4:2:2 / 4:2:0 / 4:1:1, grayscale, restart
 intervals, sizes from 1x1 up, qualities 10..100, and progressive files (synthetic ones and aeon's two
 images re-encoded progressive).
+
+Note: Pillow maps subsampling "4:1:1" to 4:2:0, so s411_q85's frame header says 2x2 / 1x1 / 1x1 like the
+4:2:0 files (the fixture keeps its name: its digests are committed).  The real 4:1:1 layout (Y 4x1) is
+the `y4x1` fixture of jpeg_layout_fixtures.npz (make_jpeg_layout_fixtures.py).
 """
 import hashlib
 import io
