@@ -26,8 +26,25 @@ DTYPE_U8 = 0
 DTYPE_F32 = 1
 # output dtype name -> (AEON_DTYPE_* code, numpy type); aeon output_type uint32_t maps to int32 storage
 DTYPES = {"uint8": (0, np.uint8), "float32": (1, np.float32), "int8": (2, np.int8), "int16": (3, np.int16),
-          "uint16": (4, np.uint16), "int32": (5, np.int32), "float64": (6, np.float64)}
+          "uint16": (4, np.uint16), "int32": (5, np.int32), "float64": (6, np.float64),
+          # image outputs only: the float32 output rounded once to the 16-bit type.  numpy has no bfloat16:
+          # its arrays are uint16 carrying the bfloat16 bits (as_torch views them as torch.bfloat16)
+          "float16": (7, np.float16), "bfloat16": (8, np.uint16)}
 NP_DTYPE = {code: t for code, t in DTYPES.values()}
+TYPE_NAME = {code: name for name, (code, _) in DTYPES.items()}
+
+
+def as_torch(array, type_name):
+    """A decoder / stage output array as a torch tensor sharing its memory: torch.float16 for "float16",
+    torch.bfloat16 for "bfloat16" (whose numpy arrays hold the bits as uint16), else the array's own type."""
+    import torch
+    if type_name == "bfloat16":
+        if array.dtype != np.uint16:
+            raise TypeError("bfloat16 outputs are uint16 arrays of the bfloat16 bits")
+        return torch.from_numpy(array.view(np.int16)).view(torch.bfloat16)
+    if type_name == "float16" and array.dtype != np.float16:
+        raise TypeError("float16 outputs are float16 arrays")
+    return torch.from_numpy(array)
 INTERP_LINEAR = 0
 INTERP_NEAREST = 1
 INTERP_CUBIC = 2
@@ -917,7 +934,8 @@ class Decoder:
                                                        ctypes.byref(ib), ctypes.byref(dt)))
             self.outputs.append({"name": name.value.decode(), "shape": tuple(shape[:nd.value]),
                                  "item_bytes": ib.value,
-                                 "dtype": NP_DTYPE.get(dt.value)})
+                                 "dtype": NP_DTYPE.get(dt.value),
+                                 "type_name": TYPE_NAME.get(dt.value)})
 
     def close(self):
         if getattr(self, "_h", None):

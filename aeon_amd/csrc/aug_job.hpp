@@ -25,15 +25,27 @@ enum PhotoFlags : int32_t {
 enum BsKind : int32_t { BS_DIAG = 0, BS_FIXPT = 1, BS_FLOAT = 2 };
 
 // Output element types, AEON_DTYPE_* codes (aeon output_type -> cv type).
-enum OutDtype : int32_t { OUT_U8 = 0, OUT_F32 = 1, OUT_S8 = 2, OUT_S16 = 3, OUT_U16 = 4, OUT_S32 = 5, OUT_F64 = 6 };
+// OUT_F16 / OUT_BF16 (images only): the float output rounded once to the 16-bit type at the store.
+enum OutDtype : int32_t {
+    OUT_U8 = 0, OUT_F32 = 1, OUT_S8 = 2, OUT_S16 = 3, OUT_U16 = 4, OUT_S32 = 5, OUT_F64 = 6, OUT_F16 = 7, OUT_BF16 = 8
+};
 
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
-inline int out_elem_bytes(int dt)
+inline bool out_is_half(int dt) { return dt == OUT_F16 || dt == OUT_BF16; }
+// element size of aeon's own output types (OUT_U8 .. OUT_F64)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int cv_elem_bytes(int dt)
 {
     return dt == OUT_U8 || dt == OUT_S8 ? 1 : (dt == OUT_S16 || dt == OUT_U16 ? 2 : (dt == OUT_F64 ? 8 : 4));
 }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int out_elem_bytes(int dt) { return out_is_half(dt) ? 2 : cv_elem_bytes(dt); }
 
 // 16-byte aligned, plain data (copied H2D as an array).  Every field a tile of a launch without
 // photometric stages reads lies in the first kJobHotBytes: such launches fetch only that half of
@@ -158,12 +170,13 @@ struct LaunchArgs {
     int32_t        out_dtype;  // OutDtype
     int32_t        channel_major;
     int32_t        bgr_to_rgb;
-    int32_t        vec_ok;     // outputs 16-byte aligned and win_w % 4 == 0 for every job
+    int32_t        vec_ok;     // outputs 16-byte aligned and win_w % 4 == 0 for every job, no canvas
     int32_t        lds_bytes;
     int32_t        has_hue;    // some job of the launch shifts hue (HSV tables in LDS)
     int32_t        partial_stride; // (tile, wave) entries per contrast slot in `partials`
     int32_t        threads;    // workgroup size (kBlockMin..kBlockMax, a multiple of 64)
-    int32_t        has_rtab;   // LDS holds a per-record table (contrast -> lighting -> standardize)
+    int32_t        has_rtab;   // LDS holds a per-record table (contrast -> lighting -> standardize), f32 also
+                               // for float16 / bfloat16 outputs (converted at the store)
     int32_t        u8_map;     // uint8 stores go through the LUT (fixed_aspect_ratio's uint8 standardize)
     int32_t        has_mean;   // double output: standardize with smean / sinv (by SOURCE channel)
     uint32_t*      tail_ctr;   // non-null: the partial last round of tiles is handed out by this counter

@@ -609,6 +609,37 @@ __device__ __forceinline__ void store_f32x4(__amdgpu_buffer_rsrc_t r, int off, f
     __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, kStoreAux);
 }
 
+// float -> the 16-bit pattern of a float16 / bfloat16 output element: one IEEE round to nearest even
+// (v_cvt_f16_f32 / v_cvt_pk_bf16_f32: subnormals, +-inf past float16's range, signed zeros kept)
+__device__ __forceinline__ uint32_t h16_bits(float x, bool bf16)
+{
+    if (bf16) {
+        const __bf16 h = (__bf16)x;
+        return __builtin_bit_cast(uint16_t, h);
+    }
+    const _Float16 h = (_Float16)x;
+    return __builtin_bit_cast(uint16_t, h);
+}
+// Four consecutive float16 / bfloat16 elements of a plane row as one 8-byte store (store_f32x4's policy)
+__device__ __forceinline__ void store_h16x4(__amdgpu_buffer_rsrc_t r, int off, bool bf16, float a, float b, float c,
+                                            float d)
+{
+    // two elements per conversion (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32: the same rounding as the scalar casts)
+    typedef float    f32x2_t __attribute__((ext_vector_type(2)));
+    typedef __bf16   bf16x2_t __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+    const f32x2_t lo = {a, b}, hi = {c, d};
+    u32x2         v;
+    if (bf16) {
+        v = (u32x2){__builtin_bit_cast(uint32_t, __builtin_convertvector(lo, bf16x2_t)),
+                    __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, bf16x2_t))};
+    } else {
+        v = (u32x2){__builtin_bit_cast(uint32_t, __builtin_convertvector(lo, f16x2_t)),
+                    __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, f16x2_t))};
+    }
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, kStoreAux);
+}
+
 // One output pixel of the resize: 3 channels from the staged source (LDS).
 // ytr = (row-0, row-1 LDS byte addresses in the staged band, b0, b1); col = byte offset of the
 // first tap's column; wx = a0 | a1 << 16.  SCALED results are 4x the pixel value plus 0..3: the

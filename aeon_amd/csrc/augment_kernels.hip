@@ -22,7 +22,9 @@
 
 namespace aeon_hip {
 
-enum OutForm : int { OF_F32_CHW_VEC = 0, OF_GENERIC = 1 };
+// OF_H16_CHW_VEC: float16 / bfloat16 CHW planes under OF_F32_CHW_VEC's conditions (the two types share
+// the form: a wave-uniform branch at the conversion)
+enum OutForm : int { OF_F32_CHW_VEC = 0, OF_GENERIC = 1, OF_H16_CHW_VEC = 2 };
 
 #ifndef AEON_HIP_INFO_JOBS // 1: a tile's geometry derived from the job's hot half in SGPRs (0: per-field LDS reads)
 #define AEON_HIP_INFO_JOBS 1
@@ -44,7 +46,8 @@ enum OutForm : int { OF_F32_CHW_VEC = 0, OF_GENERIC = 1 };
 // saturation + hue into an HWC uint8 intermediate + exact per-(tile, wave) channel sums), KM_RAW
 // (resize only, HWC uint8: the pre-passes).  RM: ResizeMode of every job in the launch.  PHOTO:
 // the launch's jobs carry photometric work.  OF: output form (OF_F32_CHW_VEC = float32 CHW planes,
-// win_w % 4 == 0, 16-byte aligned items: the ImageNet configuration).  TAIL: some LINEAR job of the
+// win_w % 4 == 0, 16-byte aligned items: the ImageNet configuration; OF_H16_CHW_VEC = the same planes as
+// float16 / bfloat16, one 8-byte store per lane and plane row).  TAIL: some LINEAR job of the
 // launch has OpenCV scalar-tail columns (3*dst_w not covered by the SIMD loops).
 
 
@@ -271,7 +274,11 @@ struct Bands {
         int      bs_kind = 0;
         if (PHOTO && (photo & PHOTO_BS)) bs_kind = SP ? (int)BS_FIXPT : JF(J, bs_kind), bsr = bs_regs(J);
 
-        const int  elem  = KM != KM_FINAL ? 1 : out_elem_bytes(a.out_dtype);
+        // (OF_F32_CHW_VEC keeps the size expression it was compiled with: its code does not change)
+        const int  elem  = KM != KM_FINAL          ? 1
+                           : OF == OF_H16_CHW_VEC ? 2
+                           : OF == OF_F32_CHW_VEC ? cv_elem_bytes(a.out_dtype)
+                                                  : out_elem_bytes(a.out_dtype);
         const int  plane = win_w * JF(J, win_h);
         const int  obytes = (KM == KM_FINAL ? JF(J, out_plane) : plane) * cn * elem;
         const auto orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)JF(J, out_ptr), (short)0, obytes, 0x00020000);
@@ -453,6 +460,23 @@ struct Bands {
                     }
                     continue;
                 }
+                if (OF == OF_H16_CHW_VEC) {
+                    // the f32 LUT / record-table values rounded once to the 16-bit type, pairwise packed
+                    const int  idx  = y * win_w + ox0;
+#ifdef AEON_HIP_EXP_H16_BF16 // development: bfloat16 only, no branch (what a form per type would run)
+                    const bool bf16 = true;
+#else
+                    const bool bf16 = a.out_dtype == OUT_BF16;
+#endif
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        const int oc = bgr ? 2 - c : c;
+                        store_h16x4(orsrc, (oc * plane + idx) * 2, bf16, lut_of(c, val[0][c]), lut_of(c, val[1][c]),
+                                    lut_of(c, val[2][c]), lut_of(c, val[3][c]));
+                        __builtin_amdgcn_sched_barrier(0); // (as OF_F32_CHW_VEC: one channel's reads in flight)
+                    }
+                    continue;
+                }
                 if (a.out_dtype == OUT_U8 && (a.channel_major || cn == 1) && nk == 4) {
                     // uint8 planes (pixel masks, uint8 images): a lane's 4 consecutive output
                     // bytes of a plane as one dword store when the 4-byte group is aligned
@@ -511,6 +535,11 @@ struct Bands {
                         case OUT_S32:
                             __builtin_amdgcn_raw_buffer_store_b32((uint32_t)v, orsrc, i * 4, 0, kStoreAux);
                             break;
+                        case OUT_F16:
+                        case OUT_BF16:
+                            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)h16_bits(lut_of(c, val[k][c]), a.out_dtype == OUT_BF16),
+                                                                  orsrc, i * 2, 0, kStoreAux);
+                            break;
                         default:
                             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)u8_out(c, val[k][c]), orsrc, i, 0, kStoreAux);
                         }
@@ -531,7 +560,8 @@ struct Bands {
         // set of nrows / nph rows per lane): 3 per row for float32 planes, 1 (a 12-byte group)
         // for the HWC uint8 intermediates; otherwise 0 (the caller then drains everything)
         const bool regular = ncg == gpr && nt % ncg == 0 && (win_w & 3) == 0 && nrows % nph == 0;
-        const int  per_row = (KM == KM_FINAL && OF == OF_F32_CHW_VEC) ? 3 : ((KM != KM_FINAL && cn == 3) ? 1 : 0);
+        const int  per_row = (KM == KM_FINAL && (OF == OF_F32_CHW_VEC || OF == OF_H16_CHW_VEC)) ? 3
+                                                                                              : ((KM != KM_FINAL && cn == 3) ? 1 : 0);
         return regular ? per_row * (nrows / nph) : 0;
     }
 };
@@ -704,7 +734,8 @@ void augment_tiles(LaunchArgs a)
 #ifndef AEON_HIP_LUT_DMA
 #define AEON_HIP_LUT_DMA 1
 #endif
-    if (KM == KM_FINAL && (a.out_dtype == OUT_F32 || a.u8_map)) {
+    // (the float16 / bfloat16 stores read the f32 LUT too: never under OF_F32_CHW_VEC, whose test stays as it was)
+    if (KM == KM_FINAL && (a.out_dtype == OUT_F32 || a.u8_map || (OF != OF_F32_CHW_VEC && out_is_half(a.out_dtype)))) {
         if (AEON_HIP_LUT_DMA) {
             // by LDS-DMA, 256 bytes per wave instruction: no VGPR round trip and no wait here, so the
             // loads are in flight together with the first jobs' fetch (one wait for both, below)
@@ -892,6 +923,9 @@ KernelFn pick_form(bool photo, int of, bool masks)
             if (of == OF_F32_CHW_VEC)
                 return photo ? augment_tiles<KM, RM, true, OF_F32_CHW_VEC, TAIL, true>
                              : augment_tiles<KM, RM, false, OF_F32_CHW_VEC, TAIL, true>;
+            if (of == OF_H16_CHW_VEC)
+                return photo ? augment_tiles<KM, RM, true, OF_H16_CHW_VEC, TAIL, true>
+                             : augment_tiles<KM, RM, false, OF_H16_CHW_VEC, TAIL, true>;
             return photo ? augment_tiles<KM, RM, true, OF_GENERIC, TAIL, true> : augment_tiles<KM, RM, false, OF_GENERIC, TAIL, true>;
         }
     }
@@ -899,12 +933,18 @@ KernelFn pick_form(bool photo, int of, bool masks)
         // the planner splits 2x-area records with photometric stages into a resize-only pre-pass
         // and a copy pass, so these forms are never instantiated
         if (photo) return nullptr;
+        if constexpr (KM == KM_FINAL)
+            if (of == OF_H16_CHW_VEC) return augment_tiles<KM, RM, false, OF_H16_CHW_VEC, false>;
         return of == OF_F32_CHW_VEC ? augment_tiles<KM, RM, false, OF_F32_CHW_VEC, false>
                                     : augment_tiles<KM, RM, false, OF_GENERIC, false>;
     } else {
         if (of == OF_F32_CHW_VEC)
             return photo ? augment_tiles<KM, RM, true, OF_F32_CHW_VEC, TAIL>
                          : augment_tiles<KM, RM, false, OF_F32_CHW_VEC, TAIL>;
+        if constexpr (KM == KM_FINAL) // (the intermediates of the other modes are uint8)
+            if (of == OF_H16_CHW_VEC)
+                return photo ? augment_tiles<KM, RM, true, OF_H16_CHW_VEC, TAIL>
+                             : augment_tiles<KM, RM, false, OF_H16_CHW_VEC, TAIL>;
         return photo ? augment_tiles<KM, RM, true, OF_GENERIC, TAIL> : augment_tiles<KM, RM, false, OF_GENERIC, TAIL>;
     }
 }
@@ -929,7 +969,11 @@ KernelFn pick_kernel(int km, int rm, bool tail, bool photo, int of, bool masks =
     return pick_rm<KM_RAW>(rm, tail, false, OF_GENERIC, false);
 }
 
-int out_form(const LaunchArgs& a) { return (a.out_dtype == OUT_F32 && a.channel_major && a.vec_ok) ? OF_F32_CHW_VEC : OF_GENERIC; }
+int out_form(const LaunchArgs& a)
+{
+    if (!a.channel_major || !a.vec_ok) return OF_GENERIC;
+    return a.out_dtype == OUT_F32 ? OF_F32_CHW_VEC : out_is_half(a.out_dtype) ? OF_H16_CHW_VEC : OF_GENERIC;
+}
 
 // start/stop (optional): events the dispatch itself stamps when the kernel starts and ends
 // (hipExtLaunchKernel), i.e. the kernel's own duration -- the same interval rocprofv3 reports --
@@ -966,8 +1010,8 @@ hipError_t set_kernel_lds_limit(int bytes)
     for (int km = 0; km < 3; km++)
         for (int rm = 0; rm < 4; rm++)
             for (int ph = 0; ph < 4; ph++)
-                for (int of = 0; of < 4; of++) {
-                    const KernelFn fn = pick_kernel(km, rm, (ph & 2) != 0, (ph & 1) != 0, of & 1, of >= 2);
+                for (int of = 0; of < 6; of++) { // every output form, without and with the mask blocks
+                    const KernelFn fn = pick_kernel(km, rm, (ph & 2) != 0, (ph & 1) != 0, of % 3, of >= 3);
                     if (!fn) continue;
                     hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
                     if (e != hipSuccess) return e;

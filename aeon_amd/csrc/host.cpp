@@ -123,7 +123,11 @@ size_t shape_type::byte_size() const
 }
 
 // ---- image::config (etl_image.cpp:25-65) ------------------------------------------------------
-image_config::image_config(const Json& js)
+// half: the config of an "image" element, which also takes "float16" / "bfloat16" (AEON_DTYPE_F16 / BF16:
+// the float output rounded once) when it says "extended_output_type": true -- without the key every config is
+// valid or invalid exactly as aeon's typemap makes it; every other user of the struct keeps aeon's typemap
+// and does not know the key.
+image_config::image_config(const Json& js, bool half)
 {
     if (js.is_null()) throw std::runtime_error("missing image config in json config");
     if (!js.has("height")) invalid("Required Argument: 'height' not set");
@@ -136,15 +140,29 @@ image_config::image_config(const Json& js)
     get_num(js, "channels", channels);
     if (!(channels == 1 || channels == 3)) invalid("value for 'channels' out of range");
     get_str(js, "output_type", output_type_name);
-    if (!output_type::is_valid_type(output_type_name)) invalid("value for 'output_type' out of range");
-    verify_config("image", {"type", "height", "width", "name", "bgr_to_rgb", "channel_major", "channels",
-                            "output_type"},
-                  js);
+    bool extended = false;
+    if (half) get_bool(js, "extended_output_type", extended);
+    const bool half_type = extended && (output_type_name == "float16" || output_type_name == "bfloat16");
+    if (!half_type && !output_type::is_valid_type(output_type_name)) invalid("value for 'output_type' out of range");
+    if (half)
+        verify_config("image", {"type", "height", "width", "name", "bgr_to_rgb", "channel_major", "channels",
+                                "output_type", "extended_output_type"},
+                      js);
+    else
+        verify_config("image", {"type", "height", "width", "name", "bgr_to_rgb", "channel_major", "channels",
+                                "output_type"},
+                      js);
     if (js.at("height").number() <= 0) invalid("invalid height");
     if (js.at("width").number() <= 0) invalid("invalid width");
     if (bgr_to_rgb && channels != 3)
         invalid("invalid config: bgr_to_rgb can be 'true' only for channels set to '3'");
-    shape.otype = output_type(output_type_name);
+    if (half_type) {
+        shape.otype.name  = output_type_name;
+        shape.otype.size  = 2;
+        shape.otype.dtype = output_type_name == "float16" ? AEON_DTYPE_F16 : AEON_DTYPE_BF16;
+    } else {
+        shape.otype = output_type(output_type_name);
+    }
     if (channel_major) {
         shape.shape = {channels, height, width};
         shape.names = {"channels", "height", "width"};
@@ -187,7 +205,7 @@ std::string empty_element(const char* what, int idx)
 class pixel_provider : public etl_provider {
 public:
     pixel_provider(const Json& js, const Json& aug, bool mask)
-        : m_cfg(js), m_factory(aug), m_mask(mask), m_name(create_name(m_cfg.name, mask ? "pixelmask" : "image"))
+        : m_cfg(js, !mask), m_factory(aug), m_mask(mask), m_name(create_name(m_cfg.name, mask ? "pixelmask" : "image"))
     {
         m_out.dtype         = m_cfg.shape.otype.dtype;
         m_out.channels      = (int)m_cfg.channels;
@@ -196,11 +214,15 @@ public:
         m_out.fixed_aspect_ratio = m_factory.fixed_aspect_ratio;
         m_out.canvas_w = (int)m_cfg.width, m_out.canvas_h = (int)m_cfg.height;
         if (mask) return;
+        // (aeon's fixed_aspect_ratio loader views the item as a uint8 canvas: no meaning for a 16-bit float)
+        if (m_out.fixed_aspect_ratio && (m_out.dtype == AEON_DTYPE_F16 || m_out.dtype == AEON_DTYPE_BF16))
+            throw unsupported_error("image: 'output_type' " + m_cfg.output_type_name + " with fixed_aspect_ratio");
         // image::loader ctor (etl_image.cpp:204-244)
         const auto& mean = m_factory.mean;
         const auto& std_ = m_factory.stddev;
         if (!mean.empty() || !std_.empty()) {
-            if (!(m_cfg.output_type_name == "float" || m_cfg.output_type_name == "double"))
+            if (!(m_cfg.output_type_name == "float" || m_cfg.output_type_name == "double" ||
+                  m_cfg.output_type_name == "float16" || m_cfg.output_type_name == "bfloat16"))
                 invalid("Standardization (mean, stddev) is supported only for float or double 'output_type'.");
             if (mean.size() != m_cfg.channels || std_.size() != m_cfg.channels)
                 invalid("Size of 'mean' and 'stddev' must be equal to number of channels or empty.");

@@ -66,7 +66,7 @@ struct image_config {
     uint32_t    channels = 3;
     std::string name;
     shape_type  shape;
-    explicit image_config(const Json& js);
+    explicit image_config(const Json& js, bool half = false); // half: "float16" / "bfloat16" with "extended_output_type": true
 };
 
 // An element of a record: an encoded JPEG file (size > 0; width/height/channels filled in from

@@ -709,7 +709,7 @@ void CallPlan::finalize(const aeon_out_desc& o, bool u8_map, const SplitKnobs& k
         if (P.jobs.empty()) continue;
         const bool last = g >= kMain;
         P.vec_ok = vec_ok;
-        P.rtab   = last && P.photo && o.dtype == AEON_DTYPE_F32;
+        P.rtab   = last && P.photo && (o.dtype == AEON_DTYPE_F32 || out_is_half(o.dtype)); // (an f32 table either way)
         // final non-photometric INTER_LINEAR float32 CHW launches (C5's images): augment_split
         P.split = last && knobs.on && !P.photo && P.rm == RESIZE_LINEAR && o.dtype == AEON_DTYPE_F32 && o.channel_major &&
                   P.vec_ok && !u8_map && !o.fixed_aspect_ratio && plan_split(knobs, P.jobs, P, P.sa);

@@ -61,7 +61,7 @@ struct LaunchPlan {
     int                 lds = 0, threads = kBlockMax;
     bool                vec_ok = true;
     bool                has_hue = false, has_contrast = false;
-    bool                rtab    = false; // final f32 launch with contrast / lighting: per-record LDS table
+    bool                rtab    = false; // final f32 / f16 / bf16 launch with contrast / lighting: per-record LDS table (f32)
     bool                split   = false; // launched as augment_split (shape set by plan_split)
     bool                out_scratch = false; // the jobs write scratch (out_ptr an offset until relocated)
     SplitArgs           sa{};

@@ -725,7 +725,7 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
     P.tail   = (key & 2) != 0;
     P.photo  = (key & 1) != 0;
     P.vec_ok = vec_ok;
-    P.rtab   = P.photo && o.dtype == AEON_DTYPE_F32;
+    P.rtab   = P.photo && (o.dtype == AEON_DTYPE_F32 || out_is_half(o.dtype));
     // non-photometric INTER_LINEAR into float32 CHW planes, one window width: augment_split (staging on
     // helper waves, split_kernels.hip); else augment_tiles' shape
     SplitArgs  sa{};
@@ -975,6 +975,11 @@ void launch_generic(aeon_hip_ctx* ctx, const GrPlan& g, const uint8_t* table, co
     }
 }
 
+std::string half_refusal(int dtype, const char* what)
+{
+    return std::string(dtype == AEON_DTYPE_BF16 ? "bfloat16" : "float16") + " output is implemented for images only, not for " + what;
+}
+
 int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* src_base,
               const aeon_aug_params* params, const aeon_out_desc* out, void* out_dev, void* stream_,
               bool is_mask, const MaskSet* ms = nullptr, const ItemMap* im = nullptr)
@@ -984,8 +989,13 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     if (n == 0) return 0;
     if (n > 65535) fail(AEON_HIP_EINVAL, "at most 65535 records per call");
     const aeon_out_desc& od = *out; // as declared; `o` below is what the kernels write (out_view)
-    if (od.dtype < AEON_DTYPE_U8 || od.dtype > AEON_DTYPE_F64) fail(AEON_HIP_EUNSUPPORTED, "unknown output dtype");
-    if (od.has_mean && od.dtype != AEON_DTYPE_F32 && od.dtype != AEON_DTYPE_F64)
+    if (od.dtype < AEON_DTYPE_U8 || od.dtype > AEON_DTYPE_BF16) fail(AEON_HIP_EUNSUPPORTED, "unknown output dtype");
+    const bool half = out_is_half(od.dtype);
+    // float16 / bfloat16 are image outputs of the tile kernel only: refused here, before any launch (the
+    // gather kernels' and the uint8 canvas view's stores know nothing of them)
+    if (half && is_mask) fail(AEON_HIP_EUNSUPPORTED, half_refusal(od.dtype, "pixel masks / depth maps"));
+    if (half && od.fixed_aspect_ratio) fail(AEON_HIP_EUNSUPPORTED, half_refusal(od.dtype, "fixed_aspect_ratio"));
+    if (od.has_mean && od.dtype != AEON_DTYPE_F32 && od.dtype != AEON_DTYPE_F64 && !half)
         fail(AEON_HIP_EINVAL,
              "Standardization (mean, stddev) is supported only for float or double 'output_type'.");
     const OutView        ov = out_view(od);
@@ -1654,6 +1664,8 @@ int aeon_hip_augment_pair_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* d
         if (!ctx || n < 0 || (n > 0 && (!mask_descs || !mask_src_base || !mask_out || !mask_out_dev)))
             fail(AEON_HIP_EINVAL, "null argument");
         if (n == 0) return 0;
+        // (before the images' launches: a refused pair call writes nothing)
+        if (out_is_half(mask_out->dtype)) fail(AEON_HIP_EUNSUPPORTED, half_refusal(mask_out->dtype, "pixel masks / depth maps"));
         // one launch when every mask is an 8-bit single-channel record without rotation into plain
         // uint8 items (the gather pass the launch's workgroups take after the image tiles); otherwise
         // exactly aeon_hip_augment_batch then aeon_hip_mask_batch

@@ -445,6 +445,9 @@ int aeon_hip_stager_create(aeon_hip_ctx* ctx, int kind, const aeon_out_desc* out
         if (batch_size <= 0) fail(AEON_HIP_EINVAL, "batch_size must be > 0");
         const int base = kind & ~AEON_STAGER_DEVICE_OUT;
         if (base != AEON_STAGER_IMAGE && base != AEON_STAGER_MASK) fail(AEON_HIP_EINVAL, "unknown stager kind");
+        if (base == AEON_STAGER_MASK && (out->dtype == AEON_DTYPE_F16 || out->dtype == AEON_DTYPE_BF16))
+            fail(AEON_HIP_EUNSUPPORTED, std::string(out->dtype == AEON_DTYPE_BF16 ? "bfloat16" : "float16") +
+                                            " output is implemented for images only, not for pixel masks / depth maps");
         if (out->item_stride == 0) fail(AEON_HIP_EINVAL, "out->item_stride is 0");
         auto s   = std::make_unique<aeon_hip_stager>();
         s->ctx   = ctx;

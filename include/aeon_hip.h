@@ -40,6 +40,10 @@ extern "C" {
 #define AEON_DTYPE_U16 4 /* uint16_t (CV_16U) */
 #define AEON_DTYPE_S32 5 /* int32_t, uint32_t (CV_32S) */
 #define AEON_DTYPE_F64 6 /* double   (CV_64F) */
+/* image outputs only, beyond aeon's output_type list: the float output rounded once (to nearest even,
+ * IEEE: subnormals, +-inf past float16's 65504, signed zeros, no clamping) to a 16-bit type */
+#define AEON_DTYPE_F16 7  /* float16:  IEEE binary16 */
+#define AEON_DTYPE_BF16 8 /* bfloat16 */
 
 /* resize interpolation (image::config "interpolation_method") */
 #define AEON_INTERP_LINEAR 0
@@ -90,11 +94,12 @@ typedef struct aeon_aug_params {
 /* image::loader configuration (src/etl_image.cpp:204-244) plus the batch-buffer geometry of
  * fixed_buffer_map (src/buffer_batch.hpp:154-188). */
 typedef struct aeon_out_desc {
-    int32_t  dtype;         /* AEON_DTYPE_* */
+    int32_t  dtype;         /* AEON_DTYPE_*; F16 / BF16 for images only (no mask, depth map or
+                             * fixed_aspect_ratio output: AEON_HIP_EUNSUPPORTED) */
     int32_t  channels;      /* 1 or 3 */
     int32_t  channel_major; /* 1: CHW planes, 0: HWC */
     int32_t  bgr_to_rgb;    /* swap channels 0 and 2 (3-channel only) */
-    int32_t  has_mean;      /* standardize with mean/stddev (float / double output only) */
+    int32_t  has_mean;      /* standardize with mean/stddev (float / double / float16 / bfloat16 output only) */
     int32_t  fixed_aspect_ratio; /* image::loader m_fixed_aspect_ratio (etl_image.cpp:258-306):
                                   * each item (its whole dtype-sized byte size) is zeroed and the
                                   * record is written at the top-left of a canvas_w x canvas_h

@@ -6,7 +6,9 @@ mkdir -p "$R/gpurun_out/pmc"
 export TMPDIR=/tmp
 cd /tmp
 CFG=${1:-C2}
-if [ "$CFG" = C5 ]; then PROG=("$R/tools/c5_run.py" 20); else PROG=("$R/tools/kbench.py" $CFG ${KNOBS:-default}); fi
+if [ "$CFG" = C5 ]; then PROG=("$R/tools/c5_run.py" 20);
+elif [ "$CFG" = half ]; then PROG=("$R/tools/half_probe.py" --steps 40); # C2 with f32 / f16 / bf16 outputs (two kernel forms)
+else PROG=("$R/tools/kbench.py" $CFG ${KNOBS:-default}); fi
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" \
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS" \
