@@ -78,8 +78,7 @@ __device__ __forceinline__ T job_get(const JobRef& J, int off)
 }
 // The hot half of a job (kJobHotBytes: every field a non-photometric tile reads) loaded from its LDS
 // copy at once -- eight 16-byte LDS reads, one wait -- into scalar registers: JF on it is a register
-// read, where JF on a JobRef is an LDS round trip per field (each one waited for before the next; in
-// augment_split's per-tile staging those waits were most of its 1.8 us).
+// read, where JF on a JobRef is an LDS round trip per field (each one waited for before the next).
 struct JobS {
     uint32_t w[kJobHotBytes / 4];
 };
@@ -279,14 +278,10 @@ __device__ __forceinline__ void hue_apply_n(STAB sdv, TAB hdiv, WTAB htab, int (
 #pragma unroll
     for (int k = 0; k < N; k++) {
         const float vf = (float)v[k] * (1.f / 255);
-#if defined(AEON_HIP_EXP_HUE_NOTAIL) // development ablation: no HSV2RGB float chain (wrong values)
-        px[k][0] = (int)w[k][0] + v[k], px[k][1] = (int)w[k][1] + (int)sf[k], px[k][2] = (int)w[k][2];
-#else
         // v, s in [0, 1] and w in [0, 1]: every product is in [0, 255], no saturation needed
         px[k][0] = u8rnd(vf * (1.f - sf[k] * w[k][0]) * 255.f);
         px[k][1] = u8rnd(vf * (1.f - sf[k] * w[k][1]) * 255.f);
         px[k][2] = u8rnd(vf * (1.f - sf[k] * w[k][2]) * 255.f);
-#endif
     }
 }
 
@@ -338,18 +333,11 @@ __device__ __forceinline__ void hue_pack_n(STAB sdv, TAB hdiv, ETAB htab8, const
 #pragma unroll
     for (int k = 0; k < N; k++) {
         const float vf = __uint_as_float((uint32_t)sv[k].y);
-#ifndef AEON_HIP_HUE_PK_F32
-#define AEON_HIP_HUE_PK_F32 1
-#endif
-#if AEON_HIP_HUE_PK_F32 // both chains as packed f32 (s*1 == s exactly; separate IEEE mul/add, no FMA)
+        // both chains as packed f32 (s*1 == s exactly; separate IEEE mul/add, no FMA)
         typedef float f32x2 __attribute__((ext_vector_type(2)));
         f32x2       t  = (f32x2){sf[k], sf[k]} * (f32x2){1.f, __uint_as_float((uint32_t)e[k].x)};
         t              = ((1.f - t) * vf) * 255.f;
         const float c1 = t.x, cw = t.y;
-#else
-        const float c1 = vf * (1.f - sf[k]) * 255.f;
-        const float cw = vf * (1.f - sf[k] * __uint_as_float((uint32_t)e[k].x)) * 255.f;
-#endif
         uint32_t    q  = __builtin_amdgcn_cvt_pk_u8_f32(c1, 1u, (uint32_t)v[k]);
         q              = __builtin_amdgcn_cvt_pk_u8_f32(cw, 2u, q);
         pk[K0 + k]     = __builtin_amdgcn_perm(0u, q, (uint32_t)e[k].y);
@@ -715,10 +703,6 @@ __device__ __forceinline__ void resize4_linear(i32x4 ytr, const int (&col)[4], c
         }
     }
 }
-__device__ __forceinline__ void resize4_linear_scaled(i32x4 ytr, const int (&col)[4], const uint32_t (&wx)[4], int (&s)[4][3])
-{
-    resize4_linear<true>(ytr, col, wx, s);
-}
 
 // Elements of OpenCV's scalar row tail (e >= xv) use FixedPtCast<int, uchar, 22> instead.
 template <bool SCALED>
@@ -736,10 +720,6 @@ __device__ __forceinline__ void tail_fix(i32x4 ytr, int col, uint32_t wx, int e0
 }
 
 // standardize LUT (LDS offset 0) entry for source channel c at scaled value s
-#ifdef AEON_HIP_EXP_NOLUT // development ablation: no LUT reads (wrong values)
-__device__ __forceinline__ float lut_at(int c, int s) { return (float)(s + c); }
-#else
 __device__ __forceinline__ float lut_at(int c, int s) { return lds_ldf(c * 1024 + (s & ~3)); }
-#endif
 
 } // namespace aeon_hip

@@ -26,10 +26,6 @@ namespace aeon_hip {
 // the form: a wave-uniform branch at the conversion)
 enum OutForm : int { OF_F32_CHW_VEC = 0, OF_GENERIC = 1, OF_H16_CHW_VEC = 2 };
 
-#ifndef AEON_HIP_INFO_JOBS // 1: a tile's geometry derived from the job's hot half in SGPRs (0: per-field LDS reads)
-#define AEON_HIP_INFO_JOBS 1
-#endif
-
 // ---- the band kernel -----------------------------------------------------------------------
 // A launch covers n_jobs x max_tiles tiles: tile t = band (t % max_tiles) of job (t / max_tiles),
 // a band being TR consecutive output rows of the job's window.  Workgroups are persistent (the
@@ -78,11 +74,7 @@ struct Bands {
         // (the job's hot half read at once into scalar registers: the derivation below is on the critical
         // path of the first tile and of every dynamic-tail tile, and each field's LDS round trip was
         // waited for before the next)
-#if AEON_HIP_INFO_JOBS
         const JobS J = job_load(jl);
-#else
-        const JobRef J = jref(f);
-#endif
         if (f.band >= JF(J, tiles)) return f;
         if (KM == KM_STATS && JF(J, stats_slot) < 0) return f;
         const int TR = a.rows_per_tile;
@@ -326,11 +318,7 @@ struct Bands {
                 int         val[4][3];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-#ifdef AEON_HIP_EXP_NORESIZE // development ablation: no gathers / resize math (wrong values)
-                    val[k][0] = ytr.x + col[k], val[k][1] = ytr.y + col[k], val[k][2] = ytr.z + (int)wxk[k];
-#else
                     resize_px<RM, SC>(ytr, col[k], wxk[k], val[k]);
-#endif
                 }
                 if (TAIL && RM == RESIZE_LINEAR && tmask) {
 #pragma unroll
@@ -347,12 +335,8 @@ struct Bands {
 #pragma unroll
                     for (int k = 0; k < 4; k++) bs_apply(BS_FIXPT, bsr, val[k][0], val[k][1], val[k][2]);
                     uint32_t pk[4];
-#if AEON_HIP_HUE_PACK4
-                    hue_pack_n<4, 0>(sdv, hdiv, htab8, val, pk);
-#else
                     hue_pack_n<2, 0>(sdv, hdiv, htab8, val, pk);
                     hue_pack_n<2, 2>(sdv, hdiv, htab8, val, pk);
-#endif
                     // the 12-byte HWC group B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3, and the exact channel
                     // sums as byte picks of those three words (9 v_dot4 instead of 12 on the pixels)
                     const u32x3 q = {__builtin_amdgcn_perm(pk[1], pk[0], 0x04020100u),
@@ -371,17 +355,11 @@ struct Bands {
                     continue;
                 }
                 if (PHOTO && photo) {
-#ifndef AEON_HIP_EXP_NOBS // development ablation: no brightness/saturation (wrong values)
                     if (photo & PHOTO_BS) {
 #pragma unroll
                         for (int k = 0; k < 4; k++) bs_apply(bs_kind, bsr, val[k][0], val[k][1], val[k][2]);
                     }
-#endif
-#ifdef AEON_HIP_EXP_NOHUE // development ablation: no hue (wrong values)
-                    if (false) {
-#else
-                    if (photo & PHOTO_HUE) {
-#endif // two pixels at a time: four cost 14 VGPRs (a wave per SIMD)
+                    if (photo & PHOTO_HUE) { // two pixels at a time: four cost 14 VGPRs (a wave per SIMD)
                         hue_apply_n<kHueBatch, 0>(sdv, hdiv, htab, val);
                         if (kHueBatch < 4) hue_apply_n<kHueBatch, kHueBatch % 4>(sdv, hdiv, htab, val);
                         if (kHueBatch == 1) {
@@ -449,9 +427,6 @@ struct Bands {
 #pragma unroll
                     for (int c = 0; c < 3; c++) {
                         const int oc = bgr ? 2 - c : c;
-#ifdef AEON_HIP_EXP_NOSTORE // development ablation: no output stores
-                        if (lut_of(c, val[0][c]) == 1234.5f)
-#endif
                         store_f32x4(orsrc, (oc * plane + idx) * 4, lut_of(c, val[0][c]), lut_of(c, val[1][c]),
                                     lut_of(c, val[2][c]), lut_of(c, val[3][c]));
                         // one channel's four LUT reads in flight at a time: hoisting all twelve
@@ -463,11 +438,7 @@ struct Bands {
                 if (OF == OF_H16_CHW_VEC) {
                     // the f32 LUT / record-table values rounded once to the 16-bit type, pairwise packed
                     const int  idx  = y * win_w + ox0;
-#ifdef AEON_HIP_EXP_H16_BF16 // development: bfloat16 only, no branch (what a form per type would run)
-                    const bool bf16 = true;
-#else
                     const bool bf16 = a.out_dtype == OUT_BF16;
-#endif
 #pragma unroll
                     for (int c = 0; c < 3; c++) {
                         const int oc = bgr ? 2 - c : c;
@@ -731,20 +702,12 @@ void augment_tiles(LaunchArgs a)
     const Bands<KM, RM, PHOTO, OF, TAIL> W{a, L, wave, nw};
 
     // per-launch tables
-#ifndef AEON_HIP_LUT_DMA
-#define AEON_HIP_LUT_DMA 1
-#endif
     // (the float16 / bfloat16 stores read the f32 LUT too: never under OF_F32_CHW_VEC, whose test stays as it was)
     if (KM == KM_FINAL && (a.out_dtype == OUT_F32 || a.u8_map || (OF != OF_F32_CHW_VEC && out_is_half(a.out_dtype)))) {
-        if (AEON_HIP_LUT_DMA) {
-            // by LDS-DMA, 256 bytes per wave instruction: no VGPR round trip and no wait here, so the
-            // loads are in flight together with the first jobs' fetch (one wait for both, below)
-            const auto rs = uniform_rsrc((const void*)a.lut, 3 * 256 * 4);
-            for (int i = wave; i < 12; i += nw) lds_dma<4>(rs, L.lut + i * 256, (uint32_t)((tid & 63) * 4 + i * 256));
-        } else {
-            const auto lut = lds_ptr<float>(L.lut);
-            for (int i = tid; i < 3 * 256; i += nt) lut[i] = a.lut[i];
-        }
+        // by LDS-DMA, 256 bytes per wave instruction: no VGPR round trip and no wait here, so the
+        // loads are in flight together with the first jobs' fetch (one wait for both, below)
+        const auto rs = uniform_rsrc((const void*)a.lut, 3 * 256 * 4);
+        for (int i = wave; i < 12; i += nw) lds_dma<4>(rs, L.lut + i * 256, (uint32_t)((tid & 63) * 4 + i * 256));
     }
     if (PHOTO && KM != KM_RAW && a.has_hue) {
         hsv_div_tables(L, a.hsv_tables);
@@ -807,13 +770,7 @@ void augment_tiles(LaunchArgs a)
     // The prologue waits for the first tile's job only: every workgroup fetches at once (768 x 128 B
     // over PCIe for C2), and the second job is not needed before the first tile's compute, so it is
     // fetched with the first tile's staging loads.
-#ifndef AEON_HIP_FETCH1
-#define AEON_HIP_FETCH1 1
-#endif
-    if (wave == 0) {
-        fetch_job(a, live ? t : -1, slot_of(0));
-        if (!AEON_HIP_FETCH1) fetch_job(a, live && t + G < t_dyn ? t + G : -1, slot_of(1));
-    }
+    if (wave == 0) fetch_job(a, live ? t : -1, slot_of(0));
     stamp(0, 10);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stamp(0, 11);
@@ -833,7 +790,7 @@ void augment_tiles(LaunchArgs a)
         const bool more2 = t + 2 * G < t_dyn; // ... and a static one after it
         stamp(it, 1);
         W.issue(f);
-        if (AEON_HIP_FETCH1 && it == 0 && wave == 0 && more) fetch_job(a, t + G, slot_of(js + 1));
+        if (it == 0 && wave == 0 && more) fetch_job(a, t + G, slot_of(js + 1));
         if (wave == 0 && more2) fetch_job(a, t + 2 * G, slot_of(js + 2));
         stamp(it, 2);
         const bool same = f.ok && f.job == prev_job; // the LDS tables still hold this record's

@@ -1021,9 +1021,7 @@ struct JpegState {
         std::vector<Arena> arenas;    // per pool worker, pinned: the H2D copies read them in place
     } sets[2];
     int         next = 0;
-    hipStream_t copy = nullptr; // the H2D of a call's staging, so that it overlaps the previous call's
-                                // kernels (AEON_HIP_JPEG_COPY_STREAM=0: on the call's stream)
-    bool        use_copy = true;
+    hipStream_t copy = nullptr; // the H2D of a call's staging, so that it overlaps the previous call's kernels
     bool       gpu_huff = true; // false: every file through the host entropy decoder
     int        huff_lanes = kHuffLanes; // jpeg_huff workgroup size (AEON_HIP_JPEG_HUFF_LANES=256 / 1024: A/B)
     std::mutex mu;
@@ -1053,7 +1051,6 @@ JpegState* jpeg_state_create(thread_pool* shared, bool gpu_huff)
 {
     auto* s = new JpegState();
     s->gpu_huff = gpu_huff;
-    if (const char* e = std::getenv("AEON_HIP_JPEG_COPY_STREAM")) s->use_copy = std::atoi(e) != 0;
     if (const char* e = std::getenv("AEON_HIP_JPEG_HUFF_LANES")) {
         const int l   = std::atoi(e);
         s->huff_lanes = l == 256 || l == 512 || l == 1024 ? l : kHuffLanes;
@@ -1295,15 +1292,12 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
                        "hipMemcpyAsync");
     };
     mark(4);
-    if (S->use_copy) { // (the set's previous kernels are done: st.done above)
-        if (!S->copy) hip_ok(hipStreamCreateWithFlags(&S->copy, hipStreamNonBlocking), "hipStreamCreate");
-        if (!st.copied) hip_ok(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming), "hipEventCreate");
-        h2d(S->copy);
-        hip_ok(hipEventRecord(st.copied, S->copy), "hipEventRecord");
-        hip_ok(hipStreamWaitEvent(stream, st.copied, 0), "hipStreamWaitEvent");
-    } else {
-        h2d(stream);
-    }
+    // on the copy stream (the set's previous kernels are done: st.done above)
+    if (!S->copy) hip_ok(hipStreamCreateWithFlags(&S->copy, hipStreamNonBlocking), "hipStreamCreate");
+    if (!st.copied) hip_ok(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming), "hipEventCreate");
+    h2d(S->copy);
+    hip_ok(hipEventRecord(st.copied, S->copy), "hipEventRecord");
+    hip_ok(hipStreamWaitEvent(stream, st.copied, 0), "hipStreamWaitEvent");
     if (n_gpu) hip_ok(hipMemsetAsync(st.work, 0, rec_bytes, stream), "hipMemsetAsync");
     if (start) hip_ok(hipEventRecord(start, stream), "hipEventRecord");
     if (n_gpu)

@@ -4,7 +4,6 @@
 #include "plan.hpp"
 
 #include <cfloat>
-#include <cstdlib>
 #include <string>
 
 #include "param_factory.hpp"
@@ -14,9 +13,6 @@ namespace aeon_hip {
 // launch-shape constants (compile-time overrides only for tuning builds, tools/build_variants.sh)
 #ifndef AEON_HIP_STAGE_BUDGET_KB
 #define AEON_HIP_STAGE_BUDGET_KB 48
-#endif
-#ifndef AEON_HIP_FIXED_THREADS
-#define AEON_HIP_FIXED_THREADS 0
 #endif
 constexpr int kStageBudget   = AEON_HIP_STAGE_BUDGET_KB * 1024; // preferred LDS bytes of the staging buffer
 constexpr int kStageBudgetHi = 140 * 1024;  // fallback for very wide crops
@@ -41,16 +37,13 @@ void LaunchPlan::shape(const std::vector<J_>& jobs)
     // contrast pass 2 (photometric over the u8 intermediate, no resize): full workgroups
     // beat the fewest-idle-lanes choice (C3: 140 vs 158 us at 512 vs 448 lanes)
     if (rm == RESIZE_COPY && photo) threads = kBlockMax;
-    if (AEON_HIP_FIXED_THREADS) threads = AEON_HIP_FIXED_THREADS;
     const int nph = threads / ncg;
     // one staging buffer and four rows per lane (a multiple of the row phases): the CU's other
     // workgroups cover a tile's staging latency.  Measured on C2/C3 against two buffers
     // (the next tile's loads in flight during the current tile's compute) at two rows per
     // lane: 42 vs 45 us (C2), 152/291 vs 186/370 us (C3 pass 2 / pass 1) -- the second
     // buffer costs occupancy and halves the rows per tile (rejected).
-    // (development: AEON_HIP_TILE_ROWS caps the rows per tile instead)
-    static const int tr_env = std::getenv("AEON_HIP_TILE_ROWS") ? std::atoi(std::getenv("AEON_HIP_TILE_ROWS")) : 0;
-    const int        tr_cap = std::min(64, std::max(1, tr_env > 0 ? tr_env : 4 * nph));
+    const int tr_cap = std::min(64, std::max(1, 4 * nph));
     int       budget = kStageBudget;
     bool hue = false, contrast = false;
     for (const J_& J : jobs) {
@@ -329,9 +322,8 @@ GrPlan::Sub GrPlan::shape(int f, int n) const
     }
     // resize_sep: bands of up to 32 rows x the window's width (at most 256 lanes of 4 bytes); resizeArea_
     // jobs as its INTER_AREA form, K = their most taps per destination index (floor(scale) + 2)
-    int               ka      = 0;
-    static const bool no_area = std::getenv("AEON_HIP_AREA_SEP") && std::atoi(std::getenv("AEON_HIP_AREA_SEP")) == 0;
-    if (jobs[f].method == GR_AREA && !no_area) { // (development: AEON_HIP_AREA_SEP=0, resize_generic)
+    int ka = 0;
+    if (jobs[f].method == GR_AREA) {
         double smax = 1;
         for (int i = f; i < f + n; i++) smax = std::max({smax, jobs[i].scale_x, jobs[i].scale_y});
         const int taps = (int)std::floor(smax) + 2;
@@ -342,10 +334,9 @@ GrPlan::Sub GrPlan::shape(int f, int n) const
     bool      one = sk != 0;
     for (int i = f; i < f + n; i++) one = one && jobs[i].method == jobs[f].method && jobs[i].cn == u.cn_max;
     if (one) {
-        static const int tr0 = std::getenv("AEON_HIP_SEP_TR") ? std::atoi(std::getenv("AEON_HIP_SEP_TR")) : 16;
         // a band's lanes (at most 256): 4 bytes of a u8 window row each, or 4 pixels of one channel of a
         // final_out job each -- cn * ceil(cw / 4) lanes, so 340 columns for 3 channels, not 341
-        int cw = std::min({ww, 1024 / u.cn_max, 4 * (256 / u.cn_max)}), tr = std::max(4, std::min(64, tr0));
+        int cw = std::min({ww, 1024 / u.cn_max, 4 * (256 / u.cn_max)}), tr = 16;
         // staged rows: whole 16-byte blocks (resize_sep), hence up to 30 bytes more per row, and 32
         // bytes of room for the replicated borders (resize_kernels.hip kSepPadL)
         auto sw = [&] { return (bytes_for(f, n, cw) + 30 + 15) / 16 * 16 + 32; };
@@ -399,13 +390,6 @@ void GrPlan::finalize()
                      (double)R.win_w * R.win_h * R.cn * (R.final_out ? 4 : 1);
         }
     }
-}
-
-// (development: AEON_HIP_IDENTITY_SEP=0 keeps identity resizes on the tile kernel)
-static bool no_identity_sep()
-{
-    static const bool v = std::getenv("AEON_HIP_IDENTITY_SEP") && std::atoi(std::getenv("AEON_HIP_IDENTITY_SEP")) == 0;
-    return v;
 }
 
 // A resize of the (cropped, padded) region of J's source to its window; the caller says where it writes.
@@ -548,7 +532,7 @@ void CallPlan::add(const aeon_img_desc& d, const void* src_base, const aeon_aug_
     // the call launches no tile kernel for its few uncropped records (an 8.5 us launch per C2:<method>
     // step: one tile's latency).
     if (gm < 0 && !is_mask && final_ok && J.crop_w == J.dst_w && J.crop_h == J.dst_h &&
-        (p.interp == AEON_INTERP_CUBIC || p.interp == AEON_INTERP_LANCZOS4 || p.interp == AEON_INTERP_AREA) && !no_identity_sep())
+        (p.interp == AEON_INTERP_CUBIC || p.interp == AEON_INTERP_LANCZOS4 || p.interp == AEON_INTERP_AREA))
         gm = p.interp == AEON_INTERP_CUBIC ? GR_CUBIC : p.interp == AEON_INTERP_LANCZOS4 ? GR_LANCZOS4 : GR_LINEAR_AREA;
     if (gm >= 0 && gm != GR_AREA_FAST && final_ok) {
         // no photometric stage and f32 output: the resize pass is the last one -- it flips,
@@ -615,48 +599,6 @@ double launch_bytes(const std::vector<J_>& jobs, int mode, size_t out_elem)
 template double launch_bytes(const std::vector<AugJob>&, int, size_t);
 template double launch_bytes(const std::vector<JobGeom>&, int, size_t);
 
-// augment_split's shape for a direct call's records (all 3-channel, INTER_LINEAR, one window width W,
-// W % 4 == 0): nwc compute waves of nph row phases x W/4 column groups plus k.helpers staging
-// waves in one workgroup of <= 1,024 lanes, rows_per_tile = nph * rpl, two staging buffers.  The LDS
-// request is held above half a CU's 160 KB so that the grid's n_cu workgroups land one per CU.  False:
-// no such shape (the caller keeps augment_tiles).
-template <typename J_>
-bool plan_split(const SplitKnobs& k, const std::vector<J_>& geo, LaunchPlan& P, SplitArgs& sa)
-{
-    if (geo.empty()) return false;
-    const int W = geo[0].win_w;
-    if (W <= 0 || (W & 3) != 0) return false;
-    for (const J_& g : geo)
-        if (g.cn != 3 || g.win_w != W || g.mode != RESIZE_LINEAR) return false;
-    const int gpr = W / 4, nh = k.helpers;
-    int       nph = 0, nwc = 0;
-    for (int p = 32; p >= 1; p--) {
-        const int w = (p * gpr + 63) / 64;
-        if (w + nh <= 16) {
-            nph = p, nwc = w;
-            break;
-        }
-    }
-    if (nph == 0) return false;
-    const int rpl = std::max(1, std::min(k.rpl, kSplitTRMax / nph));
-    const int tr  = nph * rpl;
-    long      by  = 0;
-    for (const J_& g : geo) by = std::max(by, stage_bytes_for(3, stage_rows_for(g, tr), stage_cols(g)));
-    by             = (by + 1023) / 1024 * 1024;
-    const int lds  = split_lds_layout(W, (int)by).total;
-    const int occ  = k.occ == 2 && !P.tail && lds <= kMaxLds / 2 ? 2 : 1; // (the TAIL form spills at 64 VGPRs)
-    if (lds > kMaxLds) return false;
-    P.tr          = tr;
-    P.stage_bytes = (int)by;
-    P.max_win_w   = W;
-    P.threads     = (nwc + nh) * 64;
-    P.lds         = occ == 2 ? lds : std::max(lds, kMaxLds / 2 + 1024);
-    sa.nwc = nwc, sa.nph = nph, sa.rpl = rpl, sa.win_w = W, sa.occ = occ;
-    return true;
-}
-template bool plan_split(const SplitKnobs&, const std::vector<AugJob>&, LaunchPlan&, SplitArgs&);
-template bool plan_split(const SplitKnobs&, const std::vector<JobGeom>&, LaunchPlan&, SplitArgs&);
-
 CallPlan::CallPlan()
 {
     for (int g = 0; g < kGroups; g++) {
@@ -685,7 +627,7 @@ void CallPlan::add_records(int n, const aeon_img_desc* descs, const void* src_ba
         add_gather(ms->descs[i], ms->src_base, params[i], ms->out, (uint64_t)ms->out_dev + (uint64_t)i * ms->out.item_stride, true);
 }
 
-void CallPlan::finalize(const aeon_out_desc& o, bool u8_map, const SplitKnobs& knobs)
+void CallPlan::finalize(const aeon_out_desc& o)
 {
     size_t     end     = 0; // of the table so far
     const auto section = [&](size_t bytes) { // the next 16-aligned `bytes` of it
@@ -710,9 +652,6 @@ void CallPlan::finalize(const aeon_out_desc& o, bool u8_map, const SplitKnobs& k
         const bool last = g >= kMain;
         P.vec_ok = vec_ok;
         P.rtab   = last && P.photo && (o.dtype == AEON_DTYPE_F32 || out_is_half(o.dtype)); // (an f32 table either way)
-        // final non-photometric INTER_LINEAR float32 CHW launches (C5's images): augment_split
-        P.split = last && knobs.on && !P.photo && P.rm == RESIZE_LINEAR && o.dtype == AEON_DTYPE_F32 && o.channel_major &&
-                  P.vec_ok && !u8_map && !o.fixed_aspect_ratio && plan_split(knobs, P.jobs, P, P.sa);
         P.finalize();
         P.blob_off = section(P.jobs.size() * sizeof(AugJob));
         for (AugJob& J : P.jobs) {

@@ -62,15 +62,13 @@ struct LaunchPlan {
     bool                vec_ok = true;
     bool                has_hue = false, has_contrast = false;
     bool                rtab    = false; // final f32 / f16 / bf16 launch with contrast / lighting: per-record LDS table (f32)
-    bool                split   = false; // launched as augment_split (shape set by plan_split)
     bool                out_scratch = false; // the jobs write scratch (out_ptr an offset until relocated)
-    SplitArgs           sa{};
 
-    // launch shape for this->jobs (unless plan_split set it), and each job's tile count
+    // launch shape for this->jobs, and each job's tile count
     void finalize()
     {
         if (jobs.empty()) return;
-        if (!split) shape(jobs);
+        shape(jobs);
         max_tiles = 0;
         for (AugJob& J : jobs) {
             J.tiles   = (J.win_h + tr - 1) / tr;
@@ -176,15 +174,6 @@ struct GrPlan {
     static constexpr size_t kSepLds     = 40 * 1024; // (four bands per CU)
 };
 
-// The context's augment_split knobs (AEON_HIP_SPLIT_HELPERS / _RPL / _OCC), and whether the call's final
-// INTER_LINEAR float32 CHW launches may take that kernel at all.
-struct SplitKnobs {
-    bool on      = false;
-    int  helpers = 2, rpl = 2, occ = 1;
-};
-template <typename J_>
-bool plan_split(const SplitKnobs& k, const std::vector<J_>& geo, LaunchPlan& P, SplitArgs& sa);
-
 // Algorithmic bytes of one launch: the resampled u8 source footprint plus
 // the bytes written (KM_STATS / KM_RAW write an HWC uint8 intermediate).
 template <typename J_>
@@ -240,7 +229,7 @@ struct CallPlan {
                      const aeon_out_desc& o, void* out_dev, bool is_mask, const MaskSet* ms, const ItemMap* im);
     // Launch shapes, tile counts, table offsets (tap offsets made absolute) and the launch maxima; `o` is
     // what the kernels write (out_view).
-    void finalize(const aeon_out_desc& o, bool u8_map, const SplitKnobs& knobs);
+    void finalize(const aeon_out_desc& o);
     // The table's host-written bytes [0, blob) into `table`, scratch offsets relocated to `scratch`, the
     // Lanczos4 tap inputs computed (on `pool` when it pays).
     void write(uint8_t* table, uint64_t scratch, const ParallelFor& pool);

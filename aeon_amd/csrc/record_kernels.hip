@@ -22,26 +22,8 @@
 
 // development ablations / variants (tools/build_variants.sh): HUE4 = four pixels per hue batch;
 // NOB / NOA = no B stores / no A compute (wrong outputs)
-#ifndef AEON_REC_HUE4
-#define AEON_REC_HUE4 0
-#endif
-#ifndef AEON_REC_NOB
-#define AEON_REC_NOB 0
-#endif
-#ifndef AEON_REC_NOA
-#define AEON_REC_NOA 0
-#endif
-#ifndef AEON_REC_HELPER_PRIO // s_setprio of the split kernel's helper waves
+#ifndef AEON_REC_HELPER_PRIO // s_setprio of contrast_records_split's helper waves
 #define AEON_REC_HELPER_PRIO 3
-#endif
-#ifndef AEON_REC_UNROLL // split kernel: the compute waves' tile loop unrolled (no register rotation)
-#define AEON_REC_UNROLL 1
-#endif
-#ifndef AEON_REC_HOIST // FAST form: a row's 16 tap words read together (resize4_linear)
-#define AEON_REC_HOIST 1
-#endif
-#ifndef AEON_REC_FUSED // FAST form: A and B of a row interleaved (rec_row_fast); 0 = B's row, then A's
-#define AEON_REC_FUSED 1
 #endif
 
 namespace aeon_hip {
@@ -197,12 +179,8 @@ __device__ __forceinline__ u32x3 rec_pixels(const RecA& R, const RecLds& L, i32x
     if (FAST && (R.photo & PHOTO_HUE)) {
         const auto htab8 = lds_ptr<const i32x2>(L.htab) + 30;
         uint32_t   pk[4];
-#if AEON_REC_HUE4
-        hue_pack_n<4, 0>(sdv, hdiv, htab8, val, pk);
-#else
         hue_pack_n<2, 0>(sdv, hdiv, htab8, val, pk);
         hue_pack_n<2, 2>(sdv, hdiv, htab8, val, pk);
-#endif
         q = (u32x3){__builtin_amdgcn_perm(pk[1], pk[0], 0x04020100u), __builtin_amdgcn_perm(pk[2], pk[1], 0x05040201u),
                     __builtin_amdgcn_perm(pk[3], pk[2], 0x06050402u)};
     } else {
@@ -262,12 +240,7 @@ __device__ __forceinline__ u32x3 rec_row_fast(const RecA& R, const RecLds& L, i3
     float b[4] = {T(0, w0, 0), T(0, w0, 3), T(0, w1, 2), T(0, w2, 1)};
     __builtin_amdgcn_sched_barrier(0);
     int val[4][3];
-#if AEON_REC_HOIST
     resize4_linear<false>(ytr, R.col, R.wx, val); // (the 16 staged words in flight together)
-#else
-#pragma unroll
-    for (int k = 0; k < 4; k++) resize_px<RESIZE_LINEAR, false>(ytr, R.col[k], R.wx[k], val[k]);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     store_f32x4(orsrc, off(bgr ? 2 : 0), b[0], b[1], b[2], b[3]);
     float g[4] = {T(1, w0, 1), T(1, w1, 0), T(1, w1, 3), T(1, w2, 2)};
@@ -458,7 +431,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
                 const int j = t * kRecTileRows + u;
                 const int y = lph + nph * j;
                 nwv[3 * u] = nwv[3 * u + 1] = nwv[3 * u + 2] = 0;
-                if (FAST && AEON_REC_FUSED && tile_a && f.ok) { // (uniform) A and B interleaved
+                if (FAST && tile_a && f.ok) { // (uniform) A and B interleaved
                     const bool  va  = active && y < H;
                     const i32x4 ytr = lds_ptr<const i32x4>(L.yt + par * kRecTRMax * 16)[min(y - t * TR, TR - 1)];
                     const u32x3 q   = rec_row_fast(R, L, ytr, va, s0, s1, s2, orsrc, plane, hasB && va ? y * W + ox0 : -1,
@@ -467,12 +440,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
                     rec[3 * u] = q.x, rec[3 * u + 1] = q.y, rec[3 * u + 2] = q.z; // (B has read them)
                     continue;
                 }
-                if (!AEON_REC_NOB && hasB && __builtin_amdgcn_ballot_w64(active && y < H) != 0) {
+                if (hasB && __builtin_amdgcn_ballot_w64(active && y < H) != 0) {
                     pending += 3;
                     if (active && y < H) rec_store(L, orsrc, plane, y * W + ox0, bgr, rec[3 * u], rec[3 * u + 1], rec[3 * u + 2]);
                 }
-                if constexpr (!(FAST && AEON_REC_FUSED)) {
-                    if (!AEON_REC_NOA && tile_a && f.ok && active && y < H) {
+                if constexpr (!FAST) {
+                    if (tile_a && f.ok && active && y < H) {
                         const i32x4 ytr = lds_ptr<const i32x4>(L.yt + par * kRecTRMax * 16)[y - t * TR];
                         const u32x3 q   = rec_pixels<FAST>(R, L, ytr, s0, s1, s2);
                         nwv[3 * u] = q.x, nwv[3 * u + 1] = q.y, nwv[3 * u + 2] = q.z;
@@ -482,7 +455,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
             wstamp(k * 8 + t);
             // rotate: drop the tile B consumed, append the tile A produced (the fused rows wrote A's
             // words over B's in place: a cyclic rotation)
-            if (FAST && AEON_REC_FUSED && tile_a && f.ok) {
+            if (FAST && tile_a && f.ok) {
 #pragma unroll
                 for (int i = 0; i < 6; i++) nwv[i] = rec[i];
             }
@@ -514,7 +487,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
     REC_TRACE_EXIT
 }
 
-// The split form (host: AEON_HIP_REC_HELPERS, default): the workgroup's nwc compute waves hold the
+// The split form (the host launches it whenever the workgroup has room for two helper waves): the workgroup's nwc compute waves hold the
 // record and do only rows and record ends; nh = blockDim/64 - nwc helper waves (2 for 224-wide
 // records: 1,024 lanes) do all of the staging -- job fetches, the next tile's LDS-DMA loads and row
 // taps, and, once their loads landed, its in-place unpack -- during the current tile.  The compute
@@ -639,7 +612,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
     }
 
     // ---- compute waves: rows (A of record k and B of record k - 1), record ends ----
-    // The tile loop is unrolled (AEON_REC_UNROLL): tile t's rows live in rec[6t .. 6t + 5] for every
+    // The tile loop is unrolled (FAST form): tile t's rows live in rec[6t .. 6t + 5] for every
     // record -- B of record k - 1 reads them and A of record k writes them back in place -- so every
     // register index is a compile-time constant without rotating the held record by one tile per tile
     // (42 moves per tile).
@@ -673,7 +646,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
         }
         const auto orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)b_out, (short)0, hasB ? plane * 12 : 0, 0x00020000);
         uint32_t   s0 = 0, s1 = 0, s2 = 0;
-        constexpr bool kUnroll = FAST && AEON_REC_UNROLL; // (the generic form's registers would spill)
+        constexpr bool kUnroll = FAST; // (the generic form's registers would spill)
 #pragma unroll kUnroll ? kRecTiles : 1
         for (int t = 0; t < kRecTiles; t++) {
             const int  rb     = kUnroll ? 6 * t : 0; // the tile's words in rec[]
@@ -696,7 +669,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
                 const int y = lrow + nph * j, yi = lidx + rstep * j; // (yi = y * W + ox0)
                 uint32_t* hw = rec + rb + 3 * u;
                 nwv[3 * u] = nwv[3 * u + 1] = nwv[3 * u + 2] = 0;
-                if (FAST && AEON_REC_FUSED && fok) { // (uniform) A and B interleaved
+                if (FAST && fok) { // (uniform) A and B interleaved
                     const bool  va  = active && y < H;
                     const i32x4 ytr = lds_ptr<const i32x4>(L.yt + par * kRecTRMax * 16)[min(y - t * TR, TR - 1)];
                     const u32x3 q   = rec_row_fast(R, L, ytr, va, s0, s1, s2, orsrc, plane, hasB && va ? yi : -1,
@@ -708,7 +681,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
                 if (hasB && __builtin_amdgcn_ballot_w64(active && y < H) != 0) {
                     if (active && y < H) rec_store(L, orsrc, plane, yi, bgr, hw[0], hw[1], hw[2]);
                 }
-                if constexpr (!(FAST && AEON_REC_FUSED)) {
+                if constexpr (!FAST) {
                     if (fok && active && y < H) {
                         const i32x4 ytr = lds_ptr<const i32x4>(L.yt + par * kRecTRMax * 16)[y - t * TR];
                         const u32x3 q   = rec_pixels<FAST>(R, L, ytr, s0, s1, s2);

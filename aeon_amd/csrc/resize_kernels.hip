@@ -26,11 +26,6 @@
 
 #include "aug_job.hpp"
 
-// (development: AEON_RG_SKIP bits drop the horizontal pass (1), the vertical pass / stores (2) or the
-// staging (4) -- wrong outputs, phase timing only)
-#ifndef AEON_RG_SKIP
-#define AEON_RG_SKIP 0
-#endif
 #ifndef AEON_SEP_SCHED // resize_sep: a row's taps read together up to this K (K = 8's 32 loads in flight: 150+ VGPRs)
 #define AEON_SEP_SCHED 4
 #endif
@@ -281,7 +276,7 @@ __global__ __launch_bounds__(256) void resize_generic(const ResizeJob* __restric
     // staging: S[r][(u - u_lo) * cn + c] = src_px(u, r_lo + r, c), 4 bytes per lane and step; (row,
     // chunk) advanced incrementally (no divisions per step).  A staged byte b of row v is the source
     // byte (u_lo + shift_x) * cn + b of that row's crop, zero outside it when padded.
-    if (staged && !(AEON_RG_SKIP & 4)) {
+    if (staged) {
         const uint8_t* src  = (const uint8_t*)J.src_ptr + (size_t)J.crop_x * cn;
         const int      nch  = (sb + 3) >> 2, total = nr * nch;
         const int      dr   = nt / nch, dc = nt - dr * nch;
@@ -328,7 +323,7 @@ __global__ __launch_bounds__(256) void resize_generic(const ResizeJob* __restric
     {
         const int per = max(nt / nx, 1);
         const int i = tid % nx, r0 = tid / nx;
-        if (r0 < per && tid < per * nx && !(AEON_RG_SKIP & 1)) {
+        if (r0 < per && tid < per * nx) {
             const int* t = xt + i * xs;
             if (area) {
                 const int n = t[1], u0 = t[0] - u_lo;
@@ -380,7 +375,7 @@ __global__ __launch_bounds__(256) void resize_generic(const ResizeJob* __restric
     const int nb  = nx * cn;          // output bytes of a tile row
     const int nq  = (nb + 3) >> 2;    // dword groups per tile row
     const int xb0 = (J.win_x + x0) * cn; // the tile's first element in the full destination row
-    for (int q = tid; q < ny * nq && !(AEON_RG_SKIP & 2); q += nt) {
+    for (int q = tid; q < ny * nq; q += nt) {
         const int  r = q / nq, e0 = (q - r * nq) * 4;
         const int* t = yt + r * xs;
         uint32_t   word = 0;
@@ -522,8 +517,7 @@ __global__ __launch_bounds__(256) void resize_sep(const ResizeJob* __restrict__ 
     // byte's page, so the over-read is always mapped), the row's first byte at S[r * SW + its
     // address & 15].  Padded jobs: byte by byte, the zero border applied (as resize_generic's).
     const uint64_t rowa0 = J.src_ptr + (uint64_t)J.crop_y * J.src_stride + (uint64_t)(J.crop_x + u_lo) * cn;
-    if (AEON_RG_SKIP & 4) {
-    } else if (!J.padded) {
+    if (!J.padded) {
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const int     nblk = (sb + 15 + 15) >> 4; // blocks of the worst-aligned row
         const int     total = nr * nblk;
@@ -669,7 +663,7 @@ __global__ __launch_bounds__(256) void resize_sep(const ResizeJob* __restrict__ 
                 int acc = 0;
 #pragma unroll
                 for (int jj = 0; jj < K; jj++) acc = mad_i24(b[q][jj], cf[q][jj], acc);
-                hw[j][q] = (HT)((AEON_RG_SKIP & 1) ? rr + q : acc);
+                hw[j][q] = (HT)acc;
             }
         } else {
 #pragma unroll
@@ -678,7 +672,7 @@ __global__ __launch_bounds__(256) void resize_sep(const ResizeJob* __restrict__ 
                 int            acc = 0;
 #pragma unroll
                 for (int jj = 0; jj < K; jj++) acc = mad_i24((int)e[jj * cn], cf[q][jj], acc);
-                hw[j][q] = (HT)((AEON_RG_SKIP & 1) ? rr + q : acc);
+                hw[j][q] = (HT)acc;
             }
         }
     };
@@ -753,12 +747,11 @@ __global__ __launch_bounds__(256) void resize_sep(const ResizeJob* __restrict__ 
             }
         }
         if (planar) {
-            if (!(AEON_RG_SKIP & 2) || word == 0x12345678u) store_planar(J, lut, bgr, chm, y0 + r, x0 + px0, lc, nx - px0, word);
+            store_planar(J, lut, bgr, chm, y0 + r, x0 + px0, lc, nx - px0, word);
             continue;
         }
         const auto dst = out + ((size_t)(y0 + r) * J.win_w + x0) * cn + e0;
-        if ((AEON_RG_SKIP & 2) && word != 0x12345678u) {
-        } else if (e0 + 4 <= nb && ((uintptr_t)dst & 3) == 0) {
+        if (e0 + 4 <= nb && ((uintptr_t)dst & 3) == 0) {
             *(__attribute__((address_space(1))) uint32_t*)dst = word;
         } else {
             for (int q = 0; q < 4 && e0 + q < nb; q++) dst[q] = (uint8_t)(word >> (8 * q));

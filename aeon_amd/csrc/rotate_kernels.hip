@@ -103,12 +103,7 @@ __global__ __launch_bounds__(256) void rotate_tiles(const RotJob* __restrict__ j
         const bool fast = row_in && cn == 3 && gx >= 0 && gx + 3 < W && off + 12 <= R.stride * H;
         const bool none = !row_in || gx + 3 < 0 || gx >= W;
         meta[i]         = j | (g << 12) | ((!fast && !none) ? 1 << 30 : 0);
-#ifdef AEON_HIP_EXP_ROT_NOSTAGE // development ablation: no source loads (wrong values)
-        v[i] = (u32x3){(uint32_t)off, 0, 0};
-        meta[i] &= (1 << 30) - 1;
-#else
         v[i] = __builtin_amdgcn_raw_buffer_load_b96(src, fast ? (uint32_t)off : kOOB, 0, 0);
-#endif
     }
 #pragma unroll
     for (int i = 0; i < kNG; i++) {
@@ -138,9 +133,6 @@ __global__ __launch_bounds__(256) void rotate_tiles(const RotJob* __restrict__ j
         *(u32x4*)&st[j * pitch + g4] = (u32x4){w4[0], w4[1], w4[2], w4[3]}; // one ds_write_b128 per group
     }
     __syncthreads();
-#ifdef AEON_HIP_EXP_ROT_NOCOMPUTE // development ablation: staging only
-    return;
-#endif
     // compute + store
     const int  ob  = R.ow * R.oh * cn;
     const auto dst = __builtin_amdgcn_make_buffer_rsrc((void*)R.out_ptr, (short)0, ob, 0x00020000);

@@ -48,13 +48,9 @@ hipError_t launch_upload_table(const void* host_dev, void* dst, size_t bytes, hi
 hipError_t launch_contrast_records(bool fast, bool split, const LaunchArgs& a, const RecArgs& r, int grid, hipStream_t stream,
                                    hipEvent_t start, hipEvent_t stop);
 hipError_t contrast_records_lds_limit(int bytes);
-hipError_t launch_split(bool tail, int occ, const LaunchArgs& a, const SplitArgs& s, int grid, hipStream_t stream,
-                        hipEvent_t start, hipEvent_t stop);
-hipError_t split_lds_limit(int bytes);
 hipError_t launch_box_targets(const BoxLaunch& L, hipStream_t stream);
 hipError_t launch_rcnn_targets(const RcnnLaunch& L, hipStream_t stream);
 hipError_t launch_clip_pad(const PadRegion* regions, int n_regions, uint64_t max_bytes, hipStream_t stream);
-hipError_t split_occupancy(bool tail, int occ, const LaunchArgs& a, int* blocks);
 hipError_t launch_resize_generic(const ResizeJob* jobs, const uint8_t* table, int n_jobs, int max_tiles, int TR, int CW,
                                  int NR, int xs, int amax, int cn_max, int SW, const float* lut, int bgr, int chm,
                                  int32_t* error, hipStream_t stream);
@@ -209,13 +205,6 @@ struct aeon_hip_ctx {
     // the jobs from the pinned slot itself
     bool                 direct = true; // AEON_HIP_DIRECT=0: the multi-pass path (device job table) for every call
     bool                 records = true; // AEON_HIP_RECORDS=0: contrast calls through the two-launch path
-    int                  rec_helpers = 2; // AEON_HIP_REC_HELPERS: staging-only waves of the record kernel
-    int                  rec_phases  = 0; // AEON_HIP_REC_PHASES (development): row phases of the record kernel
-    bool                 split = false;     // AEON_HIP_SPLIT=1: non-photometric INTER_LINEAR f32 launches through
-                                            // augment_split (measured slower than augment_tiles)
-    int                  split_helpers = 2; // AEON_HIP_SPLIT_HELPERS: staging waves of augment_split
-    int                  split_rpl = 2;     // AEON_HIP_SPLIT_RPL: output rows per compute lane per tile
-    int                  split_occ = 1;     // AEON_HIP_SPLIT_OCC: augment_split workgroups per CU (1 or 2)
     bool                 fuse_masks = false; // AEON_HIP_FUSE_MASKS=1: a pair call's masks inside the image launch
     bool                 vram_jobs = false; // job tables written by the host into device memory (large-BAR GPUs;
                                             // AEON_HIP_VRAM_JOBS=0: pinned host tables)
@@ -491,11 +480,6 @@ const float* resident_lut(aeon_hip_ctx* ctx, const aeon_out_desc& o, bool u8_map
     return dev;
 }
 
-SplitKnobs split_knobs(const aeon_hip_ctx* ctx, bool allowed)
-{
-    return SplitKnobs{ctx->split && allowed, ctx->split_helpers, ctx->split_rpl, ctx->split_occ};
-}
-
 // Persistent grid: as many workgroups as the CUs hold at once, never more than the tiles.
 int grid_for(aeon_hip_ctx* ctx, int mode, const LaunchPlan& P, const LaunchArgs& a)
 {
@@ -561,18 +545,6 @@ void timed_launch(aeon_hip_ctx* ctx, int mode, const LaunchPlan& P, const Launch
 bool take_timing(aeon_hip_ctx* ctx)
 {
     return ctx->timing && (ctx->timing_calls++ % ctx->timing_every) == ctx->timing_every - 1;
-}
-
-// A final launch: as augment_split with shape `sa` (plan_split), or (null) as augment_tiles.
-void launch_final(aeon_hip_ctx* ctx, const LaunchPlan& P, const SplitArgs* sa, const LaunchArgs& a, hipStream_t stream,
-                  double bytes, bool timed)
-{
-    if (!sa) return timed_launch(ctx, KM_FINAL, P, a, stream, bytes, timed);
-    KernelTimer t{};
-    if (timed) t = take_timer(ctx, KM_FINAL, bytes);
-    const int grid = std::min(a.total_tiles, sa->occ * ctx->n_cu); // sa->occ workgroups per CU (the LDS request holds it)
-    HIP_OK(launch_split(P.tail, sa->occ, a, *sa, grid, stream, timed ? t.start : nullptr, timed ? t.stop : nullptr));
-    if (timed) ctx->timers.push_back(t);
 }
 
 // fixed_aspect_ratio: std::fill_n of each item's canvas, its whole byte size as declared (etl_image.cpp:263)
@@ -726,12 +698,7 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
     P.photo  = (key & 1) != 0;
     P.vec_ok = vec_ok;
     P.rtab   = P.photo && (o.dtype == AEON_DTYPE_F32 || out_is_half(o.dtype));
-    // non-photometric INTER_LINEAR into float32 CHW planes, one window width: augment_split (staging on
-    // helper waves, split_kernels.hip); else augment_tiles' shape
-    SplitArgs  sa{};
-    const bool split = ctx->split && !P.photo && P.rm == RESIZE_LINEAR && o.dtype == AEON_DTYPE_F32 && o.channel_major &&
-                       vec_ok && !ov.u8_map && !o.fixed_aspect_ratio && plan_split(split_knobs(ctx, true), geo, P, sa);
-    if (!split) P.shape(geo);
+    P.shape(geo);
     P.max_tiles = (max_h + P.tr - 1) / P.tr;
     // every tile reads its job over PCIe: past ~512 KB of such reads per launch the multi-pass path's
     // device table wins (C5's image launch, 4,096 tiles of 256 B: 98 vs 90 us of kernels per step;
@@ -784,7 +751,7 @@ bool run_direct(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void
     a.jobs_host       = 1; // (read-through loads: pinned host memory, or the uncached HBM copy)
     // (the algorithmic bytes only for a timed launch: a pass over the records the call does not need)
     const double lbytes = timed ? launch_bytes(geo, KM_FINAL, out_elem_bytes(o.dtype)) : 0;
-    launch_final(ctx, P, split ? &sa : nullptr, a, stream, lbytes, timed);
+    timed_launch(ctx, KM_FINAL, P, a, stream, lbytes, timed);
     phase(6);
     release_slot(ctx, slot, stream);
     phase(7);
@@ -810,9 +777,7 @@ bool run_records(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const voi
     for (int i = 0; im && i < n; i++)
         if ((im->item[i] & 15) != 0) return false;
     const int W = params[0].out_w, H = params[0].out_h;
-    int       nph = rec_phases(W, H);
-    if (ctx->rec_phases > 0 && W / 4 * ctx->rec_phases <= 1024 && (H + ctx->rec_phases - 1) / ctx->rec_phases <= kRecRows)
-        nph = ctx->rec_phases; // (development: AEON_HIP_REC_PHASES)
+    const int nph = rec_phases(W, H);
     if (W <= 0 || (W & 3) != 0 || W > 4 * 256 || H <= 0 || nph <= 0) return false;
     if (simd_boundary(W * 3) < W * 3) return false; // OpenCV's scalar row tail
     bool      contrast = false;
@@ -869,8 +834,9 @@ bool run_records(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const voi
     a.bgr_to_rgb  = o.bgr_to_rgb && o.channels == 3;
     a.threads     = (nph * (W / 4) + 63) / 64 * 64;
     // helper waves (record_kernels.hip: staging only) when the workgroup has room for them
-    const bool split = ctx->rec_helpers > 0 && a.threads + 64 * ctx->rec_helpers <= 1024;
-    if (split) a.threads += 64 * ctx->rec_helpers;
+    constexpr int kRecHelpers = 2;
+    const bool    split       = a.threads + 64 * kRecHelpers <= 1024;
+    if (split) a.threads += 64 * kRecHelpers;
     a.lds_bytes   = lds;
 #ifdef AEON_HIP_TRACE
     a.trace = ctx->trace; // development builds only (tools/trace_records.py)
@@ -907,7 +873,7 @@ MaskFuse fuse_masks(const CallPlan& plan)
 #define AEON_HIP_FUSED_MASK_ROWS 64
 #endif
     f.rows = std::min(mask16_rows(plan.m16_max_w, plan.m16_max_seg), AEON_HIP_FUSED_MASK_ROWS);
-    if (groups != 1 || f.into < plan.tiles + CallPlan::kMain || f.rows < 1 || f.into->has_contrast || f.into->split) return MaskFuse{};
+    if (groups != 1 || f.into < plan.tiles + CallPlan::kMain || f.rows < 1 || f.into->has_contrast) return MaskFuse{};
     const LaunchPlan& P = *f.into;
     f.pitch = mask16_pitch(plan.m16_max_seg);
     f.slots = std::max(1, std::min(plan.m16_max_slots, f.rows));
@@ -1036,7 +1002,7 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     plan.clear();
     plan.add_records(n, descs, src_base, params, o, out_dev, is_mask, ms, im);
     phase(1);
-    plan.finalize(o, ov.u8_map, split_knobs(ctx, !(ms && ctx->fuse_masks)));
+    plan.finalize(o);
     if (std::max(plan.gr_short.n_taps, plan.gr_main.n_taps) > 4096 && !ctx->plan_pool)
         ctx->plan_pool.reset(new thread_pool(thread_affinity_map("")));
     phase(2);
@@ -1096,7 +1062,7 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
                 a.lds_bytes = mf.lds;
                 bytes += plan.m16_bytes;
             }
-            launch_final(ctx, P, P.split ? &P.sa : nullptr, a, stream, bytes, timed);
+            timed_launch(ctx, KM_FINAL, P, a, stream, bytes, timed);
         }
     };
     launch_generic(ctx, plan.gr_short, table, o, d_lut, stream, timed);
@@ -1489,7 +1455,6 @@ int aeon_hip_ctx_create(int device, aeon_hip_ctx** out)
             HIP_OK(hipSetDevice(device));
             HIP_OK(set_kernel_lds_limit(kMaxLds));
             HIP_OK(contrast_records_lds_limit(kMaxLds));
-            HIP_OK(split_lds_limit(kMaxLds));
             HIP_OK(hipMalloc((void**)&c->d_error, sizeof(int32_t) * aeon_hip_ctx::kErrWords));
             HIP_OK(hipMemset(c->d_error, 0, sizeof(int32_t) * aeon_hip_ctx::kErrWords));
             // per slot: the dynamic-tail counter, then (kSlots on) the mask-block counter of pair calls
@@ -1523,11 +1488,7 @@ int aeon_hip_ctx_create(int device, aeon_hip_ctx** out)
             for (Slot& s : c->slots) {
                 // the ring's completion events only tell the host that the GPU is done reading a
                 // slot: no system-scope fence needed (each one idled the GPU ~6 us between launches)
-#ifndef AEON_HIP_DONE_FENCE
-#define AEON_HIP_DONE_FENCE 0
-#endif
-                HIP_OK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming |
-                                                            (AEON_HIP_DONE_FENCE ? 0 : hipEventDisableSystemFence)));
+                HIP_OK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming | hipEventDisableSystemFence));
                 // s.copied orders the SDMA job-table upload (copy_stream) before the kernels that read
                 // it on the launch stream: it keeps the system-scope release
                 HIP_OK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
@@ -1547,12 +1508,6 @@ int aeon_hip_ctx_create(int device, aeon_hip_ctx** out)
             if (c->host_profile) std::fprintf(stderr, "[aeon_hip] job tables in HBM (BAR writes): %d\n", (int)c->vram_jobs);
             if (const char* e = std::getenv("AEON_HIP_DIRECT")) c->direct = std::atoi(e) != 0;
             if (const char* e = std::getenv("AEON_HIP_RECORDS")) c->records = std::atoi(e) != 0;
-            if (const char* e = std::getenv("AEON_HIP_REC_HELPERS")) c->rec_helpers = std::max(0, std::min(4, std::atoi(e)));
-            if (const char* e = std::getenv("AEON_HIP_REC_PHASES")) c->rec_phases = std::atoi(e);
-            if (const char* e = std::getenv("AEON_HIP_SPLIT")) c->split = std::atoi(e) != 0;
-            if (const char* e = std::getenv("AEON_HIP_SPLIT_HELPERS")) c->split_helpers = std::max(1, std::min(4, std::atoi(e)));
-            if (const char* e = std::getenv("AEON_HIP_SPLIT_RPL")) c->split_rpl = std::max(1, std::min(4, std::atoi(e)));
-            if (const char* e = std::getenv("AEON_HIP_SPLIT_OCC")) c->split_occ = std::max(1, std::min(2, std::atoi(e)));
             if (const char* e = std::getenv("AEON_HIP_JPEG_HUFF")) c->jpeg_gpu_huff = std::strcmp(e, "host") != 0;
             if (const char* e = std::getenv("AEON_HIP_FUSE_MASKS")) c->fuse_masks = std::atoi(e) != 0;
 #ifdef AEON_HIP_TRACE

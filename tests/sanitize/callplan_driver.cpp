@@ -100,7 +100,7 @@ void plan_call(CallPlan& plan, const Call& c, std::vector<uint8_t>& table)
     plan.clear();
     plan.add_records((int)c.d.size(), c.d.data(), (const void*)kSrc, c.p.data(), ov.ko, (void*)kOut, c.is_mask,
                      c.pair ? &ms : nullptr, c.items.empty() ? nullptr : &im);
-    plan.finalize(ov.ko, ov.u8_map, SplitKnobs{});
+    plan.finalize(ov.ko);
     if (table.size() < plan.ring_need) table.resize(plan.ring_need);
     std::memset(table.data(), 0, plan.table_cap);
     plan.write(table.data(), kScratch, nullptr);
@@ -268,9 +268,9 @@ void print_case(CallPlan& plan, const Call& c, std::vector<uint8_t>& table)
         }
         if (P.jobs.empty()) return;
         std::printf(" | %s rm=%d tail=%d photo=%d n=%zu tr=%d threads=%d lds=%d stage=%d max_win_w=%d max_tiles=%d vec_ok=%d "
-                    "rtab=%d hue=%d contrast=%d split=%d",
+                    "rtab=%d hue=%d contrast=%d",
                     pass, P.rm, (int)P.tail, (int)P.photo, P.jobs.size(), P.tr, P.threads, P.lds, P.stage_bytes, P.max_win_w,
-                    P.max_tiles, (int)P.vec_ok, (int)P.rtab, (int)P.has_hue, (int)P.has_contrast, (int)P.split);
+                    P.max_tiles, (int)P.vec_ok, (int)P.rtab, (int)P.has_hue, (int)P.has_contrast);
     });
     std::printf("\nrule %s %s\n", c.name.c_str(), check_layout(plan, table.data()).c_str());
 }

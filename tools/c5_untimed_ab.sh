@@ -1,6 +1,6 @@
 #!/bin/bash
 # C5 A/B through bench.run_c5 (the bench line's C5 extra: untimed rate), three interleaved rounds per
-# case.  A case is name[:VAR=VAL[,VAR=VAL...]].  Usage: tools/c5_untimed_ab.sh base tr48:AEON_HIP_TILE_ROWS=48
+# case.  A case is name[:VAR=VAL[,VAR=VAL...]].  Usage: tools/c5_untimed_ab.sh base fused:AEON_HIP_FUSE_MASKS=1
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R" || exit 1
 for round in 1 2 3; do
