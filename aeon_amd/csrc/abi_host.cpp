@@ -1,0 +1,206 @@
+// abi_host.cpp -- the host-only entries of the C ABI (include/aeon_hip.h): the param factory, the PNG
+// decoder, the JPEG header and entropy probes, aeon's rounding and scale helpers, and the thread-local text
+// behind aeon_hip_last_error.  No entry touches a device, and nothing here needs the runtime: the sanitizer
+// builds link this file as it is.
+#include <mutex>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "../../include/aeon_hip.h"
+#include "error.hpp"
+#include "jpeg.hpp"
+#include "json.hpp"
+#include "param_factory.hpp"
+#include "png.hpp"
+#include "rcnn_host.hpp"
+
+using namespace aeon_hip;
+
+struct aeon_param_factory {
+    param_factory f;
+    std::mutex    mu; // make_params calls are serialised (the lighting normal_distribution caches a draw)
+    explicit aeon_param_factory(const Json& j) : f(j) {}
+};
+
+namespace {
+thread_local std::string g_err;
+using TrackedEngine = tracked_engine; // rcnn_host.hpp
+} // namespace
+
+void aeon_hip::set_last_error(const char* what) { g_err = what; }
+
+extern "C" {
+
+int aeon_param_factory_create(const char* aug_json, aeon_param_factory** out)
+{
+    return guarded([&] {
+        if (!out) fail(AEON_HIP_EINVAL, "null out");
+        Json j = aug_json && *aug_json ? Json::parse(aug_json) : Json();
+        *out   = new aeon_param_factory(j);
+        return 0;
+    });
+}
+
+int aeon_param_factory_destroy(aeon_param_factory* f)
+{
+    delete f;
+    return 0;
+}
+
+int aeon_make_params(aeon_param_factory* f, uint32_t* state, int in_w, int in_h, int out_w, int out_h,
+                     aeon_aug_params* out)
+{
+    return guarded([&] {
+        if (!f || !state || !out) fail(AEON_HIP_EINVAL, "null argument");
+        std::lock_guard<std::mutex> lock(f->mu);
+        TrackedEngine eng(*state);
+        f->f.make_params(eng, in_w, in_h, out_w, out_h, out);
+        *state = eng.last;
+        return 0;
+    });
+}
+
+int aeon_make_ssd_params(aeon_param_factory* f, uint32_t* state, int in_w, int in_h, int out_w, int out_h,
+                         const float* boxes, int n_boxes, aeon_aug_params* out)
+{
+    return guarded([&] {
+        if (!f || !state || !out || n_boxes < 0 || (n_boxes > 0 && !boxes)) fail(AEON_HIP_EINVAL, "null argument");
+        std::lock_guard<std::mutex> lock(f->mu);
+        TrackedEngine eng(*state);
+        f->f.make_ssd_params(eng, in_w, in_h, out_w, out_h, boxes, n_boxes, out);
+        *state = eng.last;
+        return 0;
+    });
+}
+
+int aeon_param_factory_emit(aeon_param_factory* f, int* type, float* min_overlap)
+{
+    return guarded([&] {
+        if (!f || !type || !min_overlap) fail(AEON_HIP_EINVAL, "null argument");
+        *type        = f->f.emit_type();
+        *min_overlap = f->f.emit_constraint_min_overlap;
+        return 0;
+    });
+}
+
+int aeon_png_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* color_type)
+{
+    return guarded([&] {
+        if (!data || !width || !height || !bit_depth || !color_type) fail(AEON_HIP_EINVAL, "null argument");
+        png_header(data, size, width, height, bit_depth, color_type);
+        return 0;
+    });
+}
+
+int aeon_decode_png(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        if (mode < AEON_PNG_BGR8 || mode > AEON_PNG_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown PNG decode mode");
+        int w, h, depth, ctype;
+        png_header(data, size, &w, &h, &depth, &ctype);
+        const size_t eb = (mode == AEON_PNG_ANYDEPTH && depth == 16 && ctype != 3) ? 2 : 1;
+        if (stride < (size_t)w * (mode == AEON_PNG_BGR8 ? 3 : 1) * eb) fail(AEON_HIP_EINVAL, "stride too small");
+        png_decode(data, size, mode, dst, stride, elem_bytes);
+        return 0;
+    });
+}
+
+int aeon_batch_sample_patches(aeon_param_factory* f, int sampler, uint32_t* state, const float* nboxes, int n,
+                              float* out, int cap, int* n_out)
+{
+    return guarded([&] {
+        if (!f || !state || !n_out || n < 0 || (n > 0 && !nboxes) || cap < 0 || (cap > 0 && !out))
+            fail(AEON_HIP_EINVAL, "null argument");
+        std::lock_guard<std::mutex> lock(f->mu);
+        if (sampler < 0 || sampler >= (int)f->f.batch_samplers.size()) fail(AEON_HIP_EINVAL, "sampler index out of range");
+        TrackedEngine     eng(*state);
+        std::vector<nbox> objects, samples;
+        for (int i = 0; i < n; i++)
+            objects.emplace_back(nboxes[4 * i], nboxes[4 * i + 1], nboxes[4 * i + 2], nboxes[4 * i + 3]);
+        f->f.batch_samplers[sampler].sample_patches(eng, objects, samples);
+        *n_out = (int)samples.size();
+        for (int i = 0; i < (int)samples.size() && i < cap; i++) {
+            out[4 * i] = samples[i].xmin, out[4 * i + 1] = samples[i].ymin;
+            out[4 * i + 2] = samples[i].xmax, out[4 * i + 3] = samples[i].ymax;
+        }
+        *state = eng.last;
+        return 0;
+    });
+}
+
+int aeon_seed_slots(uint32_t seed, int n, uint32_t* states)
+{
+    return guarded([&] {
+        if (n < 0 || (n > 0 && !states)) fail(AEON_HIP_EINVAL, "bad arguments");
+        std::minstd_rand0 g(seed);
+        for (int i = 0; i < n; i++) {
+            uint32_t s = g() % 2147483647u;
+            states[i]  = s == 0 ? 1 : s;
+        }
+        return 0;
+    });
+}
+
+int aeon_jpeg_info(const void* data, size_t size, int* width, int* height, int* components)
+{
+    return guarded([&] {
+        if (!data || !width || !height || !components) fail(AEON_HIP_EINVAL, "null argument");
+        jpeg_info(data, size, width, height, components);
+        return 0;
+    });
+}
+
+int aeon_jpeg_entropy_decode(const void* data, size_t size, int* width, int* height, int* components,
+                             int64_t* n_blocks, int64_t* n_values, uint64_t* hash)
+{
+    return guarded([&] {
+        if (!data || !width || !height || !components || !n_blocks || !n_values || !hash)
+            fail(AEON_HIP_EINVAL, "null argument");
+        jpeg_entropy_only(data, size, width, height, components, n_blocks, n_values, hash);
+        return 0;
+    });
+}
+
+int aeon_jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* staged_bytes)
+{
+    return guarded([&] {
+        if (!data || !gpu_entropy || !staged_bytes) fail(AEON_HIP_EINVAL, "null argument");
+        jpeg_host_stage(data, size, gpu_entropy, staged_bytes);
+        return 0;
+    });
+}
+
+int aeon_unbiased_round(float x, int64_t* out)
+{
+    return guarded([&] {
+        if (!out) fail(AEON_HIP_EINVAL, "null out");
+        *out = unbiased_round(x);
+        return 0;
+    });
+}
+
+int aeon_calculate_scale(int width, int height, int output_width, int output_height, float* scale)
+{
+    return guarded([&] {
+        if (!scale) fail(AEON_HIP_EINVAL, "null out");
+        *scale = calculate_scale(width, height, output_width, output_height);
+        return 0;
+    });
+}
+
+int aeon_cropbox_max_proportional(float in_w, float in_h, float out_w, float out_h, float* res_w, float* res_h)
+{
+    return guarded([&] {
+        if (!res_w || !res_h) fail(AEON_HIP_EINVAL, "null out");
+        cropbox_max_proportional(in_w, in_h, out_w, out_h, res_w, res_h);
+        return 0;
+    });
+}
+
+const char* aeon_hip_last_error(void) { return g_err.c_str(); }
+
+const char* aeon_hip_version(void) { return "aeon-hip 0.1 (gfx950)"; }
+
+} // extern "C"

@@ -19,6 +19,7 @@
 
 #include "augment_device.hpp"
 #include "mask16_device.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
 
@@ -867,7 +868,7 @@ __global__ __launch_bounds__(64) void contrast_reduce(LaunchArgs a, int n_jobs)
     }
 }
 
-// ---- host-side launch helpers (stage.cpp) ----------------------------------------------------
+// ---- host-side launch helpers (launch.hpp) ---------------------------------------------------
 typedef void (*KernelFn)(LaunchArgs);
 
 template <int KM, int RM, bool TAIL>

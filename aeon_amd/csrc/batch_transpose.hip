@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.hpp"
+
 namespace aeon_hip {
 
 constexpr int kTile = 64;

@@ -1,5 +1,5 @@
 // box_job.hpp -- the device table of one box targets call (aeon_hip_box_targets_batch, aeon_hip_rcnn_targets_batch
-// or a decode window's box provider; stage.cpp and host.cpp write it, box_kernels.hip and rcnn_kernels.hip
+// or a decode window's box provider; targets.cpp and host.cpp write it, box_kernels.hip and rcnn_kernels.hip
 // read it) and the box kernel's launch description.
 #pragma once
 #include <stddef.h>

@@ -22,6 +22,7 @@
 #include "../../include/aeon_hip.h"
 #include "box_device.hpp"
 #include "box_job.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
 

@@ -431,7 +431,7 @@ std::vector<int> parse_cpu_list(const std::string& cpu_list);
 // of 256 CPUs, CPUs the workers can actually be pinned to), capped by OMP_NUM_THREADS.
 std::vector<int> thread_affinity_map(const std::string& cpu_list);
 int aeon_thread_count(const std::string& cpu_list); // thread_affinity_map(cpu_list).size()
-// the decoder's pool runs its context's JPEG entropy decoding too (stage.cpp)
+// the decoder's pool runs its context's JPEG entropy decoding too (context.cpp)
 void ctx_share_pool(aeon_hip_ctx* ctx, thread_pool* pool);
 // aeon_hip_box_targets_batch over a box table that already lies in device memory (the decoder stages it
 // in the window's arena with the pixels, so a window makes one H2D): table = n BoxRec, then `total`

@@ -19,16 +19,14 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <stdexcept>
-#include <string>
+#include "../../include/aeon_hip.h"
+#include "error.hpp" // jpeg_error
+
+// the runtime's stream and event handles, named without its headers (the host-only callers include none)
+struct ihipStream_t;
+struct ihipEvent_t;
 
 namespace aeon_hip {
-
-// Host-side error of the JPEG stage, carrying its AEON_HIP_E* code across to the C ABI.
-struct jpeg_error : std::runtime_error {
-    int code;
-    jpeg_error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 struct JpegState;
 class thread_pool;
@@ -37,6 +35,21 @@ class thread_pool;
 // gpu_huff false: every file through the host entropy decoder (AEON_HIP_JPEG_HUFF=host, A/B runs)
 JpegState* jpeg_state_create(thread_pool* shared = nullptr, bool gpu_huff = true);
 void       jpeg_state_destroy(JpegState* s);
+
+// The host functions of the stage (jpeg_host.cpp).  jpeg_decode_batch: n files decoded into the records at
+// dst_base on `stream`; `error` is the stream's device error word, start / stop optional timing events.
+void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
+                       void* dst_base, int32_t* error, ihipStream_t* stream, ihipEvent_t* start, ihipEvent_t* stop);
+// header and entropy probes of one file, no device involved (aeon_jpeg_info, aeon_jpeg_entropy_decode,
+// aeon_jpeg_host_stage)
+void jpeg_info(const void* data, size_t size, int* w, int* h, int* ncomp);
+void jpeg_entropy_only(const void* data, size_t size, int* w, int* h, int* ncomp, int64_t* n_blocks,
+                       int64_t* n_values, uint64_t* hash);
+void jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* staged_bytes);
+// the GPU entropy decoder's algorithm run on the host (for tests): 0 when the file goes to the host decoder,
+// 1 when decoded, -1 on corrupt entropy-coded data
+int  jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, int* h, int* ncomp, int64_t* n_blocks,
+                              int64_t* n_values, uint64_t* hash, int* rounds);
 
 // One 8x8 block: bit z of `mask` = zigzag coefficient z is non-zero; its values follow in zigzag
 // order at values[val_off ...] of the block's image.

@@ -25,13 +25,9 @@
 #include "host.hpp"
 #include "jpeg.hpp"
 #include "jpeg_huff.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
-hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, hipStream_t stream);
-int        jpeg_huff_stage_cap(int lanes);
-hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, int stage_bytes, int32_t* error,
-                            hipStream_t stream);
 
 namespace {
 

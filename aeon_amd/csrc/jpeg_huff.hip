@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "jpeg_huff.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
 namespace {

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "jpeg.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
 

@@ -23,6 +23,7 @@
 #include "aug_job.hpp"
 #include "mask16.hpp"
 #include "mask16_device.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
 

@@ -1,6 +1,6 @@
 // plan.hpp -- the image path's planner: the host-side arithmetic aeon does per record before touching
 // pixels, and where every byte of a call's job table and scratch goes.  Host-only (no HIP runtime):
-// stage.cpp acts on a finished CallPlan, tests/sanitize/callplan_driver.cpp checks one on a CPU.
+// image_path.cpp acts on a finished CallPlan, tests/sanitize/callplan_driver.cpp checks one on a CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -1,6 +1,6 @@
 // plan_record.hpp -- the per-record arithmetic aeon does on the host before touching pixels
 // (cv::resize dispatch, cropbox window, cv::transform matrix, lighting pixel): the host planner's
-// (stage.cpp) job of one record, built with -ffp-contract=off so every float/double expression
+// (image_path.cpp) job of one record, built with -ffp-contract=off so every float/double expression
 // rounds as aeon's x86 build does.
 #pragma once
 #include <stdint.h>
@@ -108,7 +108,7 @@ AEON_HD inline bool expands(const aeon_aug_params& p) { return p.expand_ratio > 
 // decoded source: crop [+ add_padding] -> resize -> [cbsjitter -> lighting] -> flip -> load, as ONE
 // job.  Callers handle rotation / resize_short (pre-passes) and contrast (two passes) by patching
 // the job this returns.  `out_item` is the record's output item; is_mask = pixel-mask transform
-// (NEAREST, no padding, no photometric).  Inputs are assumed validated (stage.cpp).
+// (NEAREST, no padding, no photometric).  Inputs are assumed validated (plan.hpp validate_record).
 AEON_HD inline void plan_direct(const aeon_img_desc& d, uint64_t src_base, const aeon_aug_params& p,
                                 const OutGeom& o, uint64_t out_item, bool is_mask, AugJob& J)
 {

@@ -25,7 +25,8 @@
 #include <vector>
 
 #include "../../include/aeon_hip.h"
-#include "jpeg.hpp" // jpeg_error: an error carrying its AEON_HIP_E* code
+#include "error.hpp" // jpeg_error: an error carrying its AEON_HIP_E* code
+#include "png.hpp"
 
 namespace aeon_hip {
 namespace {

@@ -1,4 +1,4 @@
-// rcnn_job.hpp -- what the host (stage.cpp, host.cpp) and the device (rcnn_kernels.hip) share about one
+// rcnn_job.hpp -- what the host (targets.cpp, host.cpp) and the device (rcnn_kernels.hip) share about one
 // localization_rcnn targets launch: the limits, what fills the per-record extension of the box table
 // (box_job.hpp's RcnnRec) and the launch description.
 //

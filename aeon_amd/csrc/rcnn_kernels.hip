@@ -29,6 +29,7 @@
 #include "../../include/aeon_hip.h"
 #include "box_device.hpp"
 #include "rcnn_job.hpp"
+#include "launch.hpp"
 #include "rcnn_shuffle.hpp"
 
 namespace aeon_hip {

@@ -19,6 +19,7 @@
 // the newest), so all register indices are compile-time constants.
 // Every byte equals the two-launch path's (tests: test_full_batch_c3_all_records and the C3 cases).
 #include "augment_device.hpp"
+#include "launch.hpp"
 
 // development ablations / variants (tools/build_variants.sh): HUE4 = four pixels per hue batch;
 // NOB / NOA = no B stores / no A compute (wrong outputs)

@@ -2,7 +2,7 @@
 // imgwarp.cpp), the interpolation methods aeon's image::config accepts besides LINEAR / NEAREST
 // (src/image.cpp:30-36; image::resize :93-106, image::resize_short :118-127).  A pre-pass per
 // record: the resized window lands in the slot scratch as HWC uint8 and the record's tile job copies
-// it through the photometric stages and the loader (stage.cpp plan_image).
+// it through the photometric stages and the loader (plan.cpp CallPlan::add).
 //
 // Arithmetic (oracle/aeon_oracle.cpp resize_cv restates the same; parity unpinned -- aeon's tests
 // hold no output of these methods):
@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "aug_job.hpp"
+#include "launch.hpp"
 
 #ifndef AEON_SEP_SCHED // resize_sep: a row's taps read together up to this K (K = 8's 32 loads in flight: 150+ VGPRs)
 #define AEON_SEP_SCHED 4
@@ -141,7 +142,7 @@ __device__ __forceinline__ void area_taps(int ssize, double scale, int d, int* t
 
 } // namespace
 
-// The loader for a final_out job (stage.cpp plan_image: no photometric stage, f32 output): element e
+// The loader for a final_out job (plan.cpp CallPlan::add: no photometric stage, f32 output): element e
 // of window row y (pixel e / cn, source channel e % cn) -> cv::flip, BGR->RGB, the standardize LUT (in
 // LDS, [source channel][value]), stored into the output item's plane (channel-major) or pixel.
 __device__ __forceinline__ void store_final(const ResizeJob& J, const float* lut, int bgr, int chm, int y, int x0, int e0,
@@ -760,7 +761,7 @@ __global__ __launch_bounds__(256) void resize_sep(const ResizeJob* __restrict__ 
 }
 
 // The device half of interpolateLanczos4 (OpenCV 2.4.9 imgwarp.cpp; the host half: lanczos4_inputs,
-// stage.cpp): per destination column / row the eight coefficients from the fraction f and the host's
+// plan.cpp): per destination column / row the eight coefficients from the fraction f and the host's
 // sin / cos of y0 -- the same IEEE float and double operations in the same order (no contraction:
 // -ffp-contract=off; correctly rounded divisions) -- normalised to sum 1 in float, then the 11-bit
 // fixed point of the taps.

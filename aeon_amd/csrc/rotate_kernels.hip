@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "aug_job.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
 

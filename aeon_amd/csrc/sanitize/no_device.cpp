@@ -1,45 +1,29 @@
-// hip_stubs.cpp -- a device-free stand-in for the HIP runtime and the device half of the C ABI, so the
-// host layer (aeon_amd/csrc/host.cpp: decoder configuration, thread_pool, window draws) links into a
-// sanitizer build without libamdhip64 (tests/sanitize/host_driver.cpp, Makefile targets `sanitize` /
-// `tsan`).  Every device entry point fails with "no device": a decode window's flush cannot run here,
-// which is the point -- the driver exercises only the host phases.  Host-only entry points the layer
-// calls (PNG / JPEG headers, PNG decode) forward to the real implementations.
+// no_device.cpp -- a device-free stand-in for the HIP runtime and the device half of the C ABI, so the
+// host layer (host.cpp: decoder configuration, thread_pool, window draws) links into a sanitizer build
+// without libamdhip64 (tests/sanitize/host_driver.cpp, Makefile targets `sanitize` / `tsan` /
+// `sanitize_video`).  Never part of the library: only the Makefile's sanitizer source lists name it, next to
+// the real abi_host.cpp.  Every device entry point fails with "no device": a decode window's flush cannot run here,
+// which is the point -- the driver exercises only the host phases.  The host-only entry points the layer
+// calls (PNG / JPEG headers, PNG decode) and aeon_hip_last_error are the library's own: these builds link
+// aeon_amd/csrc/abi_host.cpp.
 #include <hip/hip_runtime_api.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <cstdlib>
 #include <string>
 
-#include "../../aeon_amd/csrc/host.hpp"
-#include "../../aeon_amd/csrc/jpeg.hpp"
+#include "../error.hpp"
+#include "../host.hpp"
 
 namespace aeon_hip {
-void jpeg_info(const void* data, size_t size, int* w, int* h, int* ncomp);
-void png_header(const void* data, size_t size, int* w, int* h, int* depth, int* ctype);
-void png_decode(const void* data, size_t size, int mode, void* dst, size_t stride, int* out_elem_bytes);
 void ctx_share_pool(aeon_hip_ctx*, thread_pool*) {}
 } // namespace aeon_hip
 
 namespace {
-thread_local std::string g_err;
 int no_device()
 {
-    g_err = "sanitizer build: no device";
+    aeon_hip::set_last_error("sanitizer build: no device");
     return AEON_HIP_EDEVICE;
-}
-template <typename F>
-int host_call(F&& f)
-{
-    try {
-        f();
-        return 0;
-    } catch (const aeon_hip::jpeg_error& e) {
-        g_err = e.what();
-        return e.code;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return AEON_HIP_EINVAL;
-    }
 }
 } // namespace
 
@@ -125,19 +109,4 @@ int aeon_hip_decode_jpeg_batch(aeon_hip_ctx*, int, const void* const*, const siz
 }
 int aeon_hip_synchronize(aeon_hip_ctx*, void*) { return no_device(); }
 int aeon_hip_release_stream(aeon_hip_ctx*, void*) { return no_device(); }
-const char* aeon_hip_last_error(void) { return g_err.c_str(); }
-
-// ---- host-only entry points: the real implementations ----
-int aeon_jpeg_info(const void* data, size_t size, int* w, int* h, int* n)
-{
-    return host_call([&] { aeon_hip::jpeg_info(data, size, w, h, n); });
-}
-int aeon_png_info(const void* data, size_t size, int* w, int* h, int* depth, int* ctype)
-{
-    return host_call([&] { aeon_hip::png_header(data, size, w, h, depth, ctype); });
-}
-int aeon_decode_png(const void* data, size_t size, int mode, void* dst, size_t stride, int* eb)
-{
-    return host_call([&] { aeon_hip::png_decode(data, size, mode, dst, stride, eb); });
-}
 } // extern "C"

@@ -1,5 +1,5 @@
 // video_job.hpp -- the table of the video call's zero-fill launch (video_kernels.hip), shared by the
-// host planner (stage.cpp) and the device.
+// host planner (image_path.cpp) and the device.
 #pragma once
 #include <stdint.h>
 

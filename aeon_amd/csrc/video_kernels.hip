@@ -1,7 +1,7 @@
 // video_kernels.hip -- the device code provider::video adds to the image path: the all-zero frames
 // video::transformer appends to a clip shorter than max_frame_count (src/etl_video.cpp:66-71), as
 // video::loader lays them out (etl_video.cpp:76-107).  The frames themselves run through the image
-// path's kernels unchanged (stage.cpp run_video: one job per frame, with the clip's plane stride).
+// path's kernels unchanged (image_path.cpp run_video: one job per frame, with the clip's plane stride).
 //
 // Pure stores, nothing read but the region table: HBM-write-bound.  A region starts at any byte
 // alignment (an item of 3*D*H*W bytes may be odd), so its 16-byte aligned middle goes out as 16-byte
@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "video_job.hpp"
+#include "launch.hpp"
 
 namespace aeon_hip {
 
@@ -27,7 +28,7 @@ constexpr int      kPadMaxGrid = 2048;                       // then the workgro
 
 // Work item w = (region w / bpr, part w % bpr): the region's aligned middle is stored in kPadChunk
 // pieces part, part + bpr, ...; part 0 also stores the unaligned head and tail.  The table lies in
-// device memory, written by an earlier launch or copy on the stream (stage.cpp run_video).
+// device memory, written by an earlier launch or copy on the stream (image_path.cpp run_video).
 __global__ __launch_bounds__(kPadThreads) void clip_pad(const PadRegion* regions, int n_regions, int bpr)
 {
     const auto     rsrc  = __builtin_amdgcn_make_buffer_rsrc((void*)regions, (short)0, n_regions * (int)sizeof(PadRegion), 0x00020000);

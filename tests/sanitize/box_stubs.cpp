@@ -1,5 +1,5 @@
 // box_stubs.cpp -- the device half of the box targets for the host-only sanitizer builds (next to
-// hip_stubs.cpp): there is no device, so the launch entries fail like the other stubs'.
+// aeon_amd/csrc/sanitize/no_device.cpp): there is no device, so the launch entries fail like the other stubs'.
 #include <stddef.h>
 
 #include "../../include/aeon_hip.h"

@@ -20,17 +20,8 @@
 
 #include "../../aeon_amd/csrc/jpeg.hpp"
 #include "../../aeon_amd/csrc/param_factory.hpp"
+#include "../../aeon_amd/csrc/png.hpp"
 #include "../../include/aeon_hip.h"
-
-namespace aeon_hip {
-void jpeg_info(const void* data, size_t size, int* w, int* h, int* ncomp);
-void jpeg_entropy_only(const void* data, size_t size, int* w, int* h, int* ncomp, int64_t* n_blocks,
-                       int64_t* n_values, uint64_t* hash);
-int  jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, int* h, int* ncomp,
-                              int64_t* n_blocks, int64_t* n_values, uint64_t* hash, int* rounds);
-void png_header(const void* data, size_t size, int* w, int* h, int* depth, int* ctype);
-void png_decode(const void* data, size_t size, int mode, void* dst, size_t stride, int* out_elem_bytes);
-} // namespace aeon_hip
 
 using namespace aeon_hip;
 

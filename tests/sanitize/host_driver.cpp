@@ -1,6 +1,6 @@
 // host_driver.cpp -- the decoder's host layer (aeon_amd/csrc/host.cpp) under AddressSanitizer +
 // UndefinedBehaviorSanitizer and under ThreadSanitizer (aeon's SANITIZER_TYPE builds,
-// /root/reference/CMakeLists.txt:80-101), linked against tests/sanitize/hip_stubs.cpp instead of the
+// /root/reference/CMakeLists.txt:80-101), linked against aeon_amd/csrc/sanitize/no_device.cpp instead of the
 // HIP runtime.  What runs: loader-config parsing and verify_config (valid and malformed configs),
 // provider_factory, the pinned thread_pool (creation, pinning, teardown, first-exception rethrow), the
 // window draws on the pool (draw_window: every record on the pool with its slot engine, the lighting
@@ -8,7 +8,8 @@
 // (an element of size 0) and the windows after it, the node slicing, and cpu lists; and the host half of a
 // decode window (batch_decoder::plan: inspect, draw and the arena layout, which needs no device) for images
 // (decoded, JPEG, PNG), label + image, image + boundingbox, localization_rcnn + boundingbox and video windows,
-// each checked against the arena's rule as the driver restates it.
+// each checked against the arena's rule as the driver restates it; and the refusals of the host-only C entries
+// (aeon_amd/csrc/abi_host.cpp, linked as the library links it).
 //
 // Usage: host_driver [rounds]   One line per case, "name<TAB>ok ..." or "name<TAB>FAIL ..."; exit 1 if
 // any case failed (a sanitizer finding aborts the run with its own exit status).
@@ -362,6 +363,50 @@ void plan_cases()
     }
 }
 
+// The host-only entries the layer calls are the library's own (aeon_amd/csrc/abi_host.cpp): calls that only
+// the real wrappers refuse -- null pointers, an unknown decode mode, a stride shorter than a row -- each with
+// AEON_HIP_EINVAL and a message.
+void abi_refusals()
+{
+    // a valid 2x2 8-bit RGB PNG: IHDR, one IDAT (two rows, filter None), IEND
+    std::vector<uint8_t> png = png_header(2, 2).bytes;
+    auto                 chunk = [&](const char* type, const std::vector<uint8_t>& body) {
+        std::vector<uint8_t> c(type, type + 4);
+        c.insert(c.end(), body.begin(), body.end());
+        for (uint8_t b : be((uint32_t)body.size(), 4)) png.push_back(b);
+        png.insert(png.end(), c.begin(), c.end());
+        for (uint8_t b : be((uint32_t)crc32(0L, c.data(), (uInt)c.size()), 4)) png.push_back(b);
+    };
+    const uint8_t        rows[14] = {0, 10, 20, 30, 40, 50, 60, 0, 70, 80, 90, 100, 110, 120};
+    std::vector<uint8_t> z(compressBound(sizeof(rows)));
+    uLongf               zn = (uLongf)z.size();
+    compress(z.data(), &zn, rows, sizeof(rows));
+    z.resize(zn);
+    chunk("IDAT", z);
+    chunk("IEND", {});
+    const std::vector<uint8_t> jpg = jpeg_header(16, 16).bytes;
+
+    std::string why;
+    auto        refused = [&](const char* what, const char* text, int rc) { // (text: the wrapper's own message)
+        const std::string msg = aeon_hip_last_error();
+        if (why.empty() && (rc != AEON_HIP_EINVAL || msg.find(text) == std::string::npos)) why = std::string(what) + ": rc " + std::to_string(rc) + " (" + msg + ")";
+    };
+    int     w = 0, h = 0, depth = 0, ctype = 0, comps = 0, eb = 0;
+    uint8_t dst[2 * 2 * 3 * 2] = {0};
+    if (aeon_png_info(png.data(), png.size(), &w, &h, &depth, &ctype) != 0 || w != 2 || h != 2 ||
+        aeon_decode_png(png.data(), png.size(), AEON_PNG_BGR8, dst, 6, &eb) != 0 || eb != 1 || dst[0] != 30 || dst[11] != 100)
+        why = std::string("the 2x2 PNG does not decode: ") + aeon_hip_last_error();
+    if (aeon_jpeg_info(jpg.data(), jpg.size(), &w, &h, &comps) != 0 || w != 16 || h != 16)
+        why = std::string("the JPEG header does not parse: ") + aeon_hip_last_error();
+    refused("png_info null data", "null argument", aeon_png_info(nullptr, png.size(), &w, &h, &depth, &ctype));
+    refused("png_info null out", "null argument", aeon_png_info(png.data(), png.size(), &w, nullptr, &depth, &ctype));
+    refused("jpeg_info null data", "null argument", aeon_jpeg_info(nullptr, jpg.size(), &w, &h, &comps));
+    refused("jpeg_info null out", "null argument", aeon_jpeg_info(jpg.data(), jpg.size(), &w, &h, nullptr));
+    refused("decode_png unknown mode", "unknown PNG decode mode", aeon_decode_png(png.data(), png.size(), AEON_PNG_ANYDEPTH + 1, dst, 6, &eb));
+    refused("decode_png stride 1", "stride too small", aeon_decode_png(png.data(), png.size(), AEON_PNG_BGR8, dst, 1, &eb));
+    report("abi_refusals", why.empty(), why.empty() ? "6 calls refused with AEON_HIP_EINVAL and a message" : why);
+}
+
 } // namespace
 
 int main(int argc, char** argv)
@@ -377,6 +422,7 @@ int main(int argc, char** argv)
     failed_window("failed_window_c3", c3);
     failed_window("failed_window_c2", c2);
     plan_cases();
+    abi_refusals();
 
     // pools started and stopped back to back (thread start-up, pinning and shutdown races)
     bool ok = true;

@@ -1,5 +1,5 @@
 // rcnn_stubs.cpp -- the device half of the localization_rcnn targets for the host-only sanitizer builds
-// (next to hip_stubs.cpp and box_stubs.cpp): there is no device, so the launch entries fail.
+// (next to aeon_amd/csrc/sanitize/no_device.cpp and box_stubs.cpp): there is no device, so the launch entries fail.
 #include <stddef.h>
 
 #include "../../include/aeon_hip.h"

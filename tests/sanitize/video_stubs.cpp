@@ -1,5 +1,5 @@
 // video_stubs.cpp -- the device half of the video provider for the host-only sanitizer builds (next to
-// hip_stubs.cpp, box_stubs.cpp and rcnn_stubs.cpp): there is no device, so the launch entry fails.
+// aeon_amd/csrc/sanitize/no_device.cpp, box_stubs.cpp and rcnn_stubs.cpp): there is no device, so the launch entry fails.
 #include <stddef.h>
 
 #include "../../include/aeon_hip.h"

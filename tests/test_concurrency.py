@@ -3,7 +3,7 @@
 aeon's loader holds one provider::image and one provider::pixelmask per decode stage, and a host may
 run more than one stage per process: their calls reach one aeon_hip_ctx from different threads.  The
 context serialises a call's host half under its mutex (ring slot, job table written into HBM through
-the BAR by that one thread, read back before the launch -- stage.cpp publish_table), then the kernels
+the BAR by that one thread, read back before the launch -- context.hpp publish_table), then the kernels
 run on the caller's stream.  Here three threads hammer one context together:
 
   * an image stager (C2 params, pageable batch buffers: one launch per window + D2H per batch),

@@ -277,7 +277,7 @@ def test_decoder_after_contexts_come_and_go():
     """Contexts created and destroyed before a decode (each with its HBM job tables): the later
     device allocations still get every kernel write.  Freed uncached table blocks once came back as
     ordinary device memory that lost 128-byte lines of a contrast record's output (zeros); the tables
-    are pooled for the process since (stage.cpp free_vram)."""
+    are pooled for the process since (context.cpp free_vram)."""
     od = C.out_desc_for(C.IMAGE_224, C.C3_AUG)
     f = A.ParamFactory(C.C3_AUG)
     eng = A.seed_slots(4, 1)

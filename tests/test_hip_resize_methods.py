@@ -177,7 +177,7 @@ def test_resize_methods_final_output(ctx, method, case):
 @pytest.mark.parametrize("method", list(METHODS))
 def test_resize_c2_batch(ctx, method):
     """A C2 batch of 64 random crops with the method set.  LANCZOS4: its taps are finished on the GPU
-    from the host's libm sin / cos (stage.cpp lanczos4_inputs -> resize_kernels.hip lanczos4_taps), as
+    from the host's libm sin / cos (plan.cpp lanczos4_inputs -> resize_kernels.hip lanczos4_taps), as
     many distinct fractions per axis as output columns and rows, against the oracle's taps computed on
     the host from end to end.  AREA: the batch holds both method classes (resizeArea_ records on
     resize_generic, upscaled axes on resize_sep<2>), launched concurrently on the slot's side stream and
@@ -195,7 +195,7 @@ def test_resize_c2_batch(ctx, method):
 
 @pytest.mark.parametrize("method", list(METHODS))
 def test_resize_shared_axes(ctx, method):
-    """Records sharing crop sizes (LANCZOS4: one tap array per distinct axis, stage.cpp GrPlan::axis_taps)
+    """Records sharing crop sizes (LANCZOS4: one tap array per distinct axis, plan.cpp GrPlan::axis_taps)
     at different crop positions, flips and source images, mixed with a record of another size and an
     identity record, equal the oracle record by record."""
     imgs = [A.synthetic_image(80 + i, 300, 260, 3) for i in range(9)]

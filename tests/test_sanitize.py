@@ -158,9 +158,11 @@ HOST_TSAN = os.path.join(ROOT, "aeon_amd", "csrc", "build_sanitize", "host_drive
 
 def _host_driver(target, exe, env_extra):
     """tests/sanitize/host_driver.cpp over host.cpp + stager.cpp with the HIP runtime stubbed
-    (tests/sanitize/hip_stubs.cpp): loader configs, the pinned thread_pool, window draws on the pool
-    against serial draws over odd and even windows, a failing window, concurrent stager stages, and the host
-    half of a decode window (batch_decoder::plan) for every provider kind against the arena's layout rule."""
+    (aeon_amd/csrc/sanitize/no_device.cpp): loader configs, the pinned thread_pool, window draws on the pool
+    against serial draws over odd and even windows, a failing window, concurrent stager stages, the host
+    half of a decode window (batch_decoder::plan) for every provider kind against the arena's layout rule,
+    and the refusals of the library's own host-only entries (abi_host.cpp: null pointers, an unknown PNG
+    mode, a stride shorter than a row)."""
     if not os.path.exists("/opt/rocm/llvm/bin/clang++"):
         pytest.skip("no clang with sanitizer runtimes")
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "aeon_amd", "csrc"), target])
@@ -178,6 +180,7 @@ def test_host_layer_under_asan_ubsan():
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     assert len(lines) >= 20 and all("\tok" in l for l in lines), r.stdout
     assert sum(l.startswith("plan_") for l in lines) == 7, r.stdout
+    assert "abi_refusals\tok 6 calls refused with AEON_HIP_EINVAL and a message" in lines, r.stdout
 
 
 def test_host_layer_under_tsan():
@@ -188,3 +191,4 @@ def test_host_layer_under_tsan():
     assert "ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
     assert len(lines) >= 20 and all("\tok" in l for l in lines), r.stdout
     assert sum(l.startswith("plan_") for l in lines) == 7, r.stdout
+    assert "abi_refusals\tok 6 calls refused with AEON_HIP_EINVAL and a message" in lines, r.stdout
