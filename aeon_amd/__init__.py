@@ -227,6 +227,11 @@ def lib():
         L.aeon_decode_png.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
                                       P(ctypes.c_int)]
         L.aeon_hip_decode_jpeg_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc), vp, vp]
+        L.aeon_hip_decode_png_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ctypes.c_int), P(ImgDesc),
+                                                vp, vp]
+        L.aeon_png_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int), P(ctypes.c_int64)]
+        L.aeon_png_decoder_route.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
+        L.aeon_png_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
         L.aeon_avi_frames.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(AviFrame), ctypes.c_int] + [P(ctypes.c_int)] * 3
         L.aeon_avi_last_error.restype = ctypes.c_char_p
         L.aeon_hip_video_batch.argtypes = [vp, ctypes.c_int, P(ctypes.c_int32), P(ImgDesc), vp, P(AugParams), ctypes.c_int,
@@ -643,6 +648,32 @@ def decode_png(data, mode=PNG_BGR8):
     return out
 
 
+def png_host_stage(data, mode=PNG_BGR8):
+    """The PNG batch decode's host work for one file (aeon_png_host_stage): (does the device take the file's
+    inflate?, bytes staged for the H2D)."""
+    g, nb = ctypes.c_int(), ctypes.c_int64()
+    _check(lib().aeon_png_host_stage(bytes(data), len(data), mode, ctypes.byref(g), ctypes.byref(nb)))
+    return bool(g.value), nb.value
+
+
+def png_decoder_route(data):
+    """Does a Decoder send this encoded PNG element through the device stage (aeon_png_decoder_route)?"""
+    g = ctypes.c_int()
+    _check(lib().aeon_png_decoder_route(bytes(data), len(data), ctypes.byref(g)))
+    return bool(g.value)
+
+
+def png_gpu_emulate(data, mode=PNG_BGR8):
+    """decode_png through the PNG stage's kernel code run on the host (aeon_png_gpu_emulate).  AeonHipError
+    for a file the stage leaves to the host decoder, or one the device would report as corrupt."""
+    w, h, d, c = png_info(data)
+    wide = mode == PNG_ANYDEPTH and d == 16 and c != 3
+    cn = 3 if mode == PNG_BGR8 else 1
+    out = np.zeros((h, w, cn) if cn == 3 else (h, w), np.uint16 if wide else np.uint8)
+    _check(lib().aeon_png_gpu_emulate(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
+    return out
+
+
 def unbiased_round(x):
     """nervana::unbiased_round (aeon src/util.cpp:212-239)."""
     r = ctypes.c_int64()
@@ -790,15 +821,28 @@ class Context:
         _check(lib().aeon_hip_decode_jpeg_batch(self._h, n, ptrs, sizes, d, ctypes.c_void_p(dst_ptr),
                                                 ctypes.c_void_p(stream or 0)))
 
+    def decode_png_batch(self, files, modes, descs, dst_ptr, stream=0):
+        """decode_png of PNG files into device memory (aeon_hip_decode_png_batch): files = list of bytes (or
+        a JpegFiles, marshalled once), modes[i] = PNG_BGR8 / PNG_GRAY8 / PNG_ANYDEPTH, descs[i] = where
+        record i goes (HWC; ANYDEPTH of a 16-bit file: native uint16)."""
+        jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
+        n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
+        m = modes if isinstance(modes, ctypes.Array) else (ctypes.c_int * n)(*[int(x) for x in modes])
+        d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
+        if len(m) < n or len(d) < n:
+            raise ValueError(f"{len(m)} modes / {len(d)} descriptors for {n} files")
+        _check(lib().aeon_hip_decode_png_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
+                                               ctypes.c_void_p(stream or 0)))
+
     def set_timing(self, every=1):
         """Time the launches of one call in `every` (0 = off) with HIP events on their stream."""
         _check(lib().aeon_hip_set_timing(self._h, int(every)))
 
     def kernel_times(self):
-        """{'augment'|'stats'|'pre'|'jpeg': (total_ms, total_algorithmic_bytes, launches)}"""
-        ms, by, ct = (ctypes.c_double * 4)(), (ctypes.c_double * 4)(), (ctypes.c_long * 4)()
-        _check(lib().aeon_hip_kernel_times(self._h, 4, ms, by, ct))
-        return {k: (ms[i], by[i], ct[i]) for i, k in enumerate(("augment", "stats", "pre", "jpeg"))}
+        """{'augment'|'stats'|'pre'|'jpeg'|'png': (total_ms, total_algorithmic_bytes, launches)}"""
+        ms, by, ct = (ctypes.c_double * 5)(), (ctypes.c_double * 5)(), (ctypes.c_long * 5)()
+        _check(lib().aeon_hip_kernel_times(self._h, 5, ms, by, ct))
+        return {k: (ms[i], by[i], ct[i]) for i, k in enumerate(("augment", "stats", "pre", "jpeg", "png"))}
 
     def synchronize(self, stream=0):
         _check(lib().aeon_hip_synchronize(self._h, ctypes.c_void_p(stream or 0)))

@@ -2,6 +2,7 @@
 // decoder, the JPEG header and entropy probes, aeon's rounding and scale helpers, and the thread-local text
 // behind aeon_hip_last_error.  No entry touches a device, and nothing here needs the runtime: the sanitizer
 // builds link this file as it is.
+#include <cstdint>
 #include <mutex>
 #include <random>
 #include <string>
@@ -103,6 +104,53 @@ int aeon_decode_png(const void* data, size_t size, int mode, void* dst, size_t s
         const size_t eb = (mode == AEON_PNG_ANYDEPTH && depth == 16 && ctype != 3) ? 2 : 1;
         if (stride < (size_t)w * (mode == AEON_PNG_BGR8 ? 3 : 1) * eb) fail(AEON_HIP_EINVAL, "stride too small");
         png_decode(data, size, mode, dst, stride, elem_bytes);
+        return 0;
+    });
+}
+
+int aeon_png_host_stage(const void* data, size_t size, int mode, int* gpu_route, int64_t* staged_bytes)
+{
+    return guarded([&] {
+        if (!data || !gpu_route || !staged_bytes) fail(AEON_HIP_EINVAL, "null argument");
+        if (mode < AEON_PNG_BGR8 || mode > AEON_PNG_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown PNG decode mode");
+        PngPlan P;
+        png_plan(data, size, mode, P);
+        *gpu_route = P.route;
+        if (P.route) {
+            PngJob               J;
+            std::vector<uint8_t> comp(P.clen + 8);
+            png_stage(data, size, mode, P, J, comp.data());
+            *staged_bytes = (int64_t)(((P.clen + 7) & ~(size_t)7) + sizeof(PngJob));
+        } else {
+            const size_t         stride = (size_t)P.w * P.channels * P.elem_bytes;
+            std::vector<uint8_t> px(stride * P.h);
+            png_decode(data, size, mode, px.data(), stride, nullptr);
+            *staged_bytes = (int64_t)px.size();
+        }
+        return 0;
+    });
+}
+
+int aeon_png_decoder_route(const void* data, size_t size, int* device)
+{
+    return guarded([&] {
+        if (!data || !device) fail(AEON_HIP_EINVAL, "null argument");
+        *device = png_routed(data, size) ? 1 : 0;
+        return 0;
+    });
+}
+
+int aeon_png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        if (mode < AEON_PNG_BGR8 || mode > AEON_PNG_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown PNG decode mode");
+        PngPlan P;
+        png_plan(data, size, mode, P);
+        if (stride < (size_t)P.w * P.channels * P.elem_bytes || stride > INT32_MAX) fail(AEON_HIP_EINVAL, "stride too small");
+        const int r = png_gpu_emulate(data, size, mode, dst, stride);
+        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "PNG: the file is not routed to the device (interlaced, or too wide)");
+        if (r < 0) fail(AEON_HIP_EDEVICE, "PNG: image data corrupt or truncated (GPU stage)");
         return 0;
     });
 }

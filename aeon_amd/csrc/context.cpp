@@ -34,7 +34,8 @@ std::string device_error_text(int err)
                 {64, "rotation source box exceeds the launch's LDS"},
                 {128, "generic resize footprint exceeds the launch's LDS"},
                 {256, "JPEG entropy-coded data corrupt or truncated (GPU Huffman decoder)"},
-                {512, "separable resize band wider than its workgroup"}};
+                {512, "separable resize band wider than its workgroup"},
+                {1024, "PNG image data corrupt or truncated (GPU inflate / unfilter)"}};
     std::string s;
     for (const auto& b : bits)
         if (err & b.bit) s += (s.empty() ? "" : "; ") + std::string(b.what);
@@ -305,6 +306,7 @@ aeon_hip_ctx::~aeon_hip_ctx()
     }
     (void)hipSetDevice(device);
     jpeg_state_destroy(jpeg);
+    png_stage_destroy(png);
     if (!open_slots.empty()) (void)hipStreamSynchronize(open_stream);
     for (Slot& s : slots)
         if (s.pending) (void)hipEventSynchronize(slots[s.cover].done);
@@ -486,7 +488,7 @@ int aeon_hip_kernel_times(aeon_hip_ctx* ctx, int kinds, double* ms, double* byte
             ctx->free_timers.push_back(t);
         }
         ctx->timers.clear();
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < AEON_HIP_TIMER_KINDS; k++) {
             if (k < kinds) ms[k] = ctx->ms[k], bytes[k] = ctx->bytes[k], count[k] = ctx->count[k];
             ctx->ms[k] = ctx->bytes[k] = 0, ctx->count[k] = 0;
         }

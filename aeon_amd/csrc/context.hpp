@@ -52,10 +52,14 @@ struct Slot {
     size_t     shifts_cap = 0;
 };
 
+struct PngStage; // image_path.cpp
+void png_stage_destroy(PngStage* s);
+
 constexpr int kTimerJpeg = 3; // KernelTimer kind of the JPEG kernels (after the KernelMode kinds)
+constexpr int kTimerPng  = 4; // ... of the PNG kernels
 struct KernelTimer {
     hipEvent_t start, stop;
-    int        kind;   // KernelMode, or kTimerJpeg
+    int        kind;   // KernelMode, kTimerJpeg or kTimerPng
     double     bytes;  // algorithmic bytes of the launch
 };
 
@@ -101,6 +105,7 @@ struct aeon_hip_ctx {
     std::vector<int>     direct_order;       // (run_direct) their table order: largest crop first
     aeon_hip::CallPlan   plan;               // (run_batch) the call's plan
     aeon_hip::JpegState* jpeg = nullptr;     // JPEG decode stage (pool, staging ring), on first use
+    aeon_hip::PngStage*  png  = nullptr;     // PNG decode stage (staging ring, scratch), on first use
     aeon_hip::thread_pool* host_pool = nullptr; // the owning decoder's pool (ctx_share_pool), for the JPEG stage
     // localization_rcnn: the anchor table of the last config seen stays resident (uploaded once), and the
     // direct call's engine end states pass through a small device array
@@ -133,13 +138,13 @@ struct aeon_hip_ctx {
     // optional per-launch timing (aeon_hip_set_timing): events recorded on the launch stream
     bool                     timing = false;
     std::vector<KernelTimer> timers, free_timers;
-    double                   ms[4]    = {0, 0, 0, 0};
+    double                   ms[AEON_HIP_TIMER_KINDS]    = {};
     // AEON_HIP_HOST_PROFILE=1: host time per run_batch phase, printed when the context is destroyed
     bool                     host_profile = false;
     std::vector<double>      host_ns[8];  // per call, per phase
     long                     host_calls   = 0;
-    double                   bytes[4] = {0, 0, 0, 0};
-    long                     count[4] = {0, 0, 0, 0};
+    double                   bytes[AEON_HIP_TIMER_KINDS] = {};
+    long                     count[AEON_HIP_TIMER_KINDS] = {};
 #ifdef AEON_HIP_TRACE
     uint32_t*                trace = nullptr; // AEON_HIP_TRACE_PTR, read once at ctx_create
 #endif

@@ -1,6 +1,7 @@
 // host.cpp -- provider plugin surface + decode stage of the HIP image path (see host.hpp).
 #include "host.hpp"
 #include "box_job.hpp"
+#include "png.hpp"
 #include "rcnn_job.hpp"
 
 #include <hip/hip_runtime.h>
@@ -252,8 +253,8 @@ public:
     }
     // image::extractor::extract of an encoded element: the file's header gives the decoded size; it is decoded
     // with the provider's channel count (CV_LOAD_IMAGE_COLOR / GRAYSCALE for images, CV_LOAD_IMAGE_ANYDEPTH
-    // for pixel masks).  PNG files are decoded on the host pool while staging (png_host.cpp), JPEG files on
-    // the device.
+    // for pixel masks).  JPEG files are decoded on the device, and so are the PNG files the PNG stage's routing
+    // rule gives it (png.hpp); the others (Adam7, very wide rows) on the host pool while staging (png_host.cpp).
     void inspect(window_part&, int idx, decoded_element& e) const override
     {
         static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
@@ -262,6 +263,7 @@ public:
             int depth = 0, ctype = 0;
             check(aeon_png_info(e.data, e.size, &e.width, &e.height, &depth, &ctype));
             e.encoded    = false;
+            e.png_device = png_routed(e.data, e.size);
             e.png_mode   = m_mask ? AEON_PNG_ANYDEPTH : (cn == 3 ? AEON_PNG_BGR8 : AEON_PNG_GRAY8);
             e.channels   = m_mask ? 1 : cn;
             e.elem_bytes = (m_mask && depth == 16 && ctype != 3) ? 2 : 1;
@@ -281,16 +283,17 @@ public:
     void layout_record(window_part& part, arena_region r, int idx, const decoded_element& e, size_t& offset,
                        jpeg_list& jpegs) const override
     {
-        if (r != (e.encoded ? arena_region::device_decoded : arena_region::staged)) return;
+        if (r != (e.encoded || e.png_device ? arena_region::device_decoded : arena_region::staged)) return;
         const size_t b = (size_t)std::max(e.width, 0) * std::max(e.height, 0) * std::max(e.channels, 0) * e.elem_bytes;
         part.descs[idx] = aeon_img_desc{offset, e.width, e.height, e.width * e.channels * e.elem_bytes, e.channels,
                                         e.elem_bytes == 2 ? 2 : 0, 0};
         if (e.encoded) jpegs.add(e.data, e.size, part.descs[idx]);
+        if (e.png_device) jpegs.png.add(e.data, e.size, e.png_mode, part.descs[idx]);
         offset += arena_align(b);
     }
     void stage_record(const decode_window& w, size_t k, int idx, const decoded_element& e) const override
     {
-        if (e.encoded) return; // decoded on the device, straight into the source arena
+        if (e.encoded || e.png_device) return; // decoded on the device, straight into the source arena
         const size_t row = (size_t)e.width * e.channels * e.elem_bytes;
         uint8_t*     dst = w.arena + w.parts[k]->descs[idx].offset;
         if (e.png_mode >= 0) { // extract on this pool thread, straight into the pinned arena
@@ -1413,6 +1416,10 @@ void batch_decoder::stage_sources(window_slot& ws, window_plan& p, hipStream_t s
         for (size_t f = 0; f < j.files.size(); f += kJpegCallFiles)
             check(aeon_hip_decode_jpeg_batch(m_ctx, (int)std::min(kJpegCallFiles, j.files.size() - f), j.files.data() + f,
                                              j.sizes.data() + f, j.descs.data() + f, ws.dev_src, stream));
+        for (size_t f = 0; f < j.png.files.size(); f += kJpegCallFiles)
+            check(aeon_hip_decode_png_batch(m_ctx, (int)std::min(kJpegCallFiles, j.png.files.size() - f), j.png.files.data() + f,
+                                            j.png.sizes.data() + f, j.png.modes.data() + f, j.png.descs.data() + f, ws.dev_src,
+                                            stream));
     }
 }
 

@@ -78,7 +78,9 @@ struct decoded_element {
     int            width = 0, height = 0, channels = 0, stride = 0;
     size_t         size    = 0;     // encoded bytes
     bool           encoded = false; // JPEG file: decoded on the device (jpeg_host.cpp)
-    int            png_mode   = -1; // PNG file: AEON_PNG_* decode on the host while staging
+    int            png_mode   = -1; // PNG file: its AEON_PNG_* decode mode
+    bool           png_device = false; // ... decoded on the device (the PNG stage, png.hpp's routing rule), else on
+                                       // the host pool while staging
     int            elem_bytes = 1;  // bytes per sample (2: a 16-bit mask / depth map)
 };
 
@@ -105,8 +107,22 @@ struct decode_window {
 enum class arena_region { box_tables, label_items, staged, device_decoded };
 inline size_t arena_align(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
-// The JPEG files one provider wants decoded into the device-decoded region, with their destinations
+// The PNG files one provider wants decoded into the device-decoded region, with their modes and destinations
+struct png_list {
+    std::vector<const void*>   files;
+    std::vector<size_t>        sizes;
+    std::vector<int>           modes;
+    std::vector<aeon_img_desc> descs;
+    void add(const void* file, size_t size, int mode, const aeon_img_desc& d)
+    {
+        files.push_back(file), sizes.push_back(size), modes.push_back(mode), descs.push_back(d);
+    }
+};
+
+// The JPEG files one provider wants decoded into the device-decoded region, with their destinations; its PNG
+// files travel beside them
 struct jpeg_list {
+    png_list                   png;
     std::vector<const void*>   files;
     std::vector<size_t>        sizes;
     std::vector<aeon_img_desc> descs;

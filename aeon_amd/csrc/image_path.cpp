@@ -1,13 +1,14 @@
 // image_path.cpp -- the image path of the device half: a call's records through run_direct (one launch),
 // run_records (contrast records in one launch) or run_batch's multi-pass launches over the CallPlan that
 // plan.cpp returns, run_video on top of them, and the C entries for augment, mask, pair, depthmap, video,
-// transpose and the JPEG batch.
+// transpose, the JPEG batch and the PNG batch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -22,6 +23,7 @@
 #include "param_factory.hpp"
 #include "plan.hpp"
 #include "plan_record.hpp"
+#include "png.hpp"
 #include "video_job.hpp"
 
 using namespace aeon_hip;
@@ -634,7 +636,144 @@ int run_video(aeon_hip_ctx* ctx, int n, const int32_t* frame_counts, const aeon_
 
 } // namespace
 
+// ---- PNG stage ------------------------------------------------------------------------------------
+// Per-context state of aeon_hip_decode_png_batch: a two-deep ring of pinned staging, its device copy and the
+// device scratch of the inflated scanlines (a call reuses a set once the call before last is done with it).
+struct aeon_hip::PngStage {
+    struct Set {
+        hipEvent_t done    = nullptr;
+        bool       pending = false;
+        uint8_t *  pinned = nullptr, *dev = nullptr, *scratch = nullptr;
+        size_t     pinned_cap = 0, dev_cap = 0, scratch_cap = 0;
+    } sets[2];
+    int        next = 0;
+    std::mutex mu;
+};
+
+void aeon_hip::png_stage_destroy(PngStage* s)
+{
+    if (!s) return;
+    for (auto& st : s->sets) {
+        if (st.pending) (void)hipEventSynchronize(st.done);
+        if (st.done) (void)hipEventDestroy(st.done);
+        if (st.pinned) (void)hipHostFree(st.pinned);
+        if (st.dev) (void)hipFree(st.dev);
+        if (st.scratch) (void)hipFree(st.scratch);
+    }
+    delete s;
+}
+
+namespace {
+
+// The decode call: each file's chunk walk (png_plan) on the pool, the layout of the call's staging -- the jobs,
+// the routed files' zlib streams, the host-decoded files' pixels -- filled on the pool, one H2D, then
+// png_inflate and png_unfilter over the jobs and a strided device copy per host-decoded file, all on `stream`.
+int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+            const aeon_img_desc* descs, void* dst_base, hipStream_t stream)
+{
+    if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !modes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
+    if (n == 0) return 0;
+    HIP_OK(hipSetDevice(ctx->device));
+    if (!ctx->png) ctx->png = new PngStage();
+    PngStage&                   S = *ctx->png;
+    std::lock_guard<std::mutex> lock(S.mu);
+    const auto each = [&](const std::function<void(int)>& f) {
+        if (ctx->host_pool) ctx->host_pool->run(n, f);
+        else
+            for (int i = 0; i < n; i++) f(i);
+    };
+    std::vector<PngPlan> plans(n);
+    each([&](int i) {
+        if (!data[i] || !sizes[i]) fail(AEON_HIP_EINVAL, "PNG: empty file");
+        if (modes[i] < AEON_PNG_BGR8 || modes[i] > AEON_PNG_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown PNG decode mode");
+        PngPlan& P = plans[i];
+        png_plan(data[i], sizes[i], modes[i], P);
+        const aeon_img_desc& d = descs[i];
+        if (d.width != P.w || d.height != P.h)
+            fail(AEON_HIP_EINVAL, "PNG: record " + std::to_string(i) + " is " + std::to_string(P.w) + "x" + std::to_string(P.h) +
+                                      ", its descriptor says " + std::to_string(d.width) + "x" + std::to_string(d.height));
+        if (d.stride < 0 || (size_t)d.stride < (size_t)P.w * P.channels * P.elem_bytes) fail(AEON_HIP_EINVAL, "stride too small");
+    });
+    // layout: the jobs, then per file its stream (8-byte aligned and padded) or its pixels (16-byte aligned)
+    std::vector<size_t> at(n), raw_at(n);
+    std::vector<int>    job_of(n, -1);
+    int                 n_gpu = 0, lds = 0;
+    for (int i = 0; i < n; i++)
+        if (plans[i].route) job_of[i] = n_gpu++;
+    size_t total = (size_t)n_gpu * sizeof(PngJob), scratch = 0;
+    for (int i = 0; i < n; i++) {
+        const PngPlan& P = plans[i];
+        total            = (total + 15) & ~(size_t)15;
+        at[i]            = total;
+        if (P.route) {
+            total += ((P.clen + 7) & ~(size_t)7) + 8;
+            raw_at[i] = scratch;
+            scratch += ((P.need + 15) & ~(size_t)15) + 16;
+        } else {
+            total += (size_t)P.w * P.channels * P.elem_bytes * P.h;
+        }
+    }
+    PngStage::Set& st = S.sets[S.next];
+    S.next ^= 1;
+    if (!st.done) HIP_OK(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    if (st.pending) HIP_OK(hipEventSynchronize(st.done));
+    st.pending = false;
+    if (total > st.pinned_cap) grow(st.pinned, st.pinned_cap, total + total / 4, true);
+    if (total > st.dev_cap) grow(st.dev, st.dev_cap, total + total / 4, false);
+    if (scratch > st.scratch_cap) grow(st.scratch, st.scratch_cap, scratch + scratch / 4, false);
+    PngJob* jobs = (PngJob*)st.pinned;
+    each([&](int i) {
+        const PngPlan& P = plans[i];
+        uint8_t*       p = st.pinned + at[i];
+        if (!P.route) {
+            png_decode(data[i], sizes[i], modes[i], p, (size_t)P.w * P.channels * P.elem_bytes, nullptr);
+            return;
+        }
+        PngJob& J = jobs[job_of[i]];
+        png_stage(data[i], sizes[i], modes[i], P, J, p);
+        std::memset(p + P.clen, 0, ((P.clen + 7) & ~(size_t)7) + 8 - P.clen);
+        J.comp   = (uint64_t)(st.dev + at[i]);
+        J.raw    = (uint64_t)(st.scratch + raw_at[i]);
+        J.out    = (uint64_t)dst_base + descs[i].offset;
+        J.stride = descs[i].stride;
+    });
+    for (int i = 0; i < n; i++)
+        if (plans[i].route) lds = std::max(lds, png_unfilter_lds(jobs[job_of[i]].rowb));
+    KernelTimer t{};
+    bool        timed = false;
+    if (ctx->timing && n_gpu) {
+        std::lock_guard<std::mutex> tl(ctx->mu);
+        if ((timed = take_timing(ctx))) t = take_timer(ctx, kTimerPng, (double)scratch);
+    }
+    HIP_OK(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, stream));
+    if (timed) HIP_OK(hipEventRecord(t.start, stream));
+    HIP_OK(launch_png((const PngJob*)st.dev, n_gpu, lds, stream_error(ctx, stream), stream));
+    if (timed) {
+        HIP_OK(hipEventRecord(t.stop, stream));
+        std::lock_guard<std::mutex> tl(ctx->mu);
+        ctx->timers.push_back(t);
+    }
+    for (int i = 0; i < n; i++) {
+        const PngPlan& P = plans[i];
+        if (P.route) continue;
+        const size_t rowb = (size_t)P.w * P.channels * P.elem_bytes;
+        HIP_OK(hipMemcpy2DAsync((uint8_t*)dst_base + descs[i].offset, (size_t)descs[i].stride, st.dev + at[i], rowb, rowb,
+                                (size_t)P.h, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_OK(hipEventRecord(st.done, stream));
+    st.pending = true;
+    return 0;
+}
+
+} // namespace
+
 extern "C" {
+
+int aeon_hip_decode_png_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                              const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return guarded([&] { return run_png(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream); });
+}
 
 int aeon_hip_transpose_batch(aeon_hip_ctx* ctx, const void* src_dev, void* dst_dev, int64_t rows, int64_t cols,
                              int element_size, void* stream)

@@ -1,8 +1,13 @@
 // png_host.cpp -- the PNG half of image::extractor::extract / pixel_mask::extractor::extract (aeon
 // src/etl_image.cpp:83-99, src/etl_pixel_mask.cpp:30-53): cv::imdecode over libpng, restated on
-// zlib's inflate.  Host code by nature: inflate is a serial bit stream and the PNG row filters
-// (Sub / Up / Average / Paeth) chain every row to the one above and every pixel to the one on its
-// left, so a record decodes on one decode-pool thread straight into the pinned staging arena.
+// zlib's inflate.  Two users: png_decode, the whole decode of one file on the calling thread (aeon_decode_png,
+// and the files the PNG stage leaves to the host: Adam7, very wide rows), and the host half of the PNG stage
+// (aeon_hip_decode_png_batch): png_plan / png_stage keep what is cheap and needs no pixels -- signature, chunk
+// walk, CRCs, IHDR, PLTE, the IDAT payloads copied back to back, the zlib header -- and leave inflate, the row
+// filters and the colour reduction to the kernels (png_kernels.hip).  Within one file inflate is a serial bit
+// stream and the filters chain rows and pixels, but a decode window holds hundreds of files: the stage runs a
+// wave per file, with wide copies and a skewed wavefront across rows inside it.  png_gpu_emulate runs the
+// kernels' own code (png_inflate.hpp) on the host.
 //
 // Output forms (what OpenCV 2.4's PngDecoder asks libpng for):
 //   AEON_PNG_BGR8   -- CV_LOAD_IMAGE_COLOR: 8-bit BGR.  16-bit samples keep their high byte
@@ -27,6 +32,7 @@
 #include "../../include/aeon_hip.h"
 #include "error.hpp" // jpeg_error: an error carrying its AEON_HIP_E* code
 #include "png.hpp"
+#include "png_inflate.hpp"
 
 namespace aeon_hip {
 namespace {
@@ -44,8 +50,18 @@ struct PngHeader {
     int     npal         = 0;
 };
 
+// Where parse leaves the IDAT stream: appended to `vec`, copied to `flat`, or only measured; its first two
+// bytes (the zlib header) are kept either way.
+struct IdatSink {
+    std::vector<uint8_t>* vec  = nullptr;
+    uint8_t*              flat = nullptr;
+    size_t                len  = 0;
+    uint8_t               head[2] = {0, 0};
+    bool                  crc = true; // check the critical chunks' CRCs (a second walk of a file need not)
+};
+
 // Walk the chunks: IHDR, PLTE, the IDAT stream (concatenated); CRCs of critical chunks checked.
-void parse(const uint8_t* d, size_t size, PngHeader& H, std::vector<uint8_t>* idat)
+void parse(const uint8_t* d, size_t size, PngHeader& H, IdatSink* idat)
 {
     if (size < 8 || std::memcmp(d, kSig, 8) != 0) png_bad("not a PNG file (bad signature)");
     size_t p        = 8;
@@ -56,7 +72,7 @@ void parse(const uint8_t* d, size_t size, PngHeader& H, std::vector<uint8_t>* id
         if (len > size - p - 12) png_bad("truncated chunk");
         const uint8_t* data     = type + 4;
         const bool     critical = !(type[0] & 0x20);
-        if (critical) {
+        if (critical && (!idat || idat->crc)) {
             const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), type, len + 4);
             if (crc != be32(data + len)) png_bad(std::string("CRC error in ") + std::string((const char*)type, 4));
         }
@@ -86,8 +102,11 @@ void parse(const uint8_t* d, size_t size, PngHeader& H, std::vector<uint8_t>* id
             for (int i = 0; i < H.npal; i++) H.pal[i][0] = data[3 * i], H.pal[i][1] = data[3 * i + 1], H.pal[i][2] = data[3 * i + 2];
         } else if (!std::memcmp(type, "IDAT", 4)) {
             if (!got_ihdr) png_bad("IDAT before IHDR");
-            if (idat) idat->insert(idat->end(), data, data + len);
-            else return; // header only
+            if (!idat) return; // header only
+            if (idat->vec) idat->vec->insert(idat->vec->end(), data, data + len);
+            if (idat->flat && len) std::memcpy(idat->flat + idat->len, data, len);
+            for (uint32_t i = 0; i < len && idat->len + i < 2; i++) idat->head[idat->len + i] = data[i];
+            idat->len += len;
         } else if (!std::memcmp(type, "IEND", 4)) {
             got_iend = true;
             break;
@@ -96,7 +115,7 @@ void parse(const uint8_t* d, size_t size, PngHeader& H, std::vector<uint8_t>* id
     }
     if (!got_ihdr) png_bad("no IHDR");
     if (H.ctype == 3 && H.npal == 0) png_bad("palette image without PLTE");
-    if (idat && !got_iend && idat->empty()) png_bad("no image data");
+    if (idat && !got_iend && idat->len == 0) png_bad("no image data");
 }
 
 // Undo the row filters of a (sub-)image of w x h pixels whose filtered rows start at `in`.
@@ -220,7 +239,9 @@ void png_decode(const void* data, size_t size, int mode, void* dst, size_t strid
 {
     PngHeader            H;
     std::vector<uint8_t> idat;
-    parse((const uint8_t*)data, size, H, &idat);
+    IdatSink             sink;
+    sink.vec = &idat;
+    parse((const uint8_t*)data, size, H, &sink);
     const int  bpp_bits = H.samples * H.depth;
     const bool out16    = mode == AEON_PNG_ANYDEPTH && H.depth == 16 && H.ctype != 3;
     if (out_elem_bytes) *out_elem_bytes = out16 ? 2 : 1;
@@ -258,6 +279,81 @@ void png_decode(const void* data, size_t size, int mode, void* dst, size_t strid
                          H.interlace ? ay0[k] + y * ady[k] : y, O);
         off += (rowb + 1) * ph[k];
     }
+}
+
+// The routing rule: the device takes a file that is not interlaced, whose row (filter byte included) fits
+// png_unfilter's LDS, and whose zlib stream -- taken as the whole file, so that the header alone decides -- and
+// inflated scanlines each stay below 2^31 bytes (the kernels' 32-bit positions).  Every other file is png_decode's.
+static bool png_route(const PngHeader& H, size_t clen, size_t* need)
+{
+    const size_t rowb = ((size_t)H.w * H.samples * H.depth + 7) / 8;
+    *need             = (rowb + 1) * (size_t)H.h;
+    return !H.interlace && rowb + 1 <= (size_t)kPngMaxRow && clen < ((size_t)1 << 31) && *need < ((size_t)1 << 31);
+}
+
+void png_plan(const void* data, size_t size, int mode, PngPlan& P)
+{
+    PngHeader H;
+    IdatSink  sink;
+    parse((const uint8_t*)data, size, H, &sink);
+    P.w = H.w, P.h = H.h, P.depth = H.depth, P.ctype = H.ctype, P.interlace = H.interlace;
+    P.channels   = mode == AEON_PNG_BGR8 ? 3 : 1;
+    P.elem_bytes = (mode == AEON_PNG_ANYDEPTH && H.depth == 16 && H.ctype != 3) ? 2 : 1;
+    P.clen       = sink.len;
+    P.route      = png_route(H, size, &P.need) ? 1 : 0;
+    if (!P.route) return;
+    // the zlib header as inflate checks it: deflate, a window of 32 KiB at most, no preset dictionary, FCHECK
+    const uint32_t cmf = sink.head[0], flg = sink.head[1];
+    if (sink.len < 2 || (cmf & 15) != 8 || (cmf >> 4) > 7 || (flg & 0x20) || ((cmf << 8) | flg) % 31 != 0)
+        png_bad("corrupt or truncated image data");
+}
+
+bool png_routed(const void* data, size_t size)
+{
+    PngHeader H;
+    IdatSink  sink;
+    size_t    need = 0;
+    sink.crc = false;
+    try {
+        parse((const uint8_t*)data, size, H, &sink);
+    } catch (const jpeg_error&) {
+        return false;
+    }
+    return png_route(H, size, &need) && sink.len * kPngDecoderMinRatio <= need;
+}
+
+void png_stage(const void* data, size_t size, int mode, const PngPlan& P, PngJob& J, uint8_t* comp_dst)
+{
+    PngHeader H;
+    IdatSink  sink;
+    sink.flat = comp_dst, sink.crc = false;
+    parse((const uint8_t*)data, size, H, &sink);
+    std::memset(&J, 0, sizeof(J));
+    J.clen = (uint32_t)P.clen, J.need = (uint32_t)P.need;
+    J.w = H.w, J.h = H.h, J.depth = H.depth, J.ctype = H.ctype, J.samples = H.samples, J.npal = H.npal;
+    J.mode = mode, J.elem_bytes = P.elem_bytes;
+    J.rowb = (int32_t)(((size_t)H.w * H.samples * H.depth + 7) / 8);
+    J.bpp  = std::max(1, H.samples * H.depth / 8);
+    J.out_row_bytes = H.w * P.channels * P.elem_bytes;
+    std::memcpy(J.pal, H.pal, sizeof(J.pal));
+}
+
+int png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride)
+{
+    PngPlan P;
+    png_plan(data, size, mode, P);
+    if (!P.route) return 0;
+    PngJob               J;
+    std::vector<uint64_t> comp((P.clen + 7) / 8 + 1, 0), raw((P.need + 15) / 8 + 2, 0); // aligned, zero-padded
+    png_stage(data, size, mode, P, J, (uint8_t*)comp.data());
+    J.comp = (uint64_t)comp.data(), J.raw = (uint64_t)raw.data(), J.out = (uint64_t)dst, J.stride = (int32_t)stride;
+    std::vector<pngdev::InflateMem> mem(1);
+    pngdev::Inflate                 S{};
+    S.in = (const uint32_t*)comp.data(), S.raw = (uint8_t*)raw.data(), S.clen = J.clen, S.need = J.need;
+    if (!pngdev::inflate_file(mem[0], S)) return -1;
+    const int lds = png_unfilter_lds(J.rowb);
+    std::vector<uint64_t> um(lds / 8 + 1);
+    return pngdev::unfilter_file(J, (uint8_t*)um.data(), lds) ? 1 : -1;
 }
 
 } // namespace aeon_hip

@@ -256,10 +256,11 @@ int aeon_hip_release_stream(aeon_hip_ctx* ctx, void* stream);
 int aeon_hip_set_timing(aeon_hip_ctx* ctx, int every);
 /* Drain the timers: per kernel kind [0]=augment (final), [1]=contrast statistics,
  * [2]=pre-passes (resize_short, CUBIC / AREA / LANCZOS4 resize, 2x-area ahead of photometric),
- * [3]=JPEG IDCT + colour kernels of aeon_hip_decode_jpeg_batch (bytes: decoded pixels): total ms,
+ * [3]=JPEG IDCT + colour kernels of aeon_hip_decode_jpeg_batch (bytes: decoded pixels),
+ * [4]=png_inflate + png_unfilter of aeon_hip_decode_png_batch (bytes: inflated scanlines): total ms,
  * total algorithmic bytes, launches.  The arrays hold `kinds` entries (AEON_HIP_TIMER_KINDS = all;
  * fewer are filled, more are left alone).  Resets the totals of every kind. */
-#define AEON_HIP_TIMER_KINDS 4
+#define AEON_HIP_TIMER_KINDS 5
 int aeon_hip_kernel_times(aeon_hip_ctx* ctx, int kinds, double* ms, double* bytes, long* count);
 
 /* ---- augmentation parameters (host) ------------------------------------------------------- */
@@ -296,6 +297,33 @@ int aeon_make_ssd_params(aeon_param_factory* f, uint32_t* engine_state, int in_w
 #define AEON_PNG_ANYDEPTH 2
 int aeon_png_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* color_type);
 int aeon_decode_png(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes);
+/* The PNG stage: n PNG files decoded into device memory as aeon_decode_png(data[i], sizes[i], modes[i], ...)
+ * decodes them, byte for byte: record i at dst_base + descs[i].offset with descs[i].stride bytes per row --
+ * BGR8 three channels, GRAY8 one, ANYDEPTH one channel of uint8 or, for a 16-bit non-palette file, native
+ * uint16; descs[i].width / height must be the file's (aeon_png_info).  The host walks the chunks (signature,
+ * CRCs, IHDR, PLTE), checks the zlib header and stages the IDAT payloads; the GPU inflates them (one wave per
+ * file), undoes the row filters and converts.  Interlaced files, rows wider than 16 KiB and streams of 2^31
+ * bytes decode on the host and go up as pixels with the same H2D.  What aeon_decode_png refuses at parse time
+ * (signature, IHDR, CRC, truncated chunk, missing PLTE, no IDAT) is refused here before any launch, same code
+ * and message.  Corrupt image data of a GPU-decoded file -- a stream zlib refuses (invalid or over-subscribed
+ * codes, a distance too far back, a wrong Adler-32), one that does not inflate to exactly the image's
+ * scanlines, a filter byte above 4, a palette index past PLTE -- is reported by aeon_hip_synchronize
+ * (AEON_HIP_EDEVICE).  Asynchronous on `stream`; the files may be released when the call returns. */
+int aeon_hip_decode_png_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                              const aeon_img_desc* descs, void* dst_base, void* stream);
+/* The host half of the stage for one file, on the calling thread, no device.  *gpu_route: 1 when the device
+ * takes the file's inflate, 0 when it decodes on the host.  *staged_bytes: what goes into the H2D. */
+int aeon_png_host_stage(const void* data, size_t size, int mode, int* gpu_route, int64_t* staged_bytes);
+/* What a decoder (aeon_decoder_*) does with an encoded PNG element: *device = 1, it goes through
+ * aeon_hip_decode_png_batch; 0, it is decoded on the host pool while staging.  The stage's routing rule and,
+ * on top, a measured one: only files whose zlib stream is at most an eighth of their inflated scanlines
+ * (pixel masks, flat and smooth images), where the device is the faster decoder.  No error: a file the chunk
+ * walk refuses gives 0 (the host decoder reports it). */
+int aeon_png_decoder_route(const void* data, size_t size, int* device);
+/* The stage's kernels run on the calling thread, lane after lane, no device (the code the kernels compile,
+ * for CPU tests and sanitizer builds): decodes like aeon_decode_png.  AEON_HIP_EUNSUPPORTED: the file is not
+ * routed to the device; AEON_HIP_EDEVICE: what the device reports as corrupt. */
+int aeon_png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
 
 /* batch_sampler::sample_patches (src/augment_image.cpp:567-586) of the factory's batch_samplers[sampler]
  * over n normalized object boxes (xmin, ymin, xmax, ymax in [0, 1]) -- what aeon's tests call as
