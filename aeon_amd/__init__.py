@@ -223,6 +223,10 @@ def lib():
         L.aeon_jpeg_entropy_decode.argtypes = ([ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 3 +
                                                [P(ctypes.c_int64)] * 2 + [P(ctypes.c_uint64)])
         L.aeon_jpeg_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int), P(ctypes.c_int64)]
+        L.aeon_jpeg_huff_layout.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int32),
+                                            P(ctypes.c_int32), ctypes.c_int]
+        L.aeon_hip_jpeg_huff_stage_cap.argtypes = [ctypes.c_int, P(ctypes.c_int)]
+        L.aeon_hip_jpeg_huff_lanes.argtypes = [vp, P(ctypes.c_int)]
         L.aeon_png_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 4
         L.aeon_decode_png.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
                                       P(ctypes.c_int)]
@@ -605,6 +609,31 @@ def jpeg_host_stage(data):
     return bool(g.value), nb.value
 
 
+def jpeg_huff_layout(data, lanes):
+    """How the host lays a file out for the GPU Huffman decoder at `lanes` lanes (aeon_jpeg_huff_layout): a dict
+    of gpu_entropy, nseg, nsub, sub_bits, data_bytes, seg_nsub (per restart segment, file order) and the decoder's
+    limits sub_min, sub_max, default_lanes, stage_max.  nsub > lanes: the strided path; else the lanes path, staged
+    when data_bytes fits jpeg_huff_stage_cap(lanes)."""
+    out = (ctypes.c_int32 * 10)()
+    _check(lib().aeon_jpeg_huff_layout(bytes(data), len(data), lanes, out, None, 0))
+    segs = (ctypes.c_int32 * max(out[1], 1))()
+    _check(lib().aeon_jpeg_huff_layout(bytes(data), len(data), lanes, out, segs, out[1]))
+    keys = ("gpu_entropy", "nseg", "nsub", "sub_bits", "data_bytes", "seg_max", "sub_min", "sub_max", "default_lanes",
+            "stage_max")
+    d = dict(zip(keys, out))
+    d["gpu_entropy"] = bool(out[0])
+    d["seg_nsub"] = list(segs[:out[1]])
+    return d
+
+
+def jpeg_huff_stage_cap(lanes):
+    """The most data bytes jpeg_huff copies into LDS per file at `lanes` lanes on the current device
+    (aeon_hip_jpeg_huff_stage_cap); 0 without a device."""
+    n = ctypes.c_int()
+    _check(lib().aeon_hip_jpeg_huff_stage_cap(lanes, ctypes.byref(n)))
+    return n.value
+
+
 def avi_frames(data, cap=None):
     """video::extractor's demux of one MJPEG AVI datum (aeon_avi_frames): (frames, width, height) with
     frames = [(offset, size)] of the chunks' data in index order (size 0: an empty chunk, whose frame
@@ -820,6 +849,12 @@ class Context:
         d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
         _check(lib().aeon_hip_decode_jpeg_batch(self._h, n, ptrs, sizes, d, ctypes.c_void_p(dst_ptr),
                                                 ctypes.c_void_p(stream or 0)))
+
+    def jpeg_huff_lanes(self):
+        """The workgroup size this context's GPU Huffman decoder runs (aeon_hip_jpeg_huff_lanes)."""
+        n = ctypes.c_int()
+        _check(lib().aeon_hip_jpeg_huff_lanes(self._h, ctypes.byref(n)))
+        return n.value
 
     def decode_png_batch(self, files, modes, descs, dst_ptr, stream=0):
         """decode_png of PNG files into device memory (aeon_hip_decode_png_batch): files = list of bytes (or

@@ -220,6 +220,16 @@ int aeon_jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_
     });
 }
 
+int aeon_jpeg_huff_layout(const void* data, size_t size, int lanes, int32_t* out, int32_t* seg_nsub, int seg_cap)
+{
+    return guarded([&] {
+        if (!data || !out || seg_cap < 0 || (seg_cap > 0 && !seg_nsub)) fail(AEON_HIP_EINVAL, "null argument");
+        if (lanes != 256 && lanes != 512 && lanes != 1024) fail(AEON_HIP_EINVAL, "jpeg_huff runs 256, 512 or 1024 lanes");
+        jpeg_huff_layout(data, size, lanes, out, seg_nsub, seg_cap);
+        return 0;
+    });
+}
+
 int aeon_unbiased_round(float x, int64_t* out)
 {
     return guarded([&] {

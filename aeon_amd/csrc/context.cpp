@@ -397,6 +397,11 @@ int aeon_hip_ctx_create(int device, aeon_hip_ctx** out)
             if (const char* e = std::getenv("AEON_HIP_DIRECT")) c->direct = std::atoi(e) != 0;
             if (const char* e = std::getenv("AEON_HIP_RECORDS")) c->records = std::atoi(e) != 0;
             if (const char* e = std::getenv("AEON_HIP_JPEG_HUFF")) c->jpeg_gpu_huff = std::strcmp(e, "host") != 0;
+            // (read here like the flag above: the JPEG state itself is made by the context's first decode call)
+            if (const char* e = std::getenv("AEON_HIP_JPEG_HUFF_LANES")) {
+                const int l        = std::atoi(e);
+                c->jpeg_huff_lanes = l == 256 || l == 512 || l == 1024 ? l : 0;
+            }
             if (const char* e = std::getenv("AEON_HIP_FUSE_MASKS")) c->fuse_masks = std::atoi(e) != 0;
 #ifdef AEON_HIP_TRACE
             // development builds only: s_memtime phase stamps of the tile kernel into this device buffer

@@ -100,6 +100,7 @@ struct aeon_hip_ctx {
     bool                 vram_jobs = false; // job tables written by the host into device memory (large-BAR GPUs;
                                             // AEON_HIP_VRAM_JOBS=0: pinned host tables)
     bool                 jpeg_gpu_huff = true; // AEON_HIP_JPEG_HUFF=host: every JPEG through the host entropy decoder
+    int                  jpeg_huff_lanes = 0;  // AEON_HIP_JPEG_HUFF_LANES=256 / 512 / 1024 (0: jpeg.hpp's kHuffLanes)
     std::vector<aeon_hip::JobGeom> geoms;        // reused per call
     std::vector<aeon_hip::AugJob>  direct_jobs;  // (run_direct) the call's jobs before they go into the slot
     std::vector<int>     direct_order;       // (run_direct) their table order: largest crop first

@@ -865,7 +865,7 @@ int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data
         if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
         if (n == 0) return 0;
         HIP_OK(hipSetDevice(ctx->device));
-        if (!ctx->jpeg) ctx->jpeg = jpeg_state_create(ctx->host_pool, ctx->jpeg_gpu_huff);
+        if (!ctx->jpeg) ctx->jpeg = jpeg_state_create(ctx->host_pool, ctx->jpeg_gpu_huff, ctx->jpeg_huff_lanes);
         KernelTimer t{};
         bool        timed = false;
         if (ctx->timing) {
@@ -884,6 +884,25 @@ int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data
             std::lock_guard<std::mutex> lock(ctx->mu);
             ctx->timers.push_back(t);
         }
+        return 0;
+    });
+}
+
+int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx* ctx, int* lanes)
+{
+    return guarded([&] {
+        if (!ctx || !lanes) fail(AEON_HIP_EINVAL, "null argument");
+        *lanes = ctx->jpeg_huff_lanes ? ctx->jpeg_huff_lanes : kHuffLanes;
+        return 0;
+    });
+}
+
+int aeon_hip_jpeg_huff_stage_cap(int lanes, int* bytes)
+{
+    return guarded([&] {
+        if (!bytes) fail(AEON_HIP_EINVAL, "null argument");
+        if (lanes != 256 && lanes != 512 && lanes != 1024) fail(AEON_HIP_EINVAL, "jpeg_huff runs 256, 512 or 1024 lanes");
+        *bytes = jpeg_huff_stage_cap(lanes);
         return 0;
     });
 }

@@ -32,8 +32,9 @@ struct JpegState;
 class thread_pool;
 // shared: entropy-decode on that pool (the decoder's own, pinned to its cpu_list -- aeon's extract
 // runs inside provide() on the decode pool); null: a pool of the stage's own (thread_affinity_map).
-// gpu_huff false: every file through the host entropy decoder (AEON_HIP_JPEG_HUFF=host, A/B runs)
-JpegState* jpeg_state_create(thread_pool* shared = nullptr, bool gpu_huff = true);
+// gpu_huff false: every file through the host entropy decoder (AEON_HIP_JPEG_HUFF=host, A/B runs); huff_lanes:
+// jpeg_huff's workgroup, 256 / 512 / 1024 (0: kHuffLanes).  The context reads both flags when it is created.
+JpegState* jpeg_state_create(thread_pool* shared = nullptr, bool gpu_huff = true, int huff_lanes = 0);
 void       jpeg_state_destroy(JpegState* s);
 
 // The host functions of the stage (jpeg_host.cpp).  jpeg_decode_batch: n files decoded into the records at
@@ -50,6 +51,11 @@ void jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* s
 // 1 when decoded, -1 on corrupt entropy-coded data
 int  jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, int* h, int* ncomp, int64_t* n_blocks,
                               int64_t* n_values, uint64_t* hash, int* rounds);
+// how prepare_gpu lays a file out for jpeg_huff<lanes> (aeon_jpeg_huff_layout, for tests): out = GPU entropy
+// decoding?, segments, subsequences, sub_bits, the data's bytes (what the kernel compares with its stage cap),
+// the largest segment's subsequences, then kHuffSubMin, kHuffSubMax, kHuffLanes, kHuffStageMax; seg_nsub (may
+// be null): the subsequences of the first seg_cap segments
+void jpeg_huff_layout(const void* data, size_t size, int lanes, int32_t out[10], int32_t* seg_nsub, int seg_cap);
 
 // One 8x8 block: bit z of `mask` = zigzag coefficient z is non-zero; its values follow in zigzag
 // order at values[val_off ...] of the block's image.

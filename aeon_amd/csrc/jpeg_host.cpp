@@ -1019,7 +1019,7 @@ struct JpegState {
     int         next = 0;
     hipStream_t copy = nullptr; // the H2D of a call's staging, so that it overlaps the previous call's kernels
     bool       gpu_huff = true; // false: every file through the host entropy decoder
-    int        huff_lanes = kHuffLanes; // jpeg_huff workgroup size (AEON_HIP_JPEG_HUFF_LANES=256 / 1024: A/B)
+    int        huff_lanes = kHuffLanes; // jpeg_huff workgroup size (the context's AEON_HIP_JPEG_HUFF_LANES=256 / 1024: A/B)
     std::mutex mu;
 };
 
@@ -1043,14 +1043,11 @@ void hip_ok(hipError_t e, const char* what)
 
 } // namespace
 
-JpegState* jpeg_state_create(thread_pool* shared, bool gpu_huff)
+JpegState* jpeg_state_create(thread_pool* shared, bool gpu_huff, int huff_lanes)
 {
     auto* s = new JpegState();
     s->gpu_huff = gpu_huff;
-    if (const char* e = std::getenv("AEON_HIP_JPEG_HUFF_LANES")) {
-        const int l   = std::atoi(e);
-        s->huff_lanes = l == 256 || l == 512 || l == 1024 ? l : kHuffLanes;
-    }
+    if (huff_lanes == 256 || huff_lanes == 512 || huff_lanes == 1024) s->huff_lanes = huff_lanes;
     if (shared) {
         s->pool = shared;
     } else {
@@ -1365,6 +1362,23 @@ void jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* s
         decode_file((const uint8_t*)data, size, f, a, blk_off, &val_off, false);
     }
     *staged_bytes = (int64_t)a.used;
+}
+
+// aeon_jpeg_huff_layout's body: prepare_gpu's layout of one file for a workgroup of `lanes`, read-only.
+void jpeg_huff_layout(const void* data, size_t size, int lanes, int32_t out[10], int32_t* seg_nsub, int seg_cap)
+{
+    Frame   f;
+    Arena   a;
+    GpuScan g;
+    for (int i = 0; i < 6; i++) out[i] = 0;
+    out[6] = kHuffSubMin, out[7] = kHuffSubMax, out[8] = kHuffLanes, out[9] = kHuffStageMax;
+    if (!prepare_gpu((const uint8_t*)data, size, f, a, g, lanes)) return;
+    const JpegHuffSeg* segs = (const JpegHuffSeg*)(a.host.data() + g.segs);
+    out[0] = 1, out[1] = g.nseg, out[2] = g.nsub, out[3] = g.sub_bits, out[4] = g.data_words * 4;
+    for (int s = 0; s < g.nseg; s++) {
+        out[5] = std::max(out[5], segs[s].nsub);
+        if (seg_nsub && s < seg_cap) seg_nsub[s] = segs[s].nsub;
+    }
 }
 
 // The GPU entropy decoder's algorithm on this thread (host-only, for tests): prepare_gpu, then

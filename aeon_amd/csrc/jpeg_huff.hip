@@ -11,7 +11,8 @@
 //   2. Jacobi rounds: a subsequence whose start differs from its predecessor's end takes that end as
 //      its start and is decoded again -- until no start changes.  The segment's first start is exact,
 //      so after round r the first r + 1 starts are; Huffman codes (and JPEG's block structure)
-//      re-synchronise within a few codewords, so two or three rounds settle a file in practice;
+//      re-synchronise within a few codewords, so a few rounds settle a photo (3-23 measured); a file
+//      written not to re-synchronise takes a round per subsequence of its longest segment;
 //   3. with exact starts, an exclusive prefix sum over the subsequences gives each one its first
 //      block and its DC predictors (blocks started, DC differences per component);
 //   4. a final decode of each subsequence writes its coefficients into the dense block slots (64 int16

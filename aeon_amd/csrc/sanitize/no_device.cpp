@@ -107,6 +107,8 @@ int aeon_hip_decode_jpeg_batch(aeon_hip_ctx*, int, const void* const*, const siz
 {
     return no_device();
 }
+int aeon_hip_jpeg_huff_stage_cap(int, int*) { return no_device(); }
+int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx*, int*) { return no_device(); }
 int aeon_hip_decode_png_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const int*, const aeon_img_desc*, void*,
                               void*)
 {

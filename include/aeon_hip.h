@@ -183,6 +183,22 @@ int aeon_jpeg_entropy_decode(const void* data, size_t size, int* width, int* hei
  * multi-scan) is entropy-decoded into the sparse stream (*gpu_entropy = 0).  *staged_bytes: what it
  * stages for the H2D.  For timing the host side of the stage per file. */
 int aeon_jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* staged_bytes);
+/* How the host lays one file out for the GPU Huffman decoder at a workgroup of `lanes` (256, 512 or 1024), on
+ * the calling thread, no device, read-only; for tests that must know which of the kernel's paths a file takes.
+ * out[0..9]: GPU entropy decoding (0: the host decodes the file, the rest of the file's entries are 0), restart
+ * segments, subsequences, bits per subsequence, bytes of entropy-coded data as staged (what the kernel compares
+ * with aeon_hip_jpeg_huff_stage_cap), the subsequences of the largest segment; then the decoder's limits, the
+ * same for every file: least and most bits per subsequence, the default workgroup size, the most data bytes a
+ * workgroup copies into LDS.  A file with more subsequences than lanes takes the strided path; any other the
+ * lanes path, staged when its data fits the cap.  seg_nsub (may be null with seg_cap 0) receives the
+ * subsequences of the first seg_cap segments, in file order. */
+int aeon_jpeg_huff_layout(const void* data, size_t size, int lanes, int32_t* out, int32_t* seg_nsub, int seg_cap);
+/* The most data bytes the GPU Huffman decoder copies into LDS per file at a workgroup of `lanes`, as the
+ * kernel's static LDS on the current device leaves it.  Device half: with no device it reads 0. */
+int aeon_hip_jpeg_huff_stage_cap(int lanes, int* bytes);
+/* The workgroup size the context's GPU Huffman decoder runs: 512, or what AEON_HIP_JPEG_HUFF_LANES (256, 512 or
+ * 1024) named when the context was created. */
+int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx* ctx, int* lanes);
 /* cv::imdecode(CV_LOAD_IMAGE_COLOR / GRAYSCALE) of n JPEG files (baseline / extended sequential /
  * progressive Huffman, 8-bit, 1, 3 or 4 components) as libjpeg decodes them (ISLOW IDCT, fancy upsampling),
  * into device memory: record i as HWC uint8 (BGR if descs[i].channels == 3, gray if 1: the Y component of a YCbCr file)

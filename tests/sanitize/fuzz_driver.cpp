@@ -6,8 +6,11 @@
 //
 // Usage: fuzz_driver FILE...   (*.jpg, *.png, *.json).  One line per file: the outcome, "ok ..." or
 // "error <code> <message>"; for a JPEG a second line "gpu<TAB>FILE<TAB>..." with the outcome of the GPU
-// entropy decoder's algorithm (jpeg_huff, emulated on the host) on the same bytes.  A sanitizer finding
-// aborts the run with a non-zero exit status.
+// entropy decoder's algorithm (jpeg_huff, emulated on the host) on the same bytes.  With --lanes as the
+// first argument a third line per JPEG, "lanes<TAB>FILE<TAB>...": per workgroup size (1,024, 512, 256; separated
+// by "; ") "lanes L rounds R nsub N sub_bits B segs S0,S1,..." -- the Jacobi rounds, the subsequences, their
+// length and the subsequences of each restart segment ("host" when the host decodes the file).  A sanitizer
+// finding aborts the run with a non-zero exit status.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -35,7 +38,7 @@ bool ends_with(const std::string& s, const char* suf)
 
 // The GPU entropy decoder's algorithm (host emulation of jpeg_huff) on the same bytes: "gpu host"
 // (the file goes to the host decoder), "gpu ok <hash> rounds <r>", "gpu corrupt" or "gpu error <code>".
-std::string run_jpeg_gpu(const std::vector<uint8_t>& d)
+std::string run_jpeg_gpu(const std::vector<uint8_t>& d, std::string* per_lanes)
 {
     try {
         int      w, h, n, rounds = 0;
@@ -49,6 +52,20 @@ std::string run_jpeg_gpu(const std::vector<uint8_t>& d)
             if (r == 0) std::snprintf(buf, sizeof(buf), "gpu host");
             else if (r < 0) std::snprintf(buf, sizeof(buf), "gpu corrupt");
             else std::snprintf(buf, sizeof(buf), "gpu ok %016llx rounds %d", (unsigned long long)hv, rounds);
+            if (per_lanes) {
+                int32_t lay[10];
+                jpeg_huff_layout(d.data(), d.size(), lanes, lay, nullptr, 0);
+                std::vector<int32_t> segs((size_t)(lay[1] > 0 ? lay[1] : 1));
+                jpeg_huff_layout(d.data(), d.size(), lanes, lay, segs.data(), lay[1]);
+                std::string& o = *per_lanes;
+                o += (o.empty() ? "lanes " : "; lanes ") + std::to_string(lanes);
+                if (r == 0) o += " host";
+                else {
+                    o += " rounds " + std::to_string(r < 0 ? -1 : rounds) + " nsub " + std::to_string(lay[2]) + " sub_bits " +
+                         std::to_string(lay[3]) + " segs ";
+                    for (int s = 0; s < lay[1]; s++) o += (s ? "," : "") + std::to_string(segs[(size_t)s]);
+                }
+            }
             const std::string got = buf, key = got.substr(0, got.find(" rounds"));
             if (res.empty()) res = got;
             else if (res.substr(0, res.find(" rounds")) != key) return "gpu lanes-disagree " + res + " / " + got;
@@ -105,14 +122,15 @@ std::string run_json(const std::vector<uint8_t>& d)
 
 int main(int argc, char** argv)
 {
-    for (int i = 1; i < argc; i++) {
+    const bool lanes = argc > 1 && std::string(argv[1]) == "--lanes";
+    for (int i = lanes ? 2 : 1; i < argc; i++) {
         const std::string    name = argv[i];
         std::ifstream        in(name, std::ios::binary);
         std::vector<uint8_t> d((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-        std::string          r, gpu;
+        std::string          r, gpu, per_lanes;
         try {
             if (ends_with(name, ".jpg")) {
-                gpu = run_jpeg_gpu(d);
+                gpu = run_jpeg_gpu(d, lanes ? &per_lanes : nullptr);
                 r   = run_jpeg(d);
             }
             else if (ends_with(name, ".png")) r = run_png(d);
@@ -129,6 +147,7 @@ int main(int argc, char** argv)
         }
         std::printf("%s\t%s\n", name.c_str(), r.c_str());
         if (!gpu.empty()) std::printf("gpu\t%s\t%s\n", name.c_str(), gpu.c_str());
+        if (!per_lanes.empty()) std::printf("lanes\t%s\t%s\n", name.c_str(), per_lanes.c_str());
     }
     return 0;
 }

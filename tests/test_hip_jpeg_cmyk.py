@@ -139,6 +139,7 @@ def test_other_huffman_workgroup_sizes(lanes):
     subsequences than lanes and takes the strided phases."""
     c = _context(AEON_HIP_JPEG_HUFF_LANES=str(lanes))
     try:
+        assert c.jpeg_huff_lanes() == lanes
         for n, r in zip(NAMES, _decode(c, [FX[n + ".jpg"].tobytes() for n in NAMES], 3)):
             assert np.array_equal(r, FX[n + ".bgr"]), (n, lanes)
     finally:

@@ -52,7 +52,8 @@ def _decode(ctx, files, channels):
 
 
 def _context(**env):
-    """A context created with `env` set (the JPEG stage reads its flags when the context is created)."""
+    """A context created with `env` set (the JPEG stage's flags are read when the context is created, not at its
+    first decode call: Context.jpeg_huff_lanes() tells the workgroup size in effect)."""
     import torch
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     os.environ.update(env)
@@ -109,11 +110,20 @@ def test_short_colour_bands(ctx, band, monkeypatch):
 @pytest.mark.parametrize("lanes", [256, 1024])
 def test_other_huffman_workgroup_sizes(lanes):
     """jpeg_huff at 256 and 1,024 lanes (512 is the default): rst1_gray_529 has more subsequences than
-    512 lanes, rst1_444_289 more than 256 -- one tiny restart segment per subsequence."""
+    512 lanes, rst1_444_289 more than 256 -- one tiny restart segment per subsequence.  Then the encoder-made
+    fixtures of jpeg_fixtures.npz against their committed digests: flowers.jpg has more than 256 subsequences
+    (the strided phases with Jacobi rounds) and more data than 512 or 1,024 lanes stage."""
     c = _context(AEON_HIP_JPEG_HUFF_LANES=str(lanes))
     try:
+        assert c.jpeg_huff_lanes() == lanes
         for cn in (3, 1):
             _check(_decode(c, FILES, cn), cn, f"lanes {lanes}")
+        flowers = A.jpeg_huff_layout(OLD["flowers.jpg"].tobytes(), lanes)
+        assert flowers["gpu_entropy"] and (flowers["nsub"] > lanes) == (lanes == 256), flowers
+        old = [OLD[n + ".jpg"].tobytes() for n in OLD_NAMES]
+        for cn, key in ((3, ".bgr"), (1, ".gray")):
+            for n, r in zip(OLD_NAMES, _decode(c, old, cn)):
+                assert np.array_equal(_sha(r), OLD[n + key]), (f"lanes {lanes}", n, cn)
     finally:
         c.close()
 
