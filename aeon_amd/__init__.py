@@ -236,6 +236,14 @@ def lib():
         L.aeon_png_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int), P(ctypes.c_int64)]
         L.aeon_png_decoder_route.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
         L.aeon_png_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
+        L.aeon_pixmap_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 5
+        L.aeon_decode_pixmap.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
+                                         P(ctypes.c_int)]
+        L.aeon_hip_decode_pixmap_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ctypes.c_int), P(ImgDesc),
+                                                   vp, vp]
+        L.aeon_pixmap_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int),
+                                             P(ctypes.c_int64)]
+        L.aeon_pixmap_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
         L.aeon_avi_frames.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(AviFrame), ctypes.c_int] + [P(ctypes.c_int)] * 3
         L.aeon_avi_last_error.restype = ctypes.c_char_p
         L.aeon_hip_video_batch.argtypes = [vp, ctypes.c_int, P(ctypes.c_int32), P(ImgDesc), vp, P(AugParams), ctypes.c_int,
@@ -703,6 +711,49 @@ def png_gpu_emulate(data, mode=PNG_BGR8):
     return out
 
 
+DECODE_BGR8, DECODE_GRAY8, DECODE_ANYDEPTH = PNG_BGR8, PNG_GRAY8, PNG_ANYDEPTH
+PIXMAP_BMP = 0  # pixmap_info's format of a BMP file; a PNM file's is its magic digit (1..6)
+
+
+def pixmap_info(data):
+    """(width, height, decoded bits per sample, the file's channels, format) of a BMP or PNM file
+    (aeon_pixmap_info); format is PIXMAP_BMP or the PNM magic's digit."""
+    v = [ctypes.c_int() for _ in range(5)]
+    _check(lib().aeon_pixmap_info(bytes(data), len(data), *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def _pixmap_out(data, mode):
+    w, h, d, _, _ = pixmap_info(data)
+    cn = 3 if mode == DECODE_BGR8 else 1
+    return np.zeros((h, w, cn) if cn == 3 else (h, w), np.uint16 if (mode == DECODE_ANYDEPTH and d == 16) else np.uint8)
+
+
+def decode_pixmap(data, mode=DECODE_BGR8):
+    """cv::imdecode of a BMP or PNM file as aeon's extractors ask for it (aeon_decode_pixmap): HxWx3 uint8 BGR
+    (DECODE_BGR8), HxW uint8 (DECODE_GRAY8), or HxW uint8 / uint16 (a PNM with maxval > 255) (DECODE_ANYDEPTH)."""
+    out = _pixmap_out(data, mode)
+    eb = ctypes.c_int()
+    _check(lib().aeon_decode_pixmap(bytes(data), len(data), mode, out.ctypes.data, out.strides[0], ctypes.byref(eb)))
+    return out
+
+
+def pixmap_host_stage(data, mode=DECODE_BGR8):
+    """The pixmap batch decode's host work for one file (aeon_pixmap_host_stage): (does the device convert the
+    file?, bytes staged for the H2D)."""
+    g, nb = ctypes.c_int(), ctypes.c_int64()
+    _check(lib().aeon_pixmap_host_stage(bytes(data), len(data), mode, ctypes.byref(g), ctypes.byref(nb)))
+    return bool(g.value), nb.value
+
+
+def pixmap_gpu_emulate(data, mode=DECODE_BGR8):
+    """decode_pixmap through the pixmap stage's kernel code run on the host (aeon_pixmap_gpu_emulate).
+    AeonHipError for a file the stage leaves to the host decoder (ASCII PNM)."""
+    out = _pixmap_out(data, mode)
+    _check(lib().aeon_pixmap_gpu_emulate(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
+    return out
+
+
 def unbiased_round(x):
     """nervana::unbiased_round (aeon src/util.cpp:212-239)."""
     r = ctypes.c_int64()
@@ -869,6 +920,19 @@ class Context:
         _check(lib().aeon_hip_decode_png_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
                                                ctypes.c_void_p(stream or 0)))
 
+    def decode_pixmap_batch(self, files, modes, descs, dst_ptr, stream=0):
+        """decode_pixmap of BMP / PNM files into device memory (aeon_hip_decode_pixmap_batch): files = list of
+        bytes (or a JpegFiles, marshalled once), modes[i] = DECODE_BGR8 / DECODE_GRAY8 / DECODE_ANYDEPTH,
+        descs[i] = where record i goes (HWC; ANYDEPTH of a 16-bit PNM: native uint16)."""
+        jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
+        n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
+        m = modes if isinstance(modes, ctypes.Array) else (ctypes.c_int * n)(*[int(x) for x in modes])
+        d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
+        if len(m) < n or len(d) < n:
+            raise ValueError(f"{len(m)} modes / {len(d)} descriptors for {n} files")
+        _check(lib().aeon_hip_decode_pixmap_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
+                                                  ctypes.c_void_p(stream or 0)))
+
     def set_timing(self, every=1):
         """Time the launches of one call in `every` (0 = off) with HIP events on their stream."""
         _check(lib().aeon_hip_set_timing(self._h, int(every)))
@@ -987,7 +1051,7 @@ def _check_host(rc):
 
 class Decoder:
     """aeon batch_decoder over provider_factory::create(config): decode windows of records (per ETL
-    element an HWC uint8 array, an encoded JPEG / PNG file, or -- boundingbox, localization_ssd and
+    element an HWC uint8 array, an encoded JPEG / PNG / BMP / PNM file, or -- boundingbox, localization_ssd and
     localization_rcnn elements -- the JSON metadata as bytes or str, a video element's MJPEG AVI file as
     bytes, a label element's text or 4 binary bytes) into the provider output buffers.  A provider may own
     several output buffers (localization_ssd: five, localization_rcnn: ten), so records have n_inputs elements and windows

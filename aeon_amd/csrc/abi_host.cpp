@@ -1,7 +1,8 @@
-// abi_host.cpp -- the host-only entries of the C ABI (include/aeon_hip.h): the param factory, the PNG
-// decoder, the JPEG header and entropy probes, aeon's rounding and scale helpers, and the thread-local text
+// abi_host.cpp -- the host-only entries of the C ABI (include/aeon_hip.h): the param factory, the PNG and
+// pixmap decoders, the JPEG header and entropy probes, aeon's rounding and scale helpers, and the thread-local text
 // behind aeon_hip_last_error.  No entry touches a device, and nothing here needs the runtime: the sanitizer
 // builds link this file as it is.
+#include <climits>
 #include <cstdint>
 #include <mutex>
 #include <random>
@@ -13,6 +14,7 @@
 #include "jpeg.hpp"
 #include "json.hpp"
 #include "param_factory.hpp"
+#include "pixmap.hpp"
 #include "png.hpp"
 #include "rcnn_host.hpp"
 
@@ -151,6 +153,71 @@ int aeon_png_gpu_emulate(const void* data, size_t size, int mode, void* dst, siz
         const int r = png_gpu_emulate(data, size, mode, dst, stride);
         if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "PNG: the file is not routed to the device (interlaced, or too wide)");
         if (r < 0) fail(AEON_HIP_EDEVICE, "PNG: image data corrupt or truncated (GPU stage)");
+        return 0;
+    });
+}
+
+int aeon_pixmap_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* channels, int* format)
+{
+    return guarded([&] {
+        if (!data || !width || !height || !bit_depth || !channels || !format) fail(AEON_HIP_EINVAL, "null argument");
+        pixmap_header(data, size, width, height, bit_depth, channels, format);
+        return 0;
+    });
+}
+
+namespace {
+// the header parse, the mode and the stride of the three pixmap entries that write a record
+void pixmap_checked_plan(const void* data, size_t size, int mode, size_t stride, PixmapPlan& P)
+{
+    if (mode < AEON_DECODE_BGR8 || mode > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown pixmap decode mode");
+    pixmap_plan(data, size, mode, P);
+    if (stride < (size_t)P.w * P.channels * P.elem_bytes || stride > INT32_MAX) fail(AEON_HIP_EINVAL, "stride too small");
+}
+} // namespace
+
+int aeon_decode_pixmap(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        PixmapPlan P;
+        pixmap_checked_plan(data, size, mode, stride, P);
+        pixmap_decode(data, size, mode, dst, stride, elem_bytes);
+        return 0;
+    });
+}
+
+int aeon_pixmap_host_stage(const void* data, size_t size, int mode, int* gpu_route, int64_t* staged_bytes)
+{
+    return guarded([&] {
+        if (!data || !gpu_route || !staged_bytes) fail(AEON_HIP_EINVAL, "null argument");
+        if (mode < AEON_DECODE_BGR8 || mode > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown pixmap decode mode");
+        PixmapPlan P;
+        pixmap_plan(data, size, mode, P);
+        *gpu_route = P.route;
+        if (P.route) {
+            PixmapJob            J;
+            std::vector<uint8_t> file(size + 16);
+            pixmap_stage(data, size, mode, P, J, file.data());
+            *staged_bytes = (int64_t)size;
+        } else {
+            const size_t         stride = (size_t)P.w * P.channels * P.elem_bytes;
+            std::vector<uint8_t> px(stride * P.h);
+            pixmap_decode(data, size, mode, px.data(), stride, nullptr);
+            *staged_bytes = (int64_t)px.size();
+        }
+        return 0;
+    });
+}
+
+int aeon_pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        PixmapPlan P;
+        pixmap_checked_plan(data, size, mode, stride, P);
+        if (!pixmap_gpu_emulate(data, size, mode, dst, stride))
+            fail(AEON_HIP_EUNSUPPORTED, "PNM: the file is not routed to the device (ASCII samples)");
         return 0;
     });
 }

@@ -307,6 +307,7 @@ aeon_hip_ctx::~aeon_hip_ctx()
     (void)hipSetDevice(device);
     jpeg_state_destroy(jpeg);
     png_stage_destroy(png);
+    png_stage_destroy(pixmap);
     if (!open_slots.empty()) (void)hipStreamSynchronize(open_stream);
     for (Slot& s : slots)
         if (s.pending) (void)hipEventSynchronize(slots[s.cover].done);

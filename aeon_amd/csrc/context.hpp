@@ -56,7 +56,7 @@ struct PngStage; // image_path.cpp
 void png_stage_destroy(PngStage* s);
 
 constexpr int kTimerJpeg = 3; // KernelTimer kind of the JPEG kernels (after the KernelMode kinds)
-constexpr int kTimerPng  = 4; // ... of the PNG kernels
+constexpr int kTimerPng  = 4; // ... of the PNG and pixmap decode kernels
 struct KernelTimer {
     hipEvent_t start, stop;
     int        kind;   // KernelMode, kTimerJpeg or kTimerPng
@@ -107,6 +107,7 @@ struct aeon_hip_ctx {
     aeon_hip::CallPlan   plan;               // (run_batch) the call's plan
     aeon_hip::JpegState* jpeg = nullptr;     // JPEG decode stage (pool, staging ring), on first use
     aeon_hip::PngStage*  png  = nullptr;     // PNG decode stage (staging ring, scratch), on first use
+    aeon_hip::PngStage*  pixmap = nullptr;   // pixmap decode stage: a staging ring of its own (no scratch), on first use
     aeon_hip::thread_pool* host_pool = nullptr; // the owning decoder's pool (ctx_share_pool), for the JPEG stage
     // localization_rcnn: the anchor table of the last config seen stays resident (uploaded once), and the
     // direct call's engine end states pass through a small device array

@@ -1,6 +1,7 @@
 // host.cpp -- provider plugin surface + decode stage of the HIP image path (see host.hpp).
 #include "host.hpp"
 #include "box_job.hpp"
+#include "pixmap.hpp"
 #include "png.hpp"
 #include "rcnn_job.hpp"
 
@@ -255,6 +256,8 @@ public:
     // with the provider's channel count (CV_LOAD_IMAGE_COLOR / GRAYSCALE for images, CV_LOAD_IMAGE_ANYDEPTH
     // for pixel masks).  JPEG files are decoded on the device, and so are the PNG files the PNG stage's routing
     // rule gives it (png.hpp); the others (Adam7, very wide rows) on the host pool while staging (png_host.cpp).
+    // BMP and binary PNM files are converted on the device (the pixmap stage, pixmap.hpp), ASCII PNM files decoded
+    // on the host pool while staging (pixmap_host.cpp).  The sniff is strict: anything else is the JPEG parser's.
     void inspect(window_part&, int idx, decoded_element& e) const override
     {
         static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
@@ -268,6 +271,15 @@ public:
             e.channels   = m_mask ? 1 : cn;
             e.elem_bytes = (m_mask && depth == 16 && ctype != 3) ? 2 : 1;
             e.stride     = e.width * e.channels * e.elem_bytes;
+        } else if (e.encoded && pixmap_sniff(e.data, e.size)) {
+            int depth = 0, fcn = 0, format = 0;
+            check(aeon_pixmap_info(e.data, e.size, &e.width, &e.height, &depth, &fcn, &format));
+            e.encoded       = false;
+            e.pixmap_mode   = m_mask ? AEON_DECODE_ANYDEPTH : (cn == 3 ? AEON_DECODE_BGR8 : AEON_DECODE_GRAY8);
+            e.pixmap_device = pixmap_routed(e.data, e.size);
+            e.channels      = m_mask ? 1 : cn;
+            e.elem_bytes    = (m_mask && depth == 16) ? 2 : 1;
+            e.stride        = e.width * e.channels * e.elem_bytes;
         } else if (e.encoded) {
             if (m_mask)
                 throw std::runtime_error("encoded pixel masks are decoded from PNG files only (JPEG masks: pass the "
@@ -283,21 +295,24 @@ public:
     void layout_record(window_part& part, arena_region r, int idx, const decoded_element& e, size_t& offset,
                        jpeg_list& jpegs) const override
     {
-        if (r != (e.encoded || e.png_device ? arena_region::device_decoded : arena_region::staged)) return;
+        if (r != (e.on_device() ? arena_region::device_decoded : arena_region::staged)) return;
         const size_t b = (size_t)std::max(e.width, 0) * std::max(e.height, 0) * std::max(e.channels, 0) * e.elem_bytes;
         part.descs[idx] = aeon_img_desc{offset, e.width, e.height, e.width * e.channels * e.elem_bytes, e.channels,
                                         e.elem_bytes == 2 ? 2 : 0, 0};
         if (e.encoded) jpegs.add(e.data, e.size, part.descs[idx]);
         if (e.png_device) jpegs.png.add(e.data, e.size, e.png_mode, part.descs[idx]);
+        if (e.pixmap_device) jpegs.pixmap.add(e.data, e.size, e.pixmap_mode, part.descs[idx]);
         offset += arena_align(b);
     }
     void stage_record(const decode_window& w, size_t k, int idx, const decoded_element& e) const override
     {
-        if (e.encoded || e.png_device) return; // decoded on the device, straight into the source arena
+        if (e.on_device()) return; // decoded on the device, straight into the source arena
         const size_t row = (size_t)e.width * e.channels * e.elem_bytes;
         uint8_t*     dst = w.arena + w.parts[k]->descs[idx].offset;
         if (e.png_mode >= 0) { // extract on this pool thread, straight into the pinned arena
             check(aeon_decode_png(e.data, e.size, e.png_mode, dst, row, nullptr));
+        } else if (e.pixmap_mode >= 0) {
+            check(aeon_decode_pixmap(e.data, e.size, e.pixmap_mode, dst, row, nullptr));
         } else if ((size_t)e.stride == row) {
             std::memcpy(dst, e.data, row * e.height);
         } else {
@@ -1420,6 +1435,10 @@ void batch_decoder::stage_sources(window_slot& ws, window_plan& p, hipStream_t s
             check(aeon_hip_decode_png_batch(m_ctx, (int)std::min(kJpegCallFiles, j.png.files.size() - f), j.png.files.data() + f,
                                             j.png.sizes.data() + f, j.png.modes.data() + f, j.png.descs.data() + f, ws.dev_src,
                                             stream));
+        for (size_t f = 0; f < j.pixmap.files.size(); f += kJpegCallFiles)
+            check(aeon_hip_decode_pixmap_batch(m_ctx, (int)std::min(kJpegCallFiles, j.pixmap.files.size() - f),
+                                               j.pixmap.files.data() + f, j.pixmap.sizes.data() + f, j.pixmap.modes.data() + f,
+                                               j.pixmap.descs.data() + f, ws.dev_src, stream));
     }
 }
 

@@ -69,7 +69,7 @@ struct image_config {
     explicit image_config(const Json& js, bool half = false); // half: "float16" / "bfloat16" with "extended_output_type": true
 };
 
-// An element of a record: an encoded JPEG file (size > 0; width/height/channels filled in from
+// An element of a record: an encoded JPEG, PNG, BMP or PNM file (size > 0; width/height/channels filled in from
 // its header by its provider's inspect step), decoded HWC uint8 pixels (what image::extractor::extract
 // returns), or the datum of a box, video or label provider (data / size: JSON metadata, an MJPEG AVI
 // file whose width / height the demux fills in from its first frame, a label's bytes).
@@ -81,7 +81,12 @@ struct decoded_element {
     int            png_mode   = -1; // PNG file: its AEON_PNG_* decode mode
     bool           png_device = false; // ... decoded on the device (the PNG stage, png.hpp's routing rule), else on
                                        // the host pool while staging
+    int            pixmap_mode   = -1; // BMP / PNM file: its AEON_DECODE_* mode
+    bool           pixmap_device = false; // ... converted on the device (the pixmap stage, pixmap.hpp's routing
+                                          // rule), else decoded on the host pool while staging (ASCII PNM)
     int            elem_bytes = 1;  // bytes per sample (2: a 16-bit mask / depth map)
+    // decoded on the device, straight into the device-decoded region of the source arena
+    bool on_device() const { return encoded || png_device || pixmap_device; }
 };
 
 // What one provider keeps of a window's n records (etl_provider::new_part): the source descriptors into the
@@ -119,10 +124,13 @@ struct png_list {
     }
 };
 
+using pixmap_list = png_list; // the BMP / PNM files likewise (AEON_DECODE_* modes)
+
 // The JPEG files one provider wants decoded into the device-decoded region, with their destinations; its PNG
-// files travel beside them
+// and pixmap files travel beside them
 struct jpeg_list {
     png_list                   png;
+    pixmap_list                pixmap;
     std::vector<const void*>   files;
     std::vector<size_t>        sizes;
     std::vector<aeon_img_desc> descs;

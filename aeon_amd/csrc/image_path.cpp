@@ -1,7 +1,7 @@
 // image_path.cpp -- the image path of the device half: a call's records through run_direct (one launch),
 // run_records (contrast records in one launch) or run_batch's multi-pass launches over the CallPlan that
 // plan.cpp returns, run_video on top of them, and the C entries for augment, mask, pair, depthmap, video,
-// transpose, the JPEG batch and the PNG batch.
+// transpose, the JPEG batch, the PNG batch and the pixmap batch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include "launch.hpp"
 #include "mask16.hpp"
 #include "param_factory.hpp"
+#include "pixmap.hpp"
 #include "plan.hpp"
 #include "plan_record.hpp"
 #include "png.hpp"
@@ -765,9 +766,122 @@ int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* siz
     return 0;
 }
 
+// ---- pixmap stage (BMP, PNM) ------------------------------------------------------------------------
+// The decode call: each file's header parse (pixmap_plan) on the pool, the layout of the call's staging -- the
+// jobs, the band table, the routed files as they are (each at a 16-byte-aligned offset, at least 16 zero bytes
+// behind it, so the kernel's aligned over-reads stay inside the buffer), the host-decoded ASCII files' pixels --
+// filled on the pool, one H2D, then pixmap_convert over the bands and a strided device copy per host-decoded
+// file, all on `stream`.  The staging ring is a PngStage of the stage's own (its scratch unused).
+int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+               const aeon_img_desc* descs, void* dst_base, hipStream_t stream)
+{
+    if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !modes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
+    if (n == 0) return 0;
+    HIP_OK(hipSetDevice(ctx->device));
+    if (!ctx->pixmap) ctx->pixmap = new PngStage();
+    PngStage&                   S = *ctx->pixmap;
+    std::lock_guard<std::mutex> lock(S.mu);
+    const auto each = [&](const std::function<void(int)>& f) {
+        if (ctx->host_pool) ctx->host_pool->run(n, f);
+        else
+            for (int i = 0; i < n; i++) f(i);
+    };
+    std::vector<PixmapPlan> plans(n);
+    each([&](int i) {
+        if (!data[i] || !sizes[i]) fail(AEON_HIP_EINVAL, "BMP / PNM: empty file");
+        if (modes[i] < AEON_DECODE_BGR8 || modes[i] > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown pixmap decode mode");
+        PixmapPlan& P = plans[i];
+        pixmap_plan(data[i], sizes[i], modes[i], P);
+        const aeon_img_desc& d = descs[i];
+        if (d.width != P.w || d.height != P.h)
+            fail(AEON_HIP_EINVAL, "BMP / PNM: record " + std::to_string(i) + " is " + std::to_string(P.w) + "x" +
+                                      std::to_string(P.h) + ", its descriptor says " + std::to_string(d.width) + "x" +
+                                      std::to_string(d.height));
+        if (d.stride < 0 || (size_t)d.stride < (size_t)P.w * P.channels * P.elem_bytes) fail(AEON_HIP_EINVAL, "stride too small");
+    });
+    // the band table needs the geometry only: built before the staging is laid out
+    std::vector<int>        job_of(n, -1);
+    std::vector<PixmapBand> bands;
+    int                     n_gpu = 0;
+    double                  bytes = 0;
+    for (int i = 0; i < n; i++) {
+        const PixmapPlan& P = plans[i];
+        if (!P.route) continue;
+        job_of[i] = n_gpu++;
+        PixmapJob g{};
+        g.pitch = P.pitch, g.w = P.w, g.h = P.h, g.sbits = P.sbits;
+        pixmap_bands(g, job_of[i], bands);
+        bytes += (double)P.h * (((double)P.w * P.sbits + 7) / 8 + (double)P.w * P.channels * P.elem_bytes);
+    }
+    if (bands.size() > (size_t)INT32_MAX) fail(AEON_HIP_EUNSUPPORTED, "BMP / PNM: too many bands for one call");
+    // layout: the jobs, the bands, then per file the file itself or its pixels (16-byte aligned)
+    std::vector<size_t> at(n);
+    const size_t        bands_at = (size_t)n_gpu * sizeof(PixmapJob);
+    size_t              total    = bands_at + bands.size() * sizeof(PixmapBand);
+    for (int i = 0; i < n; i++) {
+        const PixmapPlan& P = plans[i];
+        total               = (total + 15) & ~(size_t)15;
+        at[i]               = total;
+        total += P.route ? sizes[i] + 16 : (size_t)P.w * P.channels * P.elem_bytes * P.h;
+    }
+    PngStage::Set& st = S.sets[S.next];
+    S.next ^= 1;
+    if (!st.done) HIP_OK(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    if (st.pending) HIP_OK(hipEventSynchronize(st.done));
+    st.pending = false;
+    if (total > st.pinned_cap) grow(st.pinned, st.pinned_cap, total + total / 4, true);
+    if (total > st.dev_cap) grow(st.dev, st.dev_cap, total + total / 4, false);
+    PixmapJob* jobs = (PixmapJob*)st.pinned;
+    if (!bands.empty()) std::memcpy(st.pinned + bands_at, bands.data(), bands.size() * sizeof(PixmapBand));
+    each([&](int i) {
+        const PixmapPlan& P = plans[i];
+        uint8_t*          p = st.pinned + at[i];
+        if (!P.route) {
+            pixmap_decode(data[i], sizes[i], modes[i], p, (size_t)P.w * P.channels * P.elem_bytes, nullptr);
+            return;
+        }
+        PixmapJob& J = jobs[job_of[i]];
+        pixmap_stage(data[i], sizes[i], modes[i], P, J, p);
+        std::memset(p + sizes[i], 0, 16);
+        J.src    = (uint64_t)(st.dev + at[i]);
+        J.out    = (uint64_t)dst_base + descs[i].offset;
+        J.stride = descs[i].stride;
+    });
+    KernelTimer t{};
+    bool        timed = false;
+    if (ctx->timing && n_gpu) {
+        std::lock_guard<std::mutex> tl(ctx->mu);
+        if ((timed = take_timing(ctx))) t = take_timer(ctx, kTimerPng, bytes);
+    }
+    HIP_OK(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, stream));
+    if (timed) HIP_OK(hipEventRecord(t.start, stream));
+    HIP_OK(launch_pixmap((const PixmapJob*)st.dev, (const PixmapBand*)(st.dev + bands_at), (int)bands.size(), stream));
+    if (timed) {
+        HIP_OK(hipEventRecord(t.stop, stream));
+        std::lock_guard<std::mutex> tl(ctx->mu);
+        ctx->timers.push_back(t);
+    }
+    for (int i = 0; i < n; i++) {
+        const PixmapPlan& P = plans[i];
+        if (P.route) continue;
+        const size_t rowb = (size_t)P.w * P.channels * P.elem_bytes;
+        HIP_OK(hipMemcpy2DAsync((uint8_t*)dst_base + descs[i].offset, (size_t)descs[i].stride, st.dev + at[i], rowb, rowb,
+                                (size_t)P.h, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_OK(hipEventRecord(st.done, stream));
+    st.pending = true;
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
+
+int aeon_hip_decode_pixmap_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                                 const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return guarded([&] { return run_pixmap(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream); });
+}
 
 int aeon_hip_decode_png_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
                               const aeon_img_desc* descs, void* dst_base, void* stream)

@@ -1,7 +1,7 @@
 // launch.hpp -- every host-callable launcher and helper that a .hip file defines and a .cpp file calls.
 // The defining .hip file and each caller include it, so the compiler holds a definition against the one
 // declaration its callers see.  The argument structs are only named here (aug_job.hpp, mask16.hpp, box_job.hpp,
-// rcnn_job.hpp, video_job.hpp, jpeg.hpp, png.hpp define them).
+// rcnn_job.hpp, video_job.hpp, jpeg.hpp, png.hpp, pixmap.hpp define them).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -25,6 +25,8 @@ struct JpegChunk;
 struct JpegRows;
 struct JpegHuffFile;
 struct PngJob;
+struct PixmapJob;
+struct PixmapBand;
 
 // augment_kernels.hip
 hipError_t launch_tiles(int km, int rm, bool tail, bool photo, const LaunchArgs& a, int grid, hipStream_t stream,
@@ -69,5 +71,7 @@ hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, i
                             hipStream_t stream);
 // png_kernels.hip: png_inflate then png_unfilter over the jobs, one wave per file each
 hipError_t launch_png(const PngJob* jobs, int n_jobs, int unfilter_lds, int32_t* error, hipStream_t stream);
+// pixmap_kernels.hip: pixmap_convert, one workgroup per band
+hipError_t launch_pixmap(const PixmapJob* jobs, const PixmapBand* bands, int n_bands, hipStream_t stream);
 
 } // namespace aeon_hip

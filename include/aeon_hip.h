@@ -273,7 +273,8 @@ int aeon_hip_set_timing(aeon_hip_ctx* ctx, int every);
 /* Drain the timers: per kernel kind [0]=augment (final), [1]=contrast statistics,
  * [2]=pre-passes (resize_short, CUBIC / AREA / LANCZOS4 resize, 2x-area ahead of photometric),
  * [3]=JPEG IDCT + colour kernels of aeon_hip_decode_jpeg_batch (bytes: decoded pixels),
- * [4]=png_inflate + png_unfilter of aeon_hip_decode_png_batch (bytes: inflated scanlines): total ms,
+ * [4]=PNG and pixmap decode kernels (png_inflate + png_unfilter of aeon_hip_decode_png_batch, bytes: inflated
+ * scanlines; pixmap_convert of aeon_hip_decode_pixmap_batch, bytes: source rows plus records): total ms,
  * total algorithmic bytes, launches.  The arrays hold `kinds` entries (AEON_HIP_TIMER_KINDS = all;
  * fewer are filled, more are left alone).  Resets the totals of every kind. */
 #define AEON_HIP_TIMER_KINDS 5
@@ -340,6 +341,39 @@ int aeon_png_decoder_route(const void* data, size_t size, int* device);
  * for CPU tests and sanitizer builds): decodes like aeon_decode_png.  AEON_HIP_EUNSUPPORTED: the file is not
  * routed to the device; AEON_HIP_EDEVICE: what the device reports as corrupt. */
 int aeon_png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+
+/* Pixmap decode -- the same extractors on BMP and PNM (PBM / PGM / PPM) files, the uncompressed containers
+ * cv::imdecode reads.  Modes are the PNG entries' under container-neutral names.  aeon_pixmap_info (header
+ * only): size, the decoded bits per sample (16 for a PNM with maxval > 255, else 8), the file's channels (3
+ * for P3 / P6 and every BMP, else 1) and *format: AEON_PIXMAP_BMP or the PNM magic's digit (1..6).
+ * aeon_decode_pixmap is the complete decoder on the host: height rows of `stride` bytes to dst, the element
+ * size (2: ANYDEPTH of a 16-bit PNM, native uint16; else 1) to *elem_bytes (may be NULL).  Decoded: P1..P6
+ * with maxval up to 65535, BI_RGB BMP files of 1, 4, 8, 24 and 32 bits per pixel with a core (12-byte) or
+ * a 40-byte-or-longer info header, bottom-up or top-down.  Refused with AEON_HIP_EUNSUPPORTED: RLE4 / RLE8
+ * and 16-bit (555 / 565 / bitfields) BMP files.  Messages start with "BMP:" / "PNM:".  The decode rules, and
+ * which of them no reference output pins, are DESIGN.md section 20. */
+#define AEON_DECODE_BGR8     AEON_PNG_BGR8
+#define AEON_DECODE_GRAY8    AEON_PNG_GRAY8
+#define AEON_DECODE_ANYDEPTH AEON_PNG_ANYDEPTH
+#define AEON_PIXMAP_BMP      0
+int aeon_pixmap_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* channels, int* format);
+int aeon_decode_pixmap(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes);
+/* The pixmap stage: n BMP / PNM files decoded into device memory as aeon_decode_pixmap(data[i], sizes[i],
+ * modes[i], ...) decodes them, byte for byte: record i at dst_base + descs[i].offset with descs[i].stride bytes
+ * per row; descs[i].width / height must be the file's (aeon_pixmap_info).  The host parses the header, builds
+ * the palette / gray table and copies the file as it is into pinned staging; the GPU converts it (pixmap_convert,
+ * one workgroup per file and band of rows).  The device takes binary PNM (P4, P5, P6) and uncompressed BMP
+ * files below 2^31 bytes; ASCII PNM (P1, P2, P3) decodes on the host and goes up as pixels with the same H2D.
+ * Whatever aeon_decode_pixmap refuses is refused here before any launch, same code and message; the stage has
+ * no device error.  Asynchronous on `stream`; the files may be released when the call returns. */
+int aeon_hip_decode_pixmap_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                                 const aeon_img_desc* descs, void* dst_base, void* stream);
+/* The host half of the stage for one file, on the calling thread, no device.  *gpu_route: 1 when the device
+ * converts the file, 0 when it decodes on the host.  *staged_bytes: the file's or the pixels' bytes in the H2D. */
+int aeon_pixmap_host_stage(const void* data, size_t size, int mode, int* gpu_route, int64_t* staged_bytes);
+/* The stage's kernel code run on the calling thread, lane after lane, no device (for CPU tests and sanitizer
+ * builds): decodes like aeon_decode_pixmap.  AEON_HIP_EUNSUPPORTED: the file is not routed to the device. */
+int aeon_pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
 
 /* batch_sampler::sample_patches (src/augment_image.cpp:567-586) of the factory's batch_samplers[sampler]
  * over n normalized object boxes (xmin, ymin, xmax, ymax in [0, 1]) -- what aeon's tests call as
