@@ -255,6 +255,7 @@ def lib():
         L.aeon_hip_stager_flush.argtypes = [vp, vp]
         L.aeon_hip_stager_launch.argtypes = [vp, vp]
         L.aeon_hip_stager_wait.argtypes = [vp, vp]
+        L.aeon_hip_stager_last_launch.argtypes = [vp, P(StagerLaunchInfo)]
         L.aeon_hip_release_stream.argtypes = [vp, vp]
         L.aeon_hip_stager_last_error.restype = ctypes.c_char_p
         L.aeon_hip_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -959,6 +960,11 @@ class Context:
 STAGER_IMAGE, STAGER_MASK, STAGER_DEVICE_OUT = 0, 1, 0x100
 
 
+class StagerLaunchInfo(ctypes.Structure):  # aeon_stager_launch_info
+    _fields_ = [("launches", ctypes.c_uint64), ("src_zero_copy", ctypes.c_int32), ("out_direct", ctypes.c_int32),
+                ("chunks", ctypes.c_int32), ("records", ctypes.c_int32)]
+
+
 def _check_stager(rc):
     if rc != 0:
         raise AeonHipError(rc, lib().aeon_hip_stager_last_error().decode())
@@ -999,6 +1005,13 @@ class Stager:
     def wait_buffer(batch_out):
         """aeon_hip_stager_wait(NULL, batch_out): whichever stager launched the buffer, if any."""
         _check_stager(lib().aeon_hip_stager_wait(None, ctypes.c_void_p(batch_out)))
+
+    def last_launch(self):
+        """The paths of the most recently launched window (aeon_hip_stager_last_launch): a dict of launches,
+        src_zero_copy, out_direct, chunks, records."""
+        info = StagerLaunchInfo()
+        _check_stager(lib().aeon_hip_stager_last_launch(self._h, ctypes.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in StagerLaunchInfo._fields_}
 
     def close(self):
         if getattr(self, "_h", None):

@@ -426,19 +426,33 @@ int aeon_hip_ctx_destroy(aeon_hip_ctx* c)
     });
 }
 
+} // extern "C"
+
+namespace {
+// The ring slots of the calls still open on this stream get their completion event now, while the
+// stream exists (the next call on another stream would record it there -- on a destroyed stream by
+// then); the context then holds no reference to the stream through its ring.
+void close_stream_slots(aeon_hip_ctx* ctx, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_OK(hipSetDevice(ctx->device));
+    if (ctx->open_stream == stream) {
+        close_slots(ctx);
+        ctx->open_stream = nullptr;
+    }
+}
+} // namespace
+
+extern "C" {
+
 int aeon_hip_release_stream(aeon_hip_ctx* ctx, void* stream)
 {
     return guarded([&] {
         if (!ctx) fail(AEON_HIP_EINVAL, "null ctx");
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        HIP_OK(hipSetDevice(ctx->device));
-        // the ring slots of the calls still open on this stream get their completion event now, while
-        // the stream exists (the next call on another stream would record it there -- on a destroyed
-        // stream by then); the context then holds no reference to the stream
-        if (ctx->open_stream == (hipStream_t)stream) {
-            close_slots(ctx);
-            ctx->open_stream = nullptr;
-        }
+        close_stream_slots(ctx, (hipStream_t)stream);
+        // its error word goes back to the table unread: whatever bits it holds are cleared ahead of its
+        // next owner's first kernel (stream_error)
+        release_stream_error(ctx, (hipStream_t)stream, /*unread=*/true);
         return 0;
     });
 }
@@ -447,17 +461,21 @@ int aeon_hip_synchronize(aeon_hip_ctx* ctx, void* stream)
 {
     return guarded([&] {
         if (!ctx) fail(AEON_HIP_EINVAL, "null ctx");
-        if (const int rc = aeon_hip_release_stream(ctx, stream)) return rc;
+        close_stream_slots(ctx, (hipStream_t)stream);
         HIP_OK(hipSetDevice(ctx->device));
-        HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-        // this stream's word (its calls' kernels are done): read and cleared on the stream itself, the
-        // word then handed back (a stream that is reused gets a word again at its next call)
+        // this stream's word: copied out behind the stream's calls and looked at only once the stream has
+        // been waited for (the copy has landed by then, whether or not the runtime held this thread for
+        // it), cleared on the stream itself when it holds a bit, and handed back only after the clear is
+        // complete (a stream that is reused gets a word again at its next call)
         int32_t* word = stream_error(ctx, (hipStream_t)stream);
         int32_t  err  = 0;
         HIP_OK(hipMemcpyAsync(&err, word, sizeof(err), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        if (err != 0) HIP_OK(hipMemsetAsync(word, 0, sizeof(int32_t), (hipStream_t)stream));
         HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-        (void)stream_error(ctx, (hipStream_t)stream, true);
+        if (err != 0) {
+            HIP_OK(hipMemsetAsync(word, 0, sizeof(int32_t), (hipStream_t)stream));
+            HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+        }
+        release_stream_error(ctx, (hipStream_t)stream, /*unread=*/false);
         if (err != 0) {
             fail(AEON_HIP_EDEVICE, "device error word " + std::to_string(err) + " (" + device_error_text(err) + ")");
         }

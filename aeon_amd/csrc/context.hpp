@@ -80,6 +80,7 @@ struct aeon_hip_ctx {
                                   // [i] the i-th stream's (stream_error)
     static constexpr int kErrWords = 64;
     hipStream_t err_stream[kErrWords] = {};
+    bool        err_unread[kErrWords] = {}; // handed back without having been read: cleared for its next owner
     std::mutex  err_mu;
     int32_t*    call_error = nullptr; // the word of the call in progress (run_batch, under mu)
     uint32_t*  d_tail  = nullptr; // per ring slot: dynamic-tail tile counters (zero between launches)
@@ -247,22 +248,40 @@ inline bool take_timing(aeon_hip_ctx* ctx)
 // The device error word of the calls on `stream`: each stream its own (so that aeon_hip_synchronize of
 // one stream -- a decode window -- never reads or clears a bit another stream's kernels set meanwhile),
 // the null stream and streams beyond the table's size share word 0.  A stream keeps its word until
-// aeon_hip_synchronize has read it.
-inline int32_t* stream_error(aeon_hip_ctx* ctx, hipStream_t stream, bool release = false)
+// aeon_hip_synchronize has read it or aeon_hip_release_stream gives the stream up
+// (release_stream_error).  A word that was given up unread may hold bits: it is cleared on its new
+// owner's stream ahead of that stream's first kernel -- the old owner's work is complete by then (the
+// contract of aeon_hip_release_stream), so no old bit arrives after the clear, and the clear is ordered
+// before every kernel of the new owner, so none of theirs is lost.
+inline int32_t* stream_error(aeon_hip_ctx* ctx, hipStream_t stream)
 {
     if (!stream) return ctx->d_error;
     std::lock_guard<std::mutex> lock(ctx->err_mu);
     int free_i = 0;
     for (int i = 1; i < aeon_hip_ctx::kErrWords; i++) {
-        if (ctx->err_stream[i] == stream) {
-            if (release) ctx->err_stream[i] = nullptr;
-            return ctx->d_error + i;
-        }
+        if (ctx->err_stream[i] == stream) return ctx->d_error + i;
         if (!free_i && !ctx->err_stream[i]) free_i = i;
     }
-    if (release || !free_i) return ctx->d_error;
+    if (!free_i) return ctx->d_error;
+    if (ctx->err_unread[free_i]) {
+        HIP_OK(hipMemsetAsync(ctx->d_error + free_i, 0, sizeof(int32_t), stream));
+        ctx->err_unread[free_i] = false;
+    }
     ctx->err_stream[free_i] = stream;
     return ctx->d_error + free_i;
+}
+
+// `stream` gives its word (if it has one) back to the table.  unread: nobody looked at the word, so it
+// may hold bits (see above); else aeon_hip_synchronize has read it and left it zero.
+inline void release_stream_error(aeon_hip_ctx* ctx, hipStream_t stream, bool unread)
+{
+    if (!stream) return;
+    std::lock_guard<std::mutex> lock(ctx->err_mu);
+    for (int i = 1; i < aeon_hip_ctx::kErrWords; i++)
+        if (ctx->err_stream[i] == stream) {
+            ctx->err_stream[i] = nullptr;
+            ctx->err_unread[i] = unread;
+        }
 }
 
 // A table the host wrote into s.vram is published to the launches behind it: a full fence so the

@@ -116,6 +116,27 @@ struct Window {
     std::atomic<int>                    copying{0}; // waits copying a pageable batch out of dev_out
 };
 
+// A wait's hold on its window's `copying` count, taken under s->mu and given back on every way out of
+// the wait -- a runtime call that fails ahead of the copy included: the window's last wait and
+// staging_window spin until the count is 0.
+struct CopyHold {
+    Window* w = nullptr;
+    CopyHold() = default;
+    CopyHold(const CopyHold&)            = delete;
+    CopyHold& operator=(const CopyHold&) = delete;
+    void take(Window& win)
+    {
+        win.copying.fetch_add(1, std::memory_order_acq_rel);
+        w = &win;
+    }
+    void drop()
+    {
+        if (w) w->copying.fetch_sub(1, std::memory_order_acq_rel);
+        w = nullptr;
+    }
+    ~CopyHold() { drop(); }
+};
+
 } // namespace
 
 struct aeon_hip_stager {
@@ -129,6 +150,7 @@ struct aeon_hip_stager {
     int           cur = 0; // the window stages go to
     uint64_t      gens = 0;
     std::vector<hipEvent_t> spare_events;
+    aeon_stager_launch_info last{}; // the last window launched (launch_window, under mu)
     std::atomic<int>        waiters{0}; // aeon_hip_stager_wait(NULL, ...) calls inside this stager (destroy waits)
 };
 
@@ -298,6 +320,7 @@ void launch_window(aeon_hip_stager* s, Window& w)
     }();
     const uint8_t* src_base = nullptr;
     if (all_out_mapped && used_chunks == 1 && !src_copy) src_base = (const uint8_t*)mapped_view(used->host);
+    const bool zero_copy = src_base != nullptr;
     if (!src_base) {
         grow(w.dev_src, w.dev_src_cap, std::max<size_t>(total, 16));
         for (const Chunk& c : w.chunks)
@@ -342,6 +365,8 @@ void launch_window(aeon_hip_stager* s, Window& w)
     w.state    = Window::LAUNCHED;
     w.gen      = ++s->gens;
     w.unwaited = (int)w.batches.size();
+    s->last    = aeon_stager_launch_info{s->last.launches + 1, zero_copy ? 1 : 0, (on_device || all_mapped) ? 1 : 0,
+                                         used_chunks, (int32_t)descs.size()};
     std::lock_guard<std::mutex> r(g_reg_mu);
     for (auto& b : w.batches) g_pending[b->out] = Pending{s, w.gen};
 }
@@ -391,6 +416,7 @@ void wait_batch(aeon_hip_stager* s, void* batch_out, bool& found)
     void*       copy_dst = nullptr; // pageable batch: its D2H, made here
     const void* copy_src = nullptr;
     size_t      copy_bytes = 0;
+    CopyHold    hold;
     {
         std::lock_guard<std::mutex> l(s->mu);
         for (Window& w : s->win) {
@@ -402,7 +428,7 @@ void wait_batch(aeon_hip_stager* s, void* batch_out, bool& found)
                     wp = &w, gen = w.gen, wdone = w.done, wstream = w.stream;
                     last = --w.unwaited == 0;
                     if (b->d2h) {
-                        w.copying.fetch_add(1, std::memory_order_acq_rel);
+                        hold.take(w);
                         copy_dst   = b->out;
                         copy_src   = w.dev_out + (size_t)b->first * s->out.item_stride;
                         copy_bytes = (size_t)b->n * s->out.item_stride;
@@ -418,7 +444,7 @@ void wait_batch(aeon_hip_stager* s, void* batch_out, bool& found)
     // (the window's device outputs stay until its last wait has returned: reset_window runs after it)
     if (copy_bytes) {
         const hipError_t e = hipMemcpy(copy_dst, copy_src, copy_bytes, hipMemcpyDeviceToHost);
-        wp->copying.fetch_sub(1, std::memory_order_acq_rel);
+        hold.drop();
         hip_ok(e, "hipMemcpy");
     }
     if (!last) return;
@@ -587,6 +613,15 @@ int aeon_hip_stager_flush(aeon_hip_stager* s, void* batch_out)
         bool found = false;
         wait_batch(s, batch_out, found);
         if (!found) fail(AEON_HIP_EINVAL, "batch buffer completed by another thread's wait");
+    });
+}
+
+int aeon_hip_stager_last_launch(aeon_hip_stager* s, aeon_stager_launch_info* info)
+{
+    return stager_guarded([&] {
+        if (!s || !info) fail(AEON_HIP_EINVAL, "null argument");
+        std::lock_guard<std::mutex> l(s->mu);
+        *info = s->last;
     });
 }
 

@@ -261,7 +261,12 @@ int aeon_hip_synchronize(aeon_hip_ctx* ctx, void* stream);
  * slots are reused after it), so a stream the calls ran on must stay valid until aeon_hip_synchronize or
  * aeon_hip_release_stream has been called on it (or the context is destroyed).  aeon_hip_release_stream:
  * the caller is about to destroy `stream` -- the pending completion event is recorded on it now and the
- * context keeps no reference to it.  No wait. */
+ * context keeps no reference to it: the stream's device error word goes back to the context's table
+ * too (there are 63; streams beyond that share the null stream's word).  The calls made on the stream
+ * must be complete by then, however the caller waited for them.  Bits they set that no
+ * aeon_hip_synchronize has read are discarded: the word is cleared on its next owner's stream ahead of
+ * that stream's first kernel, so it reaches no other stream with a bit set and loses none the new
+ * owner's kernels set.  No wait. */
 int aeon_hip_release_stream(aeon_hip_ctx* ctx, void* stream);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
@@ -666,6 +671,19 @@ int aeon_hip_stager_stage(aeon_hip_stager* stager, void* batch_out, int idx, con
 int aeon_hip_stager_launch(aeon_hip_stager* stager, void* batch_out);
 int aeon_hip_stager_wait(aeon_hip_stager* stager, void* batch_out);
 int aeon_hip_stager_flush(aeon_hip_stager* stager, void* batch_out);
+/* Read-only: the paths the stager's most recently launched window took (as aeon_png_host_stage's gpu_route:
+ * a test can prove which path it compared).  launches == 0: nothing was launched yet, the rest is 0.  A
+ * window whose launch failed and was dropped leaves the previous report in place. */
+typedef struct aeon_stager_launch_info {
+    uint64_t launches;      /* windows this stager has launched so far */
+    int32_t  src_zero_copy; /* 1: the kernels read the sources from the window's pinned chunk over PCIe;
+                             * 0: one H2D per chunk into device memory ahead of them */
+    int32_t  out_direct;    /* 1: the kernels stored into the batch buffers (device, or pinned and mapped);
+                             * 0: into device memory, each batch's D2H made by its wait */
+    int32_t  chunks;        /* pinned staging chunks that held records of the window */
+    int32_t  records;       /* records of the window */
+} aeon_stager_launch_info;
+int aeon_hip_stager_last_launch(aeon_hip_stager* stager, aeon_stager_launch_info* info);
 const char* aeon_hip_stager_last_error(void);
 
 /* ---- host staging (replaces the dead cuMemAllocHost branch, src/buffer_batch.cpp:150-186) -- */
