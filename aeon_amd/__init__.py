@@ -244,7 +244,15 @@ def lib():
         L.aeon_pixmap_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int),
                                              P(ctypes.c_int64)]
         L.aeon_pixmap_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
-        L.aeon_avi_frames.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(AviFrame), ctypes.c_int] + [P(ctypes.c_int)] * 3
+        L.aeon_tiff_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 4
+        L.aeon_decode_tiff.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t, P(ctypes.c_int)]
+        L.aeon_hip_decode_tiff_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ctypes.c_int), P(ImgDesc),
+                                                 vp, vp]
+        L.aeon_tiff_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int),
+                                           P(ctypes.c_int64)]
+        L.aeon_tiff_decoder_route.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
+        L.aeon_tiff_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
+        L.aeon_avi_frames.argtypes =[ctypes.c_char_p, ctypes.c_size_t, P(AviFrame), ctypes.c_int] + [P(ctypes.c_int)] * 3
         L.aeon_avi_last_error.restype = ctypes.c_char_p
         L.aeon_hip_video_batch.argtypes = [vp, ctypes.c_int, P(ctypes.c_int32), P(ImgDesc), vp, P(AugParams), ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint64, vp]
@@ -755,6 +763,53 @@ def pixmap_gpu_emulate(data, mode=DECODE_BGR8):
     return out
 
 
+def tiff_info(data):
+    """(width, height, the file's channels, the element bytes DECODE_ANYDEPTH gives) of a TIFF file (aeon_tiff_info)."""
+    v = [ctypes.c_int() for _ in range(4)]
+    _check(lib().aeon_tiff_info(bytes(data), len(data), *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def _tiff_out(data, mode):
+    w, h, _, eb = tiff_info(data)
+    cn = 3 if mode == DECODE_BGR8 else 1
+    return np.zeros((h, w, cn) if cn == 3 else (h, w), np.uint16 if (mode == DECODE_ANYDEPTH and eb == 2) else np.uint8)
+
+
+def decode_tiff(data, mode=DECODE_BGR8):
+    """cv::imdecode of a TIFF file as aeon's extractors ask for it (aeon_decode_tiff): HxWx3 uint8 BGR (DECODE_BGR8),
+    HxW uint8 (DECODE_GRAY8), or HxW uint8 / uint16 (a 16-bit gray file) (DECODE_ANYDEPTH)."""
+    out = _tiff_out(data, mode)
+    eb = ctypes.c_int()
+    _check(lib().aeon_decode_tiff(bytes(data), len(data), mode, out.ctypes.data, out.strides[0], ctypes.byref(eb)))
+    return out
+
+
+def tiff_host_stage(data, mode=DECODE_BGR8):
+    """The TIFF batch decode's host work for one file (aeon_tiff_host_stage): (does the device decode the file?,
+    bytes staged for the H2D)."""
+    g, nb = ctypes.c_int(), ctypes.c_int64()
+    _check(lib().aeon_tiff_host_stage(bytes(data), len(data), mode, ctypes.byref(g), ctypes.byref(nb)))
+    return bool(g.value), nb.value
+
+
+def tiff_decoder_route(data):
+    """Does the decoder send this TIFF file through the stage (aeon_tiff_decoder_route)?"""
+    g = ctypes.c_int()
+    _check(lib().aeon_tiff_decoder_route(bytes(data), len(data), ctypes.byref(g)))
+    return bool(g.value)
+
+
+def tiff_gpu_emulate(data, mode=DECODE_BGR8, out=None):
+    """decode_tiff through the TIFF stage's kernel code run on the host (aeon_tiff_gpu_emulate), into `out` (a
+    2-D uint8 view with any row stride) if given.  AeonHipError for a file the stage leaves to the host decoder
+    or one the device would report as corrupt."""
+    if out is None:
+        out = _tiff_out(data, mode)
+    _check(lib().aeon_tiff_gpu_emulate(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
+    return out
+
+
 def unbiased_round(x):
     """nervana::unbiased_round (aeon src/util.cpp:212-239)."""
     r = ctypes.c_int64()
@@ -933,6 +988,19 @@ class Context:
             raise ValueError(f"{len(m)} modes / {len(d)} descriptors for {n} files")
         _check(lib().aeon_hip_decode_pixmap_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
                                                   ctypes.c_void_p(stream or 0)))
+
+    def decode_tiff_batch(self, files, modes, descs, dst_ptr, stream=0):
+        """decode_tiff of TIFF files into device memory (aeon_hip_decode_tiff_batch): files = list of bytes (or a
+        JpegFiles, marshalled once), modes[i] = DECODE_BGR8 / DECODE_GRAY8 / DECODE_ANYDEPTH, descs[i] = where
+        record i goes (HWC; ANYDEPTH of a 16-bit gray file: native uint16)."""
+        jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
+        n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
+        m = modes if isinstance(modes, ctypes.Array) else (ctypes.c_int * n)(*[int(x) for x in modes])
+        d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
+        if len(m) < n or len(d) < n:
+            raise ValueError(f"{len(m)} modes / {len(d)} descriptors for {n} files")
+        _check(lib().aeon_hip_decode_tiff_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
+                                                ctypes.c_void_p(stream or 0)))
 
     def set_timing(self, every=1):
         """Time the launches of one call in `every` (0 = off) with HIP events on their stream."""

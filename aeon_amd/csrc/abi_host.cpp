@@ -15,6 +15,7 @@
 #include "json.hpp"
 #include "param_factory.hpp"
 #include "pixmap.hpp"
+#include "tiff.hpp"
 #include "png.hpp"
 #include "rcnn_host.hpp"
 
@@ -218,6 +219,85 @@ int aeon_pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, 
         pixmap_checked_plan(data, size, mode, stride, P);
         if (!pixmap_gpu_emulate(data, size, mode, dst, stride))
             fail(AEON_HIP_EUNSUPPORTED, "PNM: the file is not routed to the device (ASCII samples)");
+        return 0;
+    });
+}
+
+int aeon_tiff_info(const void* data, size_t size, int* width, int* height, int* channels, int* elem_bytes)
+{
+    return guarded([&] {
+        if (!data || !width || !height || !channels || !elem_bytes) fail(AEON_HIP_EINVAL, "null argument");
+        TiffPlan P;
+        tiff_plan(data, size, AEON_DECODE_ANYDEPTH, P);
+        *width = P.w, *height = P.h, *channels = P.file_channels, *elem_bytes = P.elem_bytes;
+        return 0;
+    });
+}
+
+namespace {
+// the IFD parse, the mode and the stride of the three TIFF entries that write a record
+void tiff_checked_plan(const void* data, size_t size, int mode, size_t stride, TiffPlan& P)
+{
+    if (mode < AEON_DECODE_BGR8 || mode > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown TIFF decode mode");
+    tiff_plan(data, size, mode, P);
+    if (stride < (size_t)P.w * P.channels * P.elem_bytes || stride > INT32_MAX) fail(AEON_HIP_EINVAL, "stride too small");
+}
+} // namespace
+
+int aeon_decode_tiff(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        TiffPlan P;
+        tiff_checked_plan(data, size, mode, stride, P);
+        tiff_decode(data, size, mode, dst, stride, elem_bytes);
+        return 0;
+    });
+}
+
+int aeon_tiff_host_stage(const void* data, size_t size, int mode, int* gpu_route, int64_t* staged_bytes)
+{
+    return guarded([&] {
+        if (!data || !gpu_route || !staged_bytes) fail(AEON_HIP_EINVAL, "null argument");
+        if (mode < AEON_DECODE_BGR8 || mode > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown TIFF decode mode");
+        TiffPlan P;
+        tiff_plan(data, size, mode, P);
+        *gpu_route = P.route;
+        if (P.route) {
+            TiffJob                J;
+            std::vector<TiffStrip> strips;
+            std::vector<TiffBand>  bands;
+            std::vector<uint8_t>   file(size + 16);
+            tiff_stage(data, size, mode, P, 0, J, strips, bands, file.data());
+            *staged_bytes = (int64_t)size;
+        } else {
+            const size_t         stride = (size_t)P.w * P.channels * P.elem_bytes;
+            std::vector<uint8_t> px(stride * P.h);
+            tiff_decode(data, size, mode, px.data(), stride, nullptr);
+            *staged_bytes = (int64_t)px.size();
+        }
+        return 0;
+    });
+}
+
+int aeon_tiff_decoder_route(const void* data, size_t size, int* device)
+{
+    return guarded([&] {
+        if (!data || !device) fail(AEON_HIP_EINVAL, "null argument");
+        *device = tiff_routed(data, size) ? 1 : 0;
+        return 0;
+    });
+}
+
+int aeon_tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        TiffPlan P;
+        tiff_checked_plan(data, size, mode, stride, P);
+        const int r = tiff_gpu_emulate(data, size, mode, dst, stride);
+        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "TIFF: the file is not routed to the device (an LZW / PackBits strip above 32 KiB)");
+        if (r < 0) fail(AEON_HIP_EDEVICE, "TIFF: strip data corrupt or truncated (GPU stage)");
         return 0;
     });
 }

@@ -35,7 +35,8 @@ std::string device_error_text(int err)
                 {128, "generic resize footprint exceeds the launch's LDS"},
                 {256, "JPEG entropy-coded data corrupt or truncated (GPU Huffman decoder)"},
                 {512, "separable resize band wider than its workgroup"},
-                {1024, "PNG image data corrupt or truncated (GPU inflate / unfilter)"}};
+                {1024, "PNG image data corrupt or truncated (GPU inflate / unfilter)"},
+                {2048, "TIFF strip data corrupt or truncated (GPU LZW / PackBits / Deflate decoder)"}};
     std::string s;
     for (const auto& b : bits)
         if (err & b.bit) s += (s.empty() ? "" : "; ") + std::string(b.what);
@@ -308,6 +309,7 @@ aeon_hip_ctx::~aeon_hip_ctx()
     jpeg_state_destroy(jpeg);
     png_stage_destroy(png);
     png_stage_destroy(pixmap);
+    png_stage_destroy(tiff);
     if (!open_slots.empty()) (void)hipStreamSynchronize(open_stream);
     for (Slot& s : slots)
         if (s.pending) (void)hipEventSynchronize(slots[s.cover].done);

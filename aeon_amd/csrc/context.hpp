@@ -109,6 +109,7 @@ struct aeon_hip_ctx {
     aeon_hip::JpegState* jpeg = nullptr;     // JPEG decode stage (pool, staging ring), on first use
     aeon_hip::PngStage*  png  = nullptr;     // PNG decode stage (staging ring, scratch), on first use
     aeon_hip::PngStage*  pixmap = nullptr;   // pixmap decode stage: a staging ring of its own (no scratch), on first use
+    aeon_hip::PngStage*  tiff = nullptr;     // TIFF decode stage (staging ring, scratch of the decoded strips), on first use
     aeon_hip::thread_pool* host_pool = nullptr; // the owning decoder's pool (ctx_share_pool), for the JPEG stage
     // localization_rcnn: the anchor table of the last config seen stays resident (uploaded once), and the
     // direct call's engine end states pass through a small device array

@@ -2,6 +2,7 @@
 #include "host.hpp"
 #include "box_job.hpp"
 #include "pixmap.hpp"
+#include "tiff.hpp"
 #include "png.hpp"
 #include "rcnn_job.hpp"
 
@@ -257,7 +258,8 @@ public:
     // for pixel masks).  JPEG files are decoded on the device, and so are the PNG files the PNG stage's routing
     // rule gives it (png.hpp); the others (Adam7, very wide rows) on the host pool while staging (png_host.cpp).
     // BMP and binary PNM files are converted on the device (the pixmap stage, pixmap.hpp), ASCII PNM files decoded
-    // on the host pool while staging (pixmap_host.cpp).  The sniff is strict: anything else is the JPEG parser's.
+    // on the host pool while staging (pixmap_host.cpp).  TIFF files in strips are decoded on the device (the TIFF
+    // stage, tiff.hpp), those with LZW / PackBits strips above 32 KiB on the host pool (tiff_host.cpp).  The sniff is strict: anything else is the JPEG parser's.
     void inspect(window_part&, int idx, decoded_element& e) const override
     {
         static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
@@ -280,6 +282,15 @@ public:
             e.channels      = m_mask ? 1 : cn;
             e.elem_bytes    = (m_mask && depth == 16) ? 2 : 1;
             e.stride        = e.width * e.channels * e.elem_bytes;
+        } else if (e.encoded && tiff_sniff(e.data, e.size)) {
+            int fcn = 0, eb = 1;
+            check(aeon_tiff_info(e.data, e.size, &e.width, &e.height, &fcn, &eb));
+            e.encoded     = false;
+            e.tiff_mode   = m_mask ? AEON_DECODE_ANYDEPTH : (cn == 3 ? AEON_DECODE_BGR8 : AEON_DECODE_GRAY8);
+            e.tiff_device = tiff_routed(e.data, e.size);
+            e.channels    = m_mask ? 1 : cn;
+            e.elem_bytes  = m_mask ? eb : 1;
+            e.stride      = e.width * e.channels * e.elem_bytes;
         } else if (e.encoded) {
             if (m_mask)
                 throw std::runtime_error("encoded pixel masks are decoded from PNG files only (JPEG masks: pass the "
@@ -302,6 +313,7 @@ public:
         if (e.encoded) jpegs.add(e.data, e.size, part.descs[idx]);
         if (e.png_device) jpegs.png.add(e.data, e.size, e.png_mode, part.descs[idx]);
         if (e.pixmap_device) jpegs.pixmap.add(e.data, e.size, e.pixmap_mode, part.descs[idx]);
+        if (e.tiff_device) jpegs.tiff.add(e.data, e.size, e.tiff_mode, part.descs[idx]);
         offset += arena_align(b);
     }
     void stage_record(const decode_window& w, size_t k, int idx, const decoded_element& e) const override
@@ -313,6 +325,8 @@ public:
             check(aeon_decode_png(e.data, e.size, e.png_mode, dst, row, nullptr));
         } else if (e.pixmap_mode >= 0) {
             check(aeon_decode_pixmap(e.data, e.size, e.pixmap_mode, dst, row, nullptr));
+        } else if (e.tiff_mode >= 0) {
+            check(aeon_decode_tiff(e.data, e.size, e.tiff_mode, dst, row, nullptr));
         } else if ((size_t)e.stride == row) {
             std::memcpy(dst, e.data, row * e.height);
         } else {
@@ -1439,6 +1453,10 @@ void batch_decoder::stage_sources(window_slot& ws, window_plan& p, hipStream_t s
             check(aeon_hip_decode_pixmap_batch(m_ctx, (int)std::min(kJpegCallFiles, j.pixmap.files.size() - f),
                                                j.pixmap.files.data() + f, j.pixmap.sizes.data() + f, j.pixmap.modes.data() + f,
                                                j.pixmap.descs.data() + f, ws.dev_src, stream));
+        for (size_t f = 0; f < j.tiff.files.size(); f += kJpegCallFiles)
+            check(aeon_hip_decode_tiff_batch(m_ctx, (int)std::min(kJpegCallFiles, j.tiff.files.size() - f), j.tiff.files.data() + f,
+                                             j.tiff.sizes.data() + f, j.tiff.modes.data() + f, j.tiff.descs.data() + f, ws.dev_src,
+                                             stream));
     }
 }
 

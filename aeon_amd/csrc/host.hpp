@@ -69,7 +69,7 @@ struct image_config {
     explicit image_config(const Json& js, bool half = false); // half: "float16" / "bfloat16" with "extended_output_type": true
 };
 
-// An element of a record: an encoded JPEG, PNG, BMP or PNM file (size > 0; width/height/channels filled in from
+// An element of a record: an encoded JPEG, PNG, BMP, PNM or TIFF file (size > 0; width/height/channels filled in from
 // its header by its provider's inspect step), decoded HWC uint8 pixels (what image::extractor::extract
 // returns), or the datum of a box, video or label provider (data / size: JSON metadata, an MJPEG AVI
 // file whose width / height the demux fills in from its first frame, a label's bytes).
@@ -84,9 +84,12 @@ struct decoded_element {
     int            pixmap_mode   = -1; // BMP / PNM file: its AEON_DECODE_* mode
     bool           pixmap_device = false; // ... converted on the device (the pixmap stage, pixmap.hpp's routing
                                           // rule), else decoded on the host pool while staging (ASCII PNM)
+    int            tiff_mode   = -1; // TIFF file: its AEON_DECODE_* mode
+    bool           tiff_device = false; // ... decoded on the device (the TIFF stage, tiff.hpp's routing rule), else on
+                                        // the host pool while staging
     int            elem_bytes = 1;  // bytes per sample (2: a 16-bit mask / depth map)
     // decoded on the device, straight into the device-decoded region of the source arena
-    bool on_device() const { return encoded || png_device || pixmap_device; }
+    bool on_device() const { return encoded || png_device || pixmap_device || tiff_device; }
 };
 
 // What one provider keeps of a window's n records (etl_provider::new_part): the source descriptors into the
@@ -125,12 +128,14 @@ struct png_list {
 };
 
 using pixmap_list = png_list; // the BMP / PNM files likewise (AEON_DECODE_* modes)
+using tiff_list   = png_list; // and the TIFF files
 
-// The JPEG files one provider wants decoded into the device-decoded region, with their destinations; its PNG
-// and pixmap files travel beside them
+// The JPEG files one provider wants decoded into the device-decoded region, with their destinations; its PNG,
+// pixmap and TIFF files travel beside them
 struct jpeg_list {
     png_list                   png;
     pixmap_list                pixmap;
+    tiff_list                  tiff;
     std::vector<const void*>   files;
     std::vector<size_t>        sizes;
     std::vector<aeon_img_desc> descs;

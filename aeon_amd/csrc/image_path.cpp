@@ -1,7 +1,7 @@
 // image_path.cpp -- the image path of the device half: a call's records through run_direct (one launch),
 // run_records (contrast records in one launch) or run_batch's multi-pass launches over the CallPlan that
 // plan.cpp returns, run_video on top of them, and the C entries for augment, mask, pair, depthmap, video,
-// transpose, the JPEG batch, the PNG batch and the pixmap batch.
+// transpose, the JPEG batch, the PNG batch, the pixmap batch and the TIFF batch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +22,7 @@
 #include "mask16.hpp"
 #include "param_factory.hpp"
 #include "pixmap.hpp"
+#include "tiff.hpp"
 #include "plan.hpp"
 #include "plan_record.hpp"
 #include "png.hpp"
@@ -873,9 +874,134 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
     return 0;
 }
 
+// ---- TIFF stage ---------------------------------------------------------------------------------------
+// The decode call: each file's IFD parse (tiff_plan) on the pool, the call's tables -- jobs, compressed strips
+// (sorted by compressed size, largest first: the long waves start first), bands -- then the layout
+// of the staging: the tables, the routed files as they are (each at a 16-byte-aligned offset, 16 zero bytes
+// behind it, so the kernels' aligned over-reads stay inside the buffer), the host-decoded files' pixels -- filled on
+// the pool, one H2D, then tiff_expand over the strips into the files' scratch, tiff_convert over the bands and a
+// strided device copy per host-decoded file, all on `stream`.
+int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+             const aeon_img_desc* descs, void* dst_base, hipStream_t stream)
+{
+    if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !modes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
+    if (n == 0) return 0;
+    HIP_OK(hipSetDevice(ctx->device));
+    if (!ctx->tiff) ctx->tiff = new PngStage();
+    PngStage&                   S = *ctx->tiff;
+    std::lock_guard<std::mutex> lock(S.mu);
+    const auto each = [&](const std::function<void(int)>& f) {
+        if (ctx->host_pool) ctx->host_pool->run(n, f);
+        else
+            for (int i = 0; i < n; i++) f(i);
+    };
+    std::vector<TiffPlan> plans(n);
+    each([&](int i) {
+        if (!data[i] || !sizes[i]) fail(AEON_HIP_EINVAL, "TIFF: empty file");
+        if (modes[i] < AEON_DECODE_BGR8 || modes[i] > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown TIFF decode mode");
+        TiffPlan& P = plans[i];
+        tiff_plan(data[i], sizes[i], modes[i], P);
+        const aeon_img_desc& d = descs[i];
+        if (d.width != P.w || d.height != P.h)
+            fail(AEON_HIP_EINVAL, "TIFF: record " + std::to_string(i) + " is " + std::to_string(P.w) + "x" + std::to_string(P.h) +
+                                      ", its descriptor says " + std::to_string(d.width) + "x" + std::to_string(d.height));
+        if (d.stride < 0 || (size_t)d.stride < (size_t)P.w * P.channels * P.elem_bytes) fail(AEON_HIP_EINVAL, "stride too small");
+    });
+    // the tables need the headers only: built before the staging is laid out
+    std::vector<int>       job_of(n, -1);
+    std::vector<TiffJob>   jobs_host;
+    std::vector<TiffStrip> strips;
+    std::vector<TiffBand>  bands;
+    std::vector<size_t>    raw_at(n, 0);
+    size_t                 scratch = 0;
+    double                 bytes = 0;
+    for (int i = 0; i < n; i++) {
+        const TiffPlan& P = plans[i];
+        if (!P.route) continue;
+        job_of[i] = (int)jobs_host.size();
+        jobs_host.emplace_back();
+        tiff_stage(data[i], sizes[i], modes[i], P, job_of[i], jobs_host.back(), strips, bands, nullptr);
+        raw_at[i] = scratch;
+        scratch += (tiff_scratch_bytes(P) + 15) & ~(size_t)15;
+        bytes += (double)P.h * ((double)P.rowb + (double)P.w * P.channels * P.elem_bytes);
+    }
+    const int n_gpu = (int)jobs_host.size();
+    if (bands.size() > (size_t)INT32_MAX || strips.size() > (size_t)INT32_MAX) fail(AEON_HIP_EUNSUPPORTED, "TIFF: too many strips for one call");
+    std::stable_sort(strips.begin(), strips.end(), [](const TiffStrip& a, const TiffStrip& b) { return a.bytes > b.bytes; });
+    // layout: the jobs, the strips, the bands, then per file the file itself or its pixels (16-byte aligned)
+    std::vector<size_t> at(n);
+    const size_t        strips_at = (size_t)n_gpu * sizeof(TiffJob);
+    const size_t        bands_at  = strips_at + strips.size() * sizeof(TiffStrip);
+    size_t              total     = bands_at + bands.size() * sizeof(TiffBand);
+    for (int i = 0; i < n; i++) {
+        const TiffPlan& P = plans[i];
+        total             = (total + 15) & ~(size_t)15;
+        at[i]             = total;
+        total += P.route ? sizes[i] + 16 : (size_t)P.w * P.channels * P.elem_bytes * P.h;
+    }
+    PngStage::Set& st = S.sets[S.next];
+    S.next ^= 1;
+    if (!st.done) HIP_OK(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    if (st.pending) HIP_OK(hipEventSynchronize(st.done));
+    st.pending = false;
+    if (total > st.pinned_cap) grow(st.pinned, st.pinned_cap, total + total / 4, true);
+    if (total > st.dev_cap) grow(st.dev, st.dev_cap, total + total / 4, false);
+    if (scratch > st.scratch_cap) grow(st.scratch, st.scratch_cap, scratch + scratch / 4, false);
+    TiffJob* jobs = (TiffJob*)st.pinned;
+    if (!strips.empty()) std::memcpy(st.pinned + strips_at, strips.data(), strips.size() * sizeof(TiffStrip));
+    if (!bands.empty()) std::memcpy(st.pinned + bands_at, bands.data(), bands.size() * sizeof(TiffBand));
+    each([&](int i) {
+        const TiffPlan& P = plans[i];
+        uint8_t*        p = st.pinned + at[i];
+        if (!P.route) {
+            tiff_decode(data[i], sizes[i], modes[i], p, (size_t)P.w * P.channels * P.elem_bytes, nullptr);
+            return;
+        }
+        TiffJob& J = jobs[job_of[i]];
+        J          = jobs_host[job_of[i]];
+        std::memcpy(p, data[i], sizes[i]);
+        std::memset(p + sizes[i], 0, 16);
+        J.src    = (uint64_t)(st.dev + at[i]);
+        J.raw    = (uint64_t)(st.scratch + raw_at[i]);
+        J.out    = (uint64_t)dst_base + descs[i].offset;
+        J.stride = descs[i].stride;
+    });
+    KernelTimer t{};
+    bool        timed = false;
+    if (ctx->timing && n_gpu) {
+        std::lock_guard<std::mutex> tl(ctx->mu);
+        if ((timed = take_timing(ctx))) t = take_timer(ctx, kTimerPng, bytes);
+    }
+    HIP_OK(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, stream));
+    if (timed) HIP_OK(hipEventRecord(t.start, stream));
+    HIP_OK(launch_tiff((const TiffJob*)st.dev, (const TiffStrip*)(st.dev + strips_at), (int)strips.size(),
+                       (const TiffBand*)(st.dev + bands_at), (int)bands.size(), stream_error(ctx, stream), stream));
+    if (timed) {
+        HIP_OK(hipEventRecord(t.stop, stream));
+        std::lock_guard<std::mutex> tl(ctx->mu);
+        ctx->timers.push_back(t);
+    }
+    for (int i = 0; i < n; i++) {
+        const TiffPlan& P = plans[i];
+        if (P.route) continue;
+        const size_t rowb = (size_t)P.w * P.channels * P.elem_bytes;
+        HIP_OK(hipMemcpy2DAsync((uint8_t*)dst_base + descs[i].offset, (size_t)descs[i].stride, st.dev + at[i], rowb, rowb,
+                                (size_t)P.h, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_OK(hipEventRecord(st.done, stream));
+    st.pending = true;
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
+
+int aeon_hip_decode_tiff_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                               const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return guarded([&] { return run_tiff(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream); });
+}
 
 int aeon_hip_decode_pixmap_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
                                  const aeon_img_desc* descs, void* dst_base, void* stream)

@@ -1,7 +1,7 @@
 // launch.hpp -- every host-callable launcher and helper that a .hip file defines and a .cpp file calls.
 // The defining .hip file and each caller include it, so the compiler holds a definition against the one
 // declaration its callers see.  The argument structs are only named here (aug_job.hpp, mask16.hpp, box_job.hpp,
-// rcnn_job.hpp, video_job.hpp, jpeg.hpp, png.hpp, pixmap.hpp define them).
+// rcnn_job.hpp, video_job.hpp, jpeg.hpp, png.hpp, pixmap.hpp, tiff.hpp define them).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -27,6 +27,9 @@ struct JpegHuffFile;
 struct PngJob;
 struct PixmapJob;
 struct PixmapBand;
+struct TiffJob;
+struct TiffStrip;
+struct TiffBand;
 
 // augment_kernels.hip
 hipError_t launch_tiles(int km, int rm, bool tail, bool photo, const LaunchArgs& a, int grid, hipStream_t stream,
@@ -73,5 +76,8 @@ hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, i
 hipError_t launch_png(const PngJob* jobs, int n_jobs, int unfilter_lds, int32_t* error, hipStream_t stream);
 // pixmap_kernels.hip: pixmap_convert, one workgroup per band
 hipError_t launch_pixmap(const PixmapJob* jobs, const PixmapBand* bands, int n_bands, hipStream_t stream);
+// tiff_kernels.hip: tiff_expand, one wave per compressed strip, then tiff_convert, one workgroup per band
+hipError_t launch_tiff(const TiffJob* jobs, const TiffStrip* strips, int n_strips, const TiffBand* bands, int n_bands, int32_t* error,
+                       hipStream_t stream);
 
 } // namespace aeon_hip

@@ -21,7 +21,11 @@
 #define PNG_SYNC() __syncthreads() // (a workgroup of one wave: orders the lanes' LDS and scratch accesses)
 #define PNG_GLOBAL __attribute__((address_space(1)))
 #else
+#if defined(__HIP__) // (the host pass over a .hip file: the kernels' calls of the templates must resolve there too)
+#define PNG_FN __host__ __device__ inline
+#else
 #define PNG_FN inline
+#endif
 #define PNG_LANE0 0
 #define PNG_LANE_STEP 1
 #define PNG_SLOT(l) (l)
@@ -304,27 +308,46 @@ PNG_FN void fixed_tables(InflateMem& M)
     build_code(M, M.dist, M.lens + 288, 32, kLitBits, true, false); // (30 and 31 decode, and are refused)
 }
 
+// What a failed step of a stream that may be cut (the TIFF stage's strips, kCut) comes to: where the bits the
+// step took reach past the stream's end, the input ran out -- zlib, which judges nothing it has not all the bits
+// of, then stops without an error -- and the stream counts if everything it is needed for is out.  A PNG's
+// stream (kCut false) fails.
+template <bool kCut>
+PNG_FN bool ran_out(InflateMem& M, Inflate& S)
+{
+    if (!kCut || !overrun(S) || S.pos != S.need) return false;
+    flush_tail(M, S);
+    return true;
+}
+
 // The file's zlib stream inflated into its scratch.  False: the stream is one zlib refuses, or does not make
 // exactly `need` bytes.  Every loop ends: a symbol consumes a bit at least, reading past the stream's end is
 // an error, and nothing is written past `need`.
-PNG_FN bool inflate_file(InflateMem& M, Inflate& S)
+// kCut (a TIFF strip, tiff_strips.hpp): the stream may make more than `need` bytes; it is inflated as zlib's
+// inflate(Z_FINISH) does into a buffer of `need` bytes: the symbol that would write past them is checked, copied as
+// far as the room goes and ends the decode; what comes behind it is not looked at.  skip: bytes ahead of the
+// stream at `in` (a strip starts at any byte of its file; `clen` counts them in).
+template <bool kCut = false>
+PNG_FN bool inflate_file(InflateMem& M, Inflate& S, uint32_t skip = 0)
 {
     for (int l = 0; l < PNG_SLOTS; l++) S.ad1[l] = S.ad2[l] = 0;
     S.pos = S.fl = 0;
-    if (S.clen < 6) return false;
-    seek(S, 2); // (the host checked the two header bytes)
+    if (S.clen < 6 + skip) return false;
+    seek(S, 2 + skip); // (the host checked the two header bytes)
     for (bool last = false; !last;) {
         refill(S);
         last                = take(S, 1) != 0;
         const uint32_t type = take(S, 2);
-        if (overrun(S)) return false;
+        if (overrun(S)) return ran_out<kCut>(M, S);
         if (type == 0) {
             const uint32_t at = (uint32_t)((bit_pos(S) + 7) >> 3); // LEN, NLEN at the next byte
-            if ((uint64_t)at + 4 > S.clen) return false;
+            if ((uint64_t)at + 4 > S.clen) return kCut && S.pos == S.need ? (flush_tail(M, S), true) : false;
             seek(S, at);
-            const uint32_t len = take(S, 16);
+            uint32_t len = take(S, 16);
             refill(S);
             if ((take(S, 16) ^ 0xffff) != len) return false;
+            bool cut = false;
+            if (kCut && len > S.need - S.pos) len = S.need - S.pos, cut = true;
             if ((uint64_t)at + 4 + len > S.clen || len > S.need - S.pos) return false;
             const PNG_GLOBAL uint8_t* src = (const PNG_GLOBAL uint8_t*)S.in + at + 4;
             for (uint32_t done = 0; done < len;) {
@@ -334,18 +357,20 @@ PNG_FN bool inflate_file(InflateMem& M, Inflate& S)
                 S.pos += n, done += n;
                 flush(M, S);
             }
+            if (kCut && cut) return flush_tail(M, S), true;
             seek(S, at + 4 + len);
             continue;
         }
         if (type == 3) return false;
         if (type == 1) fixed_tables(M);
-        else if (!dynamic_tables(M, S)) return false;
+        else if (!dynamic_tables(M, S)) return ran_out<kCut>(M, S);
         for (;;) {
             refill(S);
             int sym = decode_sym(S, M.lit, kLitBits);
+            if (kCut && overrun(S)) return ran_out<kCut>(M, S);
             if (sym < 0 || overrun(S)) return false;
             if (sym < 256) {
-                if (S.pos >= S.need) return false;
+                if (S.pos >= S.need) return kCut ? (flush_tail(M, S), true) : false;
                 for (int l = PNG_LANE0; l < 1; l += PNG_LANE_STEP) M.ring[S.pos & kRingMask] = (uint8_t)sym;
                 S.pos++;
             } else if (sym == 256) {
@@ -353,12 +378,19 @@ PNG_FN bool inflate_file(InflateMem& M, Inflate& S)
             } else {
                 sym -= 257;
                 if (sym >= 29) return false; // 286, 287
-                const uint32_t len = len_base((uint32_t)sym) + take(S, len_extra((uint32_t)sym));
+                uint32_t len = len_base((uint32_t)sym) + take(S, len_extra((uint32_t)sym));
                 refill(S);
                 const int ds = decode_sym(S, M.dist, kLitBits);
+                if (kCut && overrun(S)) return ran_out<kCut>(M, S);
                 if (ds < 0 || ds >= 30) return false;
                 const uint32_t dist = dist_base((uint32_t)ds) + take(S, dist_extra((uint32_t)ds));
-                if (overrun(S) || dist > S.pos || len > S.need - S.pos) return false;
+                if (kCut && overrun(S)) return ran_out<kCut>(M, S);
+                if (overrun(S) || dist > S.pos) return false;
+                if (len > S.need - S.pos) {
+                    if (!kCut) return false;
+                    copy_match(M, S, S.need - S.pos, dist);
+                    return flush_tail(M, S), true;
+                }
                 copy_match(M, S, len, dist);
             }
             flush(M, S);
@@ -367,7 +399,7 @@ PNG_FN bool inflate_file(InflateMem& M, Inflate& S)
     if (S.pos != S.need) return false; // short output
     const uint32_t adler = flush_tail(M, S);
     const uint32_t at    = (uint32_t)((bit_pos(S) + 7) >> 3);
-    if ((uint64_t)at + 4 > S.clen) return false;
+    if ((uint64_t)at + 4 > S.clen) return kCut;
     seek(S, at);
     const uint32_t t0 = take(S, 16);
     refill(S);

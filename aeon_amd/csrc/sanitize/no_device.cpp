@@ -119,6 +119,11 @@ int aeon_hip_decode_pixmap_batch(aeon_hip_ctx*, int, const void* const*, const s
 {
     return no_device();
 }
+int aeon_hip_decode_tiff_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const int*, const aeon_img_desc*, void*,
+                               void*)
+{
+    return no_device();
+}
 int aeon_hip_synchronize(aeon_hip_ctx*, void*) { return no_device(); }
 int aeon_hip_release_stream(aeon_hip_ctx*, void*) { return no_device(); }
 } // extern "C"

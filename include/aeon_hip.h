@@ -380,6 +380,40 @@ int aeon_pixmap_host_stage(const void* data, size_t size, int mode, int* gpu_rou
  * builds): decodes like aeon_decode_pixmap.  AEON_HIP_EUNSUPPORTED: the file is not routed to the device. */
 int aeon_pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
 
+/* TIFF decode -- the same extractors on classic TIFF files in strips (first IFD, both byte orders).  Modes are
+ * AEON_DECODE_*.  aeon_tiff_info: size, the file's channels (3 for RGB and palette files, else 1) and the element
+ * size ANYDEPTH gives (2 for a 16-bit gray file, else 1).  aeon_decode_tiff is the complete decoder on the host:
+ * height rows of `stride` bytes to dst, the element size to *elem_bytes (may be NULL).  Decoded: Compression 1,
+ * 5 (LZW), 8 / 32946 (Deflate) and 32773 (PackBits); 8 or 16 bits per sample; gray (WhiteIsZero, BlackIsZero),
+ * RGB and 8-bit palette files, each with at most one associated or unspecified extra sample; Predictor 1 and 2.
+ * Refused with AEON_HIP_EUNSUPPORTED and a message naming the variant: BigTIFF, tiles, planar-separate files,
+ * 1 / 2 / 4 / 32-bit and float samples, Predictor 3, CCITT and JPEG compression, CMYK / YCbCr / CIELab,
+ * FillOrder 2, unassociated alpha, old-style LZW, more than 2^28 pixels.  A malformed file is AEON_HIP_EINVAL.
+ * Messages start with "TIFF:".  The decode rules, and which of them no reference output pins, are DESIGN.md
+ * section 21. */
+int aeon_tiff_info(const void* data, size_t size, int* width, int* height, int* channels, int* elem_bytes);
+int aeon_decode_tiff(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes);
+/* The TIFF stage: n files decoded into device memory as aeon_decode_tiff(data[i], sizes[i], modes[i], ...) decodes
+ * them, byte for byte: record i at dst_base + descs[i].offset with descs[i].stride bytes per row; descs[i].width /
+ * height must be the file's (aeon_tiff_info).  The host parses the IFD and copies the file as it is into pinned
+ * staging; the GPU decodes its strips (tiff_expand, one wave per compressed strip) and converts the rows
+ * (tiff_convert, one workgroup per band of rows).  The device takes a file below 2^31 bytes whose LZW / PackBits
+ * strips decode to at most 32 KiB each; the others decode on the host and go up as pixels with the same H2D.
+ * Whatever aeon_decode_tiff refuses from the header is refused here before any launch, same code and message;
+ * corrupt strip data of a device-routed file sets the stream's device error (aeon_hip_synchronize:
+ * AEON_HIP_EDEVICE).  Asynchronous on `stream`; the files may be released when the call returns. */
+int aeon_hip_decode_tiff_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                               const aeon_img_desc* descs, void* dst_base, void* stream);
+/* The host half of the stage for one file, on the calling thread, no device.  *gpu_route: 1 when the device
+ * decodes the file, 0 when it decodes on the host.  *staged_bytes: the file's or the pixels' bytes in the H2D. */
+int aeon_tiff_host_stage(const void* data, size_t size, int mode, int* gpu_route, int64_t* staged_bytes);
+/* What the decoder's providers do with a TIFF file: *device 1 when it goes through the stage. */
+int aeon_tiff_decoder_route(const void* data, size_t size, int* device);
+/* The stage's kernel code run on the calling thread, lane after lane, no device (for CPU tests and sanitizer
+ * builds): decodes like aeon_decode_tiff.  AEON_HIP_EUNSUPPORTED: the file is not routed to the device;
+ * AEON_HIP_EDEVICE: what the device reports as corrupt. */
+int aeon_tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+
 /* batch_sampler::sample_patches (src/augment_image.cpp:567-586) of the factory's batch_samplers[sampler]
  * over n normalized object boxes (xmin, ymin, xmax, ymax in [0, 1]) -- what aeon's tests call as
  * factory.m_batch_samplers[i].sample_patches (test/test_augmentation.cpp:347-443).  Writes up to cap
