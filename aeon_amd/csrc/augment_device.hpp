@@ -286,11 +286,12 @@ __device__ __forceinline__ void hue_apply_n(STAB sdv, TAB hdiv, WTAB htab, int (
 }
 
 // The division tables in LDS (kHsvLdsDivBytes): {sdiv[v], (float)v * (1.f / 255)} pairs, hdiv180.
-__device__ __forceinline__ void hsv_div_tables(const LdsLayout& L, const int32_t* g)
+// (by the workgroup's first `nt` lanes: all of them, or the lanes of the waves that call this)
+__device__ __forceinline__ void hsv_div_tables(const LdsLayout& L, const int32_t* g, int nt = blockDim.x)
 {
     const auto sdv = lds_ptr<i32x2>(L.hsv);
     const auto hd  = lds_ptr<int32_t>(L.hsv + 256 * 8);
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
+    for (int i = threadIdx.x; i < 256; i += nt) {
         sdv[i] = (i32x2){g[i], (int)__float_as_uint((float)i * (1.f / 255))};
         hd[i]  = g[256 + i];
     }

@@ -353,7 +353,7 @@ MaskFuse fuse_masks(const CallPlan& plan)
 #define AEON_HIP_FUSED_MASK_ROWS 64
 #endif
     f.rows = std::min(mask16_rows(plan.m16_max_w, plan.m16_max_seg), AEON_HIP_FUSED_MASK_ROWS);
-    if (groups != 1 || f.into < plan.tiles + CallPlan::kMain || f.rows < 1 || f.into->has_contrast) return MaskFuse{};
+    if (groups != 1 || f.into < plan.tiles + CallPlan::kMain || f.into >= plan.tiles + CallPlan::kWide || f.rows < 1 || f.into->has_contrast) return MaskFuse{};
     const LaunchPlan& P = *f.into;
     f.pitch = mask16_pitch(plan.m16_max_seg);
     f.slots = std::max(1, std::min(plan.m16_max_slots, f.rows));
@@ -547,10 +547,11 @@ int run_batch(aeon_hip_ctx* ctx, int n, const aeon_img_desc* descs, const void* 
     };
     launch_generic(ctx, plan.gr_short, table, o, d_lut, stream, timed);
     pass(CallPlan::kPre, CallPlan::kPre2, KM_RAW);
+    pass(CallPlan::kWide, CallPlan::kGroups, KM_RAW);
     launch_generic(ctx, plan.gr_main, table, o, d_lut, stream, timed);
     pass(CallPlan::kPre2, CallPlan::kPass1, KM_RAW);
     pass(CallPlan::kPass1, CallPlan::kMain, KM_STATS);
-    pass(CallPlan::kMain, CallPlan::kGroups, KM_FINAL);
+    pass(CallPlan::kMain, CallPlan::kWide, KM_FINAL);
     phase(6);
     lease.release();
     phase(7);

@@ -517,7 +517,7 @@ void CallPlan::add(const aeon_img_desc& d, const void* src_base, const aeon_aug_
             R.out_scratch = 1;
             gr_short.add(R);
         } else {
-            push(kPre, P);
+            push(P.win_w > kWideCols ? kWide : kPre, P);
         }
         reads_scratch(J, P.out_ptr, p.crop_w, p.crop_h, cn);
         J.crop_x = 0, J.crop_y = 0;
@@ -603,10 +603,11 @@ CallPlan::CallPlan()
 {
     for (int g = 0; g < kGroups; g++) {
         LaunchPlan& P = tiles[g];
-        P.rm = g < kMain ? (g & 7) >> 1 : (g - kMain) >> 2;
-        P.tail = g < kMain ? (g & 1) != 0 : (g & 2) != 0;
-        P.photo = g < kMain ? g >= kPass1 : (g & 1) != 0;
-        P.out_scratch = g < kMain;
+        const bool pre = g < kMain || g >= kWide; // (a pass into scratch)
+        P.rm = pre ? (g & 7) >> 1 : (g - kMain) >> 2;
+        P.tail = pre ? (g & 1) != 0 : (g & 2) != 0;
+        P.photo = pre ? g >= kPass1 && g < kMain : (g & 1) != 0;
+        P.out_scratch = pre;
     }
 }
 
@@ -649,13 +650,13 @@ void CallPlan::finalize(const aeon_out_desc& o)
     for (int g = 0; g < kGroups; g++) {
         LaunchPlan& P = tiles[g];
         if (P.jobs.empty()) continue;
-        const bool last = g >= kMain;
+        const bool last = g >= kMain && g < kWide;
         P.vec_ok = vec_ok;
         P.rtab   = last && P.photo && (o.dtype == AEON_DTYPE_F32 || out_is_half(o.dtype)); // (an f32 table either way)
         P.finalize();
         P.blob_off = section(P.jobs.size() * sizeof(AugJob));
         for (AugJob& J : P.jobs) {
-            if (g >= kPass1 && !last) {
+            if (g >= kPass1 && g < kMain) {
                 slot_tiles[J.stats_slot] = J.tiles;
                 partial_stride           = std::max(partial_stride, J.tiles * 8); // (tile, wave) sums
             }

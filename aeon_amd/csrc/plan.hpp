@@ -189,7 +189,7 @@ struct MaskSet {
 };
 
 // One run_batch call's plan: its launches in launch order -- rot (image::rotate) -> exp (image::expand) ->
-// m16 (the mask gather) -> gr_short / kPre (resize_short, generic or tile) -> gr_main (CUBIC / LANCZOS4 / AREA
+// m16 (the mask gather) -> gr_short / kPre, kWide (resize_short, generic or tile) -> gr_main (CUBIC / LANCZOS4 / AREA
 // resize of the crop) -> kPre2 (2x-area resize ahead of photometric stages) -> kPass1 (contrast statistics) ->
 // kMain; each reads only what an earlier one wrote -- and, after finalize(), where each one's jobs lie in
 // the call's table and what its launch needs.  Reused from call to call (clear() keeps the vectors' memory).
@@ -200,7 +200,11 @@ struct CallPlan {
     GrPlan                 gr_short, gr_main;
     // the tile launches, one per (resize mode, scalar tail) and for kMain (resize mode, scalar tail,
     // photometric) group: the kernels are specialised on all three
-    enum { kPre = 0, kPre2 = 8, kPass1 = 16, kMain = 24, kGroups = 40 };
+    // kWide: resize_short pre-pass jobs whose window is wider than kWideCols, launched right after kPre's, apart
+    // from them: a window's column taps take 8 bytes of LDS a column, and in one launch with records whose
+    // staged rows are large the two maxima together passed the workgroup's LDS
+    enum { kPre = 0, kPre2 = 8, kPass1 = 16, kMain = 24, kWide = 40, kGroups = 48 };
+    static constexpr int kWideCols = 8192;
     LaunchPlan tiles[kGroups];
     size_t     scratch_bytes = 0; // of the slot's scratch, every region 16-aligned with 16 bytes of slack
     int        n_stats       = 0; // contrast records: pass-1 jobs, stats slots

@@ -531,7 +531,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (tid - nwc * 64 < 6) lds_ptr<uint32_t>(L.sums)[(tid - nwc * 64) / 3 * 4 + (tid - nwc * 64) % 3] = 0;
     } else {
-        hsv_div_tables(LdsLayout{0, L.hsv, 0, 0, 0, 0, 0, 0, 0, 0}, a.hsv_tables);
+        // (the compute waves alone, as the two copies below: at the workgroup's stride, records narrower than
+        // 64 columns -- fewer than 256 compute lanes -- left entries nwc * 64 .. 255 of the tables unwritten)
+        hsv_div_tables(LdsLayout{0, L.hsv, 0, 0, 0, 0, 0, 0, 0, 0}, a.hsv_tables, nwc * 64);
         for (int i = tid; i < 3 * 256; i += nwc * 64) lds_ptr<float>(L.lut)[i] = a.lut[i];
         for (int i = tid; i < 256 * 4; i += nwc * 64) lds_ptr<int32_t>(L.hwt)[i] = a.hsv_tables[kHsvDivWords + i];
     }

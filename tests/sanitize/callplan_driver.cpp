@@ -33,7 +33,8 @@ void each_group(CallPlan& c, F&& fn)
         if (g < CallPlan::kPre2) fn("pre", O_PRE, true, c.tiles[g]);
         else if (g < CallPlan::kPass1) fn("pre2", O_PRE2, true, c.tiles[g]);
         else if (g < CallPlan::kMain) fn("pass1", O_PASS1, true, c.tiles[g]);
-        else fn("main", O_MAIN, false, c.tiles[g]);
+        else if (g < CallPlan::kWide) fn("main", O_MAIN, false, c.tiles[g]);
+        else fn("pre", O_PRE, true, c.tiles[g]); // (the wide resize_short windows: launched with the pre-pass)
     }
 }
 

@@ -314,6 +314,10 @@ EDGE_CASES = [
     ("u8_chw_c3_odd", (256, 256), dict(crop_x=0, crop_y=0, crop_w=256, crop_h=256, out_w=223, out_h=31,
                                       brightness=0.8, saturation=1.3, contrast=0.7, hue=-12),
      dict(dtype="uint8", mean=None, stddev=None, item_stride=223 * 31 * 3)),
+    # contrast records narrower than 64 columns (found by the size sweep): the records kernel's split form has
+    # fewer than 256 compute lanes there, and they alone fill the 256-entry RGB2HSV division tables in LDS
+    ("contrast_records_16_wide", (40, 30), dict(crop_x=3, crop_y=2, crop_w=21, crop_h=13, out_w=16, out_h=8, flip=1,
+                                                brightness=0.8, saturation=1.6, contrast=0.7, hue=-12), {}),
 ] + [
     # contrast pass 1's specialised loop (fixed-point brightness/saturation + hue, packed HSV2RGB
     # with the per-H channel selector): every hue wrap, sector boundaries included
@@ -332,6 +336,19 @@ def test_edge_cases(ctx, name, src, pk, ok):
     kw.update(ok)
     out = A.out_desc(**kw)
     _assert_same(H.hip_records(ctx, imgs, params, out), H.oracle_records(imgs, params, out), name)
+
+
+def test_resize_short_wide_window_beside_large_staging(ctx):
+    """Found by the size sweep (its width 2046): a resize_short call holding a 14,936-column, one-row cropbox
+    (119,488 bytes of column taps in LDS) and a 6,138-column one of three source rows (55,296 bytes of staged
+    rows; 178,704 bytes with the rest against 163,840) was refused, both maxima counted for one launch; windows
+    above 8,192 columns launch on their own."""
+    geo = [(9, 0, 6138, 2, 2046, 3, 6147, 3), (10, 0, 14936, 1, 2046, 2, 14946, 1)]  # crop x y w h, out w h, src w h
+    imgs = [A.synthetic_image(70 + i, g[6], g[7], 3) for i, g in enumerate(geo)]
+    params = [A.aug_params(crop_x=g[0], crop_y=g[1], crop_w=g[2], crop_h=g[3], out_w=g[4], out_h=g[5], flip=i,
+                           resize_short_size=g[7] + 1) for i, g in enumerate(geo)]
+    out = A.out_desc(channels=3, channel_major=False, dtype="uint8", item_stride=2046 * 3 * 3)
+    _assert_same(H.hip_records(ctx, imgs, params, out), H.oracle_records(imgs, params, out), "wide resize_short")
 
 
 def test_grayscale(ctx):
