@@ -264,6 +264,9 @@ def lib():
         L.aeon_hip_stager_launch.argtypes = [vp, vp]
         L.aeon_hip_stager_wait.argtypes = [vp, vp]
         L.aeon_hip_stager_last_launch.argtypes = [vp, P(StagerLaunchInfo)]
+        L.aeon_encoded_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int] + [P(ctypes.c_int)] * 6
+        L.aeon_hip_stager_stage_encoded.argtypes = [vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, P(AugParams)]
+        L.aeon_hip_stager_last_decode.argtypes = [vp, P(StagerDecodeInfo)]
         L.aeon_hip_release_stream.argtypes = [vp, vp]
         L.aeon_hip_stager_last_error.restype = ctypes.c_char_p
         L.aeon_hip_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -810,6 +813,23 @@ def tiff_gpu_emulate(data, mode=DECODE_BGR8, out=None):
     return out
 
 
+FORMAT_JPEG, FORMAT_PNG, FORMAT_PIXMAP, FORMAT_TIFF = 0, 1, 2, 3
+FORMAT_NAMES = ("jpeg", "png", "pixmap", "tiff")
+
+
+def encoded_info(data, mask=False):
+    """What a Decoder finds out about an encoded element before it decodes it (aeon_encoded_info): a dict of
+    format (FORMAT_*), width, height, file_channels, elem_bytes (2: a mask that decodes to uint16) and
+    device_route (does the decoder's routing rule send the file through its device stage?).  mask: the file
+    is a pixel mask (ANYDEPTH), for which a JPEG file is refused."""
+    v = [ctypes.c_int() for _ in range(6)]
+    _check(lib().aeon_encoded_info(bytes(data), len(data), 1 if mask else 0, *[ctypes.byref(x) for x in v]))
+    keys = ("format", "width", "height", "file_channels", "elem_bytes", "device_route")
+    d = {k: x.value for k, x in zip(keys, v)}
+    d["device_route"] = bool(d["device_route"])
+    return d
+
+
 def unbiased_round(x):
     """nervana::unbiased_round (aeon src/util.cpp:212-239)."""
     r = ctypes.c_int64()
@@ -1033,6 +1053,11 @@ class StagerLaunchInfo(ctypes.Structure):  # aeon_stager_launch_info
                 ("chunks", ctypes.c_int32), ("records", ctypes.c_int32)]
 
 
+class StagerDecodeInfo(ctypes.Structure):  # aeon_stager_decode_info
+    _fields_ = [("launches", ctypes.c_uint64), ("device", ctypes.c_int32 * 4), ("host", ctypes.c_int32 * 4),
+                ("pixels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 def _check_stager(rc):
     if rc != 0:
         raise AeonHipError(rc, lib().aeon_hip_stager_last_error().decode())
@@ -1060,6 +1085,13 @@ class Stager:
         _check_stager(lib().aeon_hip_stager_stage(self._h, ctypes.c_void_p(batch_out), idx, a.ctypes.data, w, h,
                                                    a.strides[0], cn, a.itemsize, ctypes.byref(params)))
 
+    def stage_encoded(self, batch_out, idx, data, params):
+        """data: the record's file (JPEG, PNG, BMP / PNM, TIFF) as bytes; decoded by the stager, on the device where
+        the decoder's routing rule says so, else on the calling thread (aeon_hip_stager_stage_encoded)."""
+        data = bytes(data)
+        _check_stager(lib().aeon_hip_stager_stage_encoded(self._h, ctypes.c_void_p(batch_out), idx, data, len(data),
+                                                          ctypes.byref(params)))
+
     def flush(self, batch_out):
         _check_stager(lib().aeon_hip_stager_flush(self._h, ctypes.c_void_p(batch_out)))
 
@@ -1080,6 +1112,14 @@ class Stager:
         info = StagerLaunchInfo()
         _check_stager(lib().aeon_hip_stager_last_launch(self._h, ctypes.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in StagerLaunchInfo._fields_}
+
+    def last_decode(self):
+        """Where the records of the most recently launched window were decoded (aeon_hip_stager_last_decode): a
+        dict of launches, device and host ({format name: records}) and pixels (staged decoded)."""
+        info = StagerDecodeInfo()
+        _check_stager(lib().aeon_hip_stager_last_decode(self._h, ctypes.byref(info)))
+        return {"launches": int(info.launches), "device": dict(zip(FORMAT_NAMES, info.device)),
+                "host": dict(zip(FORMAT_NAMES, info.host)), "pixels": int(info.pixels)}
 
     def close(self):
         if getattr(self, "_h", None):

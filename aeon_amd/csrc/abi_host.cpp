@@ -4,6 +4,7 @@
 // builds link this file as it is.
 #include <climits>
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <random>
 #include <string>
@@ -298,6 +299,48 @@ int aeon_tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, si
         const int r = tiff_gpu_emulate(data, size, mode, dst, stride);
         if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "TIFF: the file is not routed to the device (an LZW / PackBits strip above 32 KiB)");
         if (r < 0) fail(AEON_HIP_EDEVICE, "TIFF: strip data corrupt or truncated (GPU stage)");
+        return 0;
+    });
+}
+
+// pixel_provider::inspect's sniff and header parse (host.cpp), for callers that hold the file themselves
+int aeon_encoded_info(const void* data, size_t size, int mask, int* format, int* width, int* height, int* file_channels,
+                      int* elem_bytes, int* device_route)
+{
+    return guarded([&] {
+        if (!data || !format || !width || !height) fail(AEON_HIP_EINVAL, "null argument");
+        static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+        int                  fcn = 0, eb = 1, route = 1;
+        if (size >= 8 && std::memcmp(data, kPngSig, 8) == 0) {
+            int depth = 0, ctype = 0;
+            png_header(data, size, width, height, &depth, &ctype);
+            *format = AEON_FORMAT_PNG;
+            fcn     = ctype == 0 ? 1 : ctype == 4 ? 2 : ctype == 6 ? 4 : 3;
+            eb      = (mask && depth == 16 && ctype != 3) ? 2 : 1;
+            route   = png_routed(data, size) ? 1 : 0;
+        } else if (pixmap_sniff(data, size)) {
+            int depth = 0, fmt = 0;
+            pixmap_header(data, size, width, height, &depth, &fcn, &fmt);
+            *format = AEON_FORMAT_PIXMAP;
+            eb      = (mask && depth == 16) ? 2 : 1;
+            route   = pixmap_routed(data, size) ? 1 : 0;
+        } else if (tiff_sniff(data, size)) {
+            TiffPlan P;
+            tiff_plan(data, size, AEON_DECODE_ANYDEPTH, P);
+            *format = AEON_FORMAT_TIFF;
+            *width = P.w, *height = P.h, fcn = P.file_channels;
+            eb    = mask ? P.elem_bytes : 1;
+            route = tiff_routed(data, size) ? 1 : 0;
+        } else {
+            if (mask)
+                fail(AEON_HIP_ERUNTIME, "encoded pixel masks are decoded from PNG files only (JPEG masks: pass the "
+                                        "decoded mask)");
+            jpeg_info(data, size, width, height, &fcn);
+            *format = AEON_FORMAT_JPEG;
+        }
+        if (file_channels) *file_channels = fcn;
+        if (elem_bytes) *elem_bytes = eb;
+        if (device_route) *device_route = route;
         return 0;
     });
 }

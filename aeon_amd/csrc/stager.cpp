@@ -6,6 +6,10 @@
 // those calls the GPU path:
 //   stage(batch_out, idx, pixels, params)  -- provide(): the decoded record's bytes into pinned memory
 //                                            (lock-free bump allocation in pinned chunks; concurrent)
+//   stage_encoded(batch_out, idx, file, params) -- provide() with the record still encoded (stager_encoded.cpp,
+//                                            through stager_encoded.hpp): decoded into pinned memory right there,
+//                                            or kept as a file that the window's launch decodes on the device
+//                                            into a slot behind the staged pixels, ahead of the augment launch
 //   launch(batch_out)                      -- post_process(): the FIRST call after a window's stages
 //                                            launches the whole window -- one H2D per pinned chunk, ONE
 //                                            augment (or mask) launch over every staged record of every
@@ -34,6 +38,7 @@
 #include <vector>
 
 #include "../../include/aeon_hip.h"
+#include "stager_encoded.hpp"
 
 namespace {
 
@@ -74,6 +79,16 @@ void* mapped_view(void* p)
 }
 
 constexpr size_t kChunkBytes = 64u << 20; // pinned staging chunk (a window usually fits in one or two)
+// the "chunk" of a desc tag whose offset is a slot of the device-decoded records, behind every chunk's bytes
+constexpr uint64_t kSlotChunk  = 0xFFFF;
+constexpr uint64_t kOffsetMask = (1ull << 48) - 1;
+
+// The decode stages, for windows with device-decoded records (installed by aeon_hip_stager_stage_encoded).
+std::atomic<aeon_hip::stager_decode_fn> g_decode{nullptr};
+
+// Where a staged record's pixels come from, for last_decode: kPixels, kHostDecoded + format or
+// kDeviceDecoded + format.
+constexpr uint8_t kPixels = 0, kHostDecoded = 1, kDeviceDecoded = 1 + AEON_FORMAT_COUNT;
 
 struct Chunk {
     uint8_t* host = nullptr;
@@ -87,6 +102,7 @@ struct Batch {
     void*                        out = nullptr; // the batch buffer (host, or device memory)
     std::vector<aeon_img_desc>   descs;         // offset = (chunk << 48) | offset in chunk until launch
     std::vector<aeon_aug_params> params;
+    std::vector<uint8_t>         origin;        // kPixels, kHostDecoded + format, kDeviceDecoded + format
     std::unique_ptr<std::atomic<uint8_t>[]> have;
     int        first = 0;     // its first record in the window's launch order
     int        n     = 0;     // records staged (idx 0..n-1)
@@ -99,6 +115,15 @@ struct Batch {
 // A decode window: its pinned staging, its batches, its own stream and device buffers, so that window
 // k's copies and kernels run while window k+1 is staged (aeon's async_manager keeps two containers in
 // flight, src/async_manager.hpp:162-204).
+// A file the window's launch decodes on the device into the slot its record's desc names.
+struct File {
+    std::unique_ptr<uint8_t[]> bytes;
+    size_t                     size = 0;
+    int                        format = 0, mode = 0;
+    Batch*                     batch = nullptr;
+    int                        idx = 0;
+};
+
 struct Window {
     enum State { IDLE, STAGING, LAUNCHED };
     State                               state = IDLE;
@@ -106,6 +131,8 @@ struct Window {
     std::vector<Chunk>                  chunks;
     int                                 cur = 0; // chunk being filled
     std::vector<std::unique_ptr<Batch>> batches; // in first-stage order
+    std::vector<File>                   files;   // records still encoded (under the stager's mutex)
+    size_t                              slot_bytes = 0; // their slots' bump offset
     int                                 unwaited = 0;
     hipStream_t                         stream  = nullptr;
     hipEvent_t                          done    = nullptr;
@@ -151,6 +178,7 @@ struct aeon_hip_stager {
     uint64_t      gens = 0;
     std::vector<hipEvent_t> spare_events;
     aeon_stager_launch_info last{}; // the last window launched (launch_window, under mu)
+    aeon_stager_decode_info last_decode{};
     std::atomic<int>        waiters{0}; // aeon_hip_stager_wait(NULL, ...) calls inside this stager (destroy waits)
 };
 
@@ -207,6 +235,8 @@ void reset_window(aeon_hip_stager* s, Window& w)
     for (auto& b : w.batches)
         if (b->done) s->spare_events.push_back(b->done);
     w.batches.clear();
+    w.files.clear();
+    w.slot_bytes = 0;
     for (Chunk& c : w.chunks) c.used = 0;
     w.cur      = 0;
     w.state    = Window::IDLE;
@@ -265,6 +295,7 @@ Batch& batch_for(aeon_hip_stager* s, Window& w, void* out)
     b->out  = out;
     b->descs.resize(s->batch);
     b->params.resize(s->batch);
+    b->origin.assign(s->batch, kPixels);
     b->have.reset(new std::atomic<uint8_t>[s->batch]);
     for (int i = 0; i < s->batch; i++) b->have[i] = 0;
     w.batches.push_back(std::move(b));
@@ -285,6 +316,7 @@ void launch_window(aeon_hip_stager* s, Window& w)
     std::vector<aeon_aug_params> params;
     std::vector<void*>           views;
     bool                         all_mapped = true;
+    aeon_stager_decode_info      decoded{};
     for (auto& bp : w.batches) {
         Batch& b = *bp;
         b.n = 0;
@@ -294,9 +326,14 @@ void launch_window(aeon_hip_stager* s, Window& w)
         b.first = (int)descs.size();
         for (int i = 0; i < b.n; i++) {
             aeon_img_desc d = b.descs[i];
-            d.offset        = w.chunks[d.offset >> 48].base + (d.offset & ((1ull << 48) - 1));
+            // (a device-decoded record's slot lies behind every chunk's bytes)
+            d.offset = ((d.offset >> 48) == kSlotChunk ? total : w.chunks[d.offset >> 48].base) + (d.offset & kOffsetMask);
             descs.push_back(d);
             params.push_back(b.params[i]);
+            const uint8_t o = b.origin[i];
+            if (o == kPixels) decoded.pixels++;
+            else if (o < kDeviceDecoded) decoded.host[o - kHostDecoded]++;
+            else decoded.device[o - kDeviceDecoded]++;
         }
         void* v = (s->kind & AEON_STAGER_DEVICE_OUT) ? nullptr : mapped_view(b.out);
         views.push_back(v);
@@ -319,15 +356,28 @@ void launch_window(aeon_hip_stager* s, Window& w)
         return e && std::atoi(e) != 0;
     }();
     const uint8_t* src_base = nullptr;
-    if (all_out_mapped && used_chunks == 1 && !src_copy) src_base = (const uint8_t*)mapped_view(used->host);
+    if (all_out_mapped && used_chunks == 1 && !src_copy && w.files.empty()) src_base = (const uint8_t*)mapped_view(used->host);
     const bool zero_copy = src_base != nullptr;
     if (!src_base) {
-        grow(w.dev_src, w.dev_src_cap, std::max<size_t>(total, 16));
+        grow(w.dev_src, w.dev_src_cap, std::max<size_t>(total + w.slot_bytes, 16));
         for (const Chunk& c : w.chunks)
             if (c.used)
                 hip_ok(hipMemcpyAsync(w.dev_src + c.base, c.host, c.used, hipMemcpyHostToDevice, w.stream),
                        "hipMemcpyAsync");
         src_base = w.dev_src;
+    }
+    // The records still encoded: decoded into their slots by the stages, which upload the files themselves (no
+    // encoded byte is in a chunk), on the window's stream ahead of the kernels that read the slots.  The stages
+    // are done with the files when they return.
+    if (!w.files.empty()) {
+        const aeon_hip::stager_decode_fn decode = g_decode.load(std::memory_order_acquire);
+        if (!decode) fail(AEON_HIP_ERUNTIME, "encoded records staged without the decode stages");
+        std::vector<aeon_hip::stager_file> files;
+        files.reserve(w.files.size());
+        for (const File& f : w.files)
+            files.push_back({f.bytes.get(), f.size, f.format, f.mode, descs[(size_t)f.batch->first + f.idx]});
+        abi_ok(decode(s->ctx, files.data(), files.size(), w.dev_src, w.stream));
+        w.files.clear();
     }
     const size_t item = s->out.item_stride;
     auto run = [&](int first, int n, void* dst) {
@@ -367,6 +417,8 @@ void launch_window(aeon_hip_stager* s, Window& w)
     w.unwaited = (int)w.batches.size();
     s->last    = aeon_stager_launch_info{s->last.launches + 1, zero_copy ? 1 : 0, (on_device || all_mapped) ? 1 : 0,
                                          used_chunks, (int32_t)descs.size()};
+    decoded.launches = s->last.launches;
+    s->last_decode   = decoded;
     std::lock_guard<std::mutex> r(g_reg_mu);
     for (auto& b : w.batches) g_pending[b->out] = Pending{s, w.gen};
 }
@@ -459,6 +511,62 @@ void wait_batch(aeon_hip_stager* s, void* batch_out, bool& found)
     abi_ok(rc);
 }
 
+// What every staged record is checked for, however its pixels arrive.
+void check_record(aeon_hip_stager* s, int idx, int width, int height, int channels, int elem_bytes)
+{
+    if (idx < 0 || idx >= s->batch) fail(AEON_HIP_EINVAL, "idx out of range of the batch");
+    if (width <= 0 || height <= 0) fail(AEON_HIP_EINVAL, "received an image with size 0, at idx " + std::to_string(idx));
+    if (channels != 1 && channels != 3) fail(AEON_HIP_EINVAL, "channels must be 1 or 3");
+    if (elem_bytes != 1 && elem_bytes != 2) fail(AEON_HIP_EINVAL, "elem_bytes must be 1 or 2");
+}
+
+// Record idx of batch_out into the staging window.  file == nullptr: its pixels go into pinned staging, written
+// by fill(dst) on the calling thread.  Else the record is still encoded: *file is kept for the window's launch
+// and the record gets a slot behind the staged pixels (fill is not called).
+template <typename Fill>
+void stage_record(aeon_hip_stager* s, void* batch_out, int idx, int width, int height, int channels, int elem_bytes,
+                  const aeon_aug_params* params, uint8_t origin, File* file, Fill&& fill)
+{
+    const size_t row = (size_t)width * channels * elem_bytes;
+    Batch*       b;
+    uint8_t*     dst = nullptr;
+    size_t       tag;
+    {
+        std::lock_guard<std::mutex> l(s->mu);
+        Window& w = staging_window(s);
+        w.state   = Window::STAGING;
+        b         = &batch_for(s, w, batch_out);
+        if (!b->done) {
+            if (!s->spare_events.empty()) {
+                b->done = s->spare_events.back();
+                s->spare_events.pop_back();
+            } else {
+                hip_ok(hipSetDevice(s->device), "hipSetDevice");
+                hip_ok(hipEventCreateWithFlags(&b->done, hipEventDisableTiming), "hipEventCreate");
+            }
+        }
+        if (b->have[idx]) fail(AEON_HIP_EINVAL, "idx " + std::to_string(idx) + " staged twice for one batch");
+        if (file) {
+            if (w.slot_bytes + row * height > kOffsetMask) fail(AEON_HIP_EINVAL, "window too large");
+            file->batch = b, file->idx = idx;
+            w.files.push_back(std::move(*file));
+            tag = (size_t)(kSlotChunk << 48) | w.slot_bytes;
+            w.slot_bytes += (row * height + 15) & ~(size_t)15;
+        } else {
+            const auto r = reserve(w, row * height);
+            dst          = w.chunks[r.first].host + r.second;
+            tag          = ((size_t)r.first << 48) | r.second;
+        }
+    }
+    // the copy (or decode) itself runs unlocked, on the calling pool thread (the window cannot launch before
+    // this provide() returns: aeon flushes after its pool run)
+    if (dst) fill(dst);
+    b->descs[idx]  = aeon_img_desc{tag, width, height, (int32_t)row, channels, elem_bytes, 0};
+    b->params[idx] = *params;
+    b->origin[idx] = origin;
+    b->have[idx].store(1, std::memory_order_release);
+}
+
 } // namespace
 
 extern "C" {
@@ -525,44 +633,16 @@ int aeon_hip_stager_stage(aeon_hip_stager* s, void* batch_out, int idx, const vo
 {
     return stager_guarded([&] {
         if (!s || !batch_out || !pixels || !params) fail(AEON_HIP_EINVAL, "null argument");
-        if (idx < 0 || idx >= s->batch) fail(AEON_HIP_EINVAL, "idx out of range of the batch");
-        if (width <= 0 || height <= 0) fail(AEON_HIP_EINVAL, "received an image with size 0, at idx " + std::to_string(idx));
-        if (channels != 1 && channels != 3) fail(AEON_HIP_EINVAL, "channels must be 1 or 3");
         if (elem_bytes == 0) elem_bytes = 1;
-        if (elem_bytes != 1 && elem_bytes != 2) fail(AEON_HIP_EINVAL, "elem_bytes must be 1 or 2");
+        check_record(s, idx, width, height, channels, elem_bytes);
         const size_t row = (size_t)width * channels * elem_bytes;
         if (stride == 0) stride = (int)row;
         if ((size_t)stride < row) fail(AEON_HIP_EINVAL, "stride < width * channels * elem_bytes");
-        Batch*   b;
-        uint8_t* dst;
-        size_t   tag;
-        {
-            std::lock_guard<std::mutex> l(s->mu);
-            Window& w = staging_window(s);
-            w.state   = Window::STAGING;
-            b         = &batch_for(s, w, batch_out);
-            if (!b->done) {
-                if (!s->spare_events.empty()) {
-                    b->done = s->spare_events.back();
-                    s->spare_events.pop_back();
-                } else {
-                    hip_ok(hipSetDevice(s->device), "hipSetDevice");
-                    hip_ok(hipEventCreateWithFlags(&b->done, hipEventDisableTiming), "hipEventCreate");
-                }
-            }
-            if (b->have[idx]) fail(AEON_HIP_EINVAL, "idx " + std::to_string(idx) + " staged twice for one batch");
-            const auto r = reserve(w, row * height);
-            dst          = w.chunks[r.first].host + r.second;
-            tag          = ((size_t)r.first << 48) | r.second;
-        }
-        // the copy itself runs unlocked, on the calling pool thread (the window cannot launch before
-        // this provide() returns: aeon flushes after its pool run)
-        if ((size_t)stride == row) std::memcpy(dst, pixels, row * height);
-        else
-            for (int y = 0; y < height; y++) std::memcpy(dst + y * row, (const uint8_t*)pixels + (size_t)y * stride, row);
-        b->descs[idx]  = aeon_img_desc{tag, width, height, (int32_t)row, channels, elem_bytes, 0};
-        b->params[idx] = *params;
-        b->have[idx].store(1, std::memory_order_release);
+        stage_record(s, batch_out, idx, width, height, channels, elem_bytes, params, kPixels, nullptr, [&](uint8_t* dst) {
+            if ((size_t)stride == row) std::memcpy(dst, pixels, row * height);
+            else
+                for (int y = 0; y < height; y++) std::memcpy(dst + y * row, (const uint8_t*)pixels + (size_t)y * stride, row);
+        });
     });
 }
 
@@ -625,6 +705,58 @@ int aeon_hip_stager_last_launch(aeon_hip_stager* s, aeon_stager_launch_info* inf
     });
 }
 
+int aeon_hip_stager_last_decode(aeon_hip_stager* s, aeon_stager_decode_info* info)
+{
+    return stager_guarded([&] {
+        if (!s || !info) fail(AEON_HIP_EINVAL, "null argument");
+        std::lock_guard<std::mutex> l(s->mu);
+        *info = s->last_decode;
+    });
+}
+
 const char* aeon_hip_stager_last_error(void) { return g_stager_err.c_str(); }
 
 } // extern "C"
+
+// ---- for stager_encoded.cpp (stager_encoded.hpp) ----
+namespace aeon_hip {
+
+void stager_set_decode(stager_decode_fn fn) { g_decode.store(fn, std::memory_order_release); }
+
+void stager_describe(const aeon_hip_stager* s, int* base_kind, int* out_channels)
+{
+    *base_kind    = s->kind & ~AEON_STAGER_DEVICE_OUT;
+    *out_channels = s->out.channels;
+}
+
+void stager_set_error(const std::string& what) { g_stager_err = what; }
+
+int stager_stage_decoded(aeon_hip_stager* s, void* batch_out, int idx, int width, int height, int channels, int elem_bytes,
+                         const aeon_aug_params* params, int format, stager_fill_fn fill_fn, void* arg)
+{
+    int rc = 0;
+    const int guard = stager_guarded([&] {
+        check_record(s, idx, width, height, channels, elem_bytes);
+        const size_t row = (size_t)width * channels * elem_bytes;
+        stage_record(s, batch_out, idx, width, height, channels, elem_bytes, params, (uint8_t)(kHostDecoded + format),
+                     nullptr, [&](uint8_t* dst) {
+                         rc = fill_fn(arg, dst, row);
+                         if (rc != 0) throw stager_error(rc, g_stager_err); // (the text is fill's)
+                     });
+    });
+    return guard;
+}
+
+int stager_stage_file(aeon_hip_stager* s, void* batch_out, int idx, int width, int height, int channels, int elem_bytes,
+                      const aeon_aug_params* params, int format, int mode, std::unique_ptr<uint8_t[]> bytes, size_t size)
+{
+    return stager_guarded([&] {
+        check_record(s, idx, width, height, channels, elem_bytes);
+        File f;
+        f.bytes = std::move(bytes), f.size = size, f.format = format, f.mode = mode;
+        stage_record(s, batch_out, idx, width, height, channels, elem_bytes, params, (uint8_t)(kDeviceDecoded + format), &f,
+                     [](uint8_t*) {});
+    });
+}
+
+} // namespace aeon_hip

@@ -720,6 +720,52 @@ typedef struct aeon_stager_launch_info {
 int aeon_hip_stager_last_launch(aeon_hip_stager* stager, aeon_stager_launch_info* info);
 const char* aeon_hip_stager_last_error(void);
 
+/* ---- the drop-in, from encoded records: provide() hands over the file, not the pixels ------------
+ * aeon_encoded_info: what a decoder (aeon_decoder_*) finds out about an encoded element before it decodes it, in
+ * its order -- PNG signature, then the BMP / PNM sniff, then the TIFF sniff, then the JPEG parser -- on the
+ * calling thread, host only, no context.  mask != 0: the file is a pixel mask (CV_LOAD_IMAGE_ANYDEPTH), else an
+ * image.  *format: AEON_FORMAT_*; *width / *height: the decoded size (what aeon_make_params needs);
+ * *file_channels: the file's own channels (JPEG: components; BMP / PNM and TIFF: as aeon_pixmap_info /
+ * aeon_tiff_info; PNG: 1 gray, 2 gray + alpha, 3 RGB and palette, 4 RGBA); *elem_bytes: 2 where ANYDEPTH gives a
+ * mask native uint16 samples (16-bit non-palette PNG, PNM with maxval > 255, 16-bit gray TIFF), else 1;
+ * *device_route: 1 when the decoder's routing rule sends the file through its device stage
+ * (aeon_png_decoder_route, the pixmap stage's rule, aeon_tiff_decoder_route; a JPEG file always), 0 when it
+ * decodes on the host.  Any out pointer but format / width / height may be NULL.  Errors are the header
+ * parser's own, code and message (aeon_hip_last_error); a JPEG file with mask != 0 is refused as the decoder
+ * refuses it ("encoded pixel masks are decoded from PNG files only ..."). */
+#define AEON_FORMAT_JPEG   0
+#define AEON_FORMAT_PNG    1
+#define AEON_FORMAT_PIXMAP 2
+#define AEON_FORMAT_TIFF   3
+#define AEON_FORMAT_COUNT  4
+int aeon_encoded_info(const void* data, size_t size, int mask, int* format, int* width, int* height,
+                      int* file_channels, int* elem_bytes, int* device_route);
+/* aeon_hip_stager_stage_encoded: aeon_hip_stager_stage for a record still encoded (from provide(), any pool
+ * thread, concurrently, mixed freely with aeon_hip_stager_stage in one window and one batch).  The decode mode
+ * follows the stager as the decoder's provider picks it: an image stager decodes BGR8 when out->channels is 3,
+ * else GRAY8; a mask stager ANYDEPTH, and refuses a JPEG file.  The file's bytes are copied, or decoded, before
+ * the call returns.  A file with device_route 0 (aeon_encoded_info) is decoded here, on the calling thread,
+ * straight into the window's pinned staging (aeon_decode_png / _pixmap / _tiff) and is an ordinary staged
+ * record from then on.  Any other file keeps its bytes until the window's launch, which decodes it into a slot
+ * of the window's device source arena with the stage of its format (aeon_hip_decode_{jpeg,png,pixmap,tiff}_batch,
+ * at most 512 files a call) on the window's stream, ahead of the augment / mask launches: such a window's sources
+ * are never read zero-copy (src_zero_copy 0).  A header the parser refuses returns here with the parser's code
+ * and message plus ", at idx N"; the window stays usable and that idx may be staged again.  Corrupt entropy-coded
+ * / compressed data of a device-decoded file is AEON_HIP_EDEVICE from the window's last wait; the next window is
+ * unaffected. */
+int aeon_hip_stager_stage_encoded(aeon_hip_stager* stager, void* batch_out, int idx, const void* data, size_t size,
+                                  const aeon_aug_params* params);
+/* Read-only: where the records of the most recently launched window were decoded, per AEON_FORMAT_*.
+ * launches is aeon_stager_launch_info's; a dropped window leaves the previous report in place. */
+typedef struct aeon_stager_decode_info {
+    uint64_t launches;
+    int32_t  device[AEON_FORMAT_COUNT]; /* decoded by the window's launch, on the device stage of the format */
+    int32_t  host[AEON_FORMAT_COUNT];   /* decoded by aeon_hip_stager_stage_encoded on the calling thread */
+    int32_t  pixels;                    /* staged decoded (aeon_hip_stager_stage) */
+    int32_t  reserved;
+} aeon_stager_decode_info;
+int aeon_hip_stager_last_decode(aeon_hip_stager* stager, aeon_stager_decode_info* info);
+
 /* ---- host staging (replaces the dead cuMemAllocHost branch, src/buffer_batch.cpp:150-186) -- */
 int aeon_hip_host_alloc(size_t bytes, void** out);
 int aeon_hip_host_free(void* p);

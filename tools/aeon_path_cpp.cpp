@@ -20,7 +20,13 @@
 // records are synthetic decoded HWC uint8 images (the bench's splitmix64 pattern) held in host memory,
 // as imdecode leaves them.  Prints one JSON line: records/s over the timed windows.
 //
-// usage: aeon_path_cpp <C1|C2> <pageable|pinned> <overlap|flush> [windows] [warmup] [batch]
+// With a list file (one path of an encoded record per line; the window cycles through them) provide() hands the
+// stager the file instead: aeon_encoded_info for the size make_params needs, then aeon_hip_stager_stage_encoded
+// (INTEGRATION.md edit 3, second form) -- no imdecode on the pool, no decoded pixels over PCIe.  `pixels` after
+// the list stages synthetic decoded records of the files' sizes instead (the decoded-pixels path on the same
+// geometry, imdecode left out as above).  The JSON line then also names the records and their bytes.
+//
+// usage: aeon_path_cpp <C1|C2> <pageable|pinned> <overlap|flush> [windows] [warmup] [batch] [list [pixels]]
 #include <pthread.h>
 #include <sched.h>
 
@@ -33,7 +39,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <fstream>
 #include <functional>
+#include <iterator>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -173,7 +181,8 @@ void synthetic_image(uint64_t index, int w, int h, int cn, uint8_t* dst)
 int main(int argc, char** argv)
 {
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s <C1|C2> <pageable|pinned> <overlap|flush> [windows] [warmup] [batch]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <C1|C2> <pageable|pinned> <overlap|flush> [windows] [warmup] [batch] [list [pixels]]\n",
+                     argv[0]);
         return 2;
     }
     const std::string cfg = argv[1];
@@ -184,6 +193,8 @@ int main(int argc, char** argv)
     const bool c1      = cfg == "C1";
     const int  batch   = argc > 6 ? std::atoi(argv[6]) : (c1 ? 32 : 256);
     const int  src_w = c1 ? 480 : 256, src_h = c1 ? 360 : 256;
+    const char* list_path = argc > 7 ? argv[7] : nullptr;
+    const bool  as_pixels = argc > 8 && std::strcmp(argv[8], "pixels") == 0;
     // the loader's pool and decode window (loader.cpp:158-166)
     std::vector<int> cpus(1024);
     int              ncpu = 0;
@@ -209,10 +220,34 @@ int main(int argc, char** argv)
     aeon_hip_stager* st = nullptr;
     STAGER_CALL(aeon_hip_stager_create(ctx, AEON_STAGER_IMAGE, &out, batch, &st));
 
+    // encoded records (the list's files, as aeon's encoded_record holds them) and their sizes
+    struct Encoded {
+        std::vector<uint8_t> bytes;
+        int                  w = 0, h = 0;
+        std::vector<uint8_t> pixels; // `pixels`: a synthetic decoded record of the file's size
+    };
+    std::vector<Encoded> files;
+    if (list_path) {
+        std::ifstream list(list_path);
+        for (std::string line; std::getline(list, line);) {
+            if (line.empty()) continue;
+            std::ifstream f(line, std::ios::binary);
+            Encoded       e;
+            e.bytes.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+            int format = 0;
+            HIP_CALL(aeon_encoded_info(e.bytes.data(), e.bytes.size(), 0, &format, &e.w, &e.h, nullptr, nullptr, nullptr));
+            if (as_pixels) {
+                e.pixels.resize((size_t)e.w * e.h * 3);
+                synthetic_image(files.size(), e.w, e.h, 3, e.pixels.data());
+            }
+            files.push_back(std::move(e));
+        }
+        if (files.empty()) die("reading the list", -1, list_path);
+    }
     // decoded records (imdecode's output, host memory) and the slot engines (seed random_seed + node_id)
     const size_t         rec_bytes = (size_t)src_w * src_h * 3;
-    std::vector<uint8_t> recs((size_t)decode_size * rec_bytes);
-    for (int i = 0; i < decode_size; i++) synthetic_image(i, src_w, src_h, 3, recs.data() + i * rec_bytes);
+    std::vector<uint8_t> recs(list_path ? 0 : (size_t)decode_size * rec_bytes);
+    for (int i = 0; i < decode_size && !list_path; i++) synthetic_image(i, src_w, src_h, 3, recs.data() + i * rec_bytes);
     std::vector<uint32_t> engines(decode_size);
     HIP_CALL(aeon_seed_slots(1, decode_size, engines.data()));
 
@@ -235,24 +270,50 @@ int main(int argc, char** argv)
     std::string         first_error;
     std::mutex          err_mu;
 
+    // where the decode thread's time goes over the timed windows (printed with a list only): waiting for a free
+    // container, the pool's provide() run, the post_process calls (a window's launch runs inside the first)
+    double wait_s = 0, provide_s = 0, post_s = 0;
+    auto   since  = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+    };
     std::thread decoder([&] { // batch_decoder::filler
         for (int w = 0; w < total; w++) {
+            auto      t = std::chrono::steady_clock::now();
             const int c = free_q.get();
             if (w == warmup) t0 = std::chrono::steady_clock::now();
+            if (w >= warmup) wait_s += since(t);
+            t = std::chrono::steady_clock::now();
             pool.run(decode_size, [&](int i) { // process(i) -> provider::image::provide
                 aeon_aug_params p{};
-                int rc = aeon_make_params(factory, &engines[i], src_w, src_h, 224, 224, &p);
-                if (rc == 0)
-                    rc = aeon_hip_stager_stage(st, cont[c][i / batch], i % batch, recs.data() + (size_t)i * rec_bytes, src_w,
-                                               src_h, src_w * 3, 3, 1, &p);
+                int             rc;
+                if (list_path) { // the record arrives encoded (or, `pixels`, decoded at the file's size)
+                    const Encoded& e = files[(size_t)i % files.size()];
+                    int            format = 0, w = e.w, h = e.h;
+                    rc = as_pixels ? 0 : aeon_encoded_info(e.bytes.data(), e.bytes.size(), 0, &format, &w, &h, nullptr, nullptr,
+                                                           nullptr);
+                    if (rc == 0) rc = aeon_make_params(factory, &engines[i], w, h, 224, 224, &p);
+                    if (rc == 0)
+                        rc = as_pixels ? aeon_hip_stager_stage(st, cont[c][i / batch], i % batch, e.pixels.data(), w, h, w * 3, 3,
+                                                               1, &p)
+                                       : aeon_hip_stager_stage_encoded(st, cont[c][i / batch], i % batch, e.bytes.data(),
+                                                                       e.bytes.size(), &p);
+                } else {
+                    rc = aeon_make_params(factory, &engines[i], src_w, src_h, 224, 224, &p);
+                    if (rc == 0)
+                        rc = aeon_hip_stager_stage(st, cont[c][i / batch], i % batch, recs.data() + (size_t)i * rec_bytes,
+                                                   src_w, src_h, src_w * 3, 3, 1, &p);
+                }
                 if (rc != 0 && !failed.exchange(true)) {
                     std::lock_guard<std::mutex> l(err_mu);
                     first_error = aeon_hip_stager_last_error();
                 }
             });
             if (failed) die("provide", -1, first_error.c_str());
+            if (w >= warmup) provide_s += since(t);
+            t = std::chrono::steady_clock::now();
             for (int b = 0; b < nb; b++) // post_process per batch (edits 1-3)
                 STAGER_CALL(overlap ? aeon_hip_stager_launch(st, cont[c][b]) : aeon_hip_stager_flush(st, cont[c][b]));
+            if (w >= warmup) post_s += since(t);
             full_q.put(c);
         }
     });
@@ -269,10 +330,28 @@ int main(int argc, char** argv)
     decoder.join();
     std::printf("{\"cfg\": \"%s\", \"buffers\": \"%s\", \"post_process\": \"%s\", \"value\": %.1f, \"unit\": \"images/s\", "
                 "\"ms_per_window\": %.3f, \"batch\": %d, \"decode_size\": %d, \"pool_threads\": %d, \"windows\": %d, "
-                "\"sink\": %llu}\n",
+                "\"sink\": %llu",
                 cfg.c_str(), pinned ? "pinned" : "pageable", overlap ? "launch+consumer wait" : "flush",
                 (double)decode_size * windows / dt, dt / windows * 1e3, batch, decode_size, ncpu, windows,
                 (unsigned long long)(sink & 1));
+    if (list_path) { // what the records were, and where the last window's were decoded
+        double file_bytes = 0, pixel_bytes = 0;
+        for (int i = 0; i < decode_size; i++) {
+            const Encoded& e = files[(size_t)i % files.size()];
+            file_bytes += (double)e.bytes.size(), pixel_bytes += (double)e.w * e.h * 3;
+        }
+        aeon_stager_decode_info di{};
+        aeon_stager_launch_info li{};
+        STAGER_CALL(aeon_hip_stager_last_decode(st, &di));
+        STAGER_CALL(aeon_hip_stager_last_launch(st, &li));
+        std::printf(", \"records\": \"%s\", \"files\": %zu, \"file_bytes_per_record\": %.0f, \"pixel_bytes_per_record\": %.0f, "
+                    "\"device_decoded\": %d, \"host_decoded\": %d, \"staged_pixels\": %d, \"src_zero_copy\": %d, "
+                    "\"container_wait_ms\": %.3f, \"provide_ms\": %.3f, \"post_process_ms\": %.3f",
+                    as_pixels ? "pixels" : "encoded", files.size(), file_bytes / decode_size, pixel_bytes / decode_size,
+                    di.device[0] + di.device[1] + di.device[2] + di.device[3], di.host[0] + di.host[1] + di.host[2] + di.host[3],
+                    di.pixels, li.src_zero_copy, wait_s / windows * 1e3, provide_s / windows * 1e3, post_s / windows * 1e3);
+    }
+    std::printf("}\n");
     STAGER_CALL(aeon_hip_stager_destroy(st));
     for (auto& c : cont)
         for (auto& b : c) {
