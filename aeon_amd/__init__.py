@@ -267,6 +267,12 @@ def lib():
         L.aeon_encoded_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int] + [P(ctypes.c_int)] * 6
         L.aeon_hip_stager_stage_encoded.argtypes = [vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, P(AugParams)]
         L.aeon_hip_stager_last_decode.argtypes = [vp, P(StagerDecodeInfo)]
+        L.aeon_hip_stager_create_video.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                                   ctypes.c_int, P(vp)]
+        L.aeon_clip_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int] + [P(ctypes.c_int)] * 3
+        L.aeon_hip_stager_stage_clip.argtypes = [vp, vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, P(AugParams)]
+        L.aeon_hip_stager_stage_frames.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, P(vp), ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, P(AugParams)]
         L.aeon_hip_release_stream.argtypes = [vp, vp]
         L.aeon_hip_stager_last_error.restype = ctypes.c_char_p
         L.aeon_hip_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -677,6 +683,15 @@ def avi_frames(data, cap=None):
 PNG_BGR8, PNG_GRAY8, PNG_ANYDEPTH = 0, 1, 2
 
 
+def clip_info(data, max_frames):
+    """(kept, width, height) of an MJPEG AVI datum (aeon_clip_info): min(frame count, max_frames) and the first kept
+    frame's decoded size, which is what provider::video draws the clip's params with."""
+    data = bytes(data)
+    k, w, h = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _check_stager(lib().aeon_clip_info(data, len(data), int(max_frames), ctypes.byref(k), ctypes.byref(w), ctypes.byref(h)))
+    return k.value, w.value, h.value
+
+
 def png_info(data):
     """(width, height, bit depth, PNG colour type) of a PNG file (aeon_png_info)."""
     w, h, d, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
@@ -1045,7 +1060,7 @@ class Context:
                                               rows, cols, element_size, ctypes.c_void_p(stream or 0)))
 
 
-STAGER_IMAGE, STAGER_MASK, STAGER_DEVICE_OUT = 0, 1, 0x100
+STAGER_IMAGE, STAGER_MASK, STAGER_VIDEO, STAGER_DEVICE_OUT = 0, 1, 2, 0x100
 
 
 class StagerLaunchInfo(ctypes.Structure):  # aeon_stager_launch_info
@@ -1091,6 +1106,38 @@ class Stager:
         data = bytes(data)
         _check_stager(lib().aeon_hip_stager_stage_encoded(self._h, ctypes.c_void_p(batch_out), idx, data, len(data),
                                                           ctypes.byref(params)))
+
+    @classmethod
+    def video(cls, ctx, max_frames, out_w, out_h, item_stride, batch_size, device_out=False):
+        """What the aeon-side provider::video holds (aeon_hip_stager_create_video): an item of a batch buffer is one
+        clip, uint8 (3, max_frames, out_h, out_w), item_stride bytes apart; stage_clip() / stage_frames() from
+        provide(), the rest as for images."""
+        self = cls.__new__(cls)
+        h = ctypes.c_void_p()
+        self._out = None
+        _check_stager(lib().aeon_hip_stager_create_video(ctx._h, STAGER_DEVICE_OUT if device_out else 0, max_frames, out_w,
+                                                         out_h, item_stride, batch_size, ctypes.byref(h)))
+        self._h = h
+        return self
+
+    def stage_clip(self, batch_out, idx, data, params):
+        """data: the record's MJPEG AVI datum as bytes; its first max_frames frames are decoded by the window's launch
+        (aeon_hip_stager_stage_clip)."""
+        data = bytes(data)
+        _check_stager(lib().aeon_hip_stager_stage_clip(self._h, ctypes.c_void_p(batch_out), idx, data, len(data),
+                                                       ctypes.byref(params)))
+
+    def stage_frames(self, batch_out, idx, frames, params):
+        """frames: the clip's decoded frames, HxWx3 uint8 arrays of one size; None after the first repeats the frame
+        before it (aeon_hip_stager_stage_frames)."""
+        arrays = [None if f is None else np.ascontiguousarray(f) for f in frames]
+        first = arrays[0] if arrays and arrays[0] is not None else np.zeros((0, 0, 3), np.uint8)
+        if any(a is not None and (a.shape != first.shape or a.dtype != np.uint8) for a in arrays) or first.ndim != 3:
+            raise ValueError("the frames of a clip are HxWx3 uint8 arrays of one size")
+        ptrs = (ctypes.c_void_p * max(len(arrays), 1))(*[None if a is None else a.ctypes.data for a in arrays])
+        h, w = first.shape[:2]
+        _check_stager(lib().aeon_hip_stager_stage_frames(self._h, ctypes.c_void_p(batch_out), idx, len(arrays), ptrs, w, h,
+                                                         w * 3, ctypes.byref(params)))
 
     def flush(self, batch_out):
         _check_stager(lib().aeon_hip_stager_flush(self._h, ctypes.c_void_p(batch_out)))

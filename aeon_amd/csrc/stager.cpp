@@ -10,6 +10,10 @@
 //                                            through stager_encoded.hpp): decoded into pinned memory right there,
 //                                            or kept as a file that the window's launch decodes on the device
 //                                            into a slot behind the staged pixels, ahead of the augment launch
+//   stage_clip / stage_frames (stager_clip.cpp, through stager_clip.hpp) -- provider::video's provide(): a clip of
+//                                            at most max_frames frames per idx, its frames still MJPEG (a slot each,
+//                                            decoded by the window's launch) or decoded (pinned staging); the
+//                                            window's launch then makes one video call per batch, not an augment one
 //   launch(batch_out)                      -- post_process(): the FIRST call after a window's stages
 //                                            launches the whole window -- one H2D per pinned chunk, ONE
 //                                            augment (or mask) launch over every staged record of every
@@ -38,6 +42,7 @@
 #include <vector>
 
 #include "../../include/aeon_hip.h"
+#include "stager_clip.hpp"
 #include "stager_encoded.hpp"
 
 namespace {
@@ -85,6 +90,12 @@ constexpr uint64_t kOffsetMask = (1ull << 48) - 1;
 
 // The decode stages, for windows with device-decoded records (installed by aeon_hip_stager_stage_encoded).
 std::atomic<aeon_hip::stager_decode_fn> g_decode{nullptr};
+// The same for the clips of a video stager, with the video call (installed by aeon_hip_stager_stage_clip /
+// _stage_frames): this file names neither.
+std::atomic<aeon_hip::stager_decode_fn> g_clip_decode{nullptr};
+std::atomic<aeon_hip::stager_video_fn>  g_video{nullptr};
+// (the video call's own limit: a window with more frames goes in several calls)
+constexpr int64_t kVideoCallFrames = 65535;
 
 // Where a staged record's pixels come from, for last_decode: kPixels, kHostDecoded + format or
 // kDeviceDecoded + format.
@@ -100,9 +111,12 @@ struct Chunk {
 // One batch buffer of the window: per idx, where its pixels are and its params.
 struct Batch {
     void*                        out = nullptr; // the batch buffer (host, or device memory)
-    std::vector<aeon_img_desc>   descs;         // offset = (chunk << 48) | offset in chunk until launch
+    std::vector<aeon_img_desc>   descs;         // offset = (chunk << 48) | offset in chunk until launch; a video
+                                                // stager's: max_frames per idx, row-major
     std::vector<aeon_aug_params> params;
     std::vector<uint8_t>         origin;        // kPixels, kHostDecoded + format, kDeviceDecoded + format
+    std::vector<int32_t>         counts;        // video: the clip's frames, and how many of them are distinct (have
+    std::vector<int32_t>         distinct;      // a slot or staging of their own: the others repeat a frame)
     std::unique_ptr<std::atomic<uint8_t>[]> have;
     int        first = 0;     // its first record in the window's launch order
     int        n     = 0;     // records staged (idx 0..n-1)
@@ -121,7 +135,7 @@ struct File {
     size_t                     size = 0;
     int                        format = 0, mode = 0;
     Batch*                     batch = nullptr;
-    int                        idx = 0;
+    int                        idx = 0, frame = 0; // (frame: of a clip)
 };
 
 struct Window {
@@ -171,6 +185,9 @@ struct aeon_hip_stager {
     int           kind  = AEON_STAGER_IMAGE;
     aeon_out_desc out{};
     int           batch = 0;
+    int           frames = 1;           // descs per idx: a video stager's max_frames
+    int           out_w = 0, out_h = 0; // video: the frame's output size
+    size_t        item_bytes = 0;       // video: a clip's bytes (copy_out); 0: items are copied strides whole
     int           device = 0;
     std::mutex    mu;
     Window        win[2];
@@ -221,6 +238,19 @@ void grow(uint8_t*& p, size_t& cap, size_t need)
     cap = n;
 }
 
+// A pageable batch's D2H out of the window's device output: n items in one copy, strides whole -- or, for clips
+// whose item_stride is wider than the clip (aeon's buffers have none that are), clip by clip, so that no byte
+// between the host items is written.
+hipError_t copy_out(const aeon_hip_stager* s, void* dst, const uint8_t* src, int n)
+{
+    const size_t stride = s->out.item_stride;
+    if (s->item_bytes == 0 || s->item_bytes == stride) return hipMemcpy(dst, src, (size_t)n * stride, hipMemcpyDeviceToHost);
+    for (int i = 0; i < n; i++)
+        if (const hipError_t e = hipMemcpy((uint8_t*)dst + i * stride, src + i * stride, s->item_bytes, hipMemcpyDeviceToHost))
+            return e;
+    return hipSuccess;
+}
+
 // Forget a completed (or dropped) window: batches gone, chunks empty (their memory is kept).  Caller
 // holds s->mu.
 void reset_window(aeon_hip_stager* s, Window& w)
@@ -257,9 +287,7 @@ Window& staging_window(aeon_hip_stager* s)
         for (auto& b : w.batches)
             if (b->d2h && !b->waited) {
                 b->waited = true;
-                hip_ok(hipMemcpy(b->out, w.dev_out + (size_t)b->first * s->out.item_stride, (size_t)b->n * s->out.item_stride,
-                                 hipMemcpyDeviceToHost),
-                       "hipMemcpy");
+                hip_ok(copy_out(s, b->out, w.dev_out + (size_t)b->first * s->out.item_stride, b->n), "hipMemcpy");
             }
         while (w.copying.load(std::memory_order_acquire) != 0) std::this_thread::yield();
         reset_window(s, w);
@@ -293,9 +321,13 @@ Batch& batch_for(aeon_hip_stager* s, Window& w, void* out)
         if (b->out == out) return *b;
     auto b  = std::make_unique<Batch>();
     b->out  = out;
-    b->descs.resize(s->batch);
+    b->descs.resize((size_t)s->batch * s->frames);
     b->params.resize(s->batch);
     b->origin.assign(s->batch, kPixels);
+    if ((s->kind & ~AEON_STAGER_DEVICE_OUT) == AEON_STAGER_VIDEO) {
+        b->counts.assign(s->batch, 0);
+        b->distinct.assign(s->batch, 0);
+    }
     b->have.reset(new std::atomic<uint8_t>[s->batch]);
     for (int i = 0; i < s->batch; i++) b->have[i] = 0;
     w.batches.push_back(std::move(b));
@@ -312,8 +344,11 @@ void launch_window(aeon_hip_stager* s, Window& w)
         c.base = total;
         total += c.used;
     }
+    const bool                   video = (s->kind & ~AEON_STAGER_DEVICE_OUT) == AEON_STAGER_VIDEO;
+    const size_t                 D     = (size_t)s->frames; // descs per record (a clip's row)
     std::vector<aeon_img_desc>   descs;
-    std::vector<aeon_aug_params> params;
+    std::vector<aeon_aug_params> params; // one per record: params.size() is the window's records
+    std::vector<int32_t>         counts; // video: one per clip
     std::vector<void*>           views;
     bool                         all_mapped = true;
     aeon_stager_decode_info      decoded{};
@@ -323,17 +358,26 @@ void launch_window(aeon_hip_stager* s, Window& w)
         while (b.n < s->batch && b.have[b.n]) b.n++;
         for (int i = b.n; i < s->batch; i++)
             if (b.have[i]) fail(AEON_HIP_EINVAL, "batch staged with a hole: idx " + std::to_string(b.n) + " missing");
-        b.first = (int)descs.size();
+        b.first = (int)params.size();
         for (int i = 0; i < b.n; i++) {
-            aeon_img_desc d = b.descs[i];
-            // (a device-decoded record's slot lies behind every chunk's bytes)
-            d.offset = ((d.offset >> 48) == kSlotChunk ? total : w.chunks[d.offset >> 48].base) + (d.offset & kOffsetMask);
-            descs.push_back(d);
+            const size_t kept = video ? (size_t)b.counts[i] : 1;
+            for (size_t f = 0; f < D; f++) {
+                aeon_img_desc d{}; // (the rest of a short clip's row is not read)
+                if (f < kept) {
+                    d = b.descs[(size_t)i * D + f];
+                    // (a device-decoded record's slot lies behind every chunk's bytes)
+                    d.offset =
+                        ((d.offset >> 48) == kSlotChunk ? total : w.chunks[d.offset >> 48].base) + (d.offset & kOffsetMask);
+                }
+                descs.push_back(d);
+            }
             params.push_back(b.params[i]);
+            if (video) counts.push_back(b.counts[i]);
             const uint8_t o = b.origin[i];
-            if (o == kPixels) decoded.pixels++;
-            else if (o < kDeviceDecoded) decoded.host[o - kHostDecoded]++;
-            else decoded.device[o - kDeviceDecoded]++;
+            const int32_t k = video ? b.distinct[i] : 1; // (a clip counts by its frames)
+            if (o == kPixels) decoded.pixels += k;
+            else if (o < kDeviceDecoded) decoded.host[o - kHostDecoded] += k;
+            else decoded.device[o - kDeviceDecoded] += k;
         }
         void* v = (s->kind & AEON_STAGER_DEVICE_OUT) ? nullptr : mapped_view(b.out);
         views.push_back(v);
@@ -370,19 +414,30 @@ void launch_window(aeon_hip_stager* s, Window& w)
     // encoded byte is in a chunk), on the window's stream ahead of the kernels that read the slots.  The stages
     // are done with the files when they return.
     if (!w.files.empty()) {
-        const aeon_hip::stager_decode_fn decode = g_decode.load(std::memory_order_acquire);
+        const aeon_hip::stager_decode_fn decode = (video ? g_clip_decode : g_decode).load(std::memory_order_acquire);
         if (!decode) fail(AEON_HIP_ERUNTIME, "encoded records staged without the decode stages");
         std::vector<aeon_hip::stager_file> files;
         files.reserve(w.files.size());
         for (const File& f : w.files)
-            files.push_back({f.bytes.get(), f.size, f.format, f.mode, descs[(size_t)f.batch->first + f.idx]});
+            files.push_back(
+                {f.bytes.get(), f.size, f.format, f.mode, descs[((size_t)f.batch->first + f.idx) * D + f.frame]});
         abi_ok(decode(s->ctx, files.data(), files.size(), w.dev_src, w.stream));
         w.files.clear();
     }
     const size_t item = s->out.item_stride;
     auto run = [&](int first, int n, void* dst) {
         if (n == 0) return;
-        if ((s->kind & ~AEON_STAGER_DEVICE_OUT) == AEON_STAGER_MASK)
+        if (video) {
+            const aeon_hip::stager_video_fn call = g_video.load(std::memory_order_acquire);
+            if (!call) fail(AEON_HIP_ERUNTIME, "clips staged without the video call");
+            // clips [a, e): as many as the video call takes frames (a clip has at most 65,535 of them: create)
+            for (int a = first, e; a < first + n; a = e) {
+                int64_t fr = 0;
+                for (e = a; e < first + n && fr + counts[e] <= kVideoCallFrames; e++) fr += counts[e];
+                abi_ok(call(s->ctx, e - a, counts.data() + a, descs.data() + (size_t)a * D, src_base, params.data() + a,
+                            s->frames, s->out_w, s->out_h, (uint8_t*)dst + (size_t)(a - first) * item, item, w.stream));
+            }
+        } else if ((s->kind & ~AEON_STAGER_DEVICE_OUT) == AEON_STAGER_MASK)
             abi_ok(aeon_hip_mask_batch(s->ctx, n, descs.data() + first, src_base, params.data() + first, &s->out,
                                        dst, w.stream));
         else
@@ -402,8 +457,8 @@ void launch_window(aeon_hip_stager* s, Window& w)
         // made by its wait (the consumer's thread): a copy into pageable memory holds the calling thread
         // until the data is out (the runtime stages it), and on the decode thread that made the
         // launch-only post_process wait for the window's kernels (overlap measured below flush)
-        grow(w.dev_out, w.dev_out_cap, std::max<size_t>(descs.size() * item, 16));
-        run(0, (int)descs.size(), w.dev_out);
+        grow(w.dev_out, w.dev_out_cap, std::max<size_t>(params.size() * item, 16));
+        run(0, (int)params.size(), w.dev_out);
         hip_ok(hipEventRecord(w.batches.front()->done, w.stream), "hipEventRecord");
         for (auto& bp : w.batches) {
             Batch& b = *bp;
@@ -416,7 +471,7 @@ void launch_window(aeon_hip_stager* s, Window& w)
     w.gen      = ++s->gens;
     w.unwaited = (int)w.batches.size();
     s->last    = aeon_stager_launch_info{s->last.launches + 1, zero_copy ? 1 : 0, (on_device || all_mapped) ? 1 : 0,
-                                         used_chunks, (int32_t)descs.size()};
+                                         used_chunks, (int32_t)params.size()};
     decoded.launches = s->last.launches;
     s->last_decode   = decoded;
     std::lock_guard<std::mutex> r(g_reg_mu);
@@ -467,7 +522,7 @@ void wait_batch(aeon_hip_stager* s, void* batch_out, bool& found)
     bool        last = false;
     void*       copy_dst = nullptr; // pageable batch: its D2H, made here
     const void* copy_src = nullptr;
-    size_t      copy_bytes = 0;
+    int         copy_n = 0;
     CopyHold    hold;
     {
         std::lock_guard<std::mutex> l(s->mu);
@@ -483,7 +538,7 @@ void wait_batch(aeon_hip_stager* s, void* batch_out, bool& found)
                         hold.take(w);
                         copy_dst   = b->out;
                         copy_src   = w.dev_out + (size_t)b->first * s->out.item_stride;
-                        copy_bytes = (size_t)b->n * s->out.item_stride;
+                        copy_n     = b->n;
                     }
                     break;
                 }
@@ -494,8 +549,8 @@ void wait_batch(aeon_hip_stager* s, void* batch_out, bool& found)
     hip_ok(hipSetDevice(s->device), "hipSetDevice");
     hip_ok(hipEventSynchronize(ev), "hipEventSynchronize");
     // (the window's device outputs stay until its last wait has returned: reset_window runs after it)
-    if (copy_bytes) {
-        const hipError_t e = hipMemcpy(copy_dst, copy_src, copy_bytes, hipMemcpyDeviceToHost);
+    if (copy_n) {
+        const hipError_t e = copy_out(s, copy_dst, (const uint8_t*)copy_src, copy_n);
         hold.drop();
         hip_ok(e, "hipMemcpy");
     }
@@ -520,6 +575,25 @@ void check_record(aeon_hip_stager* s, int idx, int width, int height, int channe
     if (elem_bytes != 1 && elem_bytes != 2) fail(AEON_HIP_EINVAL, "elem_bytes must be 1 or 2");
 }
 
+// batch_out's batch of the staging window w, made on its first stage and given its completion event, for a
+// stage of idx, which must be its first.  Caller holds s->mu.
+Batch& open_batch(aeon_hip_stager* s, Window& w, void* batch_out, int idx)
+{
+    w.state  = Window::STAGING;
+    Batch& b = batch_for(s, w, batch_out);
+    if (!b.done) {
+        if (!s->spare_events.empty()) {
+            b.done = s->spare_events.back();
+            s->spare_events.pop_back();
+        } else {
+            hip_ok(hipSetDevice(s->device), "hipSetDevice");
+            hip_ok(hipEventCreateWithFlags(&b.done, hipEventDisableTiming), "hipEventCreate");
+        }
+    }
+    if (b.have[idx]) fail(AEON_HIP_EINVAL, "idx " + std::to_string(idx) + " staged twice for one batch");
+    return b;
+}
+
 // Record idx of batch_out into the staging window.  file == nullptr: its pixels go into pinned staging, written
 // by fill(dst) on the calling thread.  Else the record is still encoded: *file is kept for the window's launch
 // and the record gets a slot behind the staged pixels (fill is not called).
@@ -534,18 +608,7 @@ void stage_record(aeon_hip_stager* s, void* batch_out, int idx, int width, int h
     {
         std::lock_guard<std::mutex> l(s->mu);
         Window& w = staging_window(s);
-        w.state   = Window::STAGING;
-        b         = &batch_for(s, w, batch_out);
-        if (!b->done) {
-            if (!s->spare_events.empty()) {
-                b->done = s->spare_events.back();
-                s->spare_events.pop_back();
-            } else {
-                hip_ok(hipSetDevice(s->device), "hipSetDevice");
-                hip_ok(hipEventCreateWithFlags(&b->done, hipEventDisableTiming), "hipEventCreate");
-            }
-        }
-        if (b->have[idx]) fail(AEON_HIP_EINVAL, "idx " + std::to_string(idx) + " staged twice for one batch");
+        b         = &open_batch(s, w, batch_out, idx);
         if (file) {
             if (w.slot_bytes + row * height > kOffsetMask) fail(AEON_HIP_EINVAL, "window too large");
             file->batch = b, file->idx = idx;
@@ -567,6 +630,84 @@ void stage_record(aeon_hip_stager* s, void* batch_out, int idx, int width, int h
     b->have[idx].store(1, std::memory_order_release);
 }
 
+// Clip idx of batch_out into the staging window: n_frames frames of width x height BGR, each with data either
+// its JPEG file (encoded: copied and kept for the window's launch, a slot behind the staged pixels each) or its
+// pixels (copied into pinned staging), or without data: the frame before it again.
+void stage_clip(aeon_hip_stager* s, void* batch_out, int idx, int n_frames, const aeon_hip::stager_clip_frame* frames,
+                bool encoded, int width, int height, int stride, const aeon_aug_params* params)
+{
+    const size_t row = (size_t)width * 3, bytes = row * height, slot = (bytes + 15) & ~(size_t)15;
+    const size_t D   = (size_t)s->frames;
+    // aeon's datum dies with provide(): the window's launch reads these copies (made unlocked)
+    std::vector<File> files;
+    int32_t           distinct = 0;
+    for (int d = 0; d < n_frames; d++) {
+        if (!frames[d].data) continue;
+        distinct++;
+        if (!encoded) continue;
+        File f;
+        f.bytes.reset(new uint8_t[frames[d].size]);
+        std::memcpy(f.bytes.get(), frames[d].data, frames[d].size);
+        f.size = frames[d].size, f.format = AEON_FORMAT_JPEG, f.mode = AEON_DECODE_BGR8, f.idx = idx, f.frame = d;
+        files.push_back(std::move(f));
+    }
+    std::vector<size_t>   tags((size_t)n_frames, 0);
+    std::vector<uint8_t*> dsts((size_t)n_frames, nullptr);
+    Batch*                b;
+    {
+        std::lock_guard<std::mutex> l(s->mu);
+        Window& w = staging_window(s);
+        b         = &open_batch(s, w, batch_out, idx);
+        if (encoded && w.slot_bytes + (size_t)distinct * slot > kOffsetMask) fail(AEON_HIP_EINVAL, "window too large");
+        size_t k = 0;
+        for (int d = 0; d < n_frames; d++) {
+            if (!frames[d].data) {
+                tags[d] = tags[d - 1]; // (the first frame has data: the entries check it)
+            } else if (encoded) {
+                files[k].batch = b;
+                w.files.push_back(std::move(files[k++]));
+                tags[d] = (size_t)(kSlotChunk << 48) | w.slot_bytes;
+                w.slot_bytes += slot;
+            } else {
+                const auto r = reserve(w, bytes);
+                dsts[d]      = w.chunks[r.first].host + r.second;
+                tags[d]      = ((size_t)r.first << 48) | r.second;
+            }
+        }
+    }
+    // the pixels' copy runs unlocked, on the calling pool thread, as a record's
+    for (int d = 0; d < n_frames; d++) {
+        if (dsts[d]) {
+            if ((size_t)stride == row) std::memcpy(dsts[d], frames[d].data, bytes);
+            else
+                for (int y = 0; y < height; y++)
+                    std::memcpy(dsts[d] + y * row, (const uint8_t*)frames[d].data + (size_t)y * stride, row);
+        }
+        b->descs[(size_t)idx * D + d] = aeon_img_desc{tags[d], width, height, (int32_t)row, 3, 1, 0};
+    }
+    b->counts[idx]   = n_frames;
+    b->distinct[idx] = distinct;
+    b->params[idx]   = *params;
+    b->origin[idx]   = encoded ? (uint8_t)(kDeviceDecoded + AEON_FORMAT_JPEG) : kPixels;
+    b->have[idx].store(1, std::memory_order_release);
+}
+
+// What the two create entries share.
+aeon_hip_stager* make_stager(aeon_hip_ctx* ctx, int kind, const aeon_out_desc& out, int batch_size)
+{
+    auto s   = std::make_unique<aeon_hip_stager>();
+    s->ctx   = ctx;
+    s->kind  = kind;
+    s->out   = out;
+    s->batch = batch_size;
+    hip_ok(hipGetDevice(&s->device), "hipGetDevice");
+    for (Window& w : s->win) {
+        hip_ok(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking), "hipStreamCreate");
+        hip_ok(hipEventCreateWithFlags(&w.done, hipEventDisableTiming), "hipEventCreate");
+    }
+    return s.release();
+}
+
 } // namespace
 
 extern "C" {
@@ -583,17 +724,30 @@ int aeon_hip_stager_create(aeon_hip_ctx* ctx, int kind, const aeon_out_desc* out
             fail(AEON_HIP_EUNSUPPORTED, std::string(out->dtype == AEON_DTYPE_BF16 ? "bfloat16" : "float16") +
                                             " output is implemented for images only, not for pixel masks / depth maps");
         if (out->item_stride == 0) fail(AEON_HIP_EINVAL, "out->item_stride is 0");
-        auto s   = std::make_unique<aeon_hip_stager>();
-        s->ctx   = ctx;
-        s->kind  = kind;
-        s->out   = *out;
-        s->batch = batch_size;
-        hip_ok(hipGetDevice(&s->device), "hipGetDevice");
-        for (Window& w : s->win) {
-            hip_ok(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking), "hipStreamCreate");
-            hip_ok(hipEventCreateWithFlags(&w.done, hipEventDisableTiming), "hipEventCreate");
-        }
-        *result = s.release();
+        *result = make_stager(ctx, kind, *out, batch_size);
+    });
+}
+
+int aeon_hip_stager_create_video(aeon_hip_ctx* ctx, int flags, int max_frames, int out_w, int out_h, uint64_t item_stride,
+                                 int batch_size, aeon_hip_stager** result)
+{
+    return stager_guarded([&] {
+        if (!ctx || !result) fail(AEON_HIP_EINVAL, "null argument");
+        if (batch_size <= 0) fail(AEON_HIP_EINVAL, "batch_size must be > 0");
+        if (flags != 0 && flags != AEON_STAGER_DEVICE_OUT) fail(AEON_HIP_EINVAL, "flags must be 0 or AEON_STAGER_DEVICE_OUT");
+        // (the decoder's video config refuses the same: one clip must fit one video call)
+        if (max_frames <= 0 || max_frames > kVideoCallFrames) fail(AEON_HIP_EINVAL, "invalid max_frame_count");
+        if (out_w <= 0 || out_h <= 0) fail(AEON_HIP_EINVAL, "video: invalid max_frame_count or frame size");
+        // the video call's own refusal and text (aeon_hip_video_batch), at create time
+        const uint64_t hw = (uint64_t)out_w * (uint64_t)out_h;
+        if (hw > INT32_MAX || 3 * (uint64_t)max_frames * hw > (uint64_t)INT32_MAX)
+            fail(AEON_HIP_EUNSUPPORTED, "video: a clip item above 2^31 - 1 bytes");
+        if (item_stride < 3 * (uint64_t)max_frames * hw) fail(AEON_HIP_EINVAL, "video: output item does not fit item_stride");
+        aeon_out_desc out{}; // what the video call writes: uint8 planes, channel x frame x height x width
+        out.dtype = AEON_DTYPE_U8, out.channels = 3, out.channel_major = 1, out.item_stride = item_stride;
+        aeon_hip_stager* s = make_stager(ctx, AEON_STAGER_VIDEO | flags, out, batch_size);
+        s->frames = max_frames, s->out_w = out_w, s->out_h = out_h, s->item_bytes = (size_t)(3 * (uint64_t)max_frames * hw);
+        *result = s;
     });
 }
 
@@ -633,6 +787,9 @@ int aeon_hip_stager_stage(aeon_hip_stager* s, void* batch_out, int idx, const vo
 {
     return stager_guarded([&] {
         if (!s || !batch_out || !pixels || !params) fail(AEON_HIP_EINVAL, "null argument");
+        if ((s->kind & ~AEON_STAGER_DEVICE_OUT) == AEON_STAGER_VIDEO)
+            fail(AEON_HIP_EINVAL, "aeon_hip_stager_stage on a video stager, which takes clips (aeon_hip_stager_stage_clip / "
+                                  "_stage_frames), at idx " + std::to_string(idx));
         if (elem_bytes == 0) elem_bytes = 1;
         check_record(s, idx, width, height, channels, elem_bytes);
         const size_t row = (size_t)width * channels * elem_bytes;
@@ -756,6 +913,38 @@ int stager_stage_file(aeon_hip_stager* s, void* batch_out, int idx, int width, i
         f.bytes = std::move(bytes), f.size = size, f.format = format, f.mode = mode;
         stage_record(s, batch_out, idx, width, height, channels, elem_bytes, params, (uint8_t)(kDeviceDecoded + format), &f,
                      [](uint8_t*) {});
+    });
+}
+
+// ---- for stager_clip.cpp (stager_clip.hpp) ----
+void stager_set_clip_hooks(stager_decode_fn decode, stager_video_fn video)
+{
+    g_clip_decode.store(decode, std::memory_order_release);
+    g_video.store(video, std::memory_order_release);
+}
+
+void stager_clip_describe(const aeon_hip_stager* s, stager_clip_shape* shape)
+{
+    *shape = stager_clip_shape{s->kind & ~AEON_STAGER_DEVICE_OUT, s->frames, s->out_w, s->out_h};
+}
+
+int stager_stage_clip_frames(aeon_hip_stager* s, void* batch_out, int idx, int n_frames, const stager_clip_frame* frames,
+                             int encoded, int width, int height, int stride, const aeon_aug_params* params)
+{
+    return stager_guarded([&] {
+        const std::string at = ", at idx " + std::to_string(idx);
+        if ((s->kind & ~AEON_STAGER_DEVICE_OUT) != AEON_STAGER_VIDEO) fail(AEON_HIP_EINVAL, "not a video stager" + at);
+        if (idx < 0 || idx >= s->batch) fail(AEON_HIP_EINVAL, "idx out of range of the batch");
+        if (n_frames < 1 || n_frames > s->frames)
+            fail(AEON_HIP_EINVAL, "n_frames " + std::to_string(n_frames) + " outside [1, max_frames " +
+                                      std::to_string(s->frames) + "]" + at);
+        if (!frames[0].data) fail(AEON_HIP_EINVAL, "the first frame of a clip has no data" + at);
+        if (width <= 0 || height <= 0) fail(AEON_HIP_EINVAL, "received encoded video with size 0" + at);
+        if (params->out_w != s->out_w || params->out_h != s->out_h)
+            fail(AEON_HIP_EINVAL, "params' output size " + std::to_string(params->out_w) + "x" + std::to_string(params->out_h) +
+                                      " is not the stager's " + std::to_string(s->out_w) + "x" + std::to_string(s->out_h) + at);
+        if (!encoded && (size_t)stride < (size_t)width * 3) fail(AEON_HIP_EINVAL, "stride < width * 3" + at);
+        stage_clip(s, batch_out, idx, n_frames, frames, encoded != 0, width, height, stride, params);
     });
 }
 

@@ -96,13 +96,18 @@ try {
         aeon_hip::stager_set_error("null argument");
         return AEON_HIP_EINVAL;
     }
+    int kind = 0, out_channels = 0;
+    aeon_hip::stager_describe(s, &kind, &out_channels);
+    if (kind == AEON_STAGER_VIDEO) {
+        aeon_hip::stager_set_error("aeon_hip_stager_stage_encoded on a video stager, which takes clips "
+                                   "(aeon_hip_stager_stage_clip / _stage_frames), at idx " + std::to_string(idx));
+        return AEON_HIP_EINVAL;
+    }
     if (!data || size == 0) {
         aeon_hip::stager_set_error("received encoded image with size 0, at idx " + std::to_string(idx));
         return AEON_HIP_EINVAL;
     }
     aeon_hip::stager_set_decode(decode_files);
-    int kind = 0, out_channels = 0;
-    aeon_hip::stager_describe(s, &kind, &out_channels);
     const bool mask = kind == AEON_STAGER_MASK;
     int        format = 0, width = 0, height = 0, elem_bytes = 1, route = 0;
     if (const int rc = aeon_encoded_info(data, size, mask ? 1 : 0, &format, &width, &height, nullptr, &elem_bytes, &route)) {

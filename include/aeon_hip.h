@@ -766,6 +766,48 @@ typedef struct aeon_stager_decode_info {
 } aeon_stager_decode_info;
 int aeon_hip_stager_last_decode(aeon_hip_stager* stager, aeon_stager_decode_info* info);
 
+/* ---- the drop-in for provider::video (src/provider.cpp:477-517): provide() stages a clip ---------------
+ * A third stager kind.  Launch, wait, flush, destroy, the two windows, aeon_hip_stager_wait(NULL, ...), the error
+ * word at a window's last wait and the three output kinds (pinned and mapped, pageable, AEON_STAGER_DEVICE_OUT)
+ * are the image stager's; an item of the batch buffer is one clip as aeon_hip_video_batch writes it (uint8 B, G,
+ * R planes, channel x frame x height x width, short clips zero-padded to max_frames).
+ * aeon_hip_stager_create_video: flags 0 or AEON_STAGER_DEVICE_OUT; 1 <= max_frames <= 65535; item_stride at least
+ *   3*max_frames*out_h*out_w, else AEON_HIP_EINVAL; an item above 2^31 - 1 bytes is AEON_HIP_EUNSUPPORTED with
+ *   the video call's message.
+ * aeon_clip_info (host only, no context): video::extractor's demux of the first max_frames frames
+ *   (aeon_avi_frames with cap = max_frames) and aeon_jpeg_info of the first kept frame: *kept =
+ *   min(frame count, max_frames), *width / *height the first frame's decoded size -- what provider::video calls
+ *   make_params with (provider.cpp:503-513), not avih's dwWidth / dwHeight.  Errors are the demux's or the JPEG
+ *   parser's own code and text, in aeon_hip_stager_last_error().
+ * aeon_hip_stager_stage_clip (from provide(), any pool thread, concurrently): clip idx of batch_out from the AVI
+ *   datum.  The first max_frames frames are kept; each non-empty one's JPEG header is parsed and must give the
+ *   first one's size; an empty chunk repeats the frame before it and takes no slot.  The frames' bytes are copied
+ *   before the call returns; each distinct frame gets a slot of the window's device source arena, which the
+ *   window's launch fills through aeon_hip_decode_jpeg_batch (at most 512 files a call) ahead of the video call.
+ *   An empty datum: "received encoded video with size 0, at idx N" (AEON_HIP_EINVAL); whatever the demux or a
+ *   frame header refuses, and a frame of another size, return here with that code and text plus ", at idx N".
+ *   The window stays usable and that idx may be staged again.
+ * aeon_hip_stager_stage_frames: clip idx from n_frames (1 .. max_frames) decoded BGR frames of width x height,
+ *   rows `stride` bytes apart (0: width*3), copied into the window's pinned staging before the call returns
+ *   (aeon's video::extractor stays on the host).  pixels[d] == NULL, d > 0, repeats the frame before it.
+ * The two forms may share a window and a batch.  params->out_w / out_h other than the stager's are
+ * AEON_HIP_EINVAL.  aeon_hip_stager_stage / _stage_encoded on a video stager, and these two on an image or mask
+ * stager, are AEON_HIP_EINVAL naming the kind.
+ * The window's launch makes one aeon_hip_video_batch per batch (a batch of more than 65,535 frames: several),
+ * into the batch buffers where they are device memory or pinned and mapped, else into the window's device output
+ * with each batch's D2H made by its wait.  aeon_stager_launch_info.records counts clips, src_zero_copy follows the
+ * image stager's rule (no device-decoded frame in the window); aeon_stager_decode_info.device[AEON_FORMAT_JPEG]
+ * counts the frames the launch decoded and .pixels the frames staged decoded (repeats count with neither). */
+#define AEON_STAGER_VIDEO 2
+int aeon_hip_stager_create_video(aeon_hip_ctx* ctx, int flags, int max_frames, int out_w, int out_h, uint64_t item_stride,
+                                 int batch_size, aeon_hip_stager** stager);
+int aeon_clip_info(const void* data, size_t size, int max_frames, int* kept, int* width, int* height);
+int aeon_hip_stager_stage_clip(aeon_hip_stager* stager, void* batch_out, int idx, const void* data, size_t size,
+                               const aeon_aug_params* params);
+int aeon_hip_stager_stage_frames(aeon_hip_stager* stager, void* batch_out, int idx, int n_frames,
+                                 const void* const* pixels, int width, int height, int stride,
+                                 const aeon_aug_params* params);
+
 /* ---- host staging (replaces the dead cuMemAllocHost branch, src/buffer_batch.cpp:150-186) -- */
 int aeon_hip_host_alloc(size_t bytes, void** out);
 int aeon_hip_host_free(void* p);
