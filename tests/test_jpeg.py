@@ -90,22 +90,9 @@ def test_interleaved_mcu_over_ten_blocks_refused(oracle):
 
 
 def _decode_gpu(ctx, files, channels):
-    import torch
-    infos = [A.jpeg_info(b) for b in files]
-    descs, off = [], 0
-    for (w, h, _) in infos:
-        descs.append(A.ImgDesc(offset=off, width=w, height=h, stride=w * channels, channels=channels))
-        off += (w * h * channels + 15) // 16 * 16
-    dst = torch.full((max(off, 16),), 0x5A, dtype=torch.uint8, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    ctx.decode_jpeg_batch(files, descs, dst.data_ptr(), stream)
-    ctx.synchronize(stream)
-    host = dst.cpu().numpy()
-    out = []
-    for d in descs:
-        a = host[d.offset:d.offset + d.width * d.height * channels]
-        out.append(a.reshape(d.height, d.width, channels) if channels == 3 else a.reshape(d.height, d.width))
-    return out
+    """Padded rows, guarded gaps (tests/jpeg_size_cases.py decode_guarded): a store outside a record fails here."""
+    from tests.jpeg_size_cases import decode_guarded
+    return decode_guarded(ctx, files, channels)
 
 
 @pytest.fixture(scope="module")
