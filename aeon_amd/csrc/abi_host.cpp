@@ -265,11 +265,10 @@ int aeon_tiff_host_stage(const void* data, size_t size, int mode, int* gpu_route
         tiff_plan(data, size, mode, P);
         *gpu_route = P.route;
         if (P.route) {
-            TiffJob                J;
-            std::vector<TiffStrip> strips;
-            std::vector<TiffBand>  bands;
-            std::vector<uint8_t>   file(size + 16);
-            tiff_stage(data, size, mode, P, 0, J, strips, bands, file.data());
+            TiffJob              J;
+            TiffTables           T;
+            std::vector<uint8_t> file(size + 16);
+            tiff_stage(data, size, mode, P, 0, J, T, file.data());
             *staged_bytes = (int64_t)size;
         } else {
             const size_t         stride = (size_t)P.w * P.channels * P.elem_bytes;
@@ -297,7 +296,7 @@ int aeon_tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, si
         TiffPlan P;
         tiff_checked_plan(data, size, mode, stride, P);
         const int r = tiff_gpu_emulate(data, size, mode, dst, stride);
-        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "TIFF: the file is not routed to the device (an LZW / PackBits strip above 32 KiB)");
+        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "TIFF: the file is not routed to the device (an LZW / PackBits strip or tile above 32 KiB)");
         if (r < 0) fail(AEON_HIP_EDEVICE, "TIFF: strip data corrupt or truncated (GPU stage)");
         return 0;
     });

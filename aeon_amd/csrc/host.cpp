@@ -258,8 +258,8 @@ public:
     // for pixel masks).  JPEG files are decoded on the device, and so are the PNG files the PNG stage's routing
     // rule gives it (png.hpp); the others (Adam7, very wide rows) on the host pool while staging (png_host.cpp).
     // BMP and binary PNM files are converted on the device (the pixmap stage, pixmap.hpp), ASCII PNM files decoded
-    // on the host pool while staging (pixmap_host.cpp).  TIFF files in strips are decoded on the device (the TIFF
-    // stage, tiff.hpp), those with LZW / PackBits strips above 32 KiB on the host pool (tiff_host.cpp).  The sniff is strict: anything else is the JPEG parser's.
+    // on the host pool while staging (pixmap_host.cpp).  TIFF files in strips or tiles are decoded on the device (the TIFF
+    // stage, tiff.hpp), those with LZW / PackBits strips or tiles above 32 KiB on the host pool (tiff_host.cpp).  The sniff is strict: anything else is the JPEG parser's.
     void inspect(window_part&, int idx, decoded_element& e) const override
     {
         static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};

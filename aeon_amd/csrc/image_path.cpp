@@ -876,12 +876,13 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
 }
 
 // ---- TIFF stage ---------------------------------------------------------------------------------------
-// The decode call: each file's IFD parse (tiff_plan) on the pool, the call's tables -- jobs, compressed strips
-// (sorted by compressed size, largest first: the long waves start first), bands -- then the layout
+// The decode call: each file's IFD parse (tiff_plan) on the pool, the call's tables -- jobs, compressed strips and tiles
+// (sorted by compressed size, largest first: the long waves start first), bands, the tiled files'
+// bands and tile sources -- then the layout
 // of the staging: the tables, the routed files as they are (each at a 16-byte-aligned offset, 16 zero bytes
 // behind it, so the kernels' aligned over-reads stay inside the buffer), the host-decoded files' pixels -- filled on
-// the pool, one H2D, then tiff_expand over the strips into the files' scratch, tiff_convert over the bands and a
-// strided device copy per host-decoded file, all on `stream`.
+// the pool, one H2D, then tiff_expand over the strips into the files' scratch, tiff_convert over the bands,
+// tiff_convert_tiled over the tiled bands (launched only when the call holds a tiled file) and a strided device copy per host-decoded file, all on `stream`.
 int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
              const aeon_img_desc* descs, void* dst_base, hipStream_t stream)
 {
@@ -911,8 +912,9 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
     // the tables need the headers only: built before the staging is laid out
     std::vector<int>       job_of(n, -1);
     std::vector<TiffJob>   jobs_host;
-    std::vector<TiffStrip> strips;
-    std::vector<TiffBand>  bands;
+    TiffTables             T;
+    std::vector<TiffStrip>& strips = T.strips;
+    std::vector<TiffBand>&  bands = T.bands;
     std::vector<size_t>    raw_at(n, 0);
     size_t                 scratch = 0;
     double                 bytes = 0;
@@ -921,19 +923,22 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
         if (!P.route) continue;
         job_of[i] = (int)jobs_host.size();
         jobs_host.emplace_back();
-        tiff_stage(data[i], sizes[i], modes[i], P, job_of[i], jobs_host.back(), strips, bands, nullptr);
+        tiff_stage(data[i], sizes[i], modes[i], P, job_of[i], jobs_host.back(), T, nullptr);
         raw_at[i] = scratch;
         scratch += (tiff_scratch_bytes(P) + 15) & ~(size_t)15;
         bytes += (double)P.h * ((double)P.rowb + (double)P.w * P.channels * P.elem_bytes);
     }
     const int n_gpu = (int)jobs_host.size();
-    if (bands.size() > (size_t)INT32_MAX || strips.size() > (size_t)INT32_MAX) fail(AEON_HIP_EUNSUPPORTED, "TIFF: too many strips for one call");
+    if (bands.size() > (size_t)INT32_MAX || strips.size() > (size_t)INT32_MAX || T.tbands.size() > (size_t)INT32_MAX || T.tile_src.size() > (size_t)INT32_MAX)
+        fail(AEON_HIP_EUNSUPPORTED, "TIFF: too many strips for one call");
     std::stable_sort(strips.begin(), strips.end(), [](const TiffStrip& a, const TiffStrip& b) { return a.bytes > b.bytes; });
-    // layout: the jobs, the strips, the bands, then per file the file itself or its pixels (16-byte aligned)
+    // layout: the jobs, the strips, the bands, the tiled bands, the tile sources, then per file the file itself or its pixels (16-byte aligned)
     std::vector<size_t> at(n);
     const size_t        strips_at = (size_t)n_gpu * sizeof(TiffJob);
     const size_t        bands_at  = strips_at + strips.size() * sizeof(TiffStrip);
-    size_t              total     = bands_at + bands.size() * sizeof(TiffBand);
+    const size_t        tbands_at = bands_at + bands.size() * sizeof(TiffBand);
+    const size_t        tiles_at  = tbands_at + T.tbands.size() * sizeof(TiffTileBand);
+    size_t              total     = tiles_at + T.tile_src.size() * sizeof(uint32_t);
     for (int i = 0; i < n; i++) {
         const TiffPlan& P = plans[i];
         total             = (total + 15) & ~(size_t)15;
@@ -951,6 +956,8 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
     TiffJob* jobs = (TiffJob*)st.pinned;
     if (!strips.empty()) std::memcpy(st.pinned + strips_at, strips.data(), strips.size() * sizeof(TiffStrip));
     if (!bands.empty()) std::memcpy(st.pinned + bands_at, bands.data(), bands.size() * sizeof(TiffBand));
+    if (!T.tbands.empty()) std::memcpy(st.pinned + tbands_at, T.tbands.data(), T.tbands.size() * sizeof(TiffTileBand));
+    if (!T.tile_src.empty()) std::memcpy(st.pinned + tiles_at, T.tile_src.data(), T.tile_src.size() * sizeof(uint32_t));
     each([&](int i) {
         const TiffPlan& P = plans[i];
         uint8_t*        p = st.pinned + at[i];
@@ -976,7 +983,8 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
     HIP_OK(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, stream));
     if (timed) HIP_OK(hipEventRecord(t.start, stream));
     HIP_OK(launch_tiff((const TiffJob*)st.dev, (const TiffStrip*)(st.dev + strips_at), (int)strips.size(),
-                       (const TiffBand*)(st.dev + bands_at), (int)bands.size(), stream_error(ctx, stream), stream));
+                       (const TiffBand*)(st.dev + bands_at), (int)bands.size(), (const TiffTileBand*)(st.dev + tbands_at),
+                       (int)T.tbands.size(), (const uint32_t*)(st.dev + tiles_at), stream_error(ctx, stream), stream));
     if (timed) {
         HIP_OK(hipEventRecord(t.stop, stream));
         std::lock_guard<std::mutex> tl(ctx->mu);

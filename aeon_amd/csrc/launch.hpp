@@ -30,6 +30,7 @@ struct PixmapBand;
 struct TiffJob;
 struct TiffStrip;
 struct TiffBand;
+struct TiffTileBand;
 
 // augment_kernels.hip
 hipError_t launch_tiles(int km, int rm, bool tail, bool photo, const LaunchArgs& a, int grid, hipStream_t stream,
@@ -76,8 +77,9 @@ hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, i
 hipError_t launch_png(const PngJob* jobs, int n_jobs, int unfilter_lds, int32_t* error, hipStream_t stream);
 // pixmap_kernels.hip: pixmap_convert, one workgroup per band
 hipError_t launch_pixmap(const PixmapJob* jobs, const PixmapBand* bands, int n_bands, hipStream_t stream);
-// tiff_kernels.hip: tiff_expand, one wave per compressed strip, then tiff_convert, one workgroup per band
-hipError_t launch_tiff(const TiffJob* jobs, const TiffStrip* strips, int n_strips, const TiffBand* bands, int n_bands, int32_t* error,
-                       hipStream_t stream);
+// tiff_kernels.hip: tiff_expand, one wave per compressed strip or tile, then tiff_convert, one workgroup per band, and
+// tiff_convert_tiled, one per band of the tiled files (each launched only where its table holds work)
+hipError_t launch_tiff(const TiffJob* jobs, const TiffStrip* strips, int n_strips, const TiffBand* bands, int n_bands,
+                       const TiffTileBand* tbands, int n_tbands, const uint32_t* tile_src, int32_t* error, hipStream_t stream);
 
 } // namespace aeon_hip

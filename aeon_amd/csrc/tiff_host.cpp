@@ -1,5 +1,5 @@
 // tiff_host.cpp -- the TIFF half of image::extractor::extract / pixel_mask::extractor::extract (aeon
-// src/etl_image.cpp:83-99, src/etl_pixel_mask.cpp:30-53): classic TIFF files in strips, restated from the TIFF 6.0
+// src/etl_image.cpp:83-99, src/etl_pixel_mask.cpp:30-53): classic TIFF files in strips or tiles, restated from the TIFF 6.0
 // specification (DESIGN section 21 says which decode rules are pinned against libtiff and which are "parity
 // unpinned").  Two users: tiff_decode, the whole decode of one file on the calling thread (aeon_decode_tiff, and
 // the files the stage leaves to the host), and the host half of the TIFF stage (aeon_hip_decode_tiff_batch):
@@ -92,9 +92,11 @@ void parse(const void* data, size_t size, TiffPlan& P)
     if (ifd < 8 || ifd + 2 > size) bad("the IFD lies past the end of the file");
     const uint32_t ne = R.u16(ifd);
     if ((size_t)ne * 12 > size - ifd - 2) bad("the IFD lies past the end of the file");
-    enum { W, H, BPS, COMP, PHOTO, FILL, SOFF, ORIENT, SPP, RPS, SCNT, PLANAR, PRED, CMAP, TILEW, EXTRA, SFMT, NTAGS };
-    static const int ids[NTAGS] = {256, 257, 258, 259, 262, 266, 273, 274, 277, 278, 279, 284, 317, 320, 322, 338, 339};
+    enum { W, H, BPS, COMP, PHOTO, FILL, SOFF, ORIENT, SPP, RPS, SCNT, PLANAR, PRED, CMAP, TILEW, TILEL, TOFF, TCNT, EXTRA, SFMT, NTAGS };
+    static const int ids[NTAGS] = {256, 257, 258, 259, 262, 266, 273, 274, 277, 278, 279, 284, 317, 320, 322, 323, 324, 325, 338, 339};
     Tag tags[NTAGS];
+    bool tiled = false;
+    for (uint32_t e = 0; e < ne; e++) tiled = tiled || R.u16(ifd + 2 + 12 * (size_t)e) == 322;
     for (uint32_t e = 0; e < ne; e++) {
         const size_t   at = ifd + 2 + 12 * (size_t)e;
         const uint32_t tag = R.u16(at), type = R.u16(at + 2), count = R.u32(at + 4);
@@ -102,6 +104,7 @@ void parse(const void* data, size_t size, TiffPlan& P)
         for (int i = 0; i < NTAGS; i++)
             if (ids[i] == (int)tag) k = i;
         if (k < 0) continue;
+        if (!tiled && (k == TILEL || k == TOFF || k == TCNT)) continue; // a strip file's stray tile tags: not read at all
         if (type != 1 && type != 3 && type != 4) bad("tag " + std::to_string(tag) + " has type " + std::to_string(type));
         const uint64_t bytes = (uint64_t)count * (type == 1 ? 1 : type == 3 ? 2 : 4);
         size_t         where = at + 8;
@@ -111,7 +114,8 @@ void parse(const void* data, size_t size, TiffPlan& P)
         }
         tags[k] = Tag{type, count, where, true};
     }
-    if (tags[TILEW].present) unsupported("tiled files (TileWidth present) are");
+    if (tiled && !(tags[TILEL].present && tags[TOFF].present && tags[TCNT].present))
+        unsupported("tiled files (TileWidth present) without TileLength, TileOffsets and TileByteCounts are");
     if (!tags[W].present || !tags[H].present) bad("no ImageWidth / ImageLength");
     const uint32_t w = value(R, tags[W], 256, 0), h = value(R, tags[H], 257, 0);
     if (w < 1 || h < 1) bad("bad image size");
@@ -186,28 +190,47 @@ void parse(const void* data, size_t size, TiffPlan& P)
     P.file_channels = photo >= 2 ? 3 : 1;
     P.rowb = (size_t)w * spp * (bps / 8);
     uint32_t rps = value(R, tags[RPS], 278, h);
-    if (rps < 1) bad("RowsPerStrip 0");
-    if (rps > h) rps = h;
-    P.rps = rps;
-    const uint32_t ns = (h + rps - 1) / rps;
-    if (!tags[SOFF].present) bad("no StripOffsets");
-    if (tags[SOFF].count < ns) bad(std::to_string(tags[SOFF].count) + " strips where the geometry needs " + std::to_string(ns));
-    if (tags[SOFF].type == 1) bad("tag 273 has type 1");
-    P.offs = values(R, Tag{tags[SOFF].type, ns, tags[SOFF].at, true});
-    if (tags[SCNT].present) {
-        if (tags[SCNT].count < ns) bad("StripByteCounts holds " + std::to_string(tags[SCNT].count) + " counts for " + std::to_string(ns) + " strips");
-        if (tags[SCNT].type == 1) bad("tag 279 has type 1");
-        P.counts = values(R, Tag{tags[SCNT].type, ns, tags[SCNT].at, true});
+    uint32_t ns;
+    if (tiled) {
+        const uint32_t tw = value(R, tags[TILEW], 322, 0), tl = value(R, tags[TILEL], 323, 0);
+        if (tw < 16 || tw % 16) unsupported("TileWidth " + std::to_string(tw) + " (not a multiple of 16) is");
+        if (tl < 16 || tl % 16) unsupported("TileLength " + std::to_string(tl) + " (not a multiple of 16) is");
+        if ((uint64_t)tw * tl > kTiffMaxPixels) unsupported("tiles above 2^28 pixels are");
+        P.tw = tw, P.tl = tl, P.tacross = (w - 1) / tw + 1, P.tdown = (h - 1) / tl + 1;
+        const uint64_t nt = (uint64_t)P.tacross * P.tdown;
+        if (tags[TOFF].count != nt) bad(std::to_string(tags[TOFF].count) + " tiles where the geometry needs " + std::to_string(nt));
+        if (tags[TCNT].count != nt) bad("TileByteCounts holds " + std::to_string(tags[TCNT].count) + " counts for " + std::to_string(nt) + " tiles");
+        if (tags[TOFF].type == 1) bad("tag 324 has type 1");
+        if (tags[TCNT].type == 1) bad("tag 325 has type 1");
+        ns      = (uint32_t)nt;
+        rps     = std::min(tl, h);
+        P.offs   = values(R, tags[TOFF]);
+        P.counts = values(R, tags[TCNT]);
     } else {
-        if (ns != 1 || P.comp != kTfNone) bad("no StripByteCounts");
-        P.counts.assign(1, (uint32_t)std::min<uint64_t>(P.rowb * h, UINT32_MAX));
+        if (rps < 1) bad("RowsPerStrip 0");
+        if (rps > h) rps = h;
+        ns = (h + rps - 1) / rps;
+        if (!tags[SOFF].present) bad("no StripOffsets");
+        if (tags[SOFF].count < ns) bad(std::to_string(tags[SOFF].count) + " strips where the geometry needs " + std::to_string(ns));
+        if (tags[SOFF].type == 1) bad("tag 273 has type 1");
+        P.offs = values(R, Tag{tags[SOFF].type, ns, tags[SOFF].at, true});
+        if (tags[SCNT].present) {
+            if (tags[SCNT].count < ns) bad("StripByteCounts holds " + std::to_string(tags[SCNT].count) + " counts for " + std::to_string(ns) + " strips");
+            if (tags[SCNT].type == 1) bad("tag 279 has type 1");
+            P.counts = values(R, Tag{tags[SCNT].type, ns, tags[SCNT].at, true});
+        } else {
+            if (ns != 1 || P.comp != kTfNone) bad("no StripByteCounts");
+            P.counts.assign(1, (uint32_t)std::min<uint64_t>(P.rowb * h, UINT32_MAX));
+        }
     }
+    P.rps = rps;
+    // every strip's (tile's) extent, and the first bytes of a compressed one
     for (uint32_t s = 0; s < ns; s++) {
-        const std::string which = "strip " + std::to_string(s);
-        const uint64_t    rows = std::min<uint32_t>(rps, h - s * rps), need = rows * P.rowb;
+        const std::string which = (tiled ? "tile " : "strip ") + std::to_string(s);
+        const uint64_t    need = tiled ? P.tile_bytes() : std::min<uint32_t>(rps, h - s * rps) * (uint64_t)P.rowb;
         if (P.offs[s] > size || P.counts[s] > size - P.offs[s]) bad(which + " lies past the end of the file");
         const uint8_t* p = d + P.offs[s];
-        if (P.comp == kTfNone && P.counts[s] < need) bad(which + " holds fewer bytes than its rows");
+        if (P.comp == kTfNone && P.counts[s] < need) bad(which + (tiled ? " holds fewer bytes than a tile" : " holds fewer bytes than its rows"));
         if (P.comp == kTfLzw) {
             if (P.counts[s] < 2) bad(which + ": the LZW data ends before its first code");
             if (p[0] != 0x80 || (p[1] & 0x80)) unsupported("old-style LZW (codes LSB first; " + which + " does not start with ClearCode) is");
@@ -331,6 +354,11 @@ bool tiff_sniff(const void* data, size_t size) { return sniff((const uint8_t*)da
 bool tiff_route(const TiffPlan& P, size_t size)
 {
     if (size >= ((size_t)1 << 31) || P.rowb * (size_t)P.h >= ((size_t)1 << 31)) return false;
+    if (P.tw) {
+        if ((uint64_t)P.offs.size() * ((P.tile_bytes() + 15) & ~(size_t)15) >= ((uint64_t)1 << 31)) return false;
+        if ((size_t)P.tw * P.spp * (P.bps / 8) > (size_t)kTiffBandBytes) return false; // one tile row is the least a band stages
+        return !((P.comp == kTfLzw || P.comp == kTfPackBits) && P.tile_bytes() > (size_t)kTiffStripCap);
+    }
     if ((P.comp == kTfLzw || P.comp == kTfPackBits) && (size_t)P.rps * P.rowb > (size_t)kTiffStripCap) return false;
     return true;
 }
@@ -354,8 +382,54 @@ bool tiff_routed(const void* data, size_t size)
     if (P.comp != kTfDeflate) return true;
     uint64_t comp_bytes = 0;
     for (uint32_t c : P.counts) comp_bytes += c;
-    return comp_bytes * kTiffDecoderDeflateMinRatio <= (uint64_t)P.rowb * (uint64_t)P.h;
+    const uint64_t decoded = P.tw ? (uint64_t)P.tile_bytes() * P.offs.size() : (uint64_t)P.rowb * (uint64_t)P.h;
+    return comp_bytes * kTiffDecoderDeflateMinRatio <= decoded;
 }
+
+namespace {
+
+// Strip or tile s decoded: `need` bytes, in the file itself or in buf
+const uint8_t* unit_bytes(const TiffPlan& P, const uint8_t* d, size_t s, size_t need, std::vector<uint8_t>& buf, const std::string& which)
+{
+    const uint8_t* src = d + P.offs[s];
+    if (P.comp == kTfNone) return src;
+    buf.resize(need);
+    if (P.comp == kTfLzw) lzw_host(src, P.counts[s], buf.data(), need, which);
+    else if (P.comp == kTfPackBits) packbits_host(src, P.counts[s], buf.data(), need, which);
+    else deflate_host(src, P.counts[s], buf.data(), need, which);
+    return buf.data();
+}
+
+// ns stored samples at p made native, the predictor undone from the first pixel on
+void native_row(const TiffPlan& P, const uint8_t* p, size_t ns, uint16_t* row)
+{
+    for (size_t i = 0; i < ns; i++)
+        row[i] = P.bps == 8 ? p[i] : P.big ? (uint16_t)(p[2 * i] << 8 | p[2 * i + 1]) : (uint16_t)(p[2 * i] | p[2 * i + 1] << 8);
+    if (P.pred == 2) {
+        const uint32_t mask = P.bps == 8 ? 255 : 65535;
+        for (size_t i = (size_t)P.spp; i < ns; i++) row[i] = (uint16_t)((row[i] + row[i - P.spp]) & mask);
+    }
+}
+
+// A tiled file: one row of tiles at a time, every tile's live rows put side by side (the predictor runs along
+// each tile's own rows), then the image's rows emitted up to w.
+void decode_tiles(const TiffPlan& P, int mode, const uint8_t* d, uint8_t* dst, size_t stride)
+{
+    const size_t          seg = (size_t)P.tw * P.spp, segb = seg * (P.bps / 8), pitch = seg * P.tacross;
+    std::vector<uint8_t>  buf;
+    std::vector<uint16_t> rows(pitch * std::min<size_t>(P.tl, (size_t)P.h));
+    for (uint32_t ty = 0; ty < P.tdown; ty++) {
+        const int y0 = (int)(ty * P.tl), live = std::min<int>((int)P.tl, P.h - y0);
+        for (uint32_t tx = 0; tx < P.tacross; tx++) {
+            const size_t   t = (size_t)ty * P.tacross + tx;
+            const uint8_t* src = unit_bytes(P, d, t, P.tile_bytes(), buf, "tile " + std::to_string(t));
+            for (int r = 0; r < live; r++) native_row(P, src + (size_t)r * segb, seg, rows.data() + (size_t)r * pitch + tx * seg);
+        }
+        for (int r = 0; r < live; r++) emit_row(P, mode, rows.data() + (size_t)r * pitch, dst + (size_t)(y0 + r) * stride);
+    }
+}
+
+} // namespace
 
 void tiff_decode(const void* data, size_t size, int mode, void* dst_, size_t stride, int* out_elem_bytes)
 {
@@ -365,29 +439,15 @@ void tiff_decode(const void* data, size_t size, int mode, void* dst_, size_t str
     if (out_elem_bytes) *out_elem_bytes = P.elem_bytes;
     const uint8_t*        d = (const uint8_t*)data;
     uint8_t*              dst = (uint8_t*)dst_;
+    if (P.tw) return decode_tiles(P, mode, d, dst, stride);
     const size_t          ns_row = (size_t)P.w * P.spp;
     std::vector<uint8_t>  buf;
     std::vector<uint16_t> row(ns_row);
     for (size_t s = 0; s < P.offs.size(); s++) {
-        const std::string which = "strip " + std::to_string(s);
-        const int         y0 = (int)(s * P.rps), rows = std::min<int>((int)P.rps, P.h - y0);
-        const size_t      need = (size_t)rows * P.rowb;
-        const uint8_t*    src = d + P.offs[s];
-        if (P.comp != kTfNone) {
-            buf.resize(need);
-            if (P.comp == kTfLzw) lzw_host(src, P.counts[s], buf.data(), need, which);
-            else if (P.comp == kTfPackBits) packbits_host(src, P.counts[s], buf.data(), need, which);
-            else deflate_host(src, P.counts[s], buf.data(), need, which);
-            src = buf.data();
-        }
+        const int      y0 = (int)(s * P.rps), rows = std::min<int>((int)P.rps, P.h - y0);
+        const uint8_t* src = unit_bytes(P, d, s, (size_t)rows * P.rowb, buf, "strip " + std::to_string(s));
         for (int r = 0; r < rows; r++) {
-            const uint8_t* p = src + (size_t)r * P.rowb;
-            for (size_t i = 0; i < ns_row; i++)
-                row[i] = P.bps == 8 ? p[i] : P.big ? (uint16_t)(p[2 * i] << 8 | p[2 * i + 1]) : (uint16_t)(p[2 * i] | p[2 * i + 1] << 8);
-            if (P.pred == 2) {
-                const uint32_t mask = P.bps == 8 ? 255 : 65535;
-                for (size_t i = (size_t)P.spp; i < ns_row; i++) row[i] = (uint16_t)((row[i] + row[i - P.spp]) & mask);
-            }
+            native_row(P, src + (size_t)r * P.rowb, ns_row, row.data());
             emit_row(P, mode, row.data(), dst + (size_t)(y0 + r) * stride);
         }
     }
@@ -397,6 +457,7 @@ size_t tiff_scratch_bytes(const TiffPlan& P)
 {
     if (P.comp == kTfNone) return 0;
     size_t total = 16; // (the band loads' aligned over-read behind the last strip)
+    if (P.tw) return total + P.offs.size() * ((P.tile_bytes() + 15) & ~(size_t)15);
     for (size_t s = 0; s < P.offs.size(); s++) {
         const size_t rows = std::min<size_t>(P.rps, (size_t)P.h - s * P.rps);
         total += (rows * P.rowb + 15) & ~(size_t)15;
@@ -404,13 +465,45 @@ size_t tiff_scratch_bytes(const TiffPlan& P)
     return total;
 }
 
-void tiff_stage(const void* data, size_t size, int mode, const TiffPlan& P, int job, TiffJob& J, std::vector<TiffStrip>& strips,
-                std::vector<TiffBand>& bands, uint8_t* file_dst)
+namespace {
+
+// A tiled file's tables: every compressed tile a strip of tiff_expand's, tile after tile in the scratch; every row
+// of tiles cut into bands of at most kTiffBandBytes -- all its tiles across times the rows that fit, or, where one
+// row of them is too wide, equal runs of tiles across, row by row.
+void stage_tiles(const TiffPlan& P, int job, TiffJob& J, TiffTables& T)
 {
+    J.tw = (int32_t)P.tw, J.tl = (int32_t)P.tl, J.tacross = (int32_t)P.tacross, J.tile0 = (int32_t)T.tile_src.size();
+    const size_t need = P.tile_bytes(), slot = (need + 15) & ~(size_t)15, segb = need / P.tl;
+    for (size_t t = 0; t < P.offs.size(); t++) {
+        if (P.comp != kTfNone) T.strips.push_back(TiffStrip{job, P.comp, P.offs[t], P.counts[t], 0, (int32_t)P.tl, (uint32_t)need, 0, t * slot, 0});
+        T.tile_src.push_back(P.comp != kTfNone ? (uint32_t)(t * slot) : P.offs[t]);
+    }
+    const uint32_t most = (uint32_t)((size_t)kTiffBandBytes / segb), runs = (P.tacross + most - 1) / most, nt = (P.tacross + runs - 1) / runs;
+    const int      band_rows = std::max<int>(1, (int)((size_t)kTiffBandBytes / (nt * segb)));
+    for (uint32_t ty = 0; ty < P.tdown; ty++) {
+        const int y0 = (int)(ty * P.tl), live = std::min<int>((int)P.tl, P.h - y0);
+        for (int r = 0; r < live; r += band_rows)
+            for (uint32_t tx = 0; tx < P.tacross; tx += nt)
+                T.tbands.push_back(TiffTileBand{job, y0 + r, std::min(band_rows, live - r), (int32_t)std::min(nt, P.tacross - tx),
+                                                (int32_t)(ty * P.tacross + tx), r, (int32_t)(tx * P.tw), 0});
+    }
+}
+
+} // namespace
+
+void tiff_stage(const void* data, size_t size, int mode, const TiffPlan& P, int job, TiffJob& J, TiffTables& T, uint8_t* file_dst)
+{
+    std::vector<TiffStrip>& strips = T.strips;
+    std::vector<TiffBand>&  bands = T.bands;
     std::memset(&J, 0, sizeof(J));
     J.w = P.w, J.h = P.h, J.spp = P.spp, J.bps = P.bps, J.photo = P.photo, J.pred = P.pred, J.big = P.big, J.comp = P.comp;
     J.mode = mode, J.elem_bytes = P.elem_bytes, J.rowb = (int32_t)P.rowb;
     std::memcpy(J.table, P.table, sizeof(J.table));
+    if (P.tw) {
+        stage_tiles(P, job, J, T);
+        if (file_dst) std::memcpy(file_dst, data, size);
+        return;
+    }
     const int band_rows = P.rowb <= (size_t)kTiffBandBytes ? (int)((size_t)kTiffBandBytes / P.rowb) : 1;
     size_t    soff = 0;
     for (size_t s = 0; s < P.offs.size(); s++) {
@@ -433,17 +526,17 @@ int tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t 
     TiffPlan P;
     tiff_plan(data, size, mode, P);
     if (!P.route) return 0;
-    TiffJob                J;
-    std::vector<TiffStrip> strips;
-    std::vector<TiffBand>  bands;
-    std::vector<uint64_t>  file((size + 15) / 16 * 2 + 2, 0), raw(tiff_scratch_bytes(P) / 8 + 2, 0); // 16-byte aligned, zero padding behind
-    tiff_stage(data, size, mode, P, 0, J, strips, bands, (uint8_t*)file.data());
+    TiffJob               J;
+    TiffTables            T;
+    std::vector<uint64_t> file((size + 15) / 16 * 2 + 2, 0), raw(tiff_scratch_bytes(P) / 8 + 2, 0); // 16-byte aligned, zero padding behind
+    tiff_stage(data, size, mode, P, 0, J, T, (uint8_t*)file.data());
     J.src = (uint64_t)file.data(), J.raw = (uint64_t)raw.data(), J.out = (uint64_t)dst, J.stride = (int32_t)stride;
     std::vector<tiffdev::ExpandMem> mem(1);
-    for (const TiffStrip& T : strips)
-        if (!tiffdev::expand_strip(J, T, mem[0])) return -1;
+    for (const TiffStrip& S : T.strips)
+        if (!tiffdev::expand_strip(J, S, mem[0])) return -1;
     std::vector<uint32_t> tab(256), lds(kTiffBandBytes / 4 + 2);
-    for (const TiffBand& B : bands) tiffdev::convert_band(J, B, tab.data(), (uint8_t*)lds.data());
+    for (const TiffBand& B : T.bands) tiffdev::convert_band(J, B, tab.data(), (uint8_t*)lds.data());
+    for (const TiffTileBand& B : T.tbands) tiffdev::convert_tiled_band(J, B, T.tile_src.data(), tab.data(), (uint8_t*)lds.data());
     return 1;
 }
 

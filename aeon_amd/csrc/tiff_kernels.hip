@@ -1,6 +1,6 @@
-// tiff_kernels.hip -- the TIFF stage's two kernels; their logic is tiff_strips.hpp, shared with the
+// tiff_kernels.hip -- the TIFF stage's three kernels; their logic is tiff_strips.hpp, shared with the
 // host emulation.
-//   tiff_expand:  one wave (a workgroup of 64) per compressed strip, through the call's strip table (sorted by
+//   tiff_expand:  one wave (a workgroup of 64) per compressed strip or tile, through the call's strip table (sorted by
 //                 compressed size, largest first).  Deflate strips go through pngdev::inflate_file as they are;
 //                 LZW strips through a wave-uniform MSB-first bit reader and a table of ranges of the strip's
 //                 own output in LDS, every code emitted as a match copy by all lanes; PackBits strips through a
@@ -10,6 +10,11 @@
 //                 by aligned dword loads from the scratch (or from the file itself when it is uncompressed),
 //                 16-bit samples made native, predictor 2 undone by a wave scan per row, then four output bytes
 //                 per lane and step.
+//   tiff_convert_tiled: one workgroup of 256 per band of a tiled file -- rows inside one row of tiles times a run
+//                 of tiles across -- through the call's tiled band table: the waves stage whole tile-row segments
+//                 side by side in LDS (16 bytes per lane from the scratch, realigned dwords from an uncompressed
+//                 file), make each native and undo its predictor by a wave scan, then the workgroup writes the
+//                 de-tiled rows as tiff_convert does, clipped at the image's edges.
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
@@ -34,13 +39,23 @@ __global__ __launch_bounds__(kTiffLanes) void tiff_convert(const TiffJob* __rest
     tiffdev::convert_band(jobs[B.job], B, tab, band);
 }
 
+__global__ __launch_bounds__(kTiffLanes) void tiff_convert_tiled(const TiffJob* __restrict__ jobs, const TiffTileBand* __restrict__ bands,
+                                                                 const uint32_t* __restrict__ tile_src)
+{
+    __shared__ uint32_t                             tab[256];
+    __shared__ __attribute__((aligned(16))) uint8_t band[kTiffBandBytes];
+    const TiffTileBand B = bands[blockIdx.x];
+    tiffdev::convert_tiled_band(jobs[B.job], B, tile_src, tab, band);
+}
+
 } // namespace
 
-hipError_t launch_tiff(const TiffJob* jobs, const TiffStrip* strips, int n_strips, const TiffBand* bands, int n_bands, int32_t* error,
-                       hipStream_t stream)
+hipError_t launch_tiff(const TiffJob* jobs, const TiffStrip* strips, int n_strips, const TiffBand* bands, int n_bands,
+                       const TiffTileBand* tbands, int n_tbands, const uint32_t* tile_src, int32_t* error, hipStream_t stream)
 {
     if (n_strips > 0) tiff_expand<<<n_strips, 64, 0, stream>>>(jobs, strips, error);
     if (n_bands > 0) tiff_convert<<<n_bands, kTiffLanes, 0, stream>>>(jobs, bands);
+    if (n_tbands > 0) tiff_convert_tiled<<<n_tbands, kTiffLanes, 0, stream>>>(jobs, tbands, tile_src);
     return hipGetLastError();
 }
 

@@ -1,9 +1,10 @@
 // tiff_strips.hpp -- the TIFF stage's per-wave and per-band logic (tiff_kernels.hip), written once for the device
-// and for the host: tiff_expand runs expand_strip on the 64 lanes of one wave, tiff_convert runs convert_band on
-// the 256 lanes of a workgroup; tiff_host.cpp's tiff_gpu_emulate runs the same code with every lane loop walked
-// serially (the PNG_* lane macros of png_inflate.hpp in the wave code, the PM_* ones of pixmap_rows.hpp in the
-// band code), so the CPU tests and the sanitizer program cover what the kernels run.  The one piece written
-// twice is the predictor's scan (scan_rows): shuffles across a wave on the device, a running sum on the host.
+// and for the host: tiff_expand runs expand_strip on the 64 lanes of one wave, tiff_convert runs convert_band and
+// tiff_convert_tiled convert_tiled_band on the 256 lanes of a workgroup; tiff_host.cpp's tiff_gpu_emulate runs the
+// same code with every lane loop walked serially (the PNG_* lane macros of png_inflate.hpp in the wave code, the
+// PM_* ones of pixmap_rows.hpp in the band code), so the CPU tests and the sanitizer program cover what the
+// kernels run.  The one piece written twice is the predictor's scan (scan_rows, finish_segment): shuffles across
+// a wave on the device, a running sum on the host.
 // Everything outside a lane loop is wave-uniform.  See DESIGN section 21.
 #pragma once
 #include <stddef.h>
@@ -313,6 +314,140 @@ PM_FN void convert_band(const TiffJob& J, const TiffBand& B, uint32_t* tab, uint
     const uint32_t P = piece_pixels((J.bps >> 3) * J.spp);
     for (uint32_t p0 = 0; p0 < (uint32_t)J.w; p0 += P)
         convert_piece(J, B, p0, (uint32_t)J.w - p0 < P ? (uint32_t)J.w - p0 : P, tab, lds, carry);
+}
+
+// ---- tiff_convert_tiled: one band of a tiled file -----------------------------------------------------------
+// A segment is one row of one tile: TileWidth pixels, a multiple of 16 bytes, so every segment of a tile lies at the
+// tile's own offset mod 16 -- 0 in the scratch, anything for an uncompressed tile in the file.  A band is `rows`
+// image rows times `nt` tiles across.  Its segments go into LDS side by side, segment (r, t) at (r * nt + t) * segment
+// bytes with its first byte on a 16-byte boundary: the LDS then holds `rows` ordinary rows of nt * TileWidth pixels
+// and the output pass needs no tile arithmetic at all.  The waves deal the segments out among themselves; the wave
+// that staged a segment also finishes it (byte order, predictor), since the predictor restarts in every segment.
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TT_WAVE ((int)threadIdx.x >> 6)
+#define TT_WAVES (kTiffLanes / 64)
+#define TT_LANE ((int)threadIdx.x & 63)
+#define TT_LANES 64
+#else
+#define TT_WAVE 0
+#define TT_WAVES 1
+#define TT_LANE 0
+#define TT_LANES 1
+#endif
+
+// Bytes sh.. of the 8 that lo and hi hold (sh 1..3)
+PM_FN uint32_t bytes_from(uint32_t lo, uint32_t hi, uint32_t sh) { return lo >> (8 * sh) | hi << (32 - 8 * sh); }
+
+// One segment from global memory into LDS: 16 bytes per lane and step where the source is 16-byte aligned, else
+// dwords put together from the two aligned words that hold them (the last lane reads at most 4 bytes past the
+// segment: inside the 16 bytes of padding behind every file and scratch).
+PM_FN void stage_segment(uint64_t g, uint8_t* seg, uint32_t segb)
+{
+    if ((g & 15) == 0) {
+        const PM_GLOBAL pngdev::u32x4* gq = (const PM_GLOBAL pngdev::u32x4*)g;
+        pngdev::u32x4*                 lq = (pngdev::u32x4*)seg;
+        for (uint32_t i = TT_LANE; i < segb / 16; i += TT_LANES) lq[i] = gq[i];
+        return;
+    }
+    const uint32_t            sh = (uint32_t)(g & 3);
+    const PM_GLOBAL uint32_t* gw = (const PM_GLOBAL uint32_t*)(g - sh);
+    uint32_t*                 lw = (uint32_t*)seg;
+    for (uint32_t i = TT_LANE; i < segb / 4; i += TT_LANES) lw[i] = sh ? bytes_from(gw[i], gw[i + 1], sh) : gw[i];
+}
+
+// A staged segment's samples made native and its predictor undone, in place: every sample the sum of the
+// segment's samples of its channel up to it, from zero at the tile's left edge.
+#if defined(__HIP_DEVICE_COMPILE__)
+// The wave's lanes on 64 consecutive pixels: an inclusive scan across the lanes per channel, the running sums
+// carried from chunk to chunk in registers.
+__device__ __forceinline__ void finish_segment(uint8_t* seg, int tw, int spp, int bs, bool swap, bool pred)
+{
+    const int lane = TT_LANE;
+    uint32_t  sum[4] = {0, 0, 0, 0};
+    for (int x0 = 0; x0 < tw; x0 += 64) {
+        const int  px = x0 + lane;
+        const bool in = px < tw;
+        uint8_t*   s  = seg + (size_t)px * spp * bs;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            if (c >= spp) continue;
+            uint32_t v = 0;
+            if (in) v = bs == 2 ? (uint32_t)s[2 * c + (swap ? 1 : 0)] | (uint32_t)s[2 * c + (swap ? 0 : 1)] << 8 : s[c];
+            if (pred) {
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = __shfl_up(v, d, 64);
+                    if (lane >= d) v += up;
+                }
+                v += sum[c];
+                sum[c] = __shfl(v, 63, 64); // (lanes past the segment hold zeros: lane 63 has the chunk's total)
+            }
+            if (in) {
+                s[bs * c] = (uint8_t)v;
+                if (bs == 2) s[2 * c + 1] = (uint8_t)(v >> 8);
+            }
+        }
+    }
+}
+#else
+inline void finish_segment(uint8_t* seg, int tw, int spp, int bs, bool swap, bool pred)
+{
+    uint32_t sum[4] = {0, 0, 0, 0};
+    for (int px = 0; px < tw; px++)
+        for (int c = 0; c < spp; c++) {
+            uint8_t* s = seg + ((size_t)px * spp + c) * bs;
+            uint32_t v = bs == 2 ? (uint32_t)s[swap ? 1 : 0] | (uint32_t)s[swap ? 0 : 1] << 8 : s[0];
+            if (pred) v = sum[c] += v;
+            s[0] = (uint8_t)v;
+            if (bs == 2) s[1] = (uint8_t)(v >> 8);
+        }
+}
+#endif
+
+// One tiled band.  tile_src: the call's table of tile sources; tab: 256 words; lds: kTiffBandBytes bytes, 16-byte aligned.
+PM_FN void convert_tiled_band(const TiffJob& J, const TiffTileBand& B, const uint32_t* tile_src, uint32_t* tab, uint8_t* lds)
+{
+    if (J.photo == 3)
+        for (int i = PM_LANE0; i < 256; i += PM_LANE_STEP) tab[i] = J.table[i];
+    const int      bs = J.bps >> 3, spp = J.spp, bpp = bs * spp, nt = B.nt, rows = B.rows;
+    const uint32_t segb = (uint32_t)J.tw * bpp, nseg = (uint32_t)rows * nt, pitch = (uint32_t)nt * segb;
+    const uint64_t base = J.comp == kTfNone ? J.src : J.raw;
+    const bool     swap = bs == 2 && J.big, pred = J.pred == 2;
+    const PM_GLOBAL uint32_t* from = (const PM_GLOBAL uint32_t*)tile_src + J.tile0 + B.tile;
+    for (uint32_t s = TT_WAVE; s < nseg; s += TT_WAVES) {
+        const uint32_t r = s / nt, t = s - r * nt;
+        stage_segment(base + from[t] + (uint64_t)(B.r0 + r) * segb, lds + (size_t)s * segb, segb);
+    }
+    if (swap || pred) {
+        PM_SYNC();
+        for (uint32_t s = TT_WAVE; s < nseg; s += TT_WAVES) finish_segment(lds + (size_t)s * segb, J.tw, spp, bs, swap, pred);
+    }
+    PM_SYNC();
+    // the rows of the band, clipped at the image's right edge (the band table clips at the bottom one): every lane
+    // four consecutive output bytes of a row per step, as convert_piece writes them
+    RowForm F;
+    F.photo = J.photo, F.bs = bs, F.bpp = bpp, F.bgr = J.mode == AEON_DECODE_BGR8, F.out16 = J.elem_bytes == 2;
+    const uint32_t opp = F.bgr ? 3 : F.out16 ? 2 : 1, p0 = (uint32_t)B.px0;
+    const uint32_t p1 = p0 + (uint32_t)nt * J.tw < (uint32_t)J.w ? p0 + (uint32_t)nt * J.tw : (uint32_t)J.w;
+    const uint32_t k0 = p0 * opp, n = (p1 - p0) * opp;
+    const uint32_t G = n / 4 + 2, total = (uint32_t)rows * G; // groups of a row: the head, the aligned dwords, the tail
+    for (uint32_t item = (uint32_t)PM_LANE0; item < total; item += PM_LANE_STEP) {
+        const uint32_t r = item / G, g = item - r * G;
+        const uint64_t da = J.out + (uint64_t)(B.y0 + (int64_t)r) * (uint64_t)J.stride + k0;
+        const uint32_t head = (uint32_t)(-da) & 3;
+        const uint32_t start = g ? head + 4 * (g - 1) : 0;
+        uint32_t       end   = g ? start + 4 : head;
+        if (end > n) end = n;
+        if (start >= end) continue;
+        const uint8_t* row = lds + (size_t)r * pitch;
+        uint32_t       v   = 0;
+        for (uint32_t j = start; j < end; j++) v |= out_byte(F, tab, row, p0, k0 + j) << (8 * (j - start));
+        PM_GLOBAL uint8_t* d = (PM_GLOBAL uint8_t*)(da + start);
+        if (end - start == 4 && g) *(PM_GLOBAL uint32_t*)d = v;
+        else
+            for (uint32_t j = 0; j < end - start; j++) d[j] = (uint8_t)(v >> (8 * j));
+    }
 }
 
 } // namespace tiffdev

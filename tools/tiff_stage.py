@@ -8,6 +8,9 @@ code, not the kernels under test).  Classes:
   gray16_deflate  512 x 512 16-bit gray (depth-like: a ramp with 6 bits of noise), Deflate + predictor 2, decoded at
                   ANYDEPTH; gray16_deflate_r3 / _r6 (not in the default list): the same with less noise, streams a third
                   and a sixth or less of the samples, for the crossover of the decoder's routing rule
+  pal_lzw_tiled      the pal_lzw masks in 128 x 128 LZW tiles (tiff_convert_tiled; pal_lzw is their strip twin)
+  rgb512_raw_tiled   512 x 512 RGB in 128 x 128 uncompressed tiles; rgb512_raw: the same images in strips of 5 rows
+  rgb512_deflate_tiled  the same in 128 x 128 Deflate tiles with predictor 2; rgb512_deflate: in strips of 5 rows
 Prints one JSON line per class: records/s, H2D bytes per record and, on the device route, the kernels' GPU time per
 record (aeon_hip_kernel_times, kind "png": the PNG, pixmap and TIFF decode kernels).  `--runs N` starts N fresh
 processes per class and route, alternating the routes, and prints min..max.
@@ -16,6 +19,7 @@ import argparse
 import io
 import json
 import os
+import struct
 import subprocess
 import sys
 import time
@@ -36,6 +40,43 @@ def _tiff(im, compression, predictor, rows):
     return buf.getvalue()
 
 
+def _tiled(a, photo, compression, predictor, tile=128, palette=None):
+    """`a` (HxW or HxWxS uint8, both multiples of `tile`) as a little-endian tiled file.  Pillow writes no tiles: every
+    tile is saved through it as a one-strip file, and that strip's bytes (libtiff's own LZW or Deflate) become the tile."""
+    from PIL import Image
+    h, w, spp = a.shape[0], a.shape[1], 1 if a.ndim == 2 else a.shape[2]
+    blobs = []
+    for y in range(0, h, tile):
+        for x in range(0, w, tile):
+            t = np.ascontiguousarray(a[y:y + tile, x:x + tile])
+            if compression is None:
+                blobs.append(t.tobytes())
+                continue
+            f = _tiff(Image.fromarray(t, "RGB" if spp == 3 else "L"), compression, predictor, tile)
+            ifd = struct.unpack_from("<I", f, 4)[0]
+            tags = {struct.unpack_from("<H", f, e)[0]: struct.unpack_from("<I", f, e + 8)[0]
+                    for e in range(ifd + 2, ifd + 2 + 12 * struct.unpack_from("<H", f, ifd)[0], 12)}
+            blobs.append(f[tags[273]:tags[273] + tags[279]])
+    comp = {None: 1, "tiff_lzw": 5, "tiff_adobe_deflate": 8}[compression]
+    tags = [(256, 4, [w]), (257, 4, [h]), (258, 3, [8] * spp), (259, 3, [comp]), (262, 3, [photo]), (277, 3, [spp]),
+            (317, 3, [2 if predictor else 1])] + ([(320, 3, palette)] if palette else []) + \
+           [(322, 3, [tile]), (323, 3, [tile]), (324, 4, None), (325, 4, [len(b) for b in blobs])]
+    body, offs = bytearray(8), []
+    for b in blobs:
+        offs.append(len(body))
+        body += b + b"\0" * (len(b) & 1)
+    ifd = struct.pack("<H", len(tags))
+    for t, ty, v in tags:
+        data = struct.pack("<" + "HI"[ty == 4] * len(v or offs), *(v or offs))
+        if len(data) > 4:
+            ifd += struct.pack("<HHII", t, ty, len(v or offs), len(body))
+            body += data
+        else:
+            ifd += struct.pack("<HHI", t, ty, len(v or offs)) + data.ljust(4, b"\0")
+    body[:8] = b"II" + struct.pack("<HI", 42, len(body))
+    return bytes(body + ifd + bytes(4))
+
+
 def _blobs(rng, side):
     cls = rng.integers(0, 5, (side // 64, side // 64)).astype(np.uint8)
     return np.roll(np.kron(cls, np.ones((64, 64), np.uint8)), int(rng.integers(0, 64)), axis=1)
@@ -51,10 +92,19 @@ def make_files(kind, n, distinct=32):
         if kind in ("rgb_raw", "rgb_lzw"):
             im = Image.fromarray(np.ascontiguousarray(A.synthetic_image(100 + i, 256, 256, 3)[:, :, ::-1]), "RGB")
             out.append(_tiff(im, None, False, 10) if kind == "rgb_raw" else _tiff(im, "tiff_lzw", True, 10))
-        elif kind == "pal_lzw":
-            im = Image.fromarray(_blobs(rng, 512), "P")
-            im.putpalette([int(v) for v in rng.integers(0, 256, 768)])
+        elif kind in ("pal_lzw", "pal_lzw_tiled"):
+            mask, pal = _blobs(rng, 512), [int(v) for v in rng.integers(0, 256, 768)]
+            if kind == "pal_lzw_tiled":  # (ColorMap: 3 x 256 shorts, plane after plane)
+                out.append(_tiled(mask, 3, "tiff_lzw", False, palette=[257 * pal[3 * i + c] for c in range(3) for i in range(256)]))
+                continue
+            im = Image.fromarray(mask, "P")
+            im.putpalette(pal)
             out.append(_tiff(im, "tiff_lzw", False, 16))
+        elif kind.startswith("rgb512"):
+            rgb = np.ascontiguousarray(A.synthetic_image(100 + i, 512, 512, 3)[:, :, ::-1])
+            compression, predictor = ("tiff_adobe_deflate", True) if "deflate" in kind else (None, False)
+            out.append(_tiled(rgb, 2, compression, predictor) if kind.endswith("_tiled") else
+                       _tiff(Image.fromarray(rgb, "RGB"), compression, predictor, 5))
         else:
             ramp = (np.add.outer(np.arange(512), np.arange(512)) * 37 + i * 101).astype(np.uint16)
             noise = {"gray16_deflate": 64, "gray16_deflate_r3": 6, "gray16_deflate_r6": 2}[kind]
@@ -64,7 +114,9 @@ def make_files(kind, n, distinct=32):
 
 
 MODE = {"rgb_raw": A.DECODE_BGR8, "rgb_lzw": A.DECODE_BGR8, "pal_lzw": A.DECODE_ANYDEPTH, "gray16_deflate": A.DECODE_ANYDEPTH,
-        "gray16_deflate_r3": A.DECODE_ANYDEPTH, "gray16_deflate_r6": A.DECODE_ANYDEPTH}
+        "gray16_deflate_r3": A.DECODE_ANYDEPTH, "gray16_deflate_r6": A.DECODE_ANYDEPTH, "pal_lzw_tiled": A.DECODE_ANYDEPTH,
+        "rgb512_raw": A.DECODE_BGR8, "rgb512_raw_tiled": A.DECODE_BGR8, "rgb512_deflate": A.DECODE_BGR8,
+        "rgb512_deflate_tiled": A.DECODE_BGR8}
 
 
 def run_stage(kind, route, n, windows, warmup):
