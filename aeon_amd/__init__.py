@@ -58,6 +58,11 @@ class ImgDesc(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class Region(ctypes.Structure):
+    """aeon_region: columns [x, x + w), rows [y, y + h) of an image."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32)]
+
+
 class AugParams(ctypes.Structure):
     """POD mirror of augment::image::params (aeon src/augment_image.hpp:99-119)."""
     _fields_ = [
@@ -231,6 +236,10 @@ def lib():
         L.aeon_decode_png.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
                                       P(ctypes.c_int)]
         L.aeon_hip_decode_jpeg_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc), vp, vp]
+        L.aeon_hip_decode_jpeg_region_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc), P(Region),
+                                                        vp, vp]
+        L.aeon_jpeg_region_plan.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(Region), P(ImgDesc), ctypes.c_int,
+                                            P(ctypes.c_int), P(ctypes.c_int32)]
         L.aeon_hip_decode_png_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ctypes.c_int), P(ImgDesc),
                                                 vp, vp]
         L.aeon_png_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int), P(ctypes.c_int64)]
@@ -617,6 +626,17 @@ def jpeg_info(data):
     return w.value, h.value, n.value
 
 
+def jpeg_region_plan(data, region=None, channels=3, desc=None):
+    """The block rectangle (first block column, first block row, block columns, block rows) of each component that
+    the region (x, y, w, h) of a JPEG file takes through the IDCT for a record of `channels` (aeon_jpeg_region_plan;
+    None: the whole image); zeros for a component the record does not need.  desc: checked as the decode call does."""
+    n, out = ctypes.c_int(), (ctypes.c_int32 * 16)()
+    r = ctypes.byref(Region(*[int(v) for v in region])) if region is not None else None
+    _check(lib().aeon_jpeg_region_plan(bytes(data), len(data), r, ctypes.byref(desc) if desc is not None else None,
+                                       int(channels), ctypes.byref(n), out))
+    return [tuple(out[4 * k:4 * k + 4]) for k in range(n.value)]
+
+
 def jpeg_entropy_decode(data):
     """Host-only Huffman decode of a JPEG file (aeon_jpeg_entropy_decode): (width, height,
     components, blocks, non-zero values, FNV-1a hash of the sparse coefficient stream)."""
@@ -982,13 +1002,23 @@ class Context:
                                           int(out_h), ctypes.c_void_p(out_ptr), int(item_stride),
                                           ctypes.c_void_p(stream or 0)))
 
-    def decode_jpeg_batch(self, files, descs, dst_ptr, stream=0):
+    def decode_jpeg_batch(self, files, descs, dst_ptr, stream=0, regions=None):
         """image::extractor::extract of JPEG files into device memory (aeon_hip_decode_jpeg_batch):
         files = list of bytes (or a JpegFiles, marshalled once), descs[i] = where record i goes (HWC,
-        channels 3 = BGR / 1 = gray)."""
+        channels 3 = BGR / 1 = gray).  regions (aeon_hip_decode_jpeg_region_batch): per file (x, y, w, h), the part
+        of the image that record i -- of exactly w x h -- holds, or None for the whole image."""
         jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
         n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
         d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
+        if regions is not None:
+            if len(regions) != n:
+                raise ValueError(f"{len(regions)} regions for {n} files")
+            whole = lambda i: (0, 0) + jpeg_info(jf.bufs[i])[:2]
+            r = (Region * max(n, 1))(*[Region(*[int(v) for v in (whole(i) if g is None else g)])
+                                       for i, g in enumerate(regions)])
+            _check(lib().aeon_hip_decode_jpeg_region_batch(self._h, n, ptrs, sizes, d, r, ctypes.c_void_p(dst_ptr),
+                                                           ctypes.c_void_p(stream or 0)))
+            return
         _check(lib().aeon_hip_decode_jpeg_batch(self._h, n, ptrs, sizes, d, ctypes.c_void_p(dst_ptr),
                                                 ctypes.c_void_p(stream or 0)))
 

@@ -1107,8 +1107,9 @@ int aeon_hip_video_batch(aeon_hip_ctx* ctx, int n, const int32_t* frame_counts, 
     });
 }
 
-int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
-                               const aeon_img_desc* descs, void* dst_base, void* stream)
+int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                      const aeon_img_desc* descs, const aeon_region* regions, void* dst_base,
+                                      void* stream)
 {
     return guarded([&] {
         if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
@@ -1126,7 +1127,7 @@ int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data
                 t = take_timer(ctx, kTimerJpeg, px);
             }
         }
-        jpeg_decode_batch(ctx->jpeg, n, data, sizes, descs, dst_base, stream_error(ctx, (hipStream_t)stream), (hipStream_t)stream,
+        jpeg_decode_batch(ctx->jpeg, n, data, sizes, descs, regions, dst_base, stream_error(ctx, (hipStream_t)stream), (hipStream_t)stream,
                           timed ? t.start : nullptr,
                           timed ? t.stop : nullptr);
         if (timed) {
@@ -1135,6 +1136,12 @@ int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data
         }
         return 0;
     });
+}
+
+int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                               const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return aeon_hip_decode_jpeg_region_batch(ctx, n, data, sizes, descs, nullptr, dst_base, stream);
 }
 
 int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx* ctx, int* lanes)

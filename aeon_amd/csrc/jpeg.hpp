@@ -39,8 +39,14 @@ void       jpeg_state_destroy(JpegState* s);
 
 // The host functions of the stage (jpeg_host.cpp).  jpeg_decode_batch: n files decoded into the records at
 // dst_base on `stream`; `error` is the stream's device error word, start / stop optional timing events.
+// regions (may be null: every file whole): the part of file i that record i holds (aeon_hip_decode_jpeg_region_batch).
 void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
-                       void* dst_base, int32_t* error, ihipStream_t* stream, ihipEvent_t* start, ihipEvent_t* stop);
+                       const aeon_region* regions, void* dst_base, int32_t* error, ihipStream_t* stream,
+                       ihipEvent_t* start, ihipEvent_t* stop);
+// the block rectangle of each component that a region of a file takes (aeon_jpeg_region_plan, no device): out =
+// per component bx, by, bw, bh (a component the record does not need: zeros); validates as the decode call does
+void jpeg_region_plan(const void* data, size_t size, const aeon_region* region, const aeon_img_desc* desc, int out_cn,
+                      int* ncomp, int32_t out[16]);
 // header and entropy probes of one file, no device involved (aeon_jpeg_info, aeon_jpeg_entropy_decode,
 // aeon_jpeg_host_stage)
 void jpeg_info(const void* data, size_t size, int* w, int* h, int* ncomp);
@@ -77,18 +83,25 @@ enum JpegColorSpace : int32_t {
     CS_YCCK = 4, // 4 components, any other Adobe transform
 };
 
-// One file of a decode call, as the kernels see it (device addresses).
+// One file of a decode call, as the kernels see it (device addresses).  The record is the region (ox, oy, ow, oh)
+// of the image (the whole image: 0, 0, W, H); of each component only the block rectangle (rx, ry, rw, rh) that the
+// region's upsampling reads goes through the IDCT, and the component's plane holds that rectangle alone.
 struct alignas(16) JpegImage {
-    uint64_t blocks[kJpegMaxComp]; // JpegBlock[bh][bw] per component
+    uint64_t blocks[kJpegMaxComp]; // JpegBlock per component: [bh][bw] (host-decoded files), [rh][rw] (GPU-decoded)
     uint64_t values;               // int16 coefficient values (sparse stream: host-decoded files)
-    uint64_t dvals[kJpegMaxComp];  // GPU-decoded files: 64 int16 per block (zigzag order, the mask's bits valid), else 0
-    uint64_t planes[kJpegMaxComp]; // IDCT output per component: (bw*8) x (bh*8) uint8, row pitch bw*8
+    uint64_t dvals[kJpegMaxComp];  // GPU-decoded files: 64 int16 per block of the rectangle (zigzag order, the mask's bits valid), else 0
+    uint64_t planes[kJpegMaxComp]; // IDCT output per component: (rw*8) x (rh*8) uint8, row pitch rw*8
     uint64_t out;                  // decoded record: HWC uint8 (BGR or gray), out_stride bytes per row
-    int32_t  W, H, ncomp, out_cn, out_stride, hmax, vmax;
+    int32_t  W, H, ncomp, out_cn, out_stride, hmax, vmax; // W, H: the whole image's (the upsamplers' edge rules)
     int32_t  cs;                   // JpegColorSpace
     int32_t  bw[kJpegMaxComp], bh[kJpegMaxComp], dw[kJpegMaxComp], dh[kJpegMaxComp], hs[kJpegMaxComp], vs[kJpegMaxComp];
     int32_t  up[kJpegMaxComp];     // JpegUpsample of each component (host-chosen: no divisions per pixel)
     int32_t  hf[kJpegMaxComp], vf[kJpegMaxComp]; // hmax / hs, vmax / vs
+    int32_t  ox, oy, ow, oh;       // the record's origin in the image and its size
+    int32_t  rx[kJpegMaxComp], ry[kJpegMaxComp], rw[kJpegMaxComp], rh[kJpegMaxComp]; // block rectangle per component
+    // block (r, c) of the rectangle is blocks / dvals [sb0 + r * sbw + c]: the frame's grid for a host-decoded
+    // file (sbw = bw, sb0 = ry * bw + rx), the rectangle itself for a GPU-decoded one (sbw = rw, sb0 = 0)
+    int32_t  sbw[kJpegMaxComp], sb0[kJpegMaxComp];
     uint16_t q[kJpegMaxComp][64];  // quantisation table of each component, natural order
     uint16_t qz[kJpegMaxComp][64]; // the same in zigzag order (the dense path of jpeg_idct: 16-byte loads)
 };
@@ -108,12 +121,28 @@ enum JpegUpsample : int32_t {
     UP_BOX  = 4, // h2v1 / h2v2 / int_upsample box replication (other ratios, h2v1 / h2v2 components < 3 samples wide)
 };
 
-// IDCT work item: blocks [first, first + count) of component `comp` of image `img`.
+// The block rectangle of a component that the region (x, y, w, h) of the image reads: the samples under the
+// region's columns and rows, widened by the neighbours the component's upsampler filters with (one sample each
+// side along a row for h2v1 / h2v2, one row each side for h1v2 / h2v2), clipped to the component's dw x dh
+// samples -- at a true image edge the upsampler's edge rule applies, at a region edge inside the image the
+// real neighbour is there -- then the 8x8 blocks that cover them.
+struct JpegRect {
+    int32_t bx, by, bw, bh;
+};
+inline JpegRect jpeg_region_rect(int up, int hf, int vf, int dw, int dh, int x, int y, int w, int h)
+{
+    const int nx = up == UP_H2V1 || up == UP_H2V2, ny = up == UP_H1V2 || up == UP_H2V2;
+    const int x0 = x / hf - nx < 0 ? 0 : x / hf - nx, x1 = (x + w - 1) / hf + nx > dw - 1 ? dw - 1 : (x + w - 1) / hf + nx;
+    const int y0 = y / vf - ny < 0 ? 0 : y / vf - ny, y1 = (y + h - 1) / vf + ny > dh - 1 ? dh - 1 : (y + h - 1) / vf + ny;
+    return JpegRect{x0 >> 3, y0 >> 3, (x1 >> 3) - (x0 >> 3) + 1, (y1 >> 3) - (y0 >> 3) + 1};
+}
+
+// IDCT work item: blocks [first, first + count) of the rectangle of component `comp` of image `img` (row-major).
 struct JpegChunk {
     int32_t img, comp, first, count;
 };
 
-// Colour work item: output rows [y0, y0 + rows) of image `img`.
+// Colour work item: image rows [y0, y0 + rows) of image `img`, inside its record's rows.
 struct JpegRows {
     int32_t img, y0, rows, pad_;
 };
@@ -165,14 +194,17 @@ struct alignas(16) JpegHuffFile {
     uint64_t sub_seg;   // int32 per subsequence: its segment
     uint64_t tabs;      // JpegHuffTab[kJpegHuffSlots]: the scan's DC tables in slots 0-1, AC in 2-3
     uint64_t subs;      // JpegHuffSub[nsub] (device scratch)
-    uint64_t blocks[kJpegMaxComp]; // JpegBlock[bh][bw] per frame component (zeroed before the launch)
-    uint64_t dvals[kJpegMaxComp];  // 64 int16 per block per frame component
+    uint64_t blocks[kJpegMaxComp]; // JpegBlock[rh][bw] per frame component: its block rectangle (zeroed before the launch)
+    uint64_t dvals[kJpegMaxComp];  // 64 int16 per block of the rectangle
     uint64_t blk_tab[2]; // byte c (c < kHuffMaxBpm) = MCU block c: frame component | x << 2 | y << 4 |
                          // its DC table slot << 6 | (its AC table slot - 2) << 7
     int32_t  nseg, nsub, restart, n_mcu; // restart: MCUs per segment (n_mcu without DRI)
     int32_t  bpm, mcux, ncomp;           // a non-interleaved (grayscale) scan: bpm 1, mcux = blocks per row
     int32_t  truncated; // first segment whose data ends with the file, not a marker (reading past it is an error); -1: none
-    int32_t  bw[kJpegMaxComp], hs[kJpegMaxComp], vs[kJpegMaxComp];
+    int32_t  bw[kJpegMaxComp], hs[kJpegMaxComp], vs[kJpegMaxComp]; // bw: blocks per row of the rectangle
+    // the rectangle's first block column and row in the frame's grid, and its rows (jpeg_huff<LANES, true> stores
+    // only the blocks inside; the whole frame: 0, 0, bh)
+    int32_t  rx0[kJpegMaxComp], ry0[kJpegMaxComp], rh[kJpegMaxComp];
     int32_t  sub_bits;   // the file's subsequence length
     int32_t  data_words; // the data's 32-bit words (padding included)
 };

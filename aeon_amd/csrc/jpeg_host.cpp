@@ -995,6 +995,56 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
     return true;
 }
 
+// The region of file f that a record holds (null: the whole image), checked against the image and the record's
+// descriptor: the refusals of aeon_hip_decode_jpeg_region_batch, before anything is launched.
+aeon_region checked_region(const Frame& f, const aeon_region* region, const aeon_img_desc* d)
+{
+    const aeon_region r = region ? *region : aeon_region{0, 0, f.W, f.H};
+    const std::string name = "region (" + std::to_string(r.x) + ", " + std::to_string(r.y) + ", " + std::to_string(r.w) +
+                             ", " + std::to_string(r.h) + ")";
+    if (r.w <= 0 || r.h <= 0) bad(name + " is empty");
+    if (r.x < 0 || r.y < 0 || (int64_t)r.x + r.w > f.W || (int64_t)r.y + r.h > f.H)
+        bad(name + " reaches outside the " + std::to_string(f.W) + "x" + std::to_string(f.H) + " image");
+    if (!d) return r;
+    if (r.w == f.W && r.h == f.H) {
+        if (f.W != d->width || f.H != d->height)
+            bad("decoded size " + std::to_string(f.W) + "x" + std::to_string(f.H) +
+                " does not match the record descriptor " + std::to_string(d->width) + "x" + std::to_string(d->height));
+    } else if (r.w != d->width || r.h != d->height) {
+        bad("record descriptor " + std::to_string(d->width) + "x" + std::to_string(d->height) + " is not the size of " + name);
+    }
+    if (d->stride < d->width * d->channels) bad("record descriptor stride too small");
+    return r;
+}
+
+// The block rectangle of each component of f that a record of out_cn channels holding region r reads
+// (jpeg_region_rect); the whole image: every component's whole grid, as the frame lays it out; else nothing for a
+// component the record does not need.
+void region_rects(const Frame& f, const aeon_region& r, int out_cn, JpegRect rect[kJpegMaxComp])
+{
+    const bool whole = r.w == f.W && r.h == f.H;
+    const int  nc    = jpeg_planes_needed(f.cs, f.ncomp, out_cn);
+    for (int k = 0; k < kJpegMaxComp; k++) {
+        rect[k] = JpegRect{0, 0, 0, 0};
+        if (k >= f.ncomp) continue;
+        const Comp& c = f.c[k];
+        if (whole) {
+            rect[k] = JpegRect{0, 0, c.bw, c.bh};
+        } else if (k < nc) {
+            const int hf = f.hmax / c.h, vf = f.vmax / c.v;
+            rect[k] = jpeg_region_rect(jpeg_upsample_mode(hf, vf, c.dw), hf, vf, c.dw, c.dh, r.x, r.y, r.w, r.h);
+        }
+    }
+}
+
+// Whether jpeg_color takes color_h2v2 for the file's even bands (its staged chroma rows: see the kernel).
+bool takes_h2v2(const Frame& f, int out_cn)
+{
+    if (f.ncomp != 3 || out_cn != 3 || f.cs > CS_YCC) return false;
+    auto up = [&](int k) { return jpeg_upsample_mode(f.hmax / f.c[k].h, f.vmax / f.c[k].v, f.c[k].dw); };
+    return up(0) == UP_FULL && up(1) == UP_H2V2 && up(2) == UP_H2V2;
+}
+
 } // namespace
 
 // Per-context JPEG state: the decode pool, worker arenas, a two-deep ring of pinned staging +
@@ -1086,7 +1136,8 @@ void jpeg_state_destroy(JpegState* s)
 // a GPU-decoded file sets kJpegCorruptBit; aeon_hip_synchronize reports it).
 // start / stop (may be null): events recorded around the GPU launches (kernel timing)
 void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
-                       void* dst_base, int32_t* error, hipStream_t stream, hipEvent_t start, hipEvent_t stop)
+                       const aeon_region* regions, void* dst_base, int32_t* error, hipStream_t stream, hipEvent_t start,
+                       hipEvent_t stop)
 {
     std::lock_guard<std::mutex> lock(S->mu);
     // (AEON_HIP_JPEG_PROFILE=1, development: host time per phase of each call on stderr)
@@ -1116,6 +1167,8 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     std::vector<size_t>  blk(NC * (size_t)n), val(n);
     std::vector<GpuScan> gs(n);
     std::vector<char>    on_gpu(n, 0);
+    std::vector<aeon_region> reg(n);            // the record's region of its image
+    std::vector<JpegRect>    rect(NC * (size_t)n); // and the block rectangle of each component it reads
     S->pool->run_indexed(n, [&](int i, int w) {
         try {
             if (!data[i] || !sizes[i]) bad("empty file");
@@ -1129,10 +1182,8 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
                 decode_file(b, sizes[i], frames[i], arenas[w], &blk[NC * (size_t)i], &val[i], d.channels == 1);
             }
             owner[i] = w;
-            if (frames[i].W != d.width || frames[i].H != d.height)
-                bad("decoded size " + std::to_string(frames[i].W) + "x" + std::to_string(frames[i].H) +
-                    " does not match the record descriptor " + std::to_string(d.width) + "x" + std::to_string(d.height));
-            if (d.stride < d.width * d.channels) bad("record descriptor stride too small");
+            reg[i] = checked_region(frames[i], regions ? &regions[i] : nullptr, &d);
+            region_rects(frames[i], reg[i], d.channels, &rect[NC * (size_t)i]);
         } catch (const jpeg_error& e) {
             throw jpeg_error(e.code, std::string(e.what()) + " (record " + std::to_string(i) + ")");
         }
@@ -1151,16 +1202,22 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     size_t                 plane_bytes = 0;
     std::vector<size_t>    plane_off(NC * (size_t)n, 0);
     int                    color_lds = 0, color4_lds = 0, n_gpu = 0;
+    bool                   huff_region = false; // a GPU-decoded file of the call stores only part of its blocks
+    bool                   any_region = false;  // a record of the call is a region: the kernels' <true> instantiations
     size_t                 rec_bytes = 0, coef_bytes = 0, sub_bytes = 0;
     std::vector<size_t>    wrec(NC * (size_t)n, 0), wcoef(NC * (size_t)n, 0), wsub(n, 0);
     for (int i = 0; i < n; i++) {
         const Frame& f  = frames[i];
         const int    nc = jpeg_planes_needed(f.cs, f.ncomp, descs[i].channels); // gray from YCbCr needs Y only
         const bool   ycc = f.cs <= CS_YCC;
+        const aeon_region& r  = reg[i];
+        const JpegRect*    rc = &rect[NC * (size_t)i];
+        if (r.w != f.W || r.h != f.H) any_region = true;
         if (on_gpu[i]) {
             n_gpu++;
+            if (r.w != f.W || r.h != f.H) huff_region = true;
             for (int k = 0; k < f.ncomp; k++) {
-                const size_t nb = (size_t)f.c[k].bw * f.c[k].bh;
+                const size_t nb = (size_t)rc[k].bw * rc[k].bh;
                 wrec[NC * (size_t)i + k] = rec_bytes, rec_bytes += (nb * sizeof(JpegBlock) + 255) & ~(size_t)255;
                 wcoef[NC * (size_t)i + k] = coef_bytes, coef_bytes += (nb * 64 * sizeof(int16_t) + 255) & ~(size_t)255;
             }
@@ -1168,24 +1225,32 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         }
         for (int k = 0; k < nc; k++) {
             plane_off[NC * (size_t)i + k] = plane_bytes;
-            plane_bytes += ((size_t)f.c[k].bw * 8 * f.c[k].bh * 8 + 255) & ~(size_t)255;
-            const int nb = f.c[k].bw * f.c[k].bh;
+            plane_bytes += ((size_t)rc[k].bw * 8 * rc[k].bh * 8 + 255) & ~(size_t)255;
+            const int nb = rc[k].bw * rc[k].bh;
             for (int b = 0; b < nb; b += kJpegIdctBlocks) chunks.push_back({i, k, b, std::min(kJpegIdctBlocks, nb - b)});
         }
         // colour bands: as many rows as the staged plane rows of the band fit the LDS (16 bytes more per
-        // staged row: the 4:2:0 path's edge columns, jpeg_kernels.hip color_h2v2)
+        // staged row: the 4:2:0 path's edge columns, jpeg_kernels.hip color_h2v2, whose staged chroma rows are
+        // at least as long as its lane groups read: 4 bytes per 8 output columns)
+        const int h2v2_cols = takes_h2v2(f, descs[i].channels) ? 4 * ((r.w + 7) / 8) : 0;
         int band = band_max, lds = 0;
         for (;; band /= 2) {
             lds = 0;
             for (int k = 0; k < nc; k++) {
                 const int hf = f.hmax / f.c[k].h, vf = f.vmax / f.c[k].v;
-                lds += jpeg_stage_rows(jpeg_upsample_mode(hf, vf, f.c[k].dw), vf, band) * (f.c[k].bw * 8 + 16);
+                lds += jpeg_stage_rows(jpeg_upsample_mode(hf, vf, f.c[k].dw), vf, band) * (std::max(rc[k].bw * 8, h2v2_cols) + 16);
             }
             if (lds <= kJpegColorLds || band == 1) break;
         }
         if (lds > kJpegColorLds) unsupported("image too wide for the colour pass's LDS rows");
         (ycc ? color_lds : color4_lds) = std::max(ycc ? color_lds : color4_lds, lds);
-        for (int y = 0; y < f.H; y += band) (ycc ? rows : rows4).push_back({i, y, std::min(band, f.H - y), 0});
+        // (a region that starts on an odd row: a first band one row short, so that the next ones start on even
+        // rows as the whole image's do, which color_h2v2's row pairs want)
+        for (int y = r.y, first = band - (band % 2 == 0 ? r.y & 1 : 0); y < r.y + r.h; first = band) {
+            const int nr = std::min(first, r.y + r.h - y);
+            (ycc ? rows : rows4).push_back({i, y, nr, 0});
+            y += nr;
+        }
     }
     const size_t img_bytes = (size_t)n * sizeof(JpegImage);
     const size_t huf_off   = (img_bytes + 255) & ~(size_t)255;
@@ -1240,6 +1305,9 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
             } else {
                 J.blocks[k] = base + blk[NC * (size_t)i + k];
             }
+            const JpegRect& rk = rect[NC * (size_t)i + k];
+            J.rx[k] = rk.bx, J.ry[k] = rk.by, J.rw[k] = rk.bw, J.rh[k] = rk.bh;
+            J.sbw[k] = on_gpu[i] ? rk.bw : f.c[k].bw, J.sb0[k] = on_gpu[i] ? 0 : rk.by * f.c[k].bw + rk.bx;
             J.planes[k] = (uint64_t)st.planes + plane_off[NC * (size_t)i + k];
             J.bw[k] = f.c[k].bw, J.bh[k] = f.c[k].bh, J.dw[k] = f.c[k].dw, J.dh[k] = f.c[k].dh;
             J.hs[k] = f.c[k].h, J.vs[k] = f.c[k].v;
@@ -1252,6 +1320,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         J.out        = (uint64_t)dst_base + descs[i].offset;
         J.W          = f.W, J.H = f.H, J.ncomp = f.ncomp, J.out_cn = descs[i].channels, J.out_stride = descs[i].stride;
         J.hmax       = f.hmax, J.vmax = f.vmax, J.cs = f.cs;
+        J.ox = reg[i].x, J.oy = reg[i].y, J.ow = reg[i].w, J.oh = reg[i].h;
         if (!on_gpu[i]) continue;
         const GpuScan& g = gs[i];
         JpegHuffFile&  H = hf[hpos[i]];
@@ -1263,7 +1332,8 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         H.subs    = work + sub_off + wsub[i];
         for (int k = 0; k < f.ncomp; k++) {
             H.blocks[k] = J.blocks[k], H.dvals[k] = J.dvals[k];
-            H.bw[k] = f.c[k].bw;
+            const JpegRect& rk = rect[NC * (size_t)i + k];
+            H.bw[k] = rk.bw, H.rx0[k] = rk.bx, H.ry0[k] = rk.by, H.rh[k] = rk.bh;
             H.hs[k] = g.interleaved ? f.c[k].h : 1, H.vs[k] = g.interleaved ? f.c[k].v : 1;
         }
         H.blk_tab[0] = g.blk_tab[0], H.blk_tab[1] = g.blk_tab[1];
@@ -1294,11 +1364,12 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     if (n_gpu) hip_ok(hipMemsetAsync(st.work, 0, rec_bytes, stream), "hipMemsetAsync");
     if (start) hip_ok(hipEventRecord(start, stream), "hipEventRecord");
     if (n_gpu)
-        hip_ok(launch_jpeg_huff((const JpegHuffFile*)(st.dev + huf_off), n_gpu, S->huff_lanes, huff_stage, error, stream),
+        hip_ok(launch_jpeg_huff((const JpegHuffFile*)(st.dev + huf_off), n_gpu, S->huff_lanes, huff_stage, huff_region, error,
+                                stream),
                "JPEG Huffman kernel");
     hip_ok(launch_jpeg((const JpegImage*)st.dev, (const JpegChunk*)(st.dev + chk_off), (int)chunks.size(),
                        (const JpegRows*)(st.dev + row_off), (int)rows.size(), color_lds,
-                       (const JpegRows*)(st.dev + row4_off), (int)rows4.size(), color4_lds, stream),
+                       (const JpegRows*)(st.dev + row4_off), (int)rows4.size(), color4_lds, any_region, stream),
            "JPEG kernels");
     if (stop) hip_ok(hipEventRecord(stop, stream), "hipEventRecord");
     hip_ok(hipEventRecord(st.done, stream), "hipEventRecord");
@@ -1316,6 +1387,31 @@ void jpeg_info(const void* data, size_t size, int* w, int* h, int* ncomp)
     const uint8_t* after = nullptr;
     parse_frame((const uint8_t*)data, size, f, &after);
     *w = f.W, *h = f.H, *ncomp = f.ncomp;
+}
+
+// aeon_jpeg_region_plan's body: the file's headers as the decode call reads them (the colour space needs every
+// marker), then the call's checks and rectangles.
+void jpeg_region_plan(const void* data, size_t size, const aeon_region* region, const aeon_img_desc* desc, int out_cn,
+                      int* ncomp, int32_t out[16])
+{
+    Frame   f;
+    Arena   a;
+    GpuScan g;
+    try {
+        if (!prepare_gpu((const uint8_t*)data, size, f, a, g, kHuffLanes)) {
+            size_t blk_off[kJpegMaxComp] = {0, 0, 0, 0}, val_off = 0;
+            f = Frame(), a.used = 0;
+            decode_file((const uint8_t*)data, size, f, a, blk_off, &val_off, false);
+        }
+        const aeon_region r = checked_region(f, region, desc);
+        JpegRect          rect[kJpegMaxComp];
+        region_rects(f, r, out_cn, rect);
+        for (int k = 0; k < kJpegMaxComp; k++)
+            out[4 * k] = rect[k].bx, out[4 * k + 1] = rect[k].by, out[4 * k + 2] = rect[k].bw, out[4 * k + 3] = rect[k].bh;
+        *ncomp = f.ncomp;
+    } catch (const jpeg_error& e) {
+        throw jpeg_error(e.code, std::string(e.what()) + " (record 0)");
+    }
 }
 
 // aeon_jpeg_entropy_decode's body: the host half of the stage alone (headers, tables, every scan's
@@ -1406,7 +1502,7 @@ int jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, i
         recs[k].assign(nb, JpegBlock{0, 0, 0});
         coef[k].assign(nb * 64, 0);
         F.blocks[k] = (uint64_t)recs[k].data(), F.dvals[k] = (uint64_t)coef[k].data();
-        F.bw[k] = f.c[k].bw, F.hs[k] = g.interleaved ? f.c[k].h : 1, F.vs[k] = g.interleaved ? f.c[k].v : 1;
+        F.bw[k] = f.c[k].bw, F.rh[k] = f.c[k].bh, F.hs[k] = g.interleaved ? f.c[k].h : 1, F.vs[k] = g.interleaved ? f.c[k].v : 1;
     }
     F.blk_tab[0] = g.blk_tab[0], F.blk_tab[1] = g.blk_tab[1];
     F.nseg = g.nseg, F.nsub = g.nsub, F.restart = g.restart, F.n_mcu = g.n_mcu;

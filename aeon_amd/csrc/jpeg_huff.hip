@@ -93,7 +93,7 @@ __device__ Sums wg_scan(Scan& X, Sums v)
 typedef __attribute__((address_space(1))) JpegHuffSub glb_sub;
 
 // A file with more subsequences than lanes: the phases over the subsequence states in F.subs.
-template <int LANES>
+template <int LANES, bool REGION>
 __device__ __forceinline__ void decode_strided(const huff::Tables& T, Scan& X, const JpegHuffFile& F, int32_t* error)
 {
     const int tid = threadIdx.x, nsub = F.nsub;
@@ -119,7 +119,7 @@ __device__ __forceinline__ void decode_strided(const huff::Tables& T, Scan& X, c
         __syncthreads();
     }
     // 4. the final decode: coefficients and masks
-    if (!huff::pass_write(T, F, subs, tid, LANES)) atomicOr(error, kJpegCorruptBit);
+    if (!huff::pass_write<REGION>(T, F, subs, tid, LANES)) atomicOr(error, kJpegCorruptBit);
 }
 
 // LDS of a file with at most LANES subsequences: each one's end state, walk bounds (stop, segment end)
@@ -139,7 +139,7 @@ struct LaneStates {
 // compacts the subsequences whose start changed into the first lanes (wave ballots), so the walks of
 // a round occupy ceil(changed / 64) waves instead of every wave holding one.  The same phases as
 // jpeg_huff.hpp's pass_* functions, which the host emulation checks.
-template <int LANES, typename WP>
+template <int LANES, bool REGION, typename WP>
 __device__ __forceinline__ void decode_lanes(const huff::Tables& T, Scan& X, LaneStates<LANES>& L,
                                              const JpegHuffFile& F, WP words, int32_t* error)
 {
@@ -224,15 +224,16 @@ __device__ __forceinline__ void decode_lanes(const huff::Tables& T, Scan& X, Lan
     const int mcu = o.blk / F.bpm;
     o.mx = mcu % F.mcux, o.my = mcu / F.mcux;
     auto b = huff::bits_from(words, S, (int)(uint32_t)st);
-    if (!huff::walk_write(T, F, b, c, k, stop, last, o)) atomicOr(error, kJpegCorruptBit);
+    if (!huff::walk_write<REGION>(T, F, b, c, k, stop, last, o)) atomicOr(error, kJpegCorruptBit);
     HUFF_STAMP("written", b.p - p0);
 }
 
 typedef __attribute__((address_space(3))) const uint32_t* lds_words;
 
 // Dynamic LDS (stage_bytes): a copy of the file's data when it fits, so every walk's start and
-// refills read LDS instead of device memory.
-template <int LANES>
+// refills read LDS instead of device memory.  REGION: the instantiation of a call in which some file keeps only the
+// blocks of a region (walk_write<true>); the whole-image calls run the other, which holds no trace of it.
+template <int LANES, bool REGION>
 __global__ __launch_bounds__(LANES) void jpeg_huff(const JpegHuffFile* __restrict__ files, int stage_bytes,
                                                    int32_t* __restrict__ error)
 {
@@ -260,9 +261,9 @@ __global__ __launch_bounds__(LANES) void jpeg_huff(const JpegHuffFile* __restric
     huff::tables_long(T, F, tid, LANES);
     __syncthreads();
     HUFF_STAMP("tables", staged);
-    if (staged) decode_lanes<LANES>(T, X, L, F, (lds_words)stage, error);
-    else if (F.nsub <= LANES) decode_lanes<LANES>(T, X, L, F, huff::gmem<const uint32_t>(F.data), error);
-    else decode_strided<LANES>(T, X, F, error);
+    if (staged) decode_lanes<LANES, REGION>(T, X, L, F, (lds_words)stage, error);
+    else if (F.nsub <= LANES) decode_lanes<LANES, REGION>(T, X, L, F, huff::gmem<const uint32_t>(F.data), error);
+    else decode_strided<LANES, REGION>(T, X, F, error);
 #ifdef AEON_HUFF_PROBE
     if (blockIdx.x == 0 && tid == 0)
         for (int i = 1; i < probe_k; i++)
@@ -280,7 +281,7 @@ int huff_static_lds()
 {
     static const int bytes = [] {
         hipFuncAttributes at{};
-        return hipFuncGetAttributes(&at, (const void*)jpeg_huff<LANES>) == hipSuccess ? (int)at.sharedSizeBytes : kCuLds;
+        return hipFuncGetAttributes(&at, (const void*)jpeg_huff<LANES, false>) == hipSuccess ? (int)at.sharedSizeBytes : kCuLds;
     }();
     return bytes;
 }
@@ -293,24 +294,29 @@ int jpeg_huff_stage_cap(int lanes)
     return cap < 0 ? 0 : (cap < kHuffStageMax ? cap : kHuffStageMax);
 }
 
-template <int LANES>
+template <int LANES, bool REGION>
 hipError_t launch_huff(const JpegHuffFile* files, int n_files, int stage_bytes, int32_t* error, hipStream_t stream)
 {
-    static const hipError_t a = hipFuncSetAttribute((const void*)jpeg_huff<LANES>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    static const hipError_t a = hipFuncSetAttribute((const void*)jpeg_huff<LANES, REGION>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                     kHuffStageMax);
     if (a != hipSuccess) return a;
-    hipLaunchKernelGGL(jpeg_huff<LANES>, dim3(n_files), dim3(LANES), stage_bytes, stream, files, stage_bytes, error);
+    hipLaunchKernelGGL((jpeg_huff<LANES, REGION>), dim3(n_files), dim3(LANES), stage_bytes, stream, files, stage_bytes, error);
     return hipGetLastError();
 }
 
-hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, int stage_bytes, int32_t* error,
+hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, int stage_bytes, bool region, int32_t* error,
                             hipStream_t stream)
 {
     if (n_files <= 0) return hipSuccess;
     stage_bytes = (stage_bytes + 15) & ~15;
-    if (lanes == 256) return launch_huff<256>(files, n_files, stage_bytes, error, stream);
-    if (lanes == 512) return launch_huff<512>(files, n_files, stage_bytes, error, stream);
-    return launch_huff<1024>(files, n_files, stage_bytes, error, stream);
+    if (region) {
+        if (lanes == 256) return launch_huff<256, true>(files, n_files, stage_bytes, error, stream);
+        if (lanes == 512) return launch_huff<512, true>(files, n_files, stage_bytes, error, stream);
+        return launch_huff<1024, true>(files, n_files, stage_bytes, error, stream);
+    }
+    if (lanes == 256) return launch_huff<256, false>(files, n_files, stage_bytes, error, stream);
+    if (lanes == 512) return launch_huff<512, false>(files, n_files, stage_bytes, error, stream);
+    return launch_huff<1024, false>(files, n_files, stage_bytes, error, stream);
 }
 
 } // namespace aeon_hip

@@ -342,7 +342,10 @@ HUFF_FN void walk_sync(const Tables& T, const JpegHuffFile& F, B& b, int& c, int
 // up to the first codeword boundary at or past `stop`, or -- the segment's last subsequence -- until the
 // segment's blocks are done.  Returns false on corrupt data: no code of <= 16 bits, a DC size above
 // 15, bits past the end of a file whose data ends without a marker.
-template <typename B>
+// REGION: the file's block slots and masks hold only the rectangle (F.rx0, F.ry0, F.bw, F.rh) of each component's
+// block grid; a block outside it is walked like any other -- the DC prediction runs over every block -- but none
+// of its coefficients and no mask is stored.
+template <bool REGION = false, typename B>
 HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, int& k, int stop, bool last, Out& o)
 {
     const BlkTab          bt{F.blk_tab[0], F.blk_tab[1]};
@@ -356,11 +359,19 @@ HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, in
     HUFF_GLOBAL int16_t*  coef = nullptr;
     HUFF_GLOBAL uint64_t* mrec = nullptr;
     bool                  own  = k == 0; // the current block started in this walk
+    bool                  in   = true;   // REGION: the current block lies in its component's rectangle
     auto open = [&]() {                  // locate the current block in its component plane
         const int    by = bt.byte(c), x = (by >> 2) & 3, y = (by >> 4) & 3;
         const int    bw = pick4(comp, bw0, bw1, bw2, bw3), hs = pick4(comp, hs0, hs1, hs2, hs3);
         const int    vs = pick4(comp, vs0, vs1, vs2, vs3);
-        const size_t idx = (size_t)(o.my * vs + y) * bw + o.mx * hs + x;
+        int          row = o.my * vs + y, col = o.mx * hs + x;
+        if constexpr (REGION) {
+            row -= pick4(comp, F.ry0[0], F.ry0[1], F.ry0[2], F.ry0[3]);
+            col -= pick4(comp, F.rx0[0], F.rx0[1], F.rx0[2], F.rx0[3]);
+            in = (unsigned)row < (unsigned)pick4(comp, F.rh[0], F.rh[1], F.rh[2], F.rh[3]) && (unsigned)col < (unsigned)bw;
+            if (!in) row = col = 0; // (no address outside the slots is formed)
+        }
+        const size_t idx = (size_t)row * bw + col;
         coef = gmem<int16_t>(pick4(comp, dv0, dv1, dv2, dv3)) + idx * 64;
         mrec = gmem<uint64_t>(pick4(comp, bk0, bk1, bk2, bk3)) + idx * 2;
     };
@@ -389,7 +400,7 @@ HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, in
             o.pred2 = comp == 2 ? pr : o.pred2;
             o.pred3 = comp == 3 ? pr : o.pred3;
             const int16_t dc = (int16_t)pr;
-            if (dc) coef[0] = dc;
+            if (dc && in) coef[0] = dc;
             mask = dc ? 1 : 0;
             k    = 1;
         } else if (kind == kEob || kind == kZrl) {
@@ -398,11 +409,12 @@ HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, in
             k += (int)((e >> 5) & 15);
             const int zz = imin(k, 63); // jpeg_natural_order's extra entries clamp a run past 63 to 63
             mask |= 1ull << zz;
-            coef[zz] = (int16_t)v;
+            if (in) coef[zz] = (int16_t)v;
             k++;
         }
         if (k >= 64) { // block done
-            if (own) mrec[0] = mask;
+            if (!in) mask = 0;
+            if (own && in) mrec[0] = mask;
             else if (mask) or_mask(mrec, mask);
             mask = 0, own = true;
             o.blk++;
@@ -415,7 +427,7 @@ HUFF_FN bool walk_write(const Tables& T, const JpegHuffFile& F, B& b, int& c, in
             if (o.blk < o.blk_end) open();
         }
     }
-    if (k > 0 && mask) or_mask(mrec, mask); // a block split with the next subsequence
+    if (k > 0 && mask && in) or_mask(mrec, mask); // a block split with the next subsequence
     return true;
 }
 
@@ -525,7 +537,7 @@ HUFF_FN void pass_rewalk(const Tables& T, const JpegHuffFile& F, SP subs, int j0
 
 // Phase 4 (after the exclusive prefix of cnt into ex): the final decode.  Returns false if any of
 // the walks met corrupt data.
-template <typename SP>
+template <bool REGION = false, typename SP>
 HUFF_FN bool pass_write(const Tables& T, const JpegHuffFile& F, SP subs, int j0, int dj)
 {
     const HUFF_GLOBAL JpegHuffSeg* segs = gmem<const JpegHuffSeg>(F.segs);
@@ -547,7 +559,7 @@ HUFF_FN bool pass_write(const Tables& T, const JpegHuffFile& F, SP subs, int j0,
         const int mcu = o.blk / F.bpm;
         o.mx = mcu % F.mcux, o.my = mcu / F.mcux;
         Bits b = bits_at(F, S, (int)(uint32_t)st);
-        if (!walk_write(T, F, b, c, k, (int)S.start_bit + (i + 1) * F.sub_bits, i + 1 == S.nsub, o)) ok = false;
+        if (!walk_write<REGION>(T, F, b, c, k, (int)S.start_bit + (i + 1) * F.sub_bits, i + 1 == S.nsub, o)) ok = false;
     }
     return ok;
 }

@@ -78,6 +78,20 @@ __device__ __forceinline__ void llm8(const int* in, int* out)
     out[3] = (t13 + tmp0 + R) >> SHIFT, out[4] = (t13 - tmp0 + R) >> SHIFT;
 }
 
+// The record's and the rectangles' geometry as a kernel instantiation reads it.  REGION false -- the kernels of a
+// call whose records are all whole images -- folds it to constants (the record is the image, a rectangle its
+// component's whole grid), which leaves those kernels the code, registers and time they had before regions; REGION
+// true reads what the host computed (JpegImage), whole images of a mixed call included.
+template <bool REGION>
+struct Geo {
+    static __device__ __forceinline__ int ox(const JpegImage& I) { return REGION ? I.ox : 0; }
+    static __device__ __forceinline__ int oy(const JpegImage& I) { return REGION ? I.oy : 0; }
+    static __device__ __forceinline__ int ow(const JpegImage& I) { return REGION ? I.ow : I.W; }
+    static __device__ __forceinline__ int rx(const JpegImage& I, int k) { return REGION ? I.rx[k] : 0; }
+    static __device__ __forceinline__ int ry(const JpegImage& I, int k) { return REGION ? I.ry[k] : 0; }
+    static __device__ __forceinline__ int rw(const JpegImage& I, int k) { return REGION ? I.rw[k] : I.bw[k]; }
+};
+
 // Natural index -> zigzag index (the inverse of kZz).
 __constant__ uint8_t kZzInv[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42,
                                    3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
@@ -98,6 +112,7 @@ __constant__ uint8_t kZzInv[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  1
 // bank (2g + 8r + j) % 64 -- conflict-free per wave.
 constexpr int kSlot = 66;
 
+template <bool REGION>
 __global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct(const JpegImage* __restrict__ imgs,
                                                             const JpegChunk* __restrict__ chunks)
 {
@@ -108,12 +123,31 @@ __global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct(const JpegImage* __r
     const JpegImage& I  = imgs[C.img];
     const int        k  = C.comp;
     const int        g = threadIdx.x >> 3, j = threadIdx.x & 7;
-    const gp<const JpegBlock> blocks = gaddr<const JpegBlock>(I.blocks[k]) + C.first;
+    const gp<const JpegBlock> blocks = gaddr<const JpegBlock>(I.blocks[k]);
     const gp<const int16_t>   vals   = gaddr<const int16_t>(I.values);
     const gp<const int16_t>   dense  = gaddr<const int16_t>(I.dvals[k]);
+    // Block b of the component's rectangle (rw blocks a row) is row b / rw, column b % rw of it: its plane holds
+    // the rectangle alone, its record and coefficients sit at sb0 + row * sbw + column (JpegImage).  b / rw
+    // through a float reciprocal: exact while rw < 512 ((b + 0.5) / rw stays 0.5 / rw from an integer, far above
+    // the float error at these sizes)
+    const int   rw  = Geo<REGION>::rw(I, k), sbw = I.sbw[k], sb0 = I.sb0[k];
+    const float rrw = 1.0f / (float)rw;
+    auto locate = [&](int b, int& row, int& col) {
+        row = rw < 512 ? (int)(((float)b + 0.5f) * rrw) : b / rw;
+        col = b - row * rw;
+    };
     JpegBlock        B[U];
+    int              src[U]; // the blocks' records and coefficient slots
 #pragma unroll
-    for (int u = 0; u < U; u++) B[u] = blocks[min(g + u * G, C.count - 1)];
+    for (int u = 0; u < U; u++) {
+        int row, col;
+        src[u] = C.first + min(g + u * G, C.count - 1);
+        if constexpr (REGION) {
+            locate(src[u], row, col);
+            src[u] = sb0 + row * sbw + col;
+        }
+        B[u] = blocks[src[u]];
+    }
     int* const s0 = slot + g * kSlot; // the group's block slot
     // pass 1 inputs: column j of every block, dequantised (jidctint.c DEQUANTIZE = coef * quantval)
     int col[U][8];
@@ -121,7 +155,7 @@ __global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct(const JpegImage* __r
         uint4 c4[U];
 #pragma unroll
         for (int u = 0; u < U; u++)
-            c4[u] = *(gp<const uint4>)(dense + (size_t)(C.first + min(g + u * G, C.count - 1)) * 64 + 8 * j);
+            c4[u] = *(gp<const uint4>)(dense + (size_t)src[u] * 64 + 8 * j);
         const uint4 q4 = *(gp<const uint4>)gaddr<const uint16_t>((uint64_t)&I.qz[k][8 * j]);
         int nat[8];
 #pragma unroll
@@ -162,8 +196,6 @@ __global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct(const JpegImage* __r
             }
     }
     int* const  s   = s0;
-    const int   bw  = I.bw[k];
-    const float rbw = 1.0f / (float)bw;
 #pragma unroll
     for (int u = 0; u < U; u++) {
         const int bi = g + u * G;
@@ -183,11 +215,9 @@ __global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct(const JpegImage* __r
         for (int c = 0; c < 8; c++) in[c] = s[j * 8 + c];
         llm8<18, true>(in, out);
         if (bi < C.count) {
-            const int b  = C.first + bi;
-            // b / bw through a float reciprocal: exact while bw < 512 ((b + 0.5) / bw stays 0.5 / bw from
-            // an integer, far above the float error at these sizes)
-            const int by = bw < 512 ? (int)(((float)b + 0.5f) * rbw) : b / bw, bx = b - by * bw;
-            const gp<uint8_t> o = gaddr<uint8_t>(I.planes[k]) + (size_t)(by * 8 + j) * (bw * 8) + bx * 8;
+            int by, bx;
+            locate(C.first + bi, by, bx);
+            const gp<uint8_t> o = gaddr<uint8_t>(I.planes[k]) + (size_t)(by * 8 + j) * (rw * 8) + bx * 8;
             const uint32_t lo = idct_limit(out[0]) | idct_limit(out[1]) << 8 | idct_limit(out[2]) << 16 |
                                 idct_limit(out[3]) << 24;
             const uint32_t hi = idct_limit(out[4]) | idct_limit(out[5]) << 8 | idct_limit(out[6]) << 16 |
@@ -198,7 +228,8 @@ __global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct(const JpegImage* __r
 }
 
 // The geometry of one component as the colour pass uses it: its staged plane rows [lo, lo + n) in
-// LDS (pitch pw), upsampler and sizes.
+// LDS (pitch pw: the component's block rectangle; P is set back by the rectangle's first sample column, so that
+// samples are addressed by their column in the image's plane), upsampler and the whole image's sizes.
 struct CompView {
     const uint8_t* P;
     int            lo, pw, dw, dh, up, hf, vf;
@@ -206,9 +237,10 @@ struct CompView {
 
 // The plane rows [lo, hi] of component k that output rows [y0, y1]'s upsampling reads (jdsample.c's
 // context rows for the triangle filters, clamped at the image edges).
+template <bool REGION>
 __device__ __forceinline__ void comp_rows(const JpegImage& I, int k, int y0, int y1, CompView& c, int& hi)
 {
-    c.pw = I.bw[k] * 8, c.dw = I.dw[k], c.dh = I.dh[k], c.up = I.up[k], c.hf = I.hf[k], c.vf = I.vf[k];
+    c.pw = Geo<REGION>::rw(I, k) * 8, c.dw = I.dw[k], c.dh = I.dh[k], c.up = I.up[k], c.hf = I.hf[k], c.vf = I.vf[k];
     if (c.up == UP_H1V2 || c.up == UP_H2V2) c.lo = max((y0 >> 1) - 1, 0), hi = min((y1 >> 1) + 1, c.dh - 1);
     else if (c.up == UP_BOX) c.lo = y0 / c.vf, hi = y1 / c.vf;
     else c.lo = y0, hi = y1;
@@ -243,13 +275,15 @@ __device__ __forceinline__ int upsampled(const CompView& c, int x, int y)
     }
 }
 
-// Output rows [y0, y0 + rows) of image I from its staged component rows cv: one lane per 4 consecutive
-// pixels -- one dword (gray) or three dwords (BGR) when the group is whole and 4-byte aligned,
-// bytewise otherwise.
+// Image rows [y0, y0 + rows) of the record of image I (its columns [ox, ox + ow)) from its staged component rows cv:
+// one lane per 4 consecutive pixels of the record -- one dword (gray) or three dwords (BGR) when the group is whole
+// and 4-byte aligned, bytewise otherwise.  A pixel is sampled at its place in the image, so the chroma phase
+// and the filters' neighbours are the whole decode's wherever the record starts.
+template <bool REGION>
 __device__ __forceinline__ void color_rows(const JpegImage& I, const CompView* cv, int y0, int nrows)
 {
-    const int W = I.W, cn = I.out_cn, nc = cn == 1 ? 1 : I.ncomp;
-    const gp<uint8_t> out = gaddr<uint8_t>(I.out);
+    const int W = Geo<REGION>::ow(I), ox = Geo<REGION>::ox(I), cn = I.out_cn, nc = cn == 1 ? 1 : I.ncomp;
+    const gp<uint8_t> out = gaddr<uint8_t>(I.out) - (size_t)Geo<REGION>::oy(I) * I.out_stride; // (row y of the image)
     const int         stride = I.out_stride;
     const int groups = (W + 3) >> 2;
     for (int q = threadIdx.x; q < groups * nrows; q += blockDim.x) {
@@ -257,7 +291,7 @@ __device__ __forceinline__ void color_rows(const JpegImage& I, const CompView* c
         uint32_t  p[4];
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-            const int x = min(x0 + e, W - 1);
+            const int x = ox + min(x0 + e, W - 1);
             const int Y = upsampled(cv[0], x, y);
             if (nc == 1) {
                 p[e] = cn == 1 ? (uint32_t)Y : (uint32_t)Y * 0x010101u;
@@ -295,6 +329,15 @@ __device__ __forceinline__ void color_rows(const JpegImage& I, const CompView* c
 // the column sums 3 * row r + neighbour row as packed 16-bit pairs, and the output pairs
 // (3 * colsum(i) + colsum(i -+ 1) + 8 / 7) >> 4 of h2v2_fancy_upsample the same way.  Luma comes
 // straight from the plane (8-byte loads).  Bit-exact with the general path: same integer formulas.
+//
+// A record that is a region of the image (columns [ox, ox + ow)): the lanes' 8-column groups stay aligned to the
+// record, so its stores keep their 8-byte form.  The chroma rows are staged from the record's first chroma column
+// c0 = ox >> 1 on (byte-shifted on the way into LDS), so group q still reads aligned dwords at i0 = 4q, with the
+// real left neighbour c0 - 1 where column -1 stands -- the image's edge rule only where the region touches the edge.
+// An odd ox flips the chroma phase of every record column: color_h2v2<true> takes pixel e of a group from output
+// e + 1 of the even-aligned 8 columns that start one to the left, whose ninth output (the even phase of chroma
+// column i0 + 4) the staged columns i0 + 3, i0 + 4 give.  Luma off an 8-byte boundary comes as three dwords,
+// byte-aligned in registers.
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
 constexpr int kH2v2Pad = 8; // staged chroma row: [8 bytes: col -1 at 7][pw bytes][8 bytes: col dw]
 
@@ -321,7 +364,8 @@ __device__ __forceinline__ ChromaCols chroma_cols(const uint8_t* row)
 // h2v2_fancy_upsample of 8 output columns of one output row: e01 = (x0, x0 + 2), o01 = (x0 + 1,
 // x0 + 3), e23 = (x0 + 4, x0 + 6), o23 = (x0 + 5, x0 + 7); `t3` = 3 * row r, `nb` the neighbour row.
 struct ChromaOut {
-    u16x2 e01, o01, e23, o23;
+    u16x2    e01, o01, e23, o23;
+    uint32_t e4; // the even output of chroma column i0 + 4 (x0 + 8): only a record starting on an odd column reads it
 };
 __device__ __forceinline__ ChromaOut chroma_row(const ChromaCols& t3, const ChromaCols& nb)
 {
@@ -333,6 +377,7 @@ __device__ __forceinline__ ChromaOut chroma_row(const ChromaCols& t3, const Chro
     o.o01 = (sq0 * three + sp1 + r7) >> four;
     o.e23 = (sq1 * three + sp1 + r8) >> four;
     o.o23 = (sq1 * three + sp2 + r7) >> four;
+    o.e4  = ((uint32_t)sp2[1] * 3 + sp2[0] + 8) >> 4;
     return o;
 }
 
@@ -369,10 +414,13 @@ __device__ __forceinline__ void store_bgr8(gp<uint8_t> o, const uint32_t (&p)[8]
     }
 }
 
+template <bool ODD, bool REGION>
 __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R, uint8_t* lds)
 {
+    using G = Geo<REGION>;
     const int y0 = R.y0, y1 = R.y0 + R.rows - 1;
-    // stage chroma rows [lo, hi] of both components, then replicate their edge columns
+    const int W = G::ow(I), groups = (W + 7) >> 3, c0 = G::ox(I) >> 1; // c0: the chroma column of the record's first pixel
+    // stage chroma rows [lo, hi] of both components from column c0 - 1 on, then replicate the image's edge columns
     int lo[2], n[2], lp[2], off[2];
     int o = 0;
 #pragma unroll
@@ -380,12 +428,23 @@ __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R
         const int k = c + 1;
         lo[c] = max((y0 >> 1) - 1, 0);
         n[c]  = min((y1 >> 1) + 1, I.dh[k] - 1) - lo[c] + 1;
-        lp[c] = I.bw[k] * 8 + 2 * kH2v2Pad, off[c] = o;
-        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)lo[c] * (I.bw[k] * 8));
-        const int per = I.bw[k]; // 8-byte words per row
-        for (int e = threadIdx.x; e < n[c] * per; e += blockDim.x) {
-            const int rr = e / per, w = e - rr * per;
-            *(uint2*)(lds + o + rr * lp[c] + kH2v2Pad + w * 8) = src[e];
+        const int pw = G::rw(I, k) * 8, s = c0 - G::rx(I, k) * 8; // the rectangle's row, column c0's place in it
+        lp[c] = (REGION ? max(pw, 4 * groups) : pw) + 2 * kH2v2Pad, off[c] = o;
+        const gp<const uint8_t> src = gaddr<const uint8_t>(I.planes[k]) + (size_t)(lo[c] - G::ry(I, k) * 8) * pw;
+        if (s == 0) { // the rows start at the image's first column: whole, 8 bytes at a time
+            const int per = pw >> 3; // 8-byte words per row
+            for (int e = threadIdx.x; e < n[c] * per; e += blockDim.x) {
+                const int rr = e / per, w = e - rr * per;
+                *(uint2*)(lds + o + rr * lp[c] + kH2v2Pad + w * 8) = ((gp<const uint2>)src)[e];
+            }
+        } else { // dword w of the staged row = the row's bytes s + 4w .., w from -1 (byte s - 1: column c0 - 1)
+            const int pwd = pw >> 2, per = ((pw - s + 3) >> 2) + 1, a0 = (s >> 2) - 1;
+            for (int e = threadIdx.x; e < n[c] * per; e += blockDim.x) {
+                const int rr = e / per, w = e - rr * per;
+                const gp<const uint32_t> rw = (gp<const uint32_t>)src + rr * pwd;
+                const uint32_t d0 = rw[min(max(a0 + w, 0), pwd - 1)], d1 = rw[min(a0 + w + 1, pwd - 1)];
+                *(uint32_t*)(lds + o + rr * lp[c] + kH2v2Pad - 4 + w * 4) = __builtin_amdgcn_alignbyte(d1, d0, (uint32_t)(s & 3));
+            }
         }
         o += n[c] * lp[c];
     }
@@ -395,22 +454,38 @@ __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R
         const int  rr = threadIdx.x - (c1 ? n[0] : 0);
         uint8_t*   row = lds + (c1 ? off[1] + rr * lp[1] : rr * lp[0]) + kH2v2Pad;
         const int  dw  = c1 ? I.dw[2] : I.dw[1];
-        row[-1] = row[0], row[dw] = row[dw - 1];
+        // (the staged rows reach the image's last column?)
+        const int  end = REGION ? (c1 ? I.rx[2] + I.rw[2] : I.rx[1] + I.rw[1]) * 8 : dw;
+        if (c0 == 0) row[-1] = row[0];
+        if (end >= dw) row[dw - c0] = row[dw - 1 - c0];
     }
     __syncthreads();
 
-    const int W = I.W, H = I.H, groups = (W + 7) >> 3, pairs = (R.rows + 1) >> 1;
-    const int pw0 = I.bw[0] * 8, dh1 = I.dh[1], dh2 = I.dh[2];
-    const gp<const uint8_t> Yp  = gaddr<const uint8_t>(I.planes[0]);
-    const gp<uint8_t>       out = gaddr<uint8_t>(I.out);
+    const int ye = REGION ? y0 & ~1 : y0, pairs = ((y1 - ye) >> 1) + 1; // (a region's first band may start on the odd row of a pair)
+    const int pw0 = G::rw(I, 0) * 8, sx = G::ox(I) - G::rx(I, 0) * 8, dh1 = I.dh[1], dh2 = I.dh[2];
+    const gp<const uint8_t> Yp  = gaddr<const uint8_t>(I.planes[0]) - (size_t)G::ry(I, 0) * 8 * pw0; // (row y of the image)
+    const gp<uint8_t>       out = gaddr<uint8_t>(I.out) - (size_t)G::oy(I) * I.out_stride;
     const float rcp   = 1.0f / (float)groups;
     const int   total = groups * pairs;
+    // 8 luma samples of row y from the rectangle's column c on: an 8-byte load, or three dwords aligned in registers
+    auto luma8 = [&](int y, int c, uint2& v) {
+        const gp<const uint8_t> row = Yp + (size_t)y * pw0;
+        if ((sx & 7) == 0) {
+            v = *(gp<const uint2>)(row + c);
+            return;
+        }
+        const gp<const uint32_t> w = (gp<const uint32_t>)row;
+        const int      a = c >> 2, last = (pw0 >> 2) - 1;
+        const uint32_t d0 = w[a], d1 = w[min(a + 1, last)], d2 = w[min(a + 2, last)];
+        v = make_uint2(__builtin_amdgcn_alignbyte(d1, d0, (uint32_t)(sx & 3)),
+                       __builtin_amdgcn_alignbyte(d2, d1, (uint32_t)(sx & 3)));
+    };
     // the luma of the lane's next item is loaded before this one is computed
     auto luma = [&](int it, uint2& a, uint2& b) {
         const int pr = (int)(((float)it + 0.5f) * rcp), q = it - pr * groups;
-        const int y = y0 + 2 * pr, x0 = q * 8;
-        a = *(gp<const uint2>)(Yp + (size_t)y * pw0 + x0);
-        b = *(gp<const uint2>)(Yp + (size_t)min(y + 1, H - 1) * pw0 + x0);
+        const int y = ye + 2 * pr;
+        luma8(y, sx + q * 8, a);
+        luma8(min(y + 1, y1), sx + q * 8, b);
     };
     uint2 na = make_uint2(0, 0), nb = make_uint2(0, 0);
     if (threadIdx.x < total) luma(threadIdx.x, na, nb);
@@ -418,7 +493,7 @@ __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R
         const uint2 ya = na, yv = nb;
         if (it + (int)blockDim.x < total) luma(it + blockDim.x, na, nb);
         const int pr = (int)(((float)it + 0.5f) * rcp), q = it - pr * groups;
-        const int y = y0 + 2 * pr, x0 = q * 8, i0 = q * 4, r = y >> 1;
+        const int y = ye + 2 * pr, x0 = q * 8, i0 = q * 4, r = y >> 1;
         ChromaOut ce[2], co[2]; // [chroma]: output row y (even), y + 1 (odd)
 #pragma unroll
         for (int c = 0; c < 2; c++) {
@@ -435,7 +510,7 @@ __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R
         const int nx = min(8, W - x0);
 #pragma unroll
         for (int v = 0; v < 2; v++) {
-            if (v == 1 && y + 1 > y1) continue; // (the band's last row, or the image's)
+            if (y + v < y0 || y + v > y1) continue; // (the pair's row outside the band, or the record)
             const uint2 yy = v ? yv : ya;
             const ChromaOut& cb = v ? co[0] : ce[0];
             const ChromaOut& cr = v ? co[1] : ce[1];
@@ -443,10 +518,13 @@ __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R
             uint32_t px[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) {
-                // pixel e: even e -> e01/e23, odd -> o01/o23; pair half = (e >> 1) & 1
-                const int      s  = (e >> 2) * 2 + (e & 1), h = (e >> 1) & 1;
+                // pixel e is output f of the aligned 8 (f = e + 1 from an odd column): even f -> e01/e23, odd ->
+                // o01/o23; pair half = (f >> 1) & 1; f = 8: e4
+                const int      f  = e + (ODD ? 1 : 0);
+                const int      s  = ((f & 7) >> 2) * 2 + (f & 1), h = (f >> 1) & 1;
                 const uint32_t yw = e < 4 ? yy.x : yy.y;
-                px[e] = ycc_bgr((int)((yw >> (8 * (e & 3))) & 0xff), (int)bq[s][h], (int)rq[s][h]);
+                const int      b8 = f < 8 ? (int)bq[s][h] : (int)cb.e4, r8 = f < 8 ? (int)rq[s][h] : (int)cr.e4;
+                px[e] = ycc_bgr((int)((yw >> (8 * (e & 3))) & 0xff), b8, r8);
             }
             store_bgr8(out + (size_t)(y + v) * I.out_stride + (size_t)x0 * 3, px, nx);
         }
@@ -455,14 +533,16 @@ __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R
 
 // A workgroup per band of output rows: the plane rows the band's upsampling reads are copied into
 // LDS with coalesced 8-byte loads (jpeg_stage_rows bounds them), then color_rows.
+template <bool REGION>
 __global__ __launch_bounds__(256) void jpeg_color(const JpegImage* __restrict__ imgs, const JpegRows* __restrict__ rows)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_b[];
     const JpegRows   R  = rows[blockIdx.x];
     const JpegImage& I  = imgs[R.img];
     if (I.ncomp == 3 && I.out_cn == 3 && I.up[0] == UP_FULL && I.up[1] == UP_H2V2 && I.up[2] == UP_H2V2 &&
-        (R.y0 & 1) == 0) {
-        color_h2v2(I, R, lds_b);
+        ((R.y0 & 1) == 0 || (REGION && R.y0 == I.oy))) { // (a region's first band ends where the even bands start)
+        if (REGION && (I.ox & 1)) color_h2v2<true, REGION>(I, R, lds_b);
+        else color_h2v2<false, REGION>(I, R, lds_b);
         return;
     }
     const int        nc = I.out_cn == 1 ? 1 : I.ncomp;
@@ -473,18 +553,18 @@ __global__ __launch_bounds__(256) void jpeg_color(const JpegImage* __restrict__ 
     for (int k = 0; k < 3; k++) {
         CompView& c = cv[k];
         int       hi;
-        comp_rows(I, k, R.y0, y1, c, hi);
-        c.P = lds_b + off;
+        comp_rows<REGION>(I, k, R.y0, y1, c, hi);
+        c.P = lds_b + off - Geo<REGION>::rx(I, k) * 8;
         if (k >= nc) continue;
         // stage plane rows [lo, hi]: whole rows of pw bytes (a multiple of 8) are contiguous
-        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)c.lo * c.pw);
+        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)(c.lo - Geo<REGION>::ry(I, k) * 8) * c.pw);
         uint2*       dst = (uint2*)(lds_b + off);
         const int    n8  = (hi - c.lo + 1) * c.pw / 8;
         for (int e = threadIdx.x; e < n8; e += blockDim.x) dst[e] = src[e];
         off += (hi - c.lo + 1) * c.pw;
     }
     __syncthreads();
-    color_rows(I, cv, R.y0, R.rows);
+    color_rows<REGION>(I, cv, R.y0, R.rows);
 }
 
 // ---- CMYK, YCCK and RGB sources ------------------------------------------------------------------
@@ -514,7 +594,8 @@ __device__ __forceinline__ uint32_t convert4(int cs, int cn, int s0, int s1, int
 
 // A workgroup per band of output rows of a CMYK, YCCK or RGB file: every component's plane rows the
 // band reads staged in LDS as jpeg_color stages them (jpeg_stage_rows bounds them), then one lane per
-// 4 consecutive pixels with color_rows' stores.
+// 4 consecutive pixels of the record with color_rows' stores, each sampled at its place in the image.
+template <bool REGION>
 __global__ __launch_bounds__(256) void jpeg_color4(const JpegImage* __restrict__ imgs, const JpegRows* __restrict__ rows)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_b[];
@@ -531,24 +612,24 @@ __global__ __launch_bounds__(256) void jpeg_color4(const JpegImage* __restrict__
             continue;
         }
         int hi;
-        comp_rows(I, k, y0, y1, c, hi);
-        c.P = lds_b + off;
-        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)c.lo * c.pw);
+        comp_rows<REGION>(I, k, y0, y1, c, hi);
+        c.P = lds_b + off - Geo<REGION>::rx(I, k) * 8;
+        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)(c.lo - Geo<REGION>::ry(I, k) * 8) * c.pw);
         uint2*       dst = (uint2*)(lds_b + off);
         const int    n8  = (hi - c.lo + 1) * c.pw / 8;
         for (int e = threadIdx.x; e < n8; e += blockDim.x) dst[e] = src[e];
         off += (hi - c.lo + 1) * c.pw;
     }
     __syncthreads();
-    const int W = I.W, cn = I.out_cn, cs = I.cs, stride = I.out_stride;
-    const gp<uint8_t> out = gaddr<uint8_t>(I.out);
+    const int W = Geo<REGION>::ow(I), ox = Geo<REGION>::ox(I), cn = I.out_cn, cs = I.cs, stride = I.out_stride;
+    const gp<uint8_t> out = gaddr<uint8_t>(I.out) - (size_t)Geo<REGION>::oy(I) * stride; // (row y of the image)
     const int groups = (W + 3) >> 2;
     for (int q = threadIdx.x; q < groups * R.rows; q += blockDim.x) {
         const int y = y0 + q / groups, x0 = (q % groups) * 4;
         uint32_t  p[4];
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-            const int x  = min(x0 + e, W - 1);
+            const int x  = ox + min(x0 + e, W - 1);
             const int s0 = upsampled(cv[0], x, y), s1 = upsampled(cv[1], x, y), s2 = upsampled(cv[2], x, y);
             const int s3 = nc == 4 ? upsampled(cv[3], x, y) : 0;
             p[e] = convert4(cs, cn, s0, s1, s2, s3);
@@ -583,13 +664,21 @@ static hipError_t launch_color(K kernel, const JpegImage* imgs, const JpegRows* 
     return hipSuccess;
 }
 
-hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, hipStream_t stream)
+template <bool REGION>
+static hipError_t launch_jpeg_as(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
+                                 int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, hipStream_t stream)
 {
-    if (n_chunks > 0) hipLaunchKernelGGL(jpeg_idct, dim3(n_chunks), dim3(kJpegIdctLanes), 0, stream, imgs, chunks);
-    hipError_t e = launch_color(jpeg_color, imgs, rows, n_rows, color_lds, stream);
-    if (e == hipSuccess) e = launch_color(jpeg_color4, imgs, rows4, n_rows4, color4_lds, stream);
+    if (n_chunks > 0) hipLaunchKernelGGL(jpeg_idct<REGION>, dim3(n_chunks), dim3(kJpegIdctLanes), 0, stream, imgs, chunks);
+    hipError_t e = launch_color(jpeg_color<REGION>, imgs, rows, n_rows, color_lds, stream);
+    if (e == hipSuccess) e = launch_color(jpeg_color4<REGION>, imgs, rows4, n_rows4, color4_lds, stream);
     return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
+                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, bool region, hipStream_t stream)
+{
+    return region ? launch_jpeg_as<true>(imgs, chunks, n_chunks, rows, n_rows, color_lds, rows4, n_rows4, color4_lds, stream)
+                  : launch_jpeg_as<false>(imgs, chunks, n_chunks, rows, n_rows, color_lds, rows4, n_rows4, color4_lds, stream);
 }
 
 } // namespace aeon_hip

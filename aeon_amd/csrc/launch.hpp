@@ -66,12 +66,13 @@ hipError_t launch_box_targets(const BoxLaunch& L, hipStream_t stream);
 hipError_t launch_rcnn_targets(const RcnnLaunch& L, hipStream_t stream);
 // video_kernels.hip
 hipError_t launch_clip_pad(const PadRegion* regions, int n_regions, uint64_t max_bytes, hipStream_t stream);
-// jpeg_kernels.hip
+// jpeg_kernels.hip (region: some record of the call is a region of its image: the <true> instantiations)
 hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, hipStream_t stream);
+                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, bool region, hipStream_t stream);
 // jpeg_huff.hip
 int        jpeg_huff_stage_cap(int lanes);
-hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, int stage_bytes, int32_t* error,
+// region: some file of the call stores only the blocks inside its components' rectangles (jpeg_huff<LANES, true>)
+hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, int stage_bytes, bool region, int32_t* error,
                             hipStream_t stream);
 // png_kernels.hip: png_inflate then png_unfilter over the jobs, one wave per file each
 hipError_t launch_png(const PngJob* jobs, int n_jobs, int unfilter_lds, int32_t* error, hipStream_t stream);

@@ -69,6 +69,12 @@ typedef struct aeon_img_desc {
     int32_t  reserved;
 } aeon_img_desc;
 
+/* A rectangle of an image, in its pixel coordinates (aeon_hip_decode_jpeg_region_batch). */
+typedef struct aeon_region {
+    int32_t x, y; /* first column and row */
+    int32_t w, h; /* columns and rows */
+} aeon_region;
+
 /* POD mirror of augment::image::params (src/augment_image.hpp:99-119): the fields the image
  * and pixel-mask transformers read.  Produced by aeon_make_params (or by aeon itself). */
 typedef struct aeon_aug_params {
@@ -214,6 +220,25 @@ int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx* ctx, int* lanes);
  * 1).  Arithmetic-coded / lossless / 12-bit / 2-component files: AEON_HIP_EUNSUPPORTED. */
 int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
                                const aeon_img_desc* descs, void* dst_base, void* stream);
+/* As aeon_hip_decode_jpeg_batch, but record i holds only the region regions[i] of file i: the pixels
+ * [y, y + h) x [x, x + w) of the whole decode, bit for bit, and descs[i] describes a record of exactly w x h
+ * (channels, stride and offset as above).  The entropy-coded data is still walked whole (a Huffman stream cannot
+ * be entered in the middle); of each component only the 8x8 blocks under the region -- widened by the neighbours
+ * the component's upsampler filters with -- have their coefficients stored, go through the IDCT and are held in
+ * device scratch, and only the region's rows and columns go through the upsampling and colour conversion.  A null
+ * `regions`, or a region that is the whole image, is aeon_hip_decode_jpeg_batch's call exactly.  Before any
+ * launch: a region with w <= 0 or h <= 0, or one that reaches outside the image, is AEON_HIP_EINVAL ("JPEG:
+ * region (x, y, w, h) ... (record i)"), and so is a descriptor whose size is not its region's. */
+int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                      const aeon_img_desc* descs, const aeon_region* regions, void* dst_base,
+                                      void* stream);
+/* The block rectangle of each component that a region of a JPEG file takes through the IDCT, as
+ * aeon_hip_decode_jpeg_region_batch computes it.  Host only, no context needed.  out[4 * k ...] = first block
+ * column, first block row, block columns, block rows of component k (*components of them; zeros for a component
+ * the record does not need: the chroma of a gray record of a YCbCr file).  region null: the whole image.  desc
+ * (may be null) is checked against the region as the decode call checks it, with the same errors. */
+int aeon_jpeg_region_plan(const void* data, size_t size, const aeon_region* region, const aeon_img_desc* desc,
+                          int out_channels, int* components, int32_t* out);
 
 /* ---- video: provider::video (src/provider.cpp:477-517, src/etl_video.{hpp,cpp}) ------------------
  * aeon_avi_frames: video::extractor's demux (MotionJpegCapture, src/cap_mjpeg_decoder.cpp:132-227 over
