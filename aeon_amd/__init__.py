@@ -261,6 +261,9 @@ def lib():
                                            P(ctypes.c_int64)]
         L.aeon_tiff_decoder_route.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
         L.aeon_tiff_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
+        L.aeon_hip_decode_tiff_large_batch.argtypes = L.aeon_hip_decode_tiff_batch.argtypes
+        L.aeon_tiff_large_route.argtypes = L.aeon_tiff_decoder_route.argtypes
+        L.aeon_tiff_gpu_emulate_large.argtypes = L.aeon_tiff_gpu_emulate.argtypes
         L.aeon_avi_frames.argtypes =[ctypes.c_char_p, ctypes.c_size_t, P(AviFrame), ctypes.c_int] + [P(ctypes.c_int)] * 3
         L.aeon_avi_last_error.restype = ctypes.c_char_p
         L.aeon_hip_video_batch.argtypes = [vp, ctypes.c_int, P(ctypes.c_int32), P(ImgDesc), vp, P(AugParams), ctypes.c_int,
@@ -838,13 +841,23 @@ def tiff_decoder_route(data):
     return bool(g.value)
 
 
-def tiff_gpu_emulate(data, mode=DECODE_BGR8, out=None):
+def tiff_large_route(data):
+    """Does Context.decode_tiff_batch(..., large_strips=True) decode this TIFF file on the device
+    (aeon_tiff_large_route)?"""
+    g = ctypes.c_int()
+    _check(lib().aeon_tiff_large_route(bytes(data), len(data), ctypes.byref(g)))
+    return bool(g.value)
+
+
+def tiff_gpu_emulate(data, mode=DECODE_BGR8, out=None, large_strips=False):
     """decode_tiff through the TIFF stage's kernel code run on the host (aeon_tiff_gpu_emulate), into `out` (a
     2-D uint8 view with any row stride) if given.  AeonHipError for a file the stage leaves to the host decoder
-    or one the device would report as corrupt."""
+    or one the device would report as corrupt.  large_strips: with the routing and the kernel code of
+    decode_tiff_batch(..., large_strips=True) (aeon_tiff_gpu_emulate_large)."""
     if out is None:
         out = _tiff_out(data, mode)
-    _check(lib().aeon_tiff_gpu_emulate(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
+    call = lib().aeon_tiff_gpu_emulate_large if large_strips else lib().aeon_tiff_gpu_emulate
+    _check(call(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
     return out
 
 
@@ -1054,18 +1067,19 @@ class Context:
         _check(lib().aeon_hip_decode_pixmap_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
                                                   ctypes.c_void_p(stream or 0)))
 
-    def decode_tiff_batch(self, files, modes, descs, dst_ptr, stream=0):
+    def decode_tiff_batch(self, files, modes, descs, dst_ptr, stream=0, large_strips=False):
         """decode_tiff of TIFF files into device memory (aeon_hip_decode_tiff_batch): files = list of bytes (or a
         JpegFiles, marshalled once), modes[i] = DECODE_BGR8 / DECODE_GRAY8 / DECODE_ANYDEPTH, descs[i] = where
-        record i goes (HWC; ANYDEPTH of a 16-bit gray file: native uint16)."""
+        record i goes (HWC; ANYDEPTH of a 16-bit gray file: native uint16).  large_strips: LZW / PackBits strips and
+        tiles above 32 KiB decode on the device too (aeon_hip_decode_tiff_large_batch, tiff_large_route)."""
         jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
         n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
         m = modes if isinstance(modes, ctypes.Array) else (ctypes.c_int * n)(*[int(x) for x in modes])
         d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
         if len(m) < n or len(d) < n:
             raise ValueError(f"{len(m)} modes / {len(d)} descriptors for {n} files")
-        _check(lib().aeon_hip_decode_tiff_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
-                                                ctypes.c_void_p(stream or 0)))
+        call = lib().aeon_hip_decode_tiff_large_batch if large_strips else lib().aeon_hip_decode_tiff_batch
+        _check(call(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream or 0)))
 
     def set_timing(self, every=1):
         """Time the launches of one call in `every` (0 = off) with HIP events on their stream."""

@@ -302,6 +302,30 @@ int aeon_tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, si
     });
 }
 
+int aeon_tiff_large_route(const void* data, size_t size, int* device)
+{
+    return guarded([&] {
+        if (!data || !device) fail(AEON_HIP_EINVAL, "null argument");
+        TiffPlan P;
+        tiff_plan(data, size, AEON_DECODE_ANYDEPTH, P, true);
+        *device = P.route;
+        return 0;
+    });
+}
+
+int aeon_tiff_gpu_emulate_large(const void* data, size_t size, int mode, void* dst, size_t stride)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        TiffPlan P;
+        tiff_checked_plan(data, size, mode, stride, P);
+        const int r = tiff_gpu_emulate(data, size, mode, dst, stride, true);
+        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "TIFF: the file is not routed to the device (2^31 bytes or more, or a tile row above 16 KiB)");
+        if (r < 0) fail(AEON_HIP_EDEVICE, "TIFF: strip data corrupt or truncated (GPU stage)");
+        return 0;
+    });
+}
+
 // pixel_provider::inspect's sniff and header parse (host.cpp), for callers that hold the file themselves
 int aeon_encoded_info(const void* data, size_t size, int mask, int* format, int* width, int* height, int* file_channels,
                       int* elem_bytes, int* device_route)

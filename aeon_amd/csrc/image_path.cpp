@@ -883,8 +883,10 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
 // behind it, so the kernels' aligned over-reads stay inside the buffer), the host-decoded files' pixels -- filled on
 // the pool, one H2D, then tiff_expand over the strips into the files' scratch, tiff_convert over the bands,
 // tiff_convert_tiled over the tiled bands (launched only when the call holds a tiled file) and a strided device copy per host-decoded file, all on `stream`.
+// large: the opt-in call -- tiff_route_large routes, and the LZW / PackBits strips and tiles above kTiffStripCap form a
+// table of their own behind the tile sources, which tiff_expand_large takes (launched only when it holds work).
 int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
-             const aeon_img_desc* descs, void* dst_base, hipStream_t stream)
+             const aeon_img_desc* descs, void* dst_base, hipStream_t stream, bool large)
 {
     if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !modes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
     if (n == 0) return 0;
@@ -902,7 +904,7 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
         if (!data[i] || !sizes[i]) fail(AEON_HIP_EINVAL, "TIFF: empty file");
         if (modes[i] < AEON_DECODE_BGR8 || modes[i] > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown TIFF decode mode");
         TiffPlan& P = plans[i];
-        tiff_plan(data[i], sizes[i], modes[i], P);
+        tiff_plan(data[i], sizes[i], modes[i], P, large);
         const aeon_img_desc& d = descs[i];
         if (d.width != P.w || d.height != P.h)
             fail(AEON_HIP_EINVAL, "TIFF: record " + std::to_string(i) + " is " + std::to_string(P.w) + "x" + std::to_string(P.h) +
@@ -929,16 +931,19 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
         bytes += (double)P.h * ((double)P.rowb + (double)P.w * P.channels * P.elem_bytes);
     }
     const int n_gpu = (int)jobs_host.size();
-    if (bands.size() > (size_t)INT32_MAX || strips.size() > (size_t)INT32_MAX || T.tbands.size() > (size_t)INT32_MAX || T.tile_src.size() > (size_t)INT32_MAX)
+    if (bands.size() > (size_t)INT32_MAX || strips.size() > (size_t)INT32_MAX || T.large.size() > (size_t)INT32_MAX || T.tbands.size() > (size_t)INT32_MAX || T.tile_src.size() > (size_t)INT32_MAX)
         fail(AEON_HIP_EUNSUPPORTED, "TIFF: too many strips for one call");
-    std::stable_sort(strips.begin(), strips.end(), [](const TiffStrip& a, const TiffStrip& b) { return a.bytes > b.bytes; });
-    // layout: the jobs, the strips, the bands, the tiled bands, the tile sources, then per file the file itself or its pixels (16-byte aligned)
+    const auto longer = [](const TiffStrip& a, const TiffStrip& b) { return a.bytes > b.bytes; };
+    std::stable_sort(strips.begin(), strips.end(), longer);
+    std::stable_sort(T.large.begin(), T.large.end(), longer);
+    // layout: the jobs, the strips, the bands, the tiled bands, the tile sources, the large strips, then per file the file itself or its pixels (16-byte aligned)
     std::vector<size_t> at(n);
     const size_t        strips_at = (size_t)n_gpu * sizeof(TiffJob);
     const size_t        bands_at  = strips_at + strips.size() * sizeof(TiffStrip);
     const size_t        tbands_at = bands_at + bands.size() * sizeof(TiffBand);
     const size_t        tiles_at  = tbands_at + T.tbands.size() * sizeof(TiffTileBand);
-    size_t              total     = tiles_at + T.tile_src.size() * sizeof(uint32_t);
+    const size_t        large_at  = (tiles_at + T.tile_src.size() * sizeof(uint32_t) + 15) & ~(size_t)15;
+    size_t              total     = large_at + T.large.size() * sizeof(TiffStrip);
     for (int i = 0; i < n; i++) {
         const TiffPlan& P = plans[i];
         total             = (total + 15) & ~(size_t)15;
@@ -958,6 +963,7 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
     if (!bands.empty()) std::memcpy(st.pinned + bands_at, bands.data(), bands.size() * sizeof(TiffBand));
     if (!T.tbands.empty()) std::memcpy(st.pinned + tbands_at, T.tbands.data(), T.tbands.size() * sizeof(TiffTileBand));
     if (!T.tile_src.empty()) std::memcpy(st.pinned + tiles_at, T.tile_src.data(), T.tile_src.size() * sizeof(uint32_t));
+    if (!T.large.empty()) std::memcpy(st.pinned + large_at, T.large.data(), T.large.size() * sizeof(TiffStrip));
     each([&](int i) {
         const TiffPlan& P = plans[i];
         uint8_t*        p = st.pinned + at[i];
@@ -983,7 +989,7 @@ int run_tiff(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
     HIP_OK(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, stream));
     if (timed) HIP_OK(hipEventRecord(t.start, stream));
     HIP_OK(launch_tiff((const TiffJob*)st.dev, (const TiffStrip*)(st.dev + strips_at), (int)strips.size(),
-                       (const TiffBand*)(st.dev + bands_at), (int)bands.size(), (const TiffTileBand*)(st.dev + tbands_at),
+                       (const TiffStrip*)(st.dev + large_at), (int)T.large.size(), (const TiffBand*)(st.dev + bands_at), (int)bands.size(), (const TiffTileBand*)(st.dev + tbands_at),
                        (int)T.tbands.size(), (const uint32_t*)(st.dev + tiles_at), stream_error(ctx, stream), stream));
     if (timed) {
         HIP_OK(hipEventRecord(t.stop, stream));
@@ -1009,7 +1015,13 @@ extern "C" {
 int aeon_hip_decode_tiff_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
                                const aeon_img_desc* descs, void* dst_base, void* stream)
 {
-    return guarded([&] { return run_tiff(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream); });
+    return guarded([&] { return run_tiff(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream, false); });
+}
+
+int aeon_hip_decode_tiff_large_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                                     const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return guarded([&] { return run_tiff(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream, true); });
 }
 
 int aeon_hip_decode_pixmap_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,

@@ -78,9 +78,10 @@ hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, i
 hipError_t launch_png(const PngJob* jobs, int n_jobs, int unfilter_lds, int32_t* error, hipStream_t stream);
 // pixmap_kernels.hip: pixmap_convert, one workgroup per band
 hipError_t launch_pixmap(const PixmapJob* jobs, const PixmapBand* bands, int n_bands, hipStream_t stream);
-// tiff_kernels.hip: tiff_expand, one wave per compressed strip or tile, then tiff_convert, one workgroup per band, and
+// tiff_kernels.hip: tiff_expand, one wave per compressed strip or tile, tiff_expand_large, one wave per LZW / PackBits
+// strip or tile above kTiffStripCap, then tiff_convert, one workgroup per band, and
 // tiff_convert_tiled, one per band of the tiled files (each launched only where its table holds work)
-hipError_t launch_tiff(const TiffJob* jobs, const TiffStrip* strips, int n_strips, const TiffBand* bands, int n_bands,
-                       const TiffTileBand* tbands, int n_tbands, const uint32_t* tile_src, int32_t* error, hipStream_t stream);
+hipError_t launch_tiff(const TiffJob* jobs, const TiffStrip* strips, int n_strips, const TiffStrip* large, int n_large,
+                       const TiffBand* bands, int n_bands, const TiffTileBand* tbands, int n_tbands, const uint32_t* tile_src, int32_t* error, hipStream_t stream);
 
 } // namespace aeon_hip

@@ -10,7 +10,9 @@
 // (one workgroup per band of rows) makes the samples native, undoes the horizontal predictor and converts the
 // rows into the record.  A tiled file's tiles stand where strips stand in tiff_expand; tiff_convert_tiled (one
 // workgroup per tiled band) puts their rows together in LDS and converts them.  Files with LZW / PackBits strips
-// or tiles above 32 KiB stay with tiff_decode on the host (tiff_route).  The decode rules are DESIGN section 21.
+// or tiles above 32 KiB stay with tiff_decode on the host (tiff_route) -- unless the caller asks for them
+// (aeon_hip_decode_tiff_large_batch, tiff_route_large): then tiff_expand_large, one wave per such strip or tile, decodes
+// them through a 16 KiB window of LDS, many LZW codes a step.  The decode rules are DESIGN section 21.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -27,6 +29,7 @@ constexpr int    kTiffCorruptBit = 2048;      // device error word: a TIFF strip
 constexpr int    kTiffLanes      = 256;       // tiff_convert workgroup
 constexpr int    kTiffBandBytes  = 16 * 1024; // most source bytes of one band or piece of a row (LDS: these + 8)
 constexpr int    kTiffStripCap   = 32 * 1024; // most decoded bytes of an LZW / PackBits strip on the device (LDS)
+constexpr int    kTiffChunk      = 16 * 1024; // tiff_expand_large: the window of a strip's output that a wave holds in LDS
 constexpr int    kTiffLzwCodes   = 4096;
 constexpr size_t kTiffMaxPixels  = (size_t)1 << 28;
 
@@ -49,7 +52,7 @@ struct alignas(16) TiffJob {
 };
 static_assert(sizeof(TiffJob) % 16 == 0, "TiffJob: 16-byte aligned array elements");
 
-// One compressed strip or tile: tiff_expand's unit of work.
+// One compressed strip or tile: tiff_expand's unit of work, and tiff_expand_large's (an LZW / PackBits one above kTiffStripCap).
 struct alignas(16) TiffStrip {
     int32_t  job, comp;
     uint32_t off, bytes; // the strip's bytes in the file
@@ -95,6 +98,7 @@ struct TiffPlan {
 // The tables of one device call, which tiff_stage appends a file's entries to.
 struct TiffTables {
     std::vector<TiffStrip>    strips;
+    std::vector<TiffStrip>    large; // the LZW / PackBits strips and tiles above kTiffStripCap (tiff_route_large alone admits them)
     std::vector<TiffBand>     bands;
     std::vector<TiffTileBand> tbands;
     std::vector<uint32_t>     tile_src; // per tile of every tiled file: its first byte in the file, or in the file's scratch
@@ -104,7 +108,8 @@ struct TiffTables {
 // MM 00 2A and an IFD offset inside the file; anything else is left to the JPEG parser and its error)
 bool tiff_sniff(const void* data, size_t size);
 // The IFD parse (refusals and messages of tiff_decode), the table and the routing rule.
-void tiff_plan(const void* data, size_t size, int mode, TiffPlan& P);
+// (large: P.route by tiff_route_large)
+void tiff_plan(const void* data, size_t size, int mode, TiffPlan& P, bool large = false);
 // the whole decode on the calling thread into rows `stride` bytes apart; out_elem_bytes (optional): 1 or 2
 void tiff_decode(const void* data, size_t size, int mode, void* dst, size_t stride, int* out_elem_bytes);
 // The routing rule: a file below 2^31 bytes (decoded too, a tiled file's padding included) whose LZW / PackBits
@@ -112,6 +117,9 @@ void tiff_decode(const void* data, size_t size, int mode, void* dst, size_t stri
 // tiff_convert: it walks a wide row in pieces; tiff_convert_tiled cuts a row of tiles into bands, and only a
 // tile whose single row is above kTiffBandBytes, 2,048 pixels of four 16-bit samples, stays on the host.)
 bool tiff_route(const TiffPlan& P, size_t size);
+// The same rule with the strip cap lifted (the 2^31 limits and the tiled band-width limit stay): what the opt-in
+// call sends to the device, its LZW / PackBits strips above the cap through tiff_expand_large.
+bool tiff_route_large(const TiffPlan& P, size_t size);
 // What the decoder's inspect step asks: does this file go through the stage?  tiff_route's plain rule, and for
 // Deflate files the measured one on top, as kPngDecoderMinRatio is for PNG: a wave inflates at the rate of the
 // symbols it decodes (the compressed bytes), the pool's zlib at the rate of the decoded bytes, and 16 host threads
@@ -129,7 +137,7 @@ size_t tiff_scratch_bytes(const TiffPlan& P);
 // file), and the file copied to file_dst (size bytes; the caller pads).
 void tiff_stage(const void* data, size_t size, int mode, const TiffPlan& P, int job, TiffJob& J, TiffTables& T, uint8_t* file_dst);
 // The stage's kernels run on this thread, lane after lane (tiff_strips.hpp): 1 decoded, 0 the file is not routed
-// to the device (nothing written), -1 the device would set kTiffCorruptBit.
-int tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+// to the device (nothing written), -1 the device would set kTiffCorruptBit.  large: the opt-in call's routing.
+int tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride, bool large = false);
 
 } // namespace aeon_hip

@@ -6,7 +6,7 @@
 // tiff_plan / tiff_stage parse the IFD, refuse what a file can be refused for from its header and the first bytes
 // of its strips, build the palette table, the strip and band tables and copy the file; the strips' decoders and
 // the conversion are the kernels' (tiff_kernels.hip).  tiff_gpu_emulate runs the kernels' own code
-// (tiff_strips.hpp) on the host.  The host's LZW and PackBits decoders here are written apart from the device's
+// (tiff_strips.hpp) on the host; with `large`, under the opt-in call's routing (tiff_route_large), tiff_expand_large's too.  The host's LZW and PackBits decoders here are written apart from the device's
 // (a prefix / suffix table, not ranges of the output), and its Deflate is zlib's: the tests hold each against the other.
 //
 // Every read of the file is checked against `size` first.
@@ -351,23 +351,29 @@ void emit_row(const TiffPlan& P, int mode, const uint16_t* s, uint8_t* o)
 
 bool tiff_sniff(const void* data, size_t size) { return sniff((const uint8_t*)data, size); }
 
-bool tiff_route(const TiffPlan& P, size_t size)
+namespace {
+// cap: the most bytes an LZW / PackBits strip or tile may decode to
+bool route(const TiffPlan& P, size_t size, size_t cap)
 {
     if (size >= ((size_t)1 << 31) || P.rowb * (size_t)P.h >= ((size_t)1 << 31)) return false;
     if (P.tw) {
         if ((uint64_t)P.offs.size() * ((P.tile_bytes() + 15) & ~(size_t)15) >= ((uint64_t)1 << 31)) return false;
         if ((size_t)P.tw * P.spp * (P.bps / 8) > (size_t)kTiffBandBytes) return false; // one tile row is the least a band stages
-        return !((P.comp == kTfLzw || P.comp == kTfPackBits) && P.tile_bytes() > (size_t)kTiffStripCap);
+        return !((P.comp == kTfLzw || P.comp == kTfPackBits) && P.tile_bytes() > cap);
     }
-    if ((P.comp == kTfLzw || P.comp == kTfPackBits) && (size_t)P.rps * P.rowb > (size_t)kTiffStripCap) return false;
+    if ((P.comp == kTfLzw || P.comp == kTfPackBits) && (size_t)P.rps * P.rowb > cap) return false;
     return true;
 }
+} // namespace
 
-void tiff_plan(const void* data, size_t size, int mode, TiffPlan& P)
+bool tiff_route(const TiffPlan& P, size_t size) { return route(P, size, (size_t)kTiffStripCap); }
+bool tiff_route_large(const TiffPlan& P, size_t size) { return route(P, size, SIZE_MAX); } // (a strip is below 2^31 as its rows are)
+
+void tiff_plan(const void* data, size_t size, int mode, TiffPlan& P, bool large)
 {
     parse(data, size, P);
     set_mode(P, mode);
-    P.route = tiff_route(P, size) ? 1 : 0;
+    P.route = (large ? tiff_route_large(P, size) : tiff_route(P, size)) ? 1 : 0;
 }
 
 bool tiff_routed(const void* data, size_t size)
@@ -467,6 +473,12 @@ size_t tiff_scratch_bytes(const TiffPlan& P)
 
 namespace {
 
+// The table a compressed strip or tile of `need` decoded bytes belongs to: tiff_expand's, or tiff_expand_large's
+std::vector<TiffStrip>& table_of(TiffTables& T, int comp, size_t need)
+{
+    return (comp == kTfLzw || comp == kTfPackBits) && need > (size_t)kTiffStripCap ? T.large : T.strips;
+}
+
 // A tiled file's tables: every compressed tile a strip of tiff_expand's, tile after tile in the scratch; every row
 // of tiles cut into bands of at most kTiffBandBytes -- all its tiles across times the rows that fit, or, where one
 // row of them is too wide, equal runs of tiles across, row by row.
@@ -475,7 +487,7 @@ void stage_tiles(const TiffPlan& P, int job, TiffJob& J, TiffTables& T)
     J.tw = (int32_t)P.tw, J.tl = (int32_t)P.tl, J.tacross = (int32_t)P.tacross, J.tile0 = (int32_t)T.tile_src.size();
     const size_t need = P.tile_bytes(), slot = (need + 15) & ~(size_t)15, segb = need / P.tl;
     for (size_t t = 0; t < P.offs.size(); t++) {
-        if (P.comp != kTfNone) T.strips.push_back(TiffStrip{job, P.comp, P.offs[t], P.counts[t], 0, (int32_t)P.tl, (uint32_t)need, 0, t * slot, 0});
+        if (P.comp != kTfNone) table_of(T, P.comp, need).push_back(TiffStrip{job, P.comp, P.offs[t], P.counts[t], 0, (int32_t)P.tl, (uint32_t)need, 0, t * slot, 0});
         T.tile_src.push_back(P.comp != kTfNone ? (uint32_t)(t * slot) : P.offs[t]);
     }
     const uint32_t most = (uint32_t)((size_t)kTiffBandBytes / segb), runs = (P.tacross + most - 1) / most, nt = (P.tacross + runs - 1) / runs;
@@ -493,8 +505,7 @@ void stage_tiles(const TiffPlan& P, int job, TiffJob& J, TiffTables& T)
 
 void tiff_stage(const void* data, size_t size, int mode, const TiffPlan& P, int job, TiffJob& J, TiffTables& T, uint8_t* file_dst)
 {
-    std::vector<TiffStrip>& strips = T.strips;
-    std::vector<TiffBand>&  bands = T.bands;
+    std::vector<TiffBand>& bands = T.bands;
     std::memset(&J, 0, sizeof(J));
     J.w = P.w, J.h = P.h, J.spp = P.spp, J.bps = P.bps, J.photo = P.photo, J.pred = P.pred, J.big = P.big, J.comp = P.comp;
     J.mode = mode, J.elem_bytes = P.elem_bytes, J.rowb = (int32_t)P.rowb;
@@ -511,7 +522,7 @@ void tiff_stage(const void* data, size_t size, int mode, const TiffPlan& P, int 
         const size_t need = (size_t)rows * P.rowb;
         int64_t      src = P.offs[s];
         if (P.comp != kTfNone) {
-            strips.push_back(TiffStrip{job, P.comp, P.offs[s], P.counts[s], y0, rows, (uint32_t)need, 0, soff, 0});
+            table_of(T, P.comp, need).push_back(TiffStrip{job, P.comp, P.offs[s], P.counts[s], y0, rows, (uint32_t)need, 0, soff, 0});
             src = (int64_t)soff;
             soff += (need + 15) & ~(size_t)15;
         }
@@ -521,10 +532,10 @@ void tiff_stage(const void* data, size_t size, int mode, const TiffPlan& P, int 
     if (file_dst) std::memcpy(file_dst, data, size);
 }
 
-int tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride)
+int tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride, bool large)
 {
     TiffPlan P;
-    tiff_plan(data, size, mode, P);
+    tiff_plan(data, size, mode, P, large);
     if (!P.route) return 0;
     TiffJob               J;
     TiffTables            T;
@@ -534,6 +545,9 @@ int tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t 
     std::vector<tiffdev::ExpandMem> mem(1);
     for (const TiffStrip& S : T.strips)
         if (!tiffdev::expand_strip(J, S, mem[0])) return -1;
+    std::vector<tiffdev::LargeMem> wide(T.large.empty() ? 0 : 1);
+    for (const TiffStrip& S : T.large)
+        if (!tiffdev::expand_strip_large(J, S, wide[0])) return -1;
     std::vector<uint32_t> tab(256), lds(kTiffBandBytes / 4 + 2);
     for (const TiffBand& B : T.bands) tiffdev::convert_band(J, B, tab.data(), (uint8_t*)lds.data());
     for (const TiffTileBand& B : T.tbands) tiffdev::convert_tiled_band(J, B, T.tile_src.data(), tab.data(), (uint8_t*)lds.data());

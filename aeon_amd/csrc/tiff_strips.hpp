@@ -3,8 +3,9 @@
 // tiff_convert_tiled convert_tiled_band on the 256 lanes of a workgroup; tiff_host.cpp's tiff_gpu_emulate runs the
 // same code with every lane loop walked serially (the PNG_* lane macros of png_inflate.hpp in the wave code, the
 // PM_* ones of pixmap_rows.hpp in the band code), so the CPU tests and the sanitizer program cover what the
-// kernels run.  The one piece written twice is the predictor's scan (scan_rows, finish_segment): shuffles across
-// a wave on the device, a running sum on the host.
+// kernels run.  tiff_expand_large runs expand_strip_large on one wave the same way.  The pieces written twice are the
+// predictor's scan (scan_rows, finish_segment) and the large strips' ballot and scan (wave_mask, wave_exscan):
+// shuffles across a wave on the device, a loop over the lanes on the host.
 // Everything outside a lane loop is wave-uniform.  See DESIGN section 21.
 #pragma once
 #include <stddef.h>
@@ -149,6 +150,272 @@ PNG_FN bool expand_strip(const TiffJob& J, const TiffStrip& T, ExpandMem& M)
     const bool ok = T.comp == kTfLzw ? lzw_strip(M.lzw, I, T.need) : packbits_strip(M.lzw, I, T.need);
     if (ok) store_strip(M.lzw.out, raw, T.need);
     return ok;
+}
+
+// ---- tiff_expand_large: one LZW / PackBits strip of any size --------------------------------------------------
+// The wave holds a window of the strip's output in LDS -- chunk: bytes [base, base + kTiffChunk), base a multiple of
+// kTiffChunk -- and a full window leaves for the scratch (flush_chunk).  A string's source below `base` is read back
+// from the scratch, one at or above it from the window (out_at).  LZW decodes up to 64 codes a step (lzw_large): a
+// lane extracts a code, the lengths of codes that name entries defined inside the batch are resolved by pointer
+// doubling, a scan of the lengths places every code, and the bytes are written in two passes.  The batch's per-lane
+// state lives in 64-entry LDS arrays between PNG_SYNC()s, so the host emulation walks the same lane loops serially;
+// the ballot and the scan (wave_mask, wave_exscan) are written twice.
+
+struct alignas(16) LargeMem {
+    uint8_t  chunk[kTiffChunk];
+    uint32_t pos[kTiffLzwCodes]; // the LZW string table: entry c is `len` bytes of the strip's own output from `pos`
+    uint16_t len[kTiffLzwCodes];
+    uint32_t b_code[64], b_len[64], b_ptr[64], b_pos[64], b_flag[64]; // the batch, per lane
+};
+
+// The strip's output: the scratch, `need` bytes, and where the window stands
+struct Out {
+    PNG_GLOBAL uint8_t* raw;
+    uint32_t            base, need;
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// bit l: lane l's flag is set
+__device__ __forceinline__ uint64_t wave_mask(const uint32_t* flag) { return __ballot(flag[threadIdx.x] != 0); }
+// out[l] = in[0] + ... + in[l - 1]
+__device__ __forceinline__ void wave_exscan(const uint32_t* in, uint32_t* out)
+{
+    const int      lane = (int)threadIdx.x;
+    const uint32_t v = in[lane];
+    uint32_t       s = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(s, d, 64);
+        if (lane >= d) s += up;
+    }
+    out[lane] = s - v;
+}
+#else
+inline uint64_t wave_mask(const uint32_t* flag)
+{
+    uint64_t m = 0;
+    for (int l = 0; l < 64; l++) m |= (uint64_t)(flag[l] != 0) << l;
+    return m;
+}
+inline void wave_exscan(const uint32_t* in, uint32_t* out)
+{
+    uint32_t s = 0;
+    for (int l = 0; l < 64; l++) out[l] = s, s += in[l];
+}
+#endif
+PNG_FN uint32_t first_lane(uint64_t mask) { return mask ? (uint32_t)__builtin_ctzll(mask) : 64u; }
+
+// The first `n` bytes of the window leave for the scratch, 16 bytes per lane and store as store_strip's (n < kTiffChunk
+// only for the strip's last bytes: the scratch has room for `need` rounded up to 16), and the window moves on.  The
+// barrier behind the stores is what lets the wave read its own flushed bytes back: DESIGN section 21.
+PNG_FN void flush_chunk(LargeMem& M, Out& O, uint32_t n)
+{
+    PNG_SYNC();
+    const uint32_t n16 = (n + 15) >> 4;
+    for (uint32_t c = PNG_LANE0; c < n16; c += PNG_LANE_STEP) {
+        const uint32_t* w = (const uint32_t*)(M.chunk + 16 * c);
+        *(PNG_GLOBAL pngdev::u32x4*)(O.raw + O.base + 16 * (size_t)c) = pngdev::u32x4{w[0], w[1], w[2], w[3]};
+    }
+    O.base += (uint32_t)kTiffChunk;
+    PNG_SYNC();
+}
+
+// Output byte q (below the position being written)
+PNG_FN uint32_t out_at(const LargeMem& M, const Out& O, uint32_t q) { return q >= O.base ? M.chunk[q - O.base] : O.raw[q]; }
+
+// n bytes at p from the string at src < p (n <= p - src + 1: a string may overlap its own output by one byte), by
+// all lanes, as lzw_strip copies one: every source is below p.  A copy that reaches the window's end flushes it
+// and goes on in the next.
+PNG_FN void emit_copy(LargeMem& M, Out& O, uint32_t p, uint32_t src, uint32_t n)
+{
+    const uint32_t dist = p - src;
+    for (uint32_t i0 = 0; i0 < n;) {
+        const uint32_t room = O.base + (uint32_t)kTiffChunk - (p + i0), m = n - i0 < room ? n - i0 : room;
+        PNG_SYNC();
+        for (uint32_t i = i0 + PNG_LANE0; i < i0 + m; i += PNG_LANE_STEP)
+            M.chunk[p + i - O.base] = (uint8_t)out_at(M, O, src + (i < dist ? i : i - dist));
+        i0 += m;
+        if (m == room) flush_chunk(M, O, (uint32_t)kTiffChunk);
+    }
+}
+
+// A lane's own word of the strip (in_word is the wave-uniform one)
+PNG_FN uint32_t in_word_lane(const In& I, uint32_t byte) { return byte < I.a + I.n ? I.w[byte >> 2] : 0u; }
+// The w bits (9..12) from bit `bit` of the strip on, MSB first; the caller has checked bit + w against the strip.
+PNG_FN uint32_t code_at(const In& I, uint64_t bit, uint32_t w)
+{
+    const uint32_t at = I.a + (uint32_t)(bit >> 3), word = at & ~3u, sh = 8 * (at & 3) + (uint32_t)(bit & 7);
+    const uint64_t v = (uint64_t)__builtin_bswap32(in_word_lane(I, word)) << 32 | __builtin_bswap32(in_word_lane(I, word + 4));
+    return (uint32_t)(v >> (64 - sh - w)) & ((1u << w) - 1);
+}
+// Between two ClearCodes a code's width follows from the table's next free entry when it is read (the width grows
+// one entry early), so the bits of the k codes read from `next` free entries on are known in advance.
+PNG_FN uint32_t lzw_width(uint32_t next) { return 9 + (next >= 511) + (next >= 1023) + (next >= 2047); }
+PNG_FN uint32_t lzw_grown(uint32_t next, uint32_t k, uint32_t at)
+{
+    const uint32_t first = next >= at ? 0 : at - next; // the first of the k codes read at `at` entries or more
+    return k > first ? k - first : 0;
+}
+PNG_FN uint32_t lzw_bits(uint32_t next, uint32_t k) { return 9 * k + lzw_grown(next, k, 511) + lzw_grown(next, k, 1023) + lzw_grown(next, k, 2047); }
+
+constexpr uint32_t kNoLane = 64;
+
+// TIFF's LZW as lzw_strip decodes it -- same strings, same refusals -- for a strip of any size.  After a ClearCode
+// the first code, a literal, is read alone.  From then on a batch: lane j reads the j-th next code (batch code j
+// is read with next + j free entries and defines entry next + j: where code j - 1 began, its length + 1; j = 0: the
+// previous code's).  The batch ends ahead of the first ClearCode, EOI, code above its free entry or code past the
+// strip's bytes (found by a ballot; met again as lane 0 of the next batch, it is acted on), where the table fills
+// (a batch in a full table defines nothing, all its codes 12 bits), and ahead of the first code that does not fit
+// the window or starts at `need`.  Lengths: 1 for a literal, the table's for a code below `next`; a code next + m
+// names the entry batch code m defines, so its length is that of code m - 1 plus 1 -- a forest over earlier lanes,
+// resolved in 6 rounds of pointer doubling.  An exclusive scan of the lengths gives the positions.  Bytes: first
+// every byte of a literal or of a code below `next` (its source lies below the batch), lanes striding over the
+// bytes, a byte's code found by bisection of the positions; then the codes that name the batch's own entries in
+// lane order, each copied by all lanes.  A batch whose first code does not fit the window is that code alone,
+// copied across the window's end.
+PNG_FN bool lzw_large(LargeMem& M, const In& I, Out& O)
+{
+    const uint64_t total = (uint64_t)8 * I.n;
+    const uint32_t need = O.need;
+    uint64_t       bit = 0;
+    uint32_t       next = 258, p = 0, prev_pos = 0, prev_len = 0;
+    bool           fresh = true; // just cleared: the next code is a literal
+    while (p < need) {
+        if (fresh) {
+            if (bit + 9 > total) return false;
+            const uint32_t code = PNG_UNI(code_at(I, bit, 9));
+            bit += 9;
+            if (code == 256) continue;
+            if (code == 257) break;
+            if (code > 255) return false;
+            PNG_SYNC();
+            for (int l = PNG_LANE0; l < 1; l += PNG_LANE_STEP) M.chunk[p - O.base] = (uint8_t)code;
+            prev_pos = p, prev_len = 1, p++, fresh = false;
+            if (p == O.base + (uint32_t)kTiffChunk) flush_chunk(M, O, (uint32_t)kTiffChunk);
+            continue;
+        }
+        const bool     full = next >= (uint32_t)kTiffLzwCodes;
+        const uint32_t nb = full || (uint32_t)kTiffLzwCodes - next > 64 ? 64 : (uint32_t)kTiffLzwCodes - next;
+        const uint32_t wend = O.base + (uint32_t)kTiffChunk;
+        PNG_SYNC();
+        // each lane its code: what it is, its length or the lane its length hangs on
+        for (uint32_t j = PNG_LANE0; j < 64; j += PNG_LANE_STEP) {
+            const uint32_t nj = full ? next : next + j, w = lzw_width(nj);
+            const uint64_t at = bit + lzw_bits(next, j);
+            uint32_t       code = 257, stop = 1, len = 0, ptr = kNoLane;
+            if (j < nb && at + w <= total) {
+                code = code_at(I, at, w);
+                stop = code == 256 || code == 257 || code > nj; // (a full table: nj is 4096, above every code)
+            }
+            if (!stop) {
+                if (code < 256) len = 1;
+                else if (code < next) len = M.len[code];
+                else if (code == next) len = prev_len + 1;
+                else len = 1, ptr = code - next - 1;
+            }
+            M.b_code[j] = code, M.b_flag[j] = stop, M.b_len[j] = len, M.b_ptr[j] = ptr;
+        }
+        PNG_SYNC();
+        const uint32_t c = first_lane(wave_mask(M.b_flag));
+        if (c == 0) { // a ClearCode; anything else ends the strip short of its rows, or is corrupt
+            if (PNG_UNI(M.b_code[0]) != 256) return false; // (a code past the strip's bytes was noted as EOI)
+            bit += lzw_width(next), next = 258, fresh = true;
+            continue;
+        }
+        // len[j] += len[ptr[j]], ptr[j] = ptr[ptr[j]]: a lane hangs on an earlier one, so 6 rounds reach every root
+        for (int r = 0; r < 6; r++) {
+            for (uint32_t j = PNG_LANE0; j < 64; j += PNG_LANE_STEP) {
+                const uint32_t q = M.b_ptr[j], add = q < kNoLane ? M.b_len[q] : 0, up = q < kNoLane ? M.b_ptr[q] : kNoLane;
+                PNG_SYNC();
+                if (q < kNoLane) M.b_len[j] += add, M.b_ptr[j] = up;
+            }
+            PNG_SYNC();
+        }
+        wave_exscan(M.b_len, M.b_pos);
+        PNG_SYNC();
+        // the codes of this step: those that start below `need` and end (cut at `need`) inside the window
+        for (uint32_t j = PNG_LANE0; j < 64; j += PNG_LANE_STEP) {
+            const uint32_t at = p + M.b_pos[j], len = M.b_len[j];
+            const uint32_t end = at < need ? (len < need - at ? at + len : need) : at;
+            M.b_pos[j] = at, M.b_flag[j] = !(j < c && at < need && end <= wend);
+        }
+        PNG_SYNC();
+        uint32_t   cn = first_lane(wave_mask(M.b_flag));
+        const bool alone = cn == 0; // code 0 crosses the window's end (a literal never does)
+        if (alone) cn = 1;
+        const uint32_t last_pos = PNG_UNI(M.b_pos[cn - 1]), last_len = PNG_UNI(M.b_len[cn - 1]);
+        const uint32_t pend = last_len < need - last_pos ? last_pos + last_len : need;
+        PNG_SYNC();
+        for (uint32_t j = PNG_LANE0; j < 64; j += PNG_LANE_STEP) {
+            if (j < cn && !full) {
+                M.pos[next + j] = j ? M.b_pos[j - 1] : prev_pos;
+                M.len[next + j] = (uint16_t)((j ? M.b_len[j - 1] : prev_len) + 1);
+            }
+            M.b_flag[j] = j < cn && (alone || M.b_code[j] >= next);
+        }
+        if (!alone) {
+            for (uint32_t q = p + PNG_LANE0; q < pend; q += PNG_LANE_STEP) {
+                uint32_t j = 0;
+                for (uint32_t step = 32; step; step >>= 1)
+                    if (j + step < cn && M.b_pos[j + step] <= q) j += step;
+                const uint32_t code = M.b_code[j];
+                if (code < 256) M.chunk[q - O.base] = (uint8_t)code;
+                else if (code < next) M.chunk[q - O.base] = (uint8_t)out_at(M, O, M.pos[code] + (q - M.b_pos[j]));
+            }
+        }
+        PNG_SYNC();
+        for (uint64_t todo = wave_mask(M.b_flag); todo; todo &= todo - 1) {
+            const uint32_t j = (uint32_t)__builtin_ctzll(todo), code = PNG_UNI(M.b_code[j]);
+            const uint32_t at = PNG_UNI(M.b_pos[j]), len = PNG_UNI(M.b_len[j]);
+            const uint32_t src = code < next ? PNG_UNI(M.pos[code]) : code == next ? prev_pos : PNG_UNI(M.b_pos[code - next - 1]);
+            emit_copy(M, O, at, src, len < need - at ? len : need - at);
+        }
+        bit += lzw_bits(next, cn);
+        if (!full) next += cn;
+        prev_pos = last_pos, prev_len = last_len, p = pend;
+        if (p == O.base + (uint32_t)kTiffChunk) flush_chunk(M, O, (uint32_t)kTiffChunk);
+    }
+    if (p < need) return false;
+    if (need > O.base) flush_chunk(M, O, need - O.base);
+    return true;
+}
+
+// PackBits as packbits_strip walks it, the runs written through the window.
+PNG_FN bool packbits_large(LargeMem& M, const In& I, Out& O)
+{
+    const PNG_GLOBAL uint8_t* bytes = (const PNG_GLOBAL uint8_t*)I.w + I.a;
+    const uint32_t            need = O.need;
+    uint32_t                  i = 0, p = 0;
+    while (p < need) {
+        if (i >= I.n) return false;
+        const uint32_t c = in_byte(I, i++);
+        if (c == 128) continue;
+        const bool     lit = c < 128;
+        const uint32_t cnt = lit ? c + 1 : 257 - c;
+        if ((lit ? cnt > I.n - i : i >= I.n) || cnt > need - p) return false;
+        const uint32_t v = lit ? 0 : in_byte(I, i);
+        for (uint32_t k0 = 0; k0 < cnt;) {
+            const uint32_t room = O.base + (uint32_t)kTiffChunk - (p + k0), m = cnt - k0 < room ? cnt - k0 : room;
+            for (uint32_t k = k0 + PNG_LANE0; k < k0 + m; k += PNG_LANE_STEP) M.chunk[p + k - O.base] = lit ? bytes[i + k] : (uint8_t)v;
+            k0 += m;
+            if (m == room) flush_chunk(M, O, (uint32_t)kTiffChunk);
+        }
+        i += lit ? cnt : 1, p += cnt;
+    }
+    if (need > O.base) flush_chunk(M, O, need - O.base);
+    return true;
+}
+
+// One strip of the call's table of large strips into its place in its file's scratch, as expand_strip does a small one.
+PNG_FN bool expand_strip_large(const TiffJob& J, const TiffStrip& T, LargeMem& M)
+{
+    const uint64_t at = J.src + T.off;
+    In             I;
+    I.w = (const PNG_GLOBAL uint32_t*)(at & ~(uint64_t)3), I.a = (uint32_t)(at & 3), I.n = T.bytes;
+    Out O;
+    O.raw = (PNG_GLOBAL uint8_t*)(J.raw + T.soff), O.base = 0, O.need = T.need;
+    if (T.comp == kTfLzw) return lzw_large(M, I, O);
+    return T.comp == kTfPackBits && packbits_large(M, I, O);
 }
 
 // ---- tiff_convert: one band of rows ----------------------------------------------------------------------

@@ -441,6 +441,17 @@ int aeon_tiff_decoder_route(const void* data, size_t size, int* device);
  * builds): decodes like aeon_decode_tiff.  AEON_HIP_EUNSUPPORTED: the file is not routed to the device;
  * AEON_HIP_EDEVICE: what the device reports as corrupt. */
 int aeon_tiff_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+/* The stage with the 32 KiB cap lifted, for callers that ask for it: aeon_hip_decode_tiff_batch in every respect,
+ * but a file's LZW / PackBits strips or tiles may decode to any size (the file and its decoded rows or tiles below
+ * 2^31 bytes, one tile row at most 16 KiB, as before).  Strips and tiles above 32 KiB go through tiff_expand_large,
+ * one wave each: the output through a 16 KiB window of LDS into the scratch, LZW up to 64 codes a step; the others
+ * through tiff_expand, so one file may feed both.  The decoder, the stager and aeon_hip_decode_tiff_batch keep the
+ * cap.  aeon_tiff_large_route: *device 1 when this call decodes the file on the device (errors: the header parser's).
+ * aeon_tiff_gpu_emulate_large: aeon_tiff_gpu_emulate with this call's routing. */
+int aeon_hip_decode_tiff_large_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                                     const aeon_img_desc* descs, void* dst_base, void* stream);
+int aeon_tiff_large_route(const void* data, size_t size, int* device);
+int aeon_tiff_gpu_emulate_large(const void* data, size_t size, int mode, void* dst, size_t stride);
 
 /* batch_sampler::sample_patches (src/augment_image.cpp:567-586) of the factory's batch_samplers[sampler]
  * over n normalized object boxes (xmin, ymin, xmax, ymax in [0, 1]) -- what aeon's tests call as

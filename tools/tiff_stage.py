@@ -11,6 +11,10 @@ code, not the kernels under test).  Classes:
   pal_lzw_tiled      the pal_lzw masks in 128 x 128 LZW tiles (tiff_convert_tiled; pal_lzw is their strip twin)
   rgb512_raw_tiled   512 x 512 RGB in 128 x 128 uncompressed tiles; rgb512_raw: the same images in strips of 5 rows
   rgb512_deflate_tiled  the same in 128 x 128 Deflate tiles with predictor 2; rgb512_deflate: in strips of 5 rows
+  rgb_lzw_64k / rgb_lzw_1strip  the rgb_lzw images in Pillow's default strips (64 KB: 85 rows) and in one strip;
+  pal_lzw_tiled256 / pal_packbits_tiled256  the pal_lzw masks in 256 x 256 LZW / PackBits tiles (pal_packbits_tiled: in
+                  128 x 128 PackBits tiles).  Their strips and tiles are above 32 KiB: `--route large` sends them
+                  through aeon_hip_decode_tiff_large_batch (tiff_expand_large); the plain device route keeps them on the host
 Prints one JSON line per class: records/s, H2D bytes per record and, on the device route, the kernels' GPU time per
 record (aeon_hip_kernel_times, kind "png": the PNG, pixmap and TIFF decode kernels).  `--runs N` starts N fresh
 processes per class and route, alternating the routes, and prints min..max.
@@ -32,7 +36,7 @@ import aeon_amd as A  # noqa: E402
 
 
 def _tiff(im, compression, predictor, rows):
-    info = {278: rows}
+    info = {278: rows} if rows else {}  # (no RowsPerStrip: Pillow's default, strips of 64 KB)
     if predictor:
         info[317] = 2
     buf = io.BytesIO()
@@ -57,7 +61,7 @@ def _tiled(a, photo, compression, predictor, tile=128, palette=None):
             tags = {struct.unpack_from("<H", f, e)[0]: struct.unpack_from("<I", f, e + 8)[0]
                     for e in range(ifd + 2, ifd + 2 + 12 * struct.unpack_from("<H", f, ifd)[0], 12)}
             blobs.append(f[tags[273]:tags[273] + tags[279]])
-    comp = {None: 1, "tiff_lzw": 5, "tiff_adobe_deflate": 8}[compression]
+    comp = {None: 1, "tiff_lzw": 5, "tiff_adobe_deflate": 8, "packbits": 32773}[compression]
     tags = [(256, 4, [w]), (257, 4, [h]), (258, 3, [8] * spp), (259, 3, [comp]), (262, 3, [photo]), (277, 3, [spp]),
             (317, 3, [2 if predictor else 1])] + ([(320, 3, palette)] if palette else []) + \
            [(322, 3, [tile]), (323, 3, [tile]), (324, 4, None), (325, 4, [len(b) for b in blobs])]
@@ -89,13 +93,15 @@ def make_files(kind, n, distinct=32):
     rng = np.random.default_rng(7)
     out = []
     for i in range(distinct):
-        if kind in ("rgb_raw", "rgb_lzw"):
+        if kind in ("rgb_raw", "rgb_lzw", "rgb_lzw_64k", "rgb_lzw_1strip"):
             im = Image.fromarray(np.ascontiguousarray(A.synthetic_image(100 + i, 256, 256, 3)[:, :, ::-1]), "RGB")
-            out.append(_tiff(im, None, False, 10) if kind == "rgb_raw" else _tiff(im, "tiff_lzw", True, 10))
-        elif kind in ("pal_lzw", "pal_lzw_tiled"):
+            rows = {"rgb_lzw_64k": None, "rgb_lzw_1strip": 256}.get(kind, 10)
+            out.append(_tiff(im, None, False, 10) if kind == "rgb_raw" else _tiff(im, "tiff_lzw", True, rows))
+        elif kind.startswith("pal_"):
             mask, pal = _blobs(rng, 512), [int(v) for v in rng.integers(0, 256, 768)]
-            if kind == "pal_lzw_tiled":  # (ColorMap: 3 x 256 shorts, plane after plane)
-                out.append(_tiled(mask, 3, "tiff_lzw", False, palette=[257 * pal[3 * i + c] for c in range(3) for i in range(256)]))
+            if "_tiled" in kind:  # (ColorMap: 3 x 256 shorts, plane after plane)
+                out.append(_tiled(mask, 3, "packbits" if "packbits" in kind else "tiff_lzw", False, tile=256 if kind.endswith("256") else 128,
+                                  palette=[257 * pal[3 * i + c] for c in range(3) for i in range(256)]))
                 continue
             im = Image.fromarray(mask, "P")
             im.putpalette(pal)
@@ -116,7 +122,8 @@ def make_files(kind, n, distinct=32):
 MODE = {"rgb_raw": A.DECODE_BGR8, "rgb_lzw": A.DECODE_BGR8, "pal_lzw": A.DECODE_ANYDEPTH, "gray16_deflate": A.DECODE_ANYDEPTH,
         "gray16_deflate_r3": A.DECODE_ANYDEPTH, "gray16_deflate_r6": A.DECODE_ANYDEPTH, "pal_lzw_tiled": A.DECODE_ANYDEPTH,
         "rgb512_raw": A.DECODE_BGR8, "rgb512_raw_tiled": A.DECODE_BGR8, "rgb512_deflate": A.DECODE_BGR8,
-        "rgb512_deflate_tiled": A.DECODE_BGR8}
+        "rgb512_deflate_tiled": A.DECODE_BGR8, "rgb_lzw_64k": A.DECODE_BGR8, "rgb_lzw_1strip": A.DECODE_BGR8,
+        "pal_lzw_tiled256": A.DECODE_ANYDEPTH, "pal_packbits_tiled256": A.DECODE_ANYDEPTH, "pal_packbits_tiled": A.DECODE_ANYDEPTH}
 
 
 def run_stage(kind, route, n, windows, warmup):
@@ -135,16 +142,17 @@ def run_stage(kind, route, n, windows, warmup):
     stream = torch.cuda.current_stream().cuda_stream
     res = {"class": kind, "route": route, "records": n, "windows": windows,
            "file_bytes_per_record": sum(len(b) for b in files) / n, "record_bytes": off / n}
-    if route == "device":
-        staged = [A.tiff_host_stage(b, mode) for b in files[:32]]
-        assert all(r for r, _ in staged), "a file of the class is not routed to the device"
-        res["h2d_bytes_per_record"] = sum(s for _, s in staged) / len(staged)
+    if route != "host":
+        large = route == "large"
+        assert all(A.tiff_large_route(b) if large else A.tiff_host_stage(b, mode)[0] for b in files[:32]), \
+            "a file of the class is not routed to the device"
+        res["h2d_bytes_per_record"] = sum(len(b) for b in files[:32]) / 32
         jf = A.JpegFiles(files)
         d = (A.ImgDesc * n)(*descs)
         m = (A.ctypes.c_int * n)(*([mode] * n))
 
         def window():
-            ctx.decode_tiff_batch(jf, m, d, dst.data_ptr(), stream)
+            ctx.decode_tiff_batch(jf, m, d, dst.data_ptr(), stream, large_strips=large)
     else:
         res["h2d_bytes_per_record"] = off / n
         pinned = torch.empty(off, dtype=torch.uint8).pin_memory()
@@ -172,7 +180,7 @@ def run_stage(kind, route, n, windows, warmup):
     dt = time.perf_counter() - t0
     res["records_per_s"] = n * windows / dt
     res["ms_per_window"] = dt / windows * 1e3
-    if route == "device":
+    if route != "host":
         ctx.set_timing(1)
         ctx.kernel_times()
         for _ in range(4):
@@ -189,7 +197,8 @@ def run_stage(kind, route, n, windows, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--classes", default="rgb_raw,rgb_lzw,pal_lzw,gray16_deflate")
-    ap.add_argument("--route", default="device", choices=["device", "host"])
+    ap.add_argument("--route", default="device", choices=["device", "large", "host"],
+                    help="with --runs: the device-side route of every pair (device or large), against host")
     ap.add_argument("--records", type=int, default=512)
     ap.add_argument("--windows", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
@@ -203,7 +212,7 @@ def main():
         got = {"device": [], "host": []}
         for _ in range(a.runs):
             for route in ("device", "host"):
-                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--classes", kind, "--route", route,
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--classes", kind, "--route", "large" if (route, a.route) == ("device", "large") else route,
                                       "--records", str(a.records), "--windows", str(a.windows), "--warmup", str(a.warmup)],
                                      capture_output=True, text=True, timeout=300, check=True).stdout
                 got[route].append(json.loads(out.strip().splitlines()[-1]))
