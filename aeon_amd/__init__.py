@@ -227,6 +227,8 @@ def lib():
         L.aeon_jpeg_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 3
         L.aeon_jpeg_entropy_decode.argtypes = ([ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 3 +
                                                [P(ctypes.c_int64)] * 2 + [P(ctypes.c_uint64)])
+        L.aeon_jpeg_prog_route.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
+        L.aeon_jpeg_prog_emulate.argtypes = L.aeon_jpeg_entropy_decode.argtypes
         L.aeon_jpeg_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int), P(ctypes.c_int64)]
         L.aeon_jpeg_huff_layout.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int32),
                                             P(ctypes.c_int32), ctypes.c_int]
@@ -236,6 +238,7 @@ def lib():
         L.aeon_decode_png.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
                                       P(ctypes.c_int)]
         L.aeon_hip_decode_jpeg_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc), vp, vp]
+        L.aeon_hip_decode_jpeg_progressive_batch.argtypes = L.aeon_hip_decode_jpeg_batch.argtypes
         L.aeon_hip_decode_jpeg_region_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc), P(Region),
                                                         vp, vp]
         L.aeon_jpeg_region_plan.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(Region), P(ImgDesc), ctypes.c_int,
@@ -650,6 +653,25 @@ def jpeg_entropy_decode(data):
     return w.value, h.value, n.value, nb.value, nv.value, hv.value
 
 
+def jpeg_prog_route(data):
+    """Does Context.decode_jpeg_batch(..., progressive=True) decode this file's scans on the device
+    (aeon_jpeg_prog_route)?"""
+    g = ctypes.c_int()
+    _check(lib().aeon_jpeg_prog_route(bytes(data), len(data), ctypes.byref(g)))
+    return bool(g.value)
+
+
+def jpeg_prog_emulate(data):
+    """The device code of the progressive path run on the host over the file as laid out for it
+    (aeon_jpeg_prog_emulate): jpeg_entropy_decode's tuple; raises for a file jpeg_prog_route refuses and for one the
+    device would report as corrupt."""
+    w, h, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    nb, nv, hv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_uint64()
+    _check(lib().aeon_jpeg_prog_emulate(bytes(data), len(data), ctypes.byref(w), ctypes.byref(h), ctypes.byref(n),
+                                        ctypes.byref(nb), ctypes.byref(nv), ctypes.byref(hv)))
+    return w.value, h.value, n.value, nb.value, nv.value, hv.value
+
+
 def jpeg_host_stage(data):
     """The JPEG batch decode's host work for one file (aeon_jpeg_host_stage): (GPU entropy decoding?,
     bytes staged for the H2D)."""
@@ -1015,11 +1037,15 @@ class Context:
                                           int(out_h), ctypes.c_void_p(out_ptr), int(item_stride),
                                           ctypes.c_void_p(stream or 0)))
 
-    def decode_jpeg_batch(self, files, descs, dst_ptr, stream=0, regions=None):
+    def decode_jpeg_batch(self, files, descs, dst_ptr, stream=0, regions=None, progressive=False):
         """image::extractor::extract of JPEG files into device memory (aeon_hip_decode_jpeg_batch):
         files = list of bytes (or a JpegFiles, marshalled once), descs[i] = where record i goes (HWC,
         channels 3 = BGR / 1 = gray).  regions (aeon_hip_decode_jpeg_region_batch): per file (x, y, w, h), the part
-        of the image that record i -- of exactly w x h -- holds, or None for the whole image."""
+        of the image that record i -- of exactly w x h -- holds, or None for the whole image.  progressive
+        (aeon_hip_decode_jpeg_progressive_batch): the scans of progressive files decode on the device too
+        (jpeg_prog_route says for which); not together with regions."""
+        if progressive and regions is not None:
+            raise ValueError("regions of progressive files are decoded on the host: pass regions or progressive=True, not both")
         jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
         n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
         d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
@@ -1032,8 +1058,8 @@ class Context:
             _check(lib().aeon_hip_decode_jpeg_region_batch(self._h, n, ptrs, sizes, d, r, ctypes.c_void_p(dst_ptr),
                                                            ctypes.c_void_p(stream or 0)))
             return
-        _check(lib().aeon_hip_decode_jpeg_batch(self._h, n, ptrs, sizes, d, ctypes.c_void_p(dst_ptr),
-                                                ctypes.c_void_p(stream or 0)))
+        call = lib().aeon_hip_decode_jpeg_progressive_batch if progressive else lib().aeon_hip_decode_jpeg_batch
+        _check(call(self._h, n, ptrs, sizes, d, ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream or 0)))
 
     def jpeg_huff_lanes(self):
         """The workgroup size this context's GPU Huffman decoder runs (aeon_hip_jpeg_huff_lanes)."""

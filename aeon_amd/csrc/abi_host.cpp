@@ -424,6 +424,28 @@ int aeon_jpeg_entropy_decode(const void* data, size_t size, int* width, int* hei
     });
 }
 
+int aeon_jpeg_prog_route(const void* data, size_t size, int* device)
+{
+    return guarded([&] {
+        if (!data || !device) fail(AEON_HIP_EINVAL, "null argument");
+        *device = jpeg_prog_route(data, size) ? 1 : 0;
+        return 0;
+    });
+}
+
+int aeon_jpeg_prog_emulate(const void* data, size_t size, int* width, int* height, int* components, int64_t* n_blocks,
+                           int64_t* n_values, uint64_t* hash)
+{
+    return guarded([&] {
+        if (!data || !width || !height || !components || !n_blocks || !n_values || !hash)
+            fail(AEON_HIP_EINVAL, "null argument");
+        const int r = jpeg_prog_emulate(data, size, width, height, components, n_blocks, n_values, hash);
+        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "JPEG: the file's scans are not routed to the device (not progressive, or past the device path's limits)");
+        if (r < 0) fail(AEON_HIP_EDEVICE, "JPEG: entropy-coded data corrupt (GPU stage)");
+        return 0;
+    });
+}
+
 int aeon_jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* staged_bytes)
 {
     return guarded([&] {

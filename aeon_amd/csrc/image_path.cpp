@@ -1119,9 +1119,13 @@ int aeon_hip_video_batch(aeon_hip_ctx* ctx, int n, const int32_t* frame_counts, 
     });
 }
 
-int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
-                                      const aeon_img_desc* descs, const aeon_region* regions, void* dst_base,
-                                      void* stream)
+} // extern "C"
+
+namespace {
+
+// The JPEG calls: regions null for whole files; progressive: the progressive files' scans on the device too.
+int run_jpeg(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
+             const aeon_region* regions, void* dst_base, void* stream, bool progressive)
 {
     return guarded([&] {
         if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
@@ -1141,7 +1145,7 @@ int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx* ctx, int n, const void* cons
         }
         jpeg_decode_batch(ctx->jpeg, n, data, sizes, descs, regions, dst_base, stream_error(ctx, (hipStream_t)stream), (hipStream_t)stream,
                           timed ? t.start : nullptr,
-                          timed ? t.stop : nullptr);
+                          timed ? t.stop : nullptr, progressive);
         if (timed) {
             std::lock_guard<std::mutex> lock(ctx->mu);
             ctx->timers.push_back(t);
@@ -1150,10 +1154,27 @@ int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx* ctx, int n, const void* cons
     });
 }
 
+} // namespace
+
+extern "C" {
+
+int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                      const aeon_img_desc* descs, const aeon_region* regions, void* dst_base,
+                                      void* stream)
+{
+    return run_jpeg(ctx, n, data, sizes, descs, regions, dst_base, stream, false);
+}
+
 int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
                                const aeon_img_desc* descs, void* dst_base, void* stream)
 {
-    return aeon_hip_decode_jpeg_region_batch(ctx, n, data, sizes, descs, nullptr, dst_base, stream);
+    return run_jpeg(ctx, n, data, sizes, descs, nullptr, dst_base, stream, false);
+}
+
+int aeon_hip_decode_jpeg_progressive_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                           const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return run_jpeg(ctx, n, data, sizes, descs, nullptr, dst_base, stream, true);
 }
 
 int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx* ctx, int* lanes)

@@ -9,7 +9,8 @@
 // a few hundred bits decoded in parallel, self-synchronising from guessed starts, then a prefix sum
 // of block counts and DC differences and a final decode that writes every block's coefficients.
 // Progressive and multi-scan files are entropy-decoded on the host pool into the sparse stream (per
-// 8x8 block a 64-bit zigzag mask of its non-zero coefficients plus those values, int16).  Everything
+// 8x8 block a 64-bit zigzag mask of its non-zero coefficients plus those values, int16); the opt-in progressive
+// call decodes the scans of progressive files on the GPU instead, one wave per scan (jpeg_prog.hip).  Everything
 // per pixel -- dequantisation, the ISLOW IDCT, fancy upsampling and the colour conversion (YCbCr -> BGR
 // in jpeg_color; CMYK, YCCK and RGB sources in jpeg_color4) -- runs on the GPU, which writes the
 // decoded HWC records straight into the device source arena the augmentation kernels read.  A file
@@ -40,9 +41,11 @@ void       jpeg_state_destroy(JpegState* s);
 // The host functions of the stage (jpeg_host.cpp).  jpeg_decode_batch: n files decoded into the records at
 // dst_base on `stream`; `error` is the stream's device error word, start / stop optional timing events.
 // regions (may be null: every file whole): the part of file i that record i holds (aeon_hip_decode_jpeg_region_batch).
+// progressive (aeon_hip_decode_jpeg_progressive_batch): the progressive files that jpeg_prog_route takes decode their
+// scans on the device (jpeg_prog.hip) instead of the pool.
 void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
                        const aeon_region* regions, void* dst_base, int32_t* error, ihipStream_t* stream,
-                       ihipEvent_t* start, ihipEvent_t* stop);
+                       ihipEvent_t* start, ihipEvent_t* stop, bool progressive = false);
 // the block rectangle of each component that a region of a file takes (aeon_jpeg_region_plan, no device): out =
 // per component bx, by, bw, bh (a component the record does not need: zeros); validates as the decode call does
 void jpeg_region_plan(const void* data, size_t size, const aeon_region* region, const aeon_img_desc* desc, int out_cn,
@@ -57,6 +60,12 @@ void jpeg_host_stage(const void* data, size_t size, int* gpu_entropy, int64_t* s
 // 1 when decoded, -1 on corrupt entropy-coded data
 int  jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, int* h, int* ncomp, int64_t* n_blocks,
                               int64_t* n_values, uint64_t* hash, int* rounds);
+// does the progressive call decode this file's scans on the device (aeon_jpeg_prog_route)?  Header errors throw.
+bool jpeg_prog_route(const void* data, size_t size);
+// jpeg_prog.hip's code run on the host over prepare_prog's layout, one wave after another, level by level, summarised
+// as jpeg_entropy_only summarises the host decoder: 0 when the file is not routed, 1 when decoded, -1 on corrupt data
+int  jpeg_prog_emulate(const void* data, size_t size, int* w, int* h, int* ncomp, int64_t* n_blocks, int64_t* n_values,
+                       uint64_t* hash);
 // how prepare_gpu lays a file out for jpeg_huff<lanes> (aeon_jpeg_huff_layout, for tests): out = GPU entropy
 // decoding?, segments, subsequences, sub_bits, the data's bytes (what the kernel compares with its stage cap),
 // the largest segment's subsequences, then kHuffSubMin, kHuffSubMax, kHuffLanes, kHuffStageMax; seg_nsub (may
@@ -209,6 +218,49 @@ struct alignas(16) JpegHuffFile {
     int32_t  data_words; // the data's 32-bit words (padding included)
 };
 static_assert(sizeof(JpegHuffFile) % 16 == 0, "JpegHuffFile: 16-byte aligned array elements");
+
+// ---- progressive files on the device (jpeg_prog.hip) ----
+//
+// prepare_prog lays a progressive (SOF2) file out as scans, each split at its restart markers into segments; one wave
+// decodes one (scan, segment) unit.  A scan's level is 1 + the highest level of an earlier scan of the file that
+// shares a component with it and overlaps its coefficient range ([0, 0] for a DC scan, [Ss, Se] for an AC scan), so
+// the units of one level touch disjoint coefficients and run in one launch; the levels run in order.
+
+constexpr int kProgMaxScans = 64;        // scans a file may hold on the device path (libjpeg's scripts: 6 and 10)
+constexpr int kProgMaxTabs  = 128;       // distinct Huffman tables its scans may name
+constexpr int kProgWaves    = 2;         // units (waves) per jpeg_prog_scan workgroup: a huff::Tables each in LDS
+constexpr int kProgMaskBlocks = 256;     // blocks per jpeg_prog_mask workgroup
+
+// One scan of a progressive file (device addresses).  A table slot t holds table tab[t] of the file's pool (-1: none):
+// a DC-first scan's DC tables sit in slots 0-1, an AC scan's table in slot 0; DC refinement scans have none.
+struct alignas(16) JpegProgScan {
+    uint64_t data;                // the file's unstuffed entropy-coded bytes (every scan's), 4-byte aligned
+    uint64_t pool;                // JpegHuffTab[]: the file's tables as they stood at the scans that use them
+    uint64_t dvals[kJpegMaxComp]; // per scan component: 64 int16 per block of its frame component
+    uint64_t blk_tab[2];          // byte c = MCU block c: scan component | x << 2 | y << 4 | its DC table slot << 6
+    int32_t  bw[kJpegMaxComp], hs[kJpegMaxComp], vs[kJpegMaxComp]; // per scan component: blocks per row, blocks per MCU
+    int32_t  tab[kJpegHuffSlots];
+    int32_t  ntab;                // slots in use
+    int32_t  Ss, Se, Ah, Al;
+    int32_t  bpm, mcux;           // blocks per MCU, MCUs per row (a one-component scan: 1, the component's own grid)
+    int32_t  pad_[3];
+};
+static_assert(sizeof(JpegProgScan) % 16 == 0, "JpegProgScan: 16-byte aligned array elements");
+
+// One unit: MCUs [first_mcu, first_mcu + n_mcu) of scan `scan` from bits [start_bit, end_bit) of the file's data (a
+// restart interval, or the whole scan; bits at or past end_bit read as zeros).
+struct alignas(16) JpegProgUnit {
+    int32_t  scan;
+    uint32_t start_bit, end_bit;
+    int32_t  first_mcu, n_mcu;
+    int32_t  pad_[3];
+};
+
+// Closing pass: the masks of blocks [0, count) of a component from its dense coefficients.
+struct alignas(16) JpegProgMask {
+    uint64_t dvals, blocks;
+    int32_t  count, pad_[3];
+};
 
 // Device error word bit of a GPU-decoded file whose entropy-coded data is corrupt or truncated.
 constexpr int kJpegCorruptBit = 256;

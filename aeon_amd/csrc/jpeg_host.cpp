@@ -25,6 +25,7 @@
 #include "host.hpp"
 #include "jpeg.hpp"
 #include "jpeg_huff.hpp"
+#include "jpeg_prog.hpp"
 #include "launch.hpp"
 
 namespace aeon_hip {
@@ -749,23 +750,15 @@ void check_code_space(const uint8_t* counts)
     }
 }
 
-// The markers, tables and scan header of a file for the GPU entropy decoder, and its entropy-coded
-// bytes unstuffed into the arena (segments split at RSTn when DRI is set; the data ends at the first
-// other marker -- jdhuff.c's fill_bit_buffer: zeros follow a marker -- or with the file).  Returns false
-// for the files the host decodes instead (decode_file): progressive (SOF2), a scan without every
-// component (non-interleaved multi-scan), a second scan, more than kHuffMaxBpm blocks per MCU, data
-// past 2^28 bytes.  Header errors throw as decode_file's do.
-bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, int lanes)
-{
-    const uint8_t* p = nullptr;
-    parse_frame(d, size, f, &p);
-    if (f.progressive) return false;
-    const uint8_t* end   = d + size;
-    const size_t   used0 = a.used;
-    JpegHuffTab    dct[4], act[4];
-    bool           dset[4] = {false, false, false, false}, aset[4] = {false, false, false, false};
-    int            restart = 0;
-    auto segment = [&](int m, const uint8_t* s, int len) {
+// The DHT / DQT / DRI / APPn segments of a file as the device paths read them (prepare_gpu, prepare_prog): each
+// Huffman table as the file defines it, validated as Huffman::build validates it.
+struct DeviceTabs {
+    JpegHuffTab dct[4], act[4];
+    bool        dset[4] = {false, false, false, false}, aset[4] = {false, false, false, false};
+    int         dpool[4] = {-1, -1, -1, -1}, apool[4] = {-1, -1, -1, -1}; // prepare_prog: the table's place in the file's pool
+    int         restart = 0;
+    void segment(Frame& f, int m, const uint8_t* s, int len)
+    {
         const uint8_t* e = s + len - 2;
         if (m == 0xC4) {
             while (s < e) {
@@ -780,6 +773,7 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
                 std::memset(t.symbols, 0, sizeof(t.symbols));
                 std::memcpy(t.symbols, s + 17, tot);
                 (tc ? aset : dset)[th] = true;
+                (tc ? apool : dpool)[th] = -1;
                 s += 17 + tot;
             }
         } else if (m == 0xDB) {
@@ -796,7 +790,67 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
         } else {
             app_segment(f, m, s, len);
         }
-    };
+    }
+};
+
+// A scan's entropy-coded bytes from p, unstuffed into out (room for what is left of the file): split into segments at
+// RSTn when `restart` is set (seg: each one's first byte), ended at the first other marker -- jdhuff.c's
+// fill_bit_buffer: zeros follow a marker -- or with the file (truncated: the segment that ran into it, else -1).
+// Returns the bytes written; p is left at the marker that ended the data.
+size_t unstuff_scan(const uint8_t*& p, const uint8_t* end, int restart, int nseg_need, uint8_t* out, std::vector<uint32_t>& seg,
+                    int& truncated)
+{
+    size_t o = 0;
+    seg.assign(1, 0);
+    truncated = -1;
+    for (;;) {
+        const uint8_t* ff   = (const uint8_t*)std::memchr(p, 0xFF, (size_t)(end - p));
+        const uint8_t* stop = ff ? ff : end;
+        std::memcpy(out + o, p, (size_t)(stop - p));
+        o += (size_t)(stop - p);
+        if (!ff) { // the data runs into the end of the file
+            truncated = (int)seg.size() - 1;
+            p         = end;
+            break;
+        }
+        const int nx = ff + 1 < end ? ff[1] : 0xD9;
+        if (nx == 0) {
+            out[o++] = 0xFF, p = ff + 2;
+        } else if (restart && nx >= 0xD0 && nx <= 0xD7) {
+            seg.push_back((uint32_t)o), p = ff + 2;
+        } else if (restart && (int)seg.size() < nseg_need) {
+            // another marker inside a restart interval: its data ends (zeros follow), and the next
+            // interval starts after the next RSTn, wherever it is (decode_file's Bits::restart)
+            const uint8_t* r = ff;
+            while (r + 1 < end && !(r[0] == 0xFF && r[1] >= 0xD0 && r[1] <= 0xD7)) r++;
+            if (r + 1 >= end) {
+                p = ff;
+                break;
+            }
+            seg.push_back((uint32_t)o), p = r + 2;
+        } else {
+            p = ff; // a marker ends the scan's data
+            break;
+        }
+    }
+    return o;
+}
+
+// The markers, tables and scan header of a file for the GPU entropy decoder, and its entropy-coded
+// bytes unstuffed into the arena (segments split at RSTn when DRI is set; the data ends at the first
+// other marker -- jdhuff.c's fill_bit_buffer: zeros follow a marker -- or with the file).  Returns false
+// for the files the host decodes instead (decode_file): progressive (SOF2), a scan without every
+// component (non-interleaved multi-scan), a second scan, more than kHuffMaxBpm blocks per MCU, data
+// past 2^28 bytes.  Header errors throw as decode_file's do.
+bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, int lanes)
+{
+    const uint8_t* p = nullptr;
+    parse_frame(d, size, f, &p);
+    if (f.progressive) return false;
+    const uint8_t* end   = d + size;
+    const size_t   used0 = a.used;
+    DeviceTabs     tabs;
+    auto           segment = [&](int m, const uint8_t* sg, int len) { tabs.segment(f, m, sg, len); };
     { // tables before SOF
         const uint8_t* q = d + 2;
         while (q < p) {
@@ -852,7 +906,7 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
         }
         if (ns != f.ncomp) return false; // components in separate scans: the host decoder
         for (int i = 0; i < ns; i++)
-            if (!dset[f.c[sc[i]].td] || !aset[f.c[sc[i]].ta]) bad("scan uses an undefined Huffman table");
+            if (!tabs.dset[f.c[sc[i]].td] || !tabs.aset[f.c[sc[i]].ta]) bad("scan uses an undefined Huffman table");
         if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0)
             unsupported("progressive scan parameters in a sequential file");
         p += len;
@@ -869,6 +923,7 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
         if (d == 2 || q == 2) return false;
         dids[d] = td, aids[q] = ta, dslot[sc[i]] = d, aslot[sc[i]] = q;
     }
+    const int restart = tabs.restart;
     // the scan's shape; each MCU block's byte: component | x << 2 | y << 4 | DC slot << 6 | AC slot - 2 << 7
     const bool inter = ns > 1;
     g.interleaved    = inter;
@@ -896,40 +951,8 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
     if (left >= ((size_t)1 << 28)) return false;
     g.data       = (size_t)(a.reserve(left + 16) - a.host.data());
     uint8_t* out = a.host.data() + g.data;
-    size_t   o   = 0;
     auto&    seg = a.seg;
-    seg.assign(1, 0);
-    g.truncated = -1;
-    for (;;) {
-        const uint8_t* ff   = (const uint8_t*)std::memchr(p, 0xFF, (size_t)(end - p));
-        const uint8_t* stop = ff ? ff : end;
-        std::memcpy(out + o, p, (size_t)(stop - p));
-        o += (size_t)(stop - p);
-        if (!ff) { // the data runs into the end of the file
-            g.truncated = (int)seg.size() - 1;
-            p           = end;
-            break;
-        }
-        const int nx = ff + 1 < end ? ff[1] : 0xD9;
-        if (nx == 0) {
-            out[o++] = 0xFF, p = ff + 2;
-        } else if (restart && nx >= 0xD0 && nx <= 0xD7) {
-            seg.push_back((uint32_t)o), p = ff + 2;
-        } else if (restart && (int)seg.size() < nseg_need) {
-            // another marker inside a restart interval: its data ends (zeros follow), and the next
-            // interval starts after the next RSTn, wherever it is (decode_file's Bits::restart)
-            const uint8_t* r = ff;
-            while (r + 1 < end && !(r[0] == 0xFF && r[1] >= 0xD0 && r[1] <= 0xD7)) r++;
-            if (r + 1 >= end) {
-                p = ff;
-                break;
-            }
-            seg.push_back((uint32_t)o), p = r + 2;
-        } else {
-            p = ff; // a marker ends the scan's data
-            break;
-        }
-    }
+    const size_t o = unstuff_scan(p, end, restart, nseg_need, out, seg, g.truncated);
     std::memset(out + o, 0, 16);
     a.used       = g.data + ((o + 16 + 3) & ~(size_t)3);
     g.data_words = (int)(((o + 16 + 3) & ~(size_t)3) / 4);
@@ -983,15 +1006,197 @@ bool prepare_gpu(const uint8_t* d, size_t size, Frame& f, Arena& a, GpuScan& g, 
     JpegHuffTab* tab = (JpegHuffTab*)(a.host.data() + g.tabs);
     std::memset(tab, 0, kJpegHuffSlots * sizeof(JpegHuffTab));
     for (int d = 0; d < 2; d++)
-        if (dids[d] >= 0) tab[d] = dct[dids[d]];
+        if (dids[d] >= 0) tab[d] = tabs.dct[dids[d]];
     for (int q = 0; q < 2; q++)
-        if (aids[q] >= 0) tab[2 + q] = act[aids[q]];
+        if (aids[q] >= 0) tab[2 + q] = tabs.act[aids[q]];
     g.segs = (size_t)(a.reserve(segs.size() * sizeof(JpegHuffSeg)) - a.host.data());
     std::memcpy(a.host.data() + g.segs, segs.data(), segs.size() * sizeof(JpegHuffSeg));
     g.sub_seg   = (size_t)(a.reserve((size_t)nsub * sizeof(int32_t)) - a.host.data());
     int32_t* ss = (int32_t*)(a.host.data() + g.sub_seg);
     for (int s = 0; s < nseg_need; s++)
         for (int j = 0; j < segs[s].nsub; j++) *ss++ = s;
+    return true;
+}
+
+// A progressive file laid out for jpeg_prog.hip: its scans in file order (device addresses filled by the caller: here
+// data, pool and dvals hold nothing yet, comp names each scan component's frame component), their units scan after
+// scan, and where its table pool and its unstuffed bytes sit in the worker's arena.
+struct ProgFile {
+    std::vector<JpegProgScan> scans;
+    std::vector<int>          level; // per scan
+    std::vector<int>          comp;  // kJpegMaxComp per scan
+    std::vector<JpegProgUnit> units; // .scan: the file's scan
+    size_t                    pool = 0, data = 0;
+    int                       nlevels = 0;
+};
+
+// The markers, tables and scans of a progressive file for jpeg_prog.hip: parsed and checked exactly as decode_file
+// parses and checks them (the same refusals, start_pass_phuff_decoder's among them); per SOS a scan record with the
+// Huffman tables in force there (snapshots in the file's pool: progressive files redefine DHT between scans), its
+// block order (an interleaved scan: MCU order; a one-component scan: the component's own ceil(dw/8) x ceil(dh/8) grid
+// at row pitch bw), its level, and its bytes unstuffed behind the earlier scans' (unstuff_scan), one unit per restart
+// interval.  Returns false for the files the host decodes (decode_file): sequential ones, more than kProgMaxScans
+// scans or kProgMaxTabs tables, a DC-first scan naming more than two DC tables (huff::fast_entry's DC slots), data at
+// or past 2^28 bytes (bit positions are 31-bit), and data that runs into the end of the file without a marker (where
+// the host decoder's refusal depends on its own buffering).
+bool prepare_prog(const uint8_t* d, size_t size, Frame& f, Arena& a, ProgFile& P)
+{
+    const uint8_t* p = nullptr;
+    parse_frame(d, size, f, &p);
+    if (!f.progressive) return false;
+    const uint8_t* end   = d + size;
+    const size_t   used0 = a.used;
+    DeviceTabs     tabs;
+    auto           segment = [&](int m, const uint8_t* sg, int len) { tabs.segment(f, m, sg, len); };
+    { // tables before SOF
+        const uint8_t* q = d + 2;
+        while (q < p) {
+            while (q < p && *q != 0xFF) q++;
+            while (q < p && *q == 0xFF) q++;
+            if (q >= p) break;
+            const int m = *q++;
+            if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+            const int len = be16(q);
+            if (m == 0xC0 || m == 0xC1 || m == 0xC2) break;
+            segment(m, q + 2, len);
+            q += len;
+        }
+    }
+    if ((size_t)(end - p) >= ((size_t)1 << 28)) return false;
+    P = ProgFile();
+    std::vector<JpegHuffTab> pool;
+    // every scan's bytes fit what is left of the file; the pool follows once its size is known
+    P.data       = (size_t)(a.reserve((size_t)(end - p) + 16) - a.host.data());
+    size_t o     = 0; // bytes unstuffed so far
+    auto   route_host = [&]() {
+        a.used = used0;
+        return false;
+    };
+    for (;;) {
+        while (p < end && *p != 0xFF) p++;
+        while (p < end && *p == 0xFF) p++;
+        if (p >= end) {
+            if (P.scans.empty()) bad("no scan data");
+            break; // missing EOI: tolerated, as libjpeg does
+        }
+        const int m = *p++;
+        if (m == 0xD9) {
+            if (P.scans.empty()) bad("no scan data");
+            break;
+        }
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+        if (p + 2 > end) bad("truncated marker segment");
+        const int len = be16(p);
+        if (len < 2 || p + len > end) bad("truncated marker segment");
+        if (m != 0xDA) {
+            if ((m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) bad("second frame header");
+            segment(m, p + 2, len);
+            p += len;
+            continue;
+        }
+        if (len < 6) bad("bad scan header");
+        const uint8_t* s  = p + 2;
+        const int      ns = s[0];
+        if (ns < 1 || ns > f.ncomp || len != 6 + 2 * ns) bad("bad scan header");
+        int sc[kJpegMaxComp] = {0, 0, 0, 0};
+        for (int i = 0; i < ns; i++) {
+            const int cid = s[1 + 2 * i], t = s[2 + 2 * i];
+            int       k   = 0;
+            while (k < f.ncomp && f.c[k].id != cid) k++;
+            if (k == f.ncomp) bad("scan names an unknown component");
+            f.c[k].td = t >> 4, f.c[k].ta = t & 15;
+            if (f.c[k].td > 3 || f.c[k].ta > 3) bad("bad Huffman table selector");
+            if (!f.qset[f.c[k].tq]) bad("component uses an undefined quantisation table");
+            sc[i] = k;
+        }
+        if (ns > 1) { // (jdinput.c per_scan_setup, as decode_file)
+            int mb = 0;
+            for (int i = 0; i < ns; i++) mb += f.c[sc[i]].h * f.c[sc[i]].v;
+            if (mb > 10) bad("sampling factors too large for an interleaved scan");
+        }
+        JpegProgScan S;
+        std::memset(&S, 0, sizeof(S));
+        S.Ss = s[1 + 2 * ns], S.Se = s[2 + 2 * ns], S.Ah = s[3 + 2 * ns] >> 4, S.Al = s[3 + 2 * ns] & 15;
+        // jdphuff.c start_pass_phuff_decoder's checks
+        const bool ok = (S.Ss == 0 ? S.Se == 0 : (S.Se >= S.Ss && S.Se <= 63 && ns == 1)) && S.Al <= 13 &&
+                        (S.Ah == 0 || S.Al == S.Ah - 1);
+        if (!ok) bad("bad progressive scan parameters");
+        for (int i = 0; i < ns; i++) {
+            const Comp& c = f.c[sc[i]];
+            if ((S.Ss == 0 && S.Ah == 0 && !tabs.dset[c.td]) || (S.Ss > 0 && !tabs.aset[c.ta]))
+                bad("scan uses an undefined Huffman table");
+        }
+        p += len;
+        if ((int)P.scans.size() == kProgMaxScans) return route_host();
+        // the scan's tables: snapshots in the pool, taken once per definition
+        for (int t = 0; t < kJpegHuffSlots; t++) S.tab[t] = -1;
+        int  slot_of[kJpegMaxComp] = {0, 0, 0, 0};
+        auto pooled = [&](bool ac, int th) {
+            int& at = (ac ? tabs.apool : tabs.dpool)[th];
+            if (at < 0) at = (int)pool.size(), pool.push_back((ac ? tabs.act : tabs.dct)[th]);
+            return at;
+        };
+        if (S.Ss > 0) {
+            S.tab[0] = pooled(true, f.c[sc[0]].ta), S.ntab = 1;
+        } else if (S.Ah == 0) {
+            for (int i = 0; i < ns; i++) {
+                const int id = pooled(false, f.c[sc[i]].td);
+                int       t  = 0;
+                while (t < S.ntab && S.tab[t] != id) t++;
+                if (t == 2) return route_host();
+                if (t == S.ntab) S.tab[S.ntab++] = id;
+                slot_of[i] = t;
+            }
+        }
+        if ((int)pool.size() > kProgMaxTabs) return route_host();
+        // block order
+        int n_mcu = 0;
+        for (int i = 0; i < ns; i++) {
+            const Comp& c = f.c[sc[i]];
+            S.bw[i] = c.bw, S.hs[i] = ns > 1 ? c.h : 1, S.vs[i] = ns > 1 ? c.v : 1;
+            for (int y = 0; y < S.vs[i]; y++)
+                for (int x = 0; x < S.hs[i]; x++) {
+                    S.blk_tab[S.bpm >> 3] |= (uint64_t)(i | x << 2 | y << 4 | slot_of[i] << 6) << (8 * (S.bpm & 7));
+                    S.bpm++;
+                }
+        }
+        if (ns > 1) S.mcux = f.mcux, n_mcu = f.mcux * f.mcuy;
+        else S.mcux = (f.c[sc[0]].dw + 7) / 8, n_mcu = S.mcux * ((f.c[sc[0]].dh + 7) / 8);
+        // level: past every earlier scan that shares a component and a coefficient
+        int       level = 0;
+        const int lo = S.Ss, hi = S.Ss == 0 ? 0 : S.Se;
+        for (size_t j = 0; j < P.scans.size(); j++) {
+            const JpegProgScan& E = P.scans[j];
+            if ((E.Ss == 0 ? 0 : E.Se) < lo || E.Ss > hi) continue;
+            bool shares = false;
+            for (int i = 0; i < ns; i++)
+                for (int e = 0; e < kJpegMaxComp; e++) shares |= P.comp[kJpegMaxComp * j + e] == sc[i];
+            if (shares) level = std::max(level, P.level[j] + 1);
+        }
+        // bytes and units
+        const int restart   = tabs.restart ? tabs.restart : n_mcu;
+        const int nseg_need = (n_mcu + restart - 1) / restart;
+        int       truncated = -1;
+        const size_t n = unstuff_scan(p, end, tabs.restart, nseg_need, a.host.data() + P.data + o, a.seg, truncated);
+        if (truncated >= 0 && truncated < nseg_need) return route_host();
+        for (int sg = 0; sg < nseg_need; sg++) {
+            const size_t b0 = sg < (int)a.seg.size() ? a.seg[sg] : n, b1 = sg + 1 < (int)a.seg.size() ? a.seg[sg + 1] : n;
+            P.units.push_back({(int32_t)P.scans.size(), (uint32_t)(8 * (o + b0)), (uint32_t)(8 * (o + b1)), sg * restart,
+                               std::min(restart, n_mcu - sg * restart), {0, 0, 0}});
+        }
+        o += n;
+        for (int i = 0; i < kJpegMaxComp; i++) P.comp.push_back(i < ns ? sc[i] : -1);
+        P.scans.push_back(S);
+        P.level.push_back(level);
+        P.nlevels = std::max(P.nlevels, level + 1);
+        // on to the next marker that is not RSTn, as decode_file does after a scan
+        while (p + 1 < end && !(p[0] == 0xFF && p[1] != 0 && !(p[1] >= 0xD0 && p[1] <= 0xD7))) p++;
+    }
+    decide_colorspace(f);
+    std::memset(a.host.data() + P.data + o, 0, 16);
+    a.used = P.data + ((o + 16 + 3) & ~(size_t)3);
+    P.pool = (size_t)(a.reserve(pool.size() * sizeof(JpegHuffTab)) - a.host.data());
+    std::memcpy(a.host.data() + P.pool, pool.data(), pool.size() * sizeof(JpegHuffTab));
     return true;
 }
 
@@ -1137,7 +1342,7 @@ void jpeg_state_destroy(JpegState* s)
 // start / stop (may be null): events recorded around the GPU launches (kernel timing)
 void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
                        const aeon_region* regions, void* dst_base, int32_t* error, hipStream_t stream, hipEvent_t start,
-                       hipEvent_t stop)
+                       hipEvent_t stop, bool progressive)
 {
     std::lock_guard<std::mutex> lock(S->mu);
     // (AEON_HIP_JPEG_PROFILE=1, development: host time per phase of each call on stderr)
@@ -1166,7 +1371,8 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     constexpr size_t     NC = kJpegMaxComp;
     std::vector<size_t>  blk(NC * (size_t)n), val(n);
     std::vector<GpuScan> gs(n);
-    std::vector<char>    on_gpu(n, 0);
+    std::vector<char>    on_gpu(n, 0); // 1: jpeg_huff decodes the file, 2: jpeg_prog_scan does (the progressive call)
+    std::vector<ProgFile> pf(progressive ? n : 0);
     std::vector<aeon_region> reg(n);            // the record's region of its image
     std::vector<JpegRect>    rect(NC * (size_t)n); // and the block rectangle of each component it reads
     S->pool->run_indexed(n, [&](int i, int w) {
@@ -1177,6 +1383,8 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
             const uint8_t* b = (const uint8_t*)data[i];
             if (S->gpu_huff && prepare_gpu(b, sizes[i], frames[i], arenas[w], gs[i], S->huff_lanes)) {
                 on_gpu[i] = 1;
+            } else if (progressive && (frames[i] = Frame(), prepare_prog(b, sizes[i], frames[i], arenas[w], pf[i]))) {
+                on_gpu[i] = 2;
             } else {
                 frames[i] = Frame();
                 decode_file(b, sizes[i], frames[i], arenas[w], &blk[NC * (size_t)i], &val[i], d.channels == 1);
@@ -1205,6 +1413,12 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     bool                   huff_region = false; // a GPU-decoded file of the call stores only part of its blocks
     bool                   any_region = false;  // a record of the call is a region: the kernels' <true> instantiations
     size_t                 rec_bytes = 0, coef_bytes = 0, sub_bytes = 0;
+    // the progressive files' coefficients lie together behind the others' (zeroed before their first scans), and the
+    // window's scans, units (level by level) and mask jobs go up with the descriptors
+    size_t                 pcoef_bytes = 0, n_pscan = 0, n_punit = 0;
+    int                    n_dev = 0, plevels = 0;
+    std::vector<size_t>    pscan0(n, 0);
+    std::vector<JpegProgMask> pmasks;
     std::vector<size_t>    wrec(NC * (size_t)n, 0), wcoef(NC * (size_t)n, 0), wsub(n, 0);
     for (int i = 0; i < n; i++) {
         const Frame& f  = frames[i];
@@ -1214,14 +1428,21 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         const JpegRect*    rc = &rect[NC * (size_t)i];
         if (r.w != f.W || r.h != f.H) any_region = true;
         if (on_gpu[i]) {
-            n_gpu++;
-            if (r.w != f.W || r.h != f.H) huff_region = true;
+            n_dev++;
+            size_t& cb = on_gpu[i] == 1 ? coef_bytes : pcoef_bytes;
             for (int k = 0; k < f.ncomp; k++) {
                 const size_t nb = (size_t)rc[k].bw * rc[k].bh;
                 wrec[NC * (size_t)i + k] = rec_bytes, rec_bytes += (nb * sizeof(JpegBlock) + 255) & ~(size_t)255;
-                wcoef[NC * (size_t)i + k] = coef_bytes, coef_bytes += (nb * 64 * sizeof(int16_t) + 255) & ~(size_t)255;
+                wcoef[NC * (size_t)i + k] = cb, cb += (nb * 64 * sizeof(int16_t) + 255) & ~(size_t)255;
             }
+        }
+        if (on_gpu[i] == 1) {
+            n_gpu++;
+            if (r.w != f.W || r.h != f.H) huff_region = true;
             wsub[i] = sub_bytes, sub_bytes += (size_t)gs[i].nsub * sizeof(JpegHuffSub);
+        } else if (on_gpu[i] == 2) {
+            pscan0[i] = n_pscan, n_pscan += pf[i].scans.size(), n_punit += pf[i].units.size();
+            plevels = std::max(plevels, pf[i].nlevels);
         }
         for (int k = 0; k < nc; k++) {
             plane_off[NC * (size_t)i + k] = plane_bytes;
@@ -1257,7 +1478,13 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     const size_t chk_off   = huf_off + (((size_t)n_gpu * sizeof(JpegHuffFile) + 255) & ~(size_t)255);
     const size_t row_off   = chk_off + ((chunks.size() * sizeof(JpegChunk) + 255) & ~(size_t)255);
     const size_t row4_off  = row_off + ((rows.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
-    size_t       total     = row4_off + ((rows4.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
+    const size_t pscan_off = row4_off + ((rows4.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
+    const size_t punit_off = pscan_off + ((n_pscan * sizeof(JpegProgScan) + 255) & ~(size_t)255);
+    size_t       pmask_off = punit_off + ((n_punit * sizeof(JpegProgUnit) + 255) & ~(size_t)255);
+    for (int i = 0; i < n; i++) // (the mask jobs: counted here, filled with the descriptors below)
+        for (int k = 0; on_gpu[i] == 2 && k < frames[i].ncomp; k++)
+            pmasks.resize(pmasks.size() + ((size_t)frames[i].c[k].bw * frames[i].c[k].bh + kProgMaskBlocks - 1) / kProgMaskBlocks);
+    size_t       total     = pmask_off + ((pmasks.size() * sizeof(JpegProgMask) + 255) & ~(size_t)255);
     const size_t head = total; // descriptors and lists: staged in st.pinned; the arenas go up from their own
     std::vector<size_t> arena_off(arenas.size());
     for (size_t w = 0; w < arenas.size(); w++) {
@@ -1268,11 +1495,14 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     grow_buf(st.pinned, st.pinned_cap, head, true);
     grow_buf(st.dev, st.dev_cap, total, false);
     grow_buf(st.planes, st.planes_cap, std::max<size_t>(plane_bytes, 256), false);
-    const size_t coef_off = rec_bytes, sub_off = rec_bytes + coef_bytes;
-    if (n_gpu) grow_buf(st.work, st.work_cap, sub_off + sub_bytes, false);
+    const size_t coef_off = rec_bytes, pcoef_off = rec_bytes + coef_bytes, sub_off = pcoef_off + pcoef_bytes;
+    if (n_dev) grow_buf(st.work, st.work_cap, sub_off + sub_bytes, false);
     const uint64_t dev  = (uint64_t)st.dev, work = (uint64_t)st.work;
     JpegImage*     imgs = (JpegImage*)st.pinned;
     JpegHuffFile*  hf   = (JpegHuffFile*)(st.pinned + huf_off);
+    std::vector<JpegProgUnit> punits; // (pad_[0]: the unit's level, until they are sorted by it)
+    size_t         n_pmask = 0;
+    punits.reserve(n_punit);
     int            huff_stage = 0; // LDS for the largest GPU-decoded file's data that fits the cap
     const int      stage_cap  = n_gpu ? jpeg_huff_stage_cap(S->huff_lanes) : 0;
     // The Huffman workgroups in order of entropy-coded size, largest first: dispatched in order, one
@@ -1284,14 +1514,14 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     {
         int64_t maxw = 1;
         for (int i = 0; i < n; i++)
-            if (on_gpu[i]) maxw = std::max<int64_t>(maxw, gs[i].data_words);
+            if (on_gpu[i] == 1) maxw = std::max<int64_t>(maxw, gs[i].data_words);
         int  cnt[65] = {0};
         auto cls     = [&](int i) { return 63 - (int)((int64_t)gs[i].data_words * 63 / maxw); };
         for (int i = 0; i < n; i++)
-            if (on_gpu[i]) cnt[cls(i) + 1]++;
+            if (on_gpu[i] == 1) cnt[cls(i) + 1]++;
         for (int c = 0; c < 64; c++) cnt[c + 1] += cnt[c];
         for (int i = 0; i < n; i++)
-            if (on_gpu[i]) hpos[i] = cnt[cls(i)]++;
+            if (on_gpu[i] == 1) hpos[i] = cnt[cls(i)]++;
     }
     for (int i = 0; i < n; i++) {
         const Frame& f = frames[i];
@@ -1301,7 +1531,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         for (int k = 0; k < f.ncomp; k++) {
             if (on_gpu[i]) {
                 J.blocks[k] = work + wrec[NC * (size_t)i + k];
-                J.dvals[k]  = work + coef_off + wcoef[NC * (size_t)i + k];
+                J.dvals[k]  = work + (on_gpu[i] == 1 ? coef_off : pcoef_off) + wcoef[NC * (size_t)i + k];
             } else {
                 J.blocks[k] = base + blk[NC * (size_t)i + k];
             }
@@ -1321,7 +1551,26 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         J.W          = f.W, J.H = f.H, J.ncomp = f.ncomp, J.out_cn = descs[i].channels, J.out_stride = descs[i].stride;
         J.hmax       = f.hmax, J.vmax = f.vmax, J.cs = f.cs;
         J.ox = reg[i].x, J.oy = reg[i].y, J.ow = reg[i].w, J.oh = reg[i].h;
-        if (!on_gpu[i]) continue;
+        if (on_gpu[i] == 2) { // the file's scans and units (device addresses), a mask job per kProgMaskBlocks blocks
+            const ProgFile& P = pf[i];
+            JpegProgScan*   ps = (JpegProgScan*)(st.pinned + pscan_off) + pscan0[i];
+            for (size_t j = 0; j < P.scans.size(); j++) {
+                ps[j]      = P.scans[j];
+                ps[j].data = base + P.data, ps[j].pool = base + P.pool;
+                for (int e = 0; e < kJpegMaxComp; e++)
+                    if (P.comp[NC * j + e] >= 0) ps[j].dvals[e] = J.dvals[P.comp[NC * j + e]];
+            }
+            for (const JpegProgUnit& u : P.units) {
+                punits.push_back(u);
+                punits.back().scan  = (int32_t)(pscan0[i] + u.scan);
+                punits.back().pad_[0] = P.level[u.scan];
+            }
+            for (int k = 0; k < f.ncomp; k++)
+                for (int b = 0, nb = f.c[k].bw * f.c[k].bh; b < nb; b += kProgMaskBlocks)
+                    pmasks[n_pmask++] = {J.dvals[k] + (uint64_t)b * 64 * sizeof(int16_t), J.blocks[k] + (uint64_t)b * sizeof(JpegBlock),
+                                         std::min(kProgMaskBlocks, nb - b), {0, 0, 0}};
+        }
+        if (on_gpu[i] != 1) continue;
         const GpuScan& g = gs[i];
         JpegHuffFile&  H = hf[hpos[i]];
         std::memset(&H, 0, sizeof(H));
@@ -1345,6 +1594,18 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     if (!chunks.empty()) std::memcpy(st.pinned + chk_off, chunks.data(), chunks.size() * sizeof(JpegChunk));
     if (!rows.empty()) std::memcpy(st.pinned + row_off, rows.data(), rows.size() * sizeof(JpegRows));
     if (!rows4.empty()) std::memcpy(st.pinned + row4_off, rows4.data(), rows4.size() * sizeof(JpegRows));
+    // the units level by level, within a level the longest first (they are dispatched in order: the long walks start
+    // first and the short ones fill in behind them)
+    std::vector<int> level_end(plevels, 0);
+    if (n_punit) {
+        std::stable_sort(punits.begin(), punits.end(), [](const JpegProgUnit& x, const JpegProgUnit& y) {
+            return x.pad_[0] != y.pad_[0] ? x.pad_[0] < y.pad_[0] : x.end_bit - x.start_bit > y.end_bit - y.start_bit;
+        });
+        for (const JpegProgUnit& u : punits) level_end[u.pad_[0]]++;
+        for (int l = 1; l < plevels; l++) level_end[l] += level_end[l - 1];
+        std::memcpy(st.pinned + punit_off, punits.data(), punits.size() * sizeof(JpegProgUnit));
+        std::memcpy(st.pinned + pmask_off, pmasks.data(), pmasks.size() * sizeof(JpegProgMask));
+    }
     mark(3);
     // (round 4 copied the arenas into st.pinned on the pool first: ~0.5 ms per 512 files)
     auto h2d = [&](hipStream_t on) {
@@ -1363,6 +1624,16 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     hip_ok(hipStreamWaitEvent(stream, st.copied, 0), "hipStreamWaitEvent");
     if (n_gpu) hip_ok(hipMemsetAsync(st.work, 0, rec_bytes, stream), "hipMemsetAsync");
     if (start) hip_ok(hipEventRecord(start, stream), "hipEventRecord");
+    if (n_punit) { // the progressive files: zeroed slots, the levels in order, the masks
+        hip_ok(hipMemsetAsync(st.work + pcoef_off, 0, pcoef_bytes, stream), "hipMemsetAsync");
+        for (int l = 0; l < plevels; l++) {
+            const int first = l ? level_end[l - 1] : 0;
+            hip_ok(launch_jpeg_prog_scan((const JpegProgScan*)(st.dev + pscan_off), (const JpegProgUnit*)(st.dev + punit_off) + first,
+                                         level_end[l] - first, error, stream),
+                   "JPEG progressive scan kernel");
+        }
+        hip_ok(launch_jpeg_prog_mask((const JpegProgMask*)(st.dev + pmask_off), (int)pmasks.size(), stream), "JPEG mask kernel");
+    }
     if (n_gpu)
         hip_ok(launch_jpeg_huff((const JpegHuffFile*)(st.dev + huf_off), n_gpu, S->huff_lanes, huff_stage, huff_region, error,
                                 stream),
@@ -1535,6 +1806,62 @@ int jpeg_gpu_entropy_emulate(const void* data, size_t size, int lanes, int* w, i
             nb++;
         }
     *w = f.W, *h = f.H, *ncomp = f.ncomp, *n_blocks = nb, *n_values = nv, *hash = hv, *rounds = r;
+    return 1;
+}
+
+// aeon_jpeg_prog_route's body.
+bool jpeg_prog_route(const void* data, size_t size)
+{
+    Frame    f;
+    Arena    a;
+    ProgFile P;
+    return prepare_prog((const uint8_t*)data, size, f, a, P);
+}
+
+// jpeg_prog.hip on this thread (host-only, for tests): prepare_prog, then level by level every unit through
+// jpeg_prog_scan's steps -- its scan's tables, prog::walk_unit -- with the wave's lanes as arrays, then
+// jpeg_prog_mask's ballot per block; summarised as jpeg_entropy_only summarises the host decoder.
+int jpeg_prog_emulate(const void* data, size_t size, int* w, int* h, int* ncomp, int64_t* n_blocks, int64_t* n_values,
+                      uint64_t* hash)
+{
+    Frame    f;
+    Arena    a;
+    ProgFile P;
+    if (!prepare_prog((const uint8_t*)data, size, f, a, P)) return 0;
+    std::vector<int16_t> coef[kJpegMaxComp];
+    for (int k = 0; k < f.ncomp; k++) coef[k].assign((size_t)f.c[k].bw * f.c[k].bh * 64, 0);
+    for (size_t j = 0; j < P.scans.size(); j++) {
+        P.scans[j].data = (uint64_t)(a.host.data() + P.data), P.scans[j].pool = (uint64_t)(a.host.data() + P.pool);
+        for (int e = 0; e < kJpegMaxComp; e++)
+            if (P.comp[kJpegMaxComp * j + e] >= 0) P.scans[j].dvals[e] = (uint64_t)coef[P.comp[kJpegMaxComp * j + e]].data();
+    }
+    std::unique_ptr<huff::Tables> T(new huff::Tables());
+    const JpegHuffFile            none{};
+    prog::Wave                    W;
+    for (int level = 0; level < P.nlevels; level++)
+        for (const JpegProgUnit& U : P.units) {
+            const JpegProgScan& S = P.scans[U.scan];
+            if (P.level[U.scan] != level) continue;
+            prog::tables_codes(*T, S, 0, 1);
+            prog::tables_fast(*T, S, 0, 1);
+            huff::tables_long(*T, none, 0, 1);
+            if (!prog::walk_unit(*T, S, U, (const uint32_t*)S.data, W)) return -1;
+        }
+    uint64_t hv  = 1469598103934665603ull;
+    auto     mix = [&](uint64_t x) {
+        for (int b = 0; b < 8; b++) hv = (hv ^ ((x >> (8 * b)) & 0xff)) * 1099511628211ull;
+    };
+    int64_t nb = 0, nv = 0;
+    prog::wave_start(W);
+    for (int k = 0; k < f.ncomp; k++)
+        for (size_t b = 0; b < coef[k].size() / 64; b++) {
+            const uint64_t m = prog::block_mask(W, coef[k].data() + b * 64);
+            mix(m);
+            for (int z = 0; z < 64; z++)
+                if (m >> z & 1) mix((uint64_t)(uint16_t)coef[k][b * 64 + z]), nv++;
+            nb++;
+        }
+    *w = f.W, *h = f.H, *ncomp = f.ncomp, *n_blocks = nb, *n_values = nv, *hash = hv;
     return 1;
 }
 

@@ -24,6 +24,9 @@ struct JpegImage;
 struct JpegChunk;
 struct JpegRows;
 struct JpegHuffFile;
+struct JpegProgScan;
+struct JpegProgUnit;
+struct JpegProgMask;
 struct PngJob;
 struct PixmapJob;
 struct PixmapBand;
@@ -74,6 +77,11 @@ int        jpeg_huff_stage_cap(int lanes);
 // region: some file of the call stores only the blocks inside its components' rectangles (jpeg_huff<LANES, true>)
 hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, int stage_bytes, bool region, int32_t* error,
                             hipStream_t stream);
+// jpeg_prog.hip: jpeg_prog_scan over the units of one level of a call's progressive files, one wave per unit (a launch
+// per level, in order), then jpeg_prog_mask over their components, one workgroup per kProgMaskBlocks blocks
+hipError_t launch_jpeg_prog_scan(const JpegProgScan* scans, const JpegProgUnit* units, int n_units, int32_t* error,
+                                 hipStream_t stream);
+hipError_t launch_jpeg_prog_mask(const JpegProgMask* jobs, int n_jobs, hipStream_t stream);
 // png_kernels.hip: png_inflate then png_unfilter over the jobs, one wave per file each
 hipError_t launch_png(const PngJob* jobs, int n_jobs, int unfilter_lds, int32_t* error, hipStream_t stream);
 // pixmap_kernels.hip: pixmap_convert, one workgroup per band

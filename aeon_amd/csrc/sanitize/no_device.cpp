@@ -112,6 +112,11 @@ int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx*, int, const void* const*, co
 {
     return no_device();
 }
+int aeon_hip_decode_jpeg_progressive_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const aeon_img_desc*, void*,
+                                           void*)
+{
+    return no_device();
+}
 int aeon_hip_jpeg_huff_stage_cap(int, int*) { return no_device(); }
 int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx*, int*) { return no_device(); }
 int aeon_hip_decode_png_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const int*, const aeon_img_desc*, void*,

@@ -232,6 +232,26 @@ int aeon_hip_decode_jpeg_batch(aeon_hip_ctx* ctx, int n, const void* const* data
 int aeon_hip_decode_jpeg_region_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
                                       const aeon_img_desc* descs, const aeon_region* regions, void* dst_base,
                                       void* stream);
+/* As aeon_hip_decode_jpeg_batch, but the scans of progressive files (SOF2) are decoded on the GPU too (opt-in):
+ * the host lays each such file out as its scans, their Huffman tables and their unstuffed bytes, and jpeg_prog_scan
+ * decodes them, one wave per scan (per restart interval of a scan), the scans that do not depend on each other in one
+ * launch, into the dense coefficients the IDCT reads.  Every other file of the call goes where
+ * aeon_hip_decode_jpeg_batch sends it, and so does a progressive file past the device path's limits (more than 64
+ * scans or 128 Huffman tables, a DC scan naming more than two DC tables, 2^28 bytes of data or more, data that ends
+ * with the file instead of a marker): aeon_jpeg_prog_route says which.  The records are aeon_hip_decode_jpeg_batch's
+ * bit for bit.  Corrupt entropy-coded data of a device-decoded progressive file -- what the host decoder refuses at
+ * the call -- is reported by aeon_hip_synchronize (AEON_HIP_EDEVICE, "JPEG ..."). */
+int aeon_hip_decode_jpeg_progressive_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                           const aeon_img_desc* descs, void* dst_base, void* stream);
+/* *device = 1 when aeon_hip_decode_jpeg_progressive_batch decodes this file's scans on the device, 0 when the file
+ * goes where aeon_hip_decode_jpeg_batch sends it (errors: the header parser's).  Host only, no context needed. */
+int aeon_jpeg_prog_route(const void* data, size_t size, int* device);
+/* jpeg_prog_scan's code run on the calling thread over the file as laid out for it, one wave after another, level by
+ * level, no device: the result as aeon_jpeg_entropy_decode reports the host decoder's (the two agree on every file
+ * the host decoder takes).  AEON_HIP_EUNSUPPORTED for a file aeon_jpeg_prog_route answers 0 for; AEON_HIP_EDEVICE
+ * where the device would set its error word. */
+int aeon_jpeg_prog_emulate(const void* data, size_t size, int* width, int* height, int* components, int64_t* n_blocks,
+                           int64_t* n_values, uint64_t* hash);
 /* The block rectangle of each component that a region of a JPEG file takes through the IDCT, as
  * aeon_hip_decode_jpeg_region_batch computes it.  Host only, no context needed.  out[4 * k ...] = first block
  * column, first block row, block columns, block rows of component k (*components of them; zeros for a component
