@@ -7,6 +7,7 @@ plumbing (device memory and streams) by callers; the binding itself takes raw po
 """
 import ctypes
 import json
+import operator
 import os
 
 import numpy as np
@@ -241,6 +242,11 @@ def lib():
         L.aeon_hip_decode_jpeg_progressive_batch.argtypes = L.aeon_hip_decode_jpeg_batch.argtypes
         L.aeon_hip_decode_jpeg_region_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc), P(Region),
                                                         vp, vp]
+        L.aeon_hip_decode_jpeg_scaled_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ImgDesc),
+                                                        P(ctypes.c_int32), vp, vp]
+        L.aeon_jpeg_scaled_plan.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ImgDesc), ctypes.c_int,
+                                            P(ctypes.c_int), P(ctypes.c_int32)]
+        L.aeon_hip_jpeg_launch_counts.argtypes = [vp, P(ctypes.c_int64)]
         L.aeon_jpeg_region_plan.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(Region), P(ImgDesc), ctypes.c_int,
                                             P(ctypes.c_int), P(ctypes.c_int32)]
         L.aeon_hip_decode_png_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ctypes.c_int), P(ImgDesc),
@@ -643,6 +649,16 @@ def jpeg_region_plan(data, region=None, channels=3, desc=None):
     return [tuple(out[4 * k:4 * k + 4]) for k in range(n.value)]
 
 
+def jpeg_scaled_plan(data, scale, channels=3, desc=None):
+    """(IDCT size n, sample columns, sample rows, upsampler) of each component of a JPEG file decoded at 1 / scale for
+    a record of `channels` (aeon_jpeg_scaled_plan); zeros for a component the record does not need.  The upsampler:
+    0 none, 1 h2v1 fancy, 2 h1v2 fancy, 3 h2v2 fancy, 4 box.  desc: checked as the decode call does."""
+    n, out = ctypes.c_int(), (ctypes.c_int32 * 16)()
+    _check(lib().aeon_jpeg_scaled_plan(bytes(data), len(data), int(scale), ctypes.byref(desc) if desc is not None else None,
+                                       int(channels), ctypes.byref(n), out))
+    return [tuple(out[4 * k:4 * k + 4]) for k in range(n.value)]
+
+
 def jpeg_entropy_decode(data):
     """Host-only Huffman decode of a JPEG file (aeon_jpeg_entropy_decode): (width, height,
     components, blocks, non-zero values, FNV-1a hash of the sparse coefficient stream)."""
@@ -1037,15 +1053,20 @@ class Context:
                                           int(out_h), ctypes.c_void_p(out_ptr), int(item_stride),
                                           ctypes.c_void_p(stream or 0)))
 
-    def decode_jpeg_batch(self, files, descs, dst_ptr, stream=0, regions=None, progressive=False):
+    def decode_jpeg_batch(self, files, descs, dst_ptr, stream=0, regions=None, progressive=False, scale=None):
         """image::extractor::extract of JPEG files into device memory (aeon_hip_decode_jpeg_batch):
         files = list of bytes (or a JpegFiles, marshalled once), descs[i] = where record i goes (HWC,
         channels 3 = BGR / 1 = gray).  regions (aeon_hip_decode_jpeg_region_batch): per file (x, y, w, h), the part
         of the image that record i -- of exactly w x h -- holds, or None for the whole image.  progressive
         (aeon_hip_decode_jpeg_progressive_batch): the scans of progressive files decode on the device too
-        (jpeg_prog_route says for which); not together with regions."""
+        (jpeg_prog_route says for which); not together with regions.  scale (aeon_hip_decode_jpeg_scaled_batch): 1, 2,
+        4 or 8, one for every file or one per file -- record i is file i at 1 / scale of its size, exactly
+        ceil(w / scale) x ceil(h / scale), through the reduced IDCTs; not together with regions or progressive=True
+        (progressive files still decode, their scans on the host)."""
         if progressive and regions is not None:
             raise ValueError("regions of progressive files are decoded on the host: pass regions or progressive=True, not both")
+        if scale is not None and (regions is not None or progressive):
+            raise ValueError("a scaled decode takes whole files with host-decoded scans: pass scale alone, without regions or progressive=True")
         jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
         n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
         d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
@@ -1058,8 +1079,25 @@ class Context:
             _check(lib().aeon_hip_decode_jpeg_region_batch(self._h, n, ptrs, sizes, d, r, ctypes.c_void_p(dst_ptr),
                                                            ctypes.c_void_p(stream or 0)))
             return
+        if scale is not None:
+            sc = [scale] * n if hasattr(scale, "__index__") else list(scale)  # (any integer type, numpy's included)
+            if any(isinstance(v, (bool, np.bool_)) for v in sc):
+                raise TypeError("scale is 1, 2, 4 or 8 (an integer), not a bool")
+            sc = [operator.index(v) for v in sc]
+            if len(sc) != n:
+                raise ValueError(f"{len(sc)} scales for {n} files")
+            _check(lib().aeon_hip_decode_jpeg_scaled_batch(self._h, n, ptrs, sizes, d, (ctypes.c_int32 * max(n, 1))(*sc),
+                                                           ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream or 0)))
+            return
         call = lib().aeon_hip_decode_jpeg_progressive_batch if progressive else lib().aeon_hip_decode_jpeg_batch
         _check(call(self._h, n, ptrs, sizes, d, ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream or 0)))
+
+    def jpeg_launch_counts(self):
+        """The kernel launches of this context's JPEG calls so far (aeon_hip_jpeg_launch_counts): a call adds one to
+        the slot of each kernel it launched; 'scaled' counts the calls whose colour kernels were the scaled ones."""
+        out = (ctypes.c_int64 * 8)()
+        _check(lib().aeon_hip_jpeg_launch_counts(self._h, out))
+        return dict(zip(("huff", "idct", "idct4", "idct2", "idct1", "color", "color4", "scaled"), out))
 
     def jpeg_huff_lanes(self):
         """The workgroup size this context's GPU Huffman decoder runs (aeon_hip_jpeg_huff_lanes)."""

@@ -466,6 +466,17 @@ int aeon_jpeg_region_plan(const void* data, size_t size, const aeon_region* regi
     });
 }
 
+int aeon_jpeg_scaled_plan(const void* data, size_t size, int scale, const aeon_img_desc* desc, int out_channels,
+                          int* components, int32_t* out)
+{
+    return guarded([&] {
+        if (!data || !components || !out) fail(AEON_HIP_EINVAL, "null argument");
+        if (out_channels != 1 && out_channels != 3) fail(AEON_HIP_EINVAL, "decoded channels must be 1 or 3");
+        jpeg_scaled_plan(data, size, scale, desc, out_channels, components, out);
+        return 0;
+    });
+}
+
 int aeon_jpeg_huff_layout(const void* data, size_t size, int lanes, int32_t* out, int32_t* seg_nsub, int seg_cap)
 {
     return guarded([&] {

@@ -1123,9 +1123,10 @@ int aeon_hip_video_batch(aeon_hip_ctx* ctx, int n, const int32_t* frame_counts, 
 
 namespace {
 
-// The JPEG calls: regions null for whole files; progressive: the progressive files' scans on the device too.
+// The JPEG calls: regions null for whole files; progressive: the progressive files' scans on the device too; scales
+// null for full-size records.
 int run_jpeg(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
-             const aeon_region* regions, void* dst_base, void* stream, bool progressive)
+             const aeon_region* regions, void* dst_base, void* stream, bool progressive, const int32_t* scales = nullptr)
 {
     return guarded([&] {
         if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
@@ -1145,7 +1146,7 @@ int run_jpeg(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* si
         }
         jpeg_decode_batch(ctx->jpeg, n, data, sizes, descs, regions, dst_base, stream_error(ctx, (hipStream_t)stream), (hipStream_t)stream,
                           timed ? t.start : nullptr,
-                          timed ? t.stop : nullptr, progressive);
+                          timed ? t.stop : nullptr, progressive, scales);
         if (timed) {
             std::lock_guard<std::mutex> lock(ctx->mu);
             ctx->timers.push_back(t);
@@ -1175,6 +1176,22 @@ int aeon_hip_decode_jpeg_progressive_batch(aeon_hip_ctx* ctx, int n, const void*
                                            const aeon_img_desc* descs, void* dst_base, void* stream)
 {
     return run_jpeg(ctx, n, data, sizes, descs, nullptr, dst_base, stream, true);
+}
+
+int aeon_hip_decode_jpeg_scaled_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                      const aeon_img_desc* descs, const int32_t* scales, void* dst_base, void* stream)
+{
+    return run_jpeg(ctx, n, data, sizes, descs, nullptr, dst_base, stream, false, scales);
+}
+
+int aeon_hip_jpeg_launch_counts(aeon_hip_ctx* ctx, int64_t out[8])
+{
+    return guarded([&] {
+        if (!ctx || !out) fail(AEON_HIP_EINVAL, "null argument");
+        for (int e = 0; e < 8; e++) out[e] = 0;
+        if (ctx->jpeg) jpeg_launch_counts(ctx->jpeg, out);
+        return 0;
+    });
 }
 
 int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx* ctx, int* lanes)

@@ -43,9 +43,17 @@ void       jpeg_state_destroy(JpegState* s);
 // regions (may be null: every file whole): the part of file i that record i holds (aeon_hip_decode_jpeg_region_batch).
 // progressive (aeon_hip_decode_jpeg_progressive_batch): the progressive files that jpeg_prog_route takes decode their
 // scans on the device (jpeg_prog.hip) instead of the pool.
+// scales (aeon_hip_decode_jpeg_scaled_batch, may be null: every file at full size; not together with regions or
+// progressive): record i is file i at 1 / scales[i] of its size, its blocks through the reduced IDCTs.
 void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
                        const aeon_region* regions, void* dst_base, int32_t* error, ihipStream_t* stream,
-                       ihipEvent_t* start, ihipEvent_t* stop, bool progressive = false);
+                       ihipEvent_t* start, ihipEvent_t* stop, bool progressive = false, const int32_t* scales = nullptr);
+// the launches of the state's calls so far, per kernel (JpegLaunchSlot)
+void jpeg_launch_counts(const JpegState* S, int64_t out[8]);
+// the geometry of each component of a file decoded at 1 / scale (aeon_jpeg_scaled_plan, no device): out = per
+// component n, dw, dh, upsampler (a component the record does not need: zeros); validates as the decode call does
+void jpeg_scaled_plan(const void* data, size_t size, int scale, const aeon_img_desc* desc, int out_cn, int* ncomp,
+                      int32_t out[16]);
 // the block rectangle of each component that a region of a file takes (aeon_jpeg_region_plan, no device): out =
 // per component bx, by, bw, bh (a component the record does not need: zeros); validates as the decode call does
 void jpeg_region_plan(const void* data, size_t size, const aeon_region* region, const aeon_img_desc* desc, int out_cn,
@@ -99,7 +107,7 @@ struct alignas(16) JpegImage {
     uint64_t blocks[kJpegMaxComp]; // JpegBlock per component: [bh][bw] (host-decoded files), [rh][rw] (GPU-decoded)
     uint64_t values;               // int16 coefficient values (sparse stream: host-decoded files)
     uint64_t dvals[kJpegMaxComp];  // GPU-decoded files: 64 int16 per block of the rectangle (zigzag order, the mask's bits valid), else 0
-    uint64_t planes[kJpegMaxComp]; // IDCT output per component: (rw*8) x (rh*8) uint8, row pitch rw*8
+    uint64_t planes[kJpegMaxComp]; // IDCT output per component: (rw*8) x (rh*8) uint8, row pitch rw*8 (a scaled call: `pitch`)
     uint64_t out;                  // decoded record: HWC uint8 (BGR or gray), out_stride bytes per row
     int32_t  W, H, ncomp, out_cn, out_stride, hmax, vmax; // W, H: the whole image's (the upsamplers' edge rules)
     int32_t  cs;                   // JpegColorSpace
@@ -111,6 +119,10 @@ struct alignas(16) JpegImage {
     // block (r, c) of the rectangle is blocks / dvals [sb0 + r * sbw + c]: the frame's grid for a host-decoded
     // file (sbw = bw, sb0 = ry * bw + rx), the rectangle itself for a GPU-decoded one (sbw = rw, sb0 = 0)
     int32_t  sbw[kJpegMaxComp], sb0[kJpegMaxComp];
+    // a call with reduced-size records (aeon_hip_decode_jpeg_scaled_batch; the other calls' kernels never read these):
+    // the IDCT size of each component (8, 4, 2 or 1 samples a side per block) and its plane's row pitch in bytes,
+    // bw * nk rounded up to 8.  There W, H, dw, dh, hf, vf and up are the reduced image's (jpeg_scaled_comp).
+    int32_t  nk[kJpegMaxComp], pitch[kJpegMaxComp];
     uint16_t q[kJpegMaxComp][64];  // quantisation table of each component, natural order
     uint16_t qz[kJpegMaxComp][64]; // the same in zigzag order (the dense path of jpeg_idct: 16-byte loads)
 };
@@ -268,6 +280,13 @@ constexpr int kJpegCorruptBit = 256;
 constexpr int kJpegIdctLanes  = 256;                             // IDCT workgroup: 8 lanes per block
 constexpr int kJpegIdctUnroll = 4;                               // blocks per lane group
 constexpr int kJpegIdctBlocks = kJpegIdctLanes / 8 * kJpegIdctUnroll; // blocks per IDCT workgroup (chunk)
+// the reduced IDCTs (jpeg_idct_reduced<N>): four lanes per block for 4x4 (kJpegIdct4Unroll blocks per lane group),
+// one lane per block for 2x2 and 1x1
+constexpr int kJpegIdct4Unroll = 2;
+inline constexpr int jpeg_idct_blocks(int nk) // blocks per IDCT workgroup (chunk) of a component of IDCT size nk
+{
+    return nk == 8 ? kJpegIdctBlocks : nk == 4 ? kJpegIdctLanes / 4 * kJpegIdct4Unroll : kJpegIdctLanes;
+}
 constexpr int kJpegRowsPerWg = 32;  // output rows per colour workgroup (fewer when the staged rows outgrow LDS)
 constexpr int kJpegColorLds  = 160 * 1024; // most LDS a colour workgroup stages
 
@@ -283,6 +302,37 @@ inline int jpeg_upsample_mode(int hf, int vf, int dw)
     if (hf == 2 && vf == 2 && fancy) return UP_H2V2;
     return UP_BOX;
 }
+
+// A component of a file decoded at 1 / scale (scale 1, 2, 4 or 8) as libjpeg's DCT-domain scaling lays it out
+// (jdmaster.c jpeg_core_output_dimensions, jdsample.c jinit_upsampler): every block comes out of the IDCT as n x n
+// samples, n doubled from 8 / scale while the component stays no finer than the output; dw x dh samples; the
+// expansion hf x vf that is left for the upsampler `up` -- no fancy filter once a block is one sample (scale 8).
+// Scale 1 is the full-size geometry.
+struct JpegScaledComp {
+    int32_t n, dw, dh, hf, vf, up;
+};
+inline JpegScaledComp jpeg_scaled_comp(int W, int H, int hs, int vs, int hmax, int vmax, int scale)
+{
+    const int      mn = 8 / scale;
+    JpegScaledComp c{mn, 0, 0, 0, 0, 0};
+    while (c.n < 8 && (hmax * mn) % (hs * c.n * 2) == 0 && (vmax * mn) % (vs * c.n * 2) == 0) c.n *= 2;
+    c.dw = (int)(((int64_t)W * hs * c.n + (int64_t)hmax * 8 - 1) / ((int64_t)hmax * 8));
+    c.dh = (int)(((int64_t)H * vs * c.n + (int64_t)vmax * 8 - 1) / ((int64_t)vmax * 8));
+    c.hf = hmax * mn / (hs * c.n), c.vf = vmax * mn / (vs * c.n);
+    c.up = jpeg_upsample_mode(c.hf, c.vf, c.dw);
+    if (mn == 1 && c.up != UP_FULL) c.up = UP_BOX;
+    return c;
+}
+// Row pitch of a reduced plane: bw * nk sample bytes rounded up to 8, so that the colour pass stages whole rows with
+// its 8-byte loads.  The IDCT kernels write the bw * nk samples only: the up to 7 pad bytes of a row are never
+// written, travel into LDS with the row as they are, and are never sampled (dw <= bw * nk).
+inline int jpeg_scaled_pitch(int bw, int nk) { return (bw * nk + 7) & ~7; }
+
+// The launches of a context's JPEG calls, counted per kernel (aeon_hip_jpeg_launch_counts).
+enum JpegLaunchSlot : int {
+    JL_HUFF = 0, JL_IDCT8 = 1, JL_IDCT4 = 2, JL_IDCT2 = 3, JL_IDCT1 = 4, JL_COLOR = 5, JL_COLOR4 = 6, JL_SCALED = 7,
+    JL_SLOTS = 8, // JL_SCALED: the calls whose colour kernels were the scaled instantiations
+};
 
 // Plane rows the colour pass stages for a band of `rows` output rows of a component (a bound; the
 // kernel stages the exact range).

@@ -1222,6 +1222,27 @@ aeon_region checked_region(const Frame& f, const aeon_region* region, const aeon
     return r;
 }
 
+// Component k of file f decoded at 1 / scale (jpeg_scaled_comp).
+JpegScaledComp scaled_comp(const Frame& f, int k, int scale)
+{
+    return jpeg_scaled_comp(f.W, f.H, f.c[k].h, f.c[k].v, f.hmax, f.vmax, scale);
+}
+
+// The refusals of aeon_hip_decode_jpeg_scaled_batch for one file, before anything is launched: the scale, the
+// files the reduced path does not take, and a record (may be null) that is not ceil(W / scale) x ceil(H / scale).
+void checked_scale(const Frame& f, int scale, const aeon_img_desc* d)
+{
+    if (scale != 1 && scale != 2 && scale != 4 && scale != 8) bad("scale " + std::to_string(scale) + " is not 1, 2, 4 or 8");
+    if (scale > 1 && f.ncomp == 4)
+        unsupported("four-component (CMYK / YCCK) files are decoded at full size only, not at scale " + std::to_string(scale));
+    if (!d) return;
+    const int w = (f.W + scale - 1) / scale, h = (f.H + scale - 1) / scale;
+    if (w != d->width || h != d->height)
+        bad("decoded size " + std::to_string(w) + "x" + std::to_string(h) + " at scale " + std::to_string(scale) +
+            " does not match the record descriptor " + std::to_string(d->width) + "x" + std::to_string(d->height));
+    if (d->stride < d->width * d->channels) bad("record descriptor stride too small");
+}
+
 // The block rectangle of each component of f that a record of out_cn channels holding region r reads
 // (jpeg_region_rect); the whole image: every component's whole grid, as the frame lays it out; else nothing for a
 // component the record does not need.
@@ -1275,6 +1296,7 @@ struct JpegState {
     hipStream_t copy = nullptr; // the H2D of a call's staging, so that it overlaps the previous call's kernels
     bool       gpu_huff = true; // false: every file through the host entropy decoder
     int        huff_lanes = kHuffLanes; // jpeg_huff workgroup size (the context's AEON_HIP_JPEG_HUFF_LANES=256 / 1024: A/B)
+    int64_t    launches[JL_SLOTS] = {}; // kernel launches so far (jpeg_launch_counts)
     std::mutex mu;
 };
 
@@ -1342,8 +1364,12 @@ void jpeg_state_destroy(JpegState* s)
 // start / stop (may be null): events recorded around the GPU launches (kernel timing)
 void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_t* sizes, const aeon_img_desc* descs,
                        const aeon_region* regions, void* dst_base, int32_t* error, hipStream_t stream, hipEvent_t start,
-                       hipEvent_t stop, bool progressive)
+                       hipEvent_t stop, bool progressive, const int32_t* scales)
 {
+    // a call with reduced-size records (all ones: the whole-size call itself); its records are checked in the pool
+    bool scaled_call = false;
+    for (int i = 0; scales && i < n; i++) scaled_call = scaled_call || scales[i] != 1;
+    if (scaled_call && (regions || progressive)) bad("a scaled call takes neither regions nor the progressive path");
     std::lock_guard<std::mutex> lock(S->mu);
     // (AEON_HIP_JPEG_PROFILE=1, development: host time per phase of each call on stderr)
     static const bool prof = std::getenv("AEON_HIP_JPEG_PROFILE") && std::atoi(std::getenv("AEON_HIP_JPEG_PROFILE"));
@@ -1375,6 +1401,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     std::vector<ProgFile> pf(progressive ? n : 0);
     std::vector<aeon_region> reg(n);            // the record's region of its image
     std::vector<JpegRect>    rect(NC * (size_t)n); // and the block rectangle of each component it reads
+    std::vector<JpegScaledComp> sg(scaled_call ? NC * (size_t)n : 0); // a scaled call: each component's reduced geometry
     S->pool->run_indexed(n, [&](int i, int w) {
         try {
             if (!data[i] || !sizes[i]) bad("empty file");
@@ -1390,7 +1417,11 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
                 decode_file(b, sizes[i], frames[i], arenas[w], &blk[NC * (size_t)i], &val[i], d.channels == 1);
             }
             owner[i] = w;
-            reg[i] = checked_region(frames[i], regions ? &regions[i] : nullptr, &d);
+            if (scaled_call) {
+                checked_scale(frames[i], scales[i], &d);
+                for (int k = 0; k < frames[i].ncomp; k++) sg[NC * (size_t)i + k] = scaled_comp(frames[i], k, scales[i]);
+            }
+            reg[i] = checked_region(frames[i], regions ? &regions[i] : nullptr, scaled_call ? nullptr : &d);
             region_rects(frames[i], reg[i], d.channels, &rect[NC * (size_t)i]);
         } catch (const jpeg_error& e) {
             throw jpeg_error(e.code, std::string(e.what()) + " (record " + std::to_string(i) + ")");
@@ -1400,7 +1431,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     // device layout of the call: [images][GPU-decoded files][chunks][rows][arena 0][arena 1]...; the
     // work buffer (device only): [block records of the GPU-decoded files][their dense coefficients]
     // [their subsequence scratch]
-    std::vector<JpegChunk> chunks;
+    std::vector<JpegChunk> chunks, rchunks[3]; // jpeg_idct's; a scaled call: jpeg_idct_reduced<4>, <2> and <1>'s
     std::vector<JpegRows>  rows, rows4; // bands of YCbCr / gray files (jpeg_color), of the others (jpeg_color4)
     // colour band height: kJpegRowsPerWg, or AEON_HIP_JPEG_BAND (tests: 1, 2, ... rows per workgroup
     // take the colour kernels' band-edge cases)
@@ -1446,18 +1477,30 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         }
         for (int k = 0; k < nc; k++) {
             plane_off[NC * (size_t)i + k] = plane_bytes;
-            plane_bytes += ((size_t)rc[k].bw * 8 * rc[k].bh * 8 + 255) & ~(size_t)255;
             const int nb = rc[k].bw * rc[k].bh;
+            if (scaled_call) { // planes of nk samples a block side; a chunk list per IDCT size
+                const int nk = sg[NC * (size_t)i + k].n, per = jpeg_idct_blocks(nk);
+                plane_bytes += ((size_t)jpeg_scaled_pitch(rc[k].bw, nk) * rc[k].bh * nk + 255) & ~(size_t)255;
+                std::vector<JpegChunk>& list = nk == 8 ? chunks : rchunks[nk == 4 ? 0 : nk == 2 ? 1 : 2];
+                for (int b = 0; b < nb; b += per) list.push_back({i, k, b, std::min(per, nb - b)});
+                continue;
+            }
+            plane_bytes += ((size_t)rc[k].bw * 8 * rc[k].bh * 8 + 255) & ~(size_t)255;
             for (int b = 0; b < nb; b += kJpegIdctBlocks) chunks.push_back({i, k, b, std::min(kJpegIdctBlocks, nb - b)});
         }
         // colour bands: as many rows as the staged plane rows of the band fit the LDS (16 bytes more per
         // staged row: the 4:2:0 path's edge columns, jpeg_kernels.hip color_h2v2, whose staged chroma rows are
         // at least as long as its lane groups read: 4 bytes per 8 output columns)
-        const int h2v2_cols = takes_h2v2(f, descs[i].channels) ? 4 * ((r.w + 7) / 8) : 0;
+        const int h2v2_cols = !scaled_call && takes_h2v2(f, descs[i].channels) ? 4 * ((r.w + 7) / 8) : 0;
         int band = band_max, lds = 0;
         for (;; band /= 2) {
             lds = 0;
             for (int k = 0; k < nc; k++) {
+                if (scaled_call) { // the reduced planes' rows, through the upsampler that is left
+                    const JpegScaledComp& c = sg[NC * (size_t)i + k];
+                    lds += jpeg_stage_rows(c.up, c.vf, band) * (jpeg_scaled_pitch(rc[k].bw, c.n) + 16);
+                    continue;
+                }
                 const int hf = f.hmax / f.c[k].h, vf = f.vmax / f.c[k].v;
                 lds += jpeg_stage_rows(jpeg_upsample_mode(hf, vf, f.c[k].dw), vf, band) * (std::max(rc[k].bw * 8, h2v2_cols) + 16);
             }
@@ -1467,8 +1510,9 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         (ycc ? color_lds : color4_lds) = std::max(ycc ? color_lds : color4_lds, lds);
         // (a region that starts on an odd row: a first band one row short, so that the next ones start on even
         // rows as the whole image's do, which color_h2v2's row pairs want)
-        for (int y = r.y, first = band - (band % 2 == 0 ? r.y & 1 : 0); y < r.y + r.h; first = band) {
-            const int nr = std::min(first, r.y + r.h - y);
+        const int rec_h = scaled_call ? descs[i].height : r.h; // (checked_scale: the reduced image's rows)
+        for (int y = r.y, first = band - (band % 2 == 0 ? r.y & 1 : 0); y < r.y + rec_h; first = band) {
+            const int nr = std::min(first, r.y + rec_h - y);
             (ycc ? rows : rows4).push_back({i, y, nr, 0});
             y += nr;
         }
@@ -1476,6 +1520,9 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
     const size_t img_bytes = (size_t)n * sizeof(JpegImage);
     const size_t huf_off   = (img_bytes + 255) & ~(size_t)255;
     const size_t chk_off   = huf_off + (((size_t)n_gpu * sizeof(JpegHuffFile) + 255) & ~(size_t)255);
+    const int    n_reduced[3] = {(int)rchunks[0].size(), (int)rchunks[1].size(), (int)rchunks[2].size()};
+    const size_t n_idct8   = chunks.size(); // the reduced kernels' chunks follow jpeg_idct's
+    for (auto& l : rchunks) chunks.insert(chunks.end(), l.begin(), l.end());
     const size_t row_off   = chk_off + ((chunks.size() * sizeof(JpegChunk) + 255) & ~(size_t)255);
     const size_t row4_off  = row_off + ((rows.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
     const size_t pscan_off = row4_off + ((rows4.size() * sizeof(JpegRows) + 255) & ~(size_t)255);
@@ -1543,6 +1590,12 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
             J.hs[k] = f.c[k].h, J.vs[k] = f.c[k].v;
             J.hf[k] = f.hmax / f.c[k].h, J.vf[k] = f.vmax / f.c[k].v;
             J.up[k] = jpeg_upsample_mode(J.hf[k], J.vf[k], f.c[k].dw);
+            J.nk[k] = 8, J.pitch[k] = rk.bw * 8;
+            if (scaled_call) {
+                const JpegScaledComp& c = sg[NC * (size_t)i + k];
+                J.dw[k] = c.dw, J.dh[k] = c.dh, J.hf[k] = c.hf, J.vf[k] = c.vf, J.up[k] = c.up;
+                J.nk[k] = c.n, J.pitch[k] = jpeg_scaled_pitch(rk.bw, c.n);
+            }
             std::memcpy(J.q[k], f.q[f.c[k].tq], sizeof(J.q[k]));
             for (int z = 0; z < 64; z++) J.qz[k][z] = f.q[f.c[k].tq][kZigzagToNatural[z]];
         }
@@ -1551,6 +1604,7 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         J.W          = f.W, J.H = f.H, J.ncomp = f.ncomp, J.out_cn = descs[i].channels, J.out_stride = descs[i].stride;
         J.hmax       = f.hmax, J.vmax = f.vmax, J.cs = f.cs;
         J.ox = reg[i].x, J.oy = reg[i].y, J.ow = reg[i].w, J.oh = reg[i].h;
+        if (scaled_call) J.W = J.ow = descs[i].width, J.H = J.oh = descs[i].height; // the reduced image
         if (on_gpu[i] == 2) { // the file's scans and units (device addresses), a mask job per kProgMaskBlocks blocks
             const ProgFile& P = pf[i];
             JpegProgScan*   ps = (JpegProgScan*)(st.pinned + pscan_off) + pscan0[i];
@@ -1638,8 +1692,11 @@ void jpeg_decode_batch(JpegState* S, int n, const void* const* data, const size_
         hip_ok(launch_jpeg_huff((const JpegHuffFile*)(st.dev + huf_off), n_gpu, S->huff_lanes, huff_stage, huff_region, error,
                                 stream),
                "JPEG Huffman kernel");
-    hip_ok(launch_jpeg((const JpegImage*)st.dev, (const JpegChunk*)(st.dev + chk_off), (int)chunks.size(),
-                       (const JpegRows*)(st.dev + row_off), (int)rows.size(), color_lds,
+    S->launches[JL_HUFF] += n_gpu > 0, S->launches[JL_IDCT8] += n_idct8 > 0, S->launches[JL_COLOR] += !rows.empty();
+    S->launches[JL_COLOR4] += !rows4.empty(), S->launches[JL_SCALED] += scaled_call;
+    for (int e = 0; e < 3; e++) S->launches[JL_IDCT4 + e] += n_reduced[e] > 0;
+    hip_ok(launch_jpeg((const JpegImage*)st.dev, (const JpegChunk*)(st.dev + chk_off), (int)n_idct8,
+                       scaled_call ? n_reduced : nullptr, (const JpegRows*)(st.dev + row_off), (int)rows.size(), color_lds,
                        (const JpegRows*)(st.dev + row4_off), (int)rows4.size(), color4_lds, any_region, stream),
            "JPEG kernels");
     if (stop) hip_ok(hipEventRecord(stop, stream), "hipEventRecord");
@@ -1683,6 +1740,37 @@ void jpeg_region_plan(const void* data, size_t size, const aeon_region* region, 
     } catch (const jpeg_error& e) {
         throw jpeg_error(e.code, std::string(e.what()) + " (record 0)");
     }
+}
+
+// aeon_jpeg_scaled_plan's body: the headers as the decode call reads them, its checks and the reduced geometry.
+void jpeg_scaled_plan(const void* data, size_t size, int scale, const aeon_img_desc* desc, int out_cn, int* ncomp,
+                      int32_t out[16])
+{
+    Frame   f;
+    Arena   a;
+    GpuScan g;
+    try {
+        if (!prepare_gpu((const uint8_t*)data, size, f, a, g, kHuffLanes)) {
+            size_t blk_off[kJpegMaxComp] = {0, 0, 0, 0}, val_off = 0;
+            f = Frame(), a.used = 0;
+            decode_file((const uint8_t*)data, size, f, a, blk_off, &val_off, false);
+        }
+        checked_scale(f, scale, desc);
+        const int nc = jpeg_planes_needed(f.cs, f.ncomp, out_cn);
+        for (int k = 0; k < kJpegMaxComp; k++) {
+            const JpegScaledComp c = k < nc ? scaled_comp(f, k, scale) : JpegScaledComp{0, 0, 0, 0, 0, 0};
+            out[4 * k] = c.n, out[4 * k + 1] = c.dw, out[4 * k + 2] = c.dh, out[4 * k + 3] = c.up;
+        }
+        *ncomp = f.ncomp;
+    } catch (const jpeg_error& e) {
+        throw jpeg_error(e.code, std::string(e.what()) + " (record 0)");
+    }
+}
+
+void jpeg_launch_counts(const JpegState* S, int64_t out[8])
+{
+    std::lock_guard<std::mutex> lock(const_cast<JpegState*>(S)->mu);
+    for (int e = 0; e < JL_SLOTS; e++) out[e] = S->launches[e];
 }
 
 // aeon_jpeg_entropy_decode's body: the host half of the stage alone (headers, tables, every scan's

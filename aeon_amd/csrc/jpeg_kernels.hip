@@ -7,6 +7,8 @@
 // the post-IDCT range limit of jdmaster.c, x & 1023 wrap) -- integer multiply-adds only -- a column
 // each, then a row each, and each lane writes its output row of the block into the component plane
 // (one 8-byte store).
+// jpeg_idct_reduced<4 / 2 / 1>: the blocks of a file decoded at 1/2, 1/4, 1/8 of its size, straight to 4x4, 2x2 or
+// 1x1 samples (jidctred.c): four lanes per block, or a lane per block (see there).
 // jpeg_color: a workgroup per band of up to kJpegRowsPerWg output rows.  4:2:0 files with BGR output
 // take color_h2v2 (8 columns of a row pair per lane, packed 16-bit upsampling); the others one lane
 // per 4 output pixels of the band: each component sampled
@@ -81,15 +83,20 @@ __device__ __forceinline__ void llm8(const int* in, int* out)
 // The record's and the rectangles' geometry as a kernel instantiation reads it.  REGION false -- the kernels of a
 // call whose records are all whole images -- folds it to constants (the record is the image, a rectangle its
 // component's whole grid), which leaves those kernels the code, registers and time they had before regions; REGION
-// true reads what the host computed (JpegImage), whole images of a mixed call included.
-template <bool REGION>
+// true reads what the host computed (JpegImage), whole images of a mixed call included.  GEO_SCALED -- the colour
+// kernels of a call with reduced-size records (no regions there) -- differs from whole in the planes' pitch alone,
+// which it reads (JpegImage.pitch); the image's sizes and upsamplers are the reduced image's already.
+enum : int { GEO_WHOLE = 0, GEO_REGION = 1, GEO_SCALED = 2 };
+template <int MODE>
 struct Geo {
+    static constexpr bool REGION = MODE == GEO_REGION;
     static __device__ __forceinline__ int ox(const JpegImage& I) { return REGION ? I.ox : 0; }
     static __device__ __forceinline__ int oy(const JpegImage& I) { return REGION ? I.oy : 0; }
     static __device__ __forceinline__ int ow(const JpegImage& I) { return REGION ? I.ow : I.W; }
     static __device__ __forceinline__ int rx(const JpegImage& I, int k) { return REGION ? I.rx[k] : 0; }
     static __device__ __forceinline__ int ry(const JpegImage& I, int k) { return REGION ? I.ry[k] : 0; }
     static __device__ __forceinline__ int rw(const JpegImage& I, int k) { return REGION ? I.rw[k] : I.bw[k]; }
+    static __device__ __forceinline__ int pitch(const JpegImage& I, int k) { return MODE == GEO_SCALED ? I.pitch[k] : rw(I, k) * 8; }
 };
 
 // Natural index -> zigzag index (the inverse of kZz).
@@ -227,6 +234,253 @@ __global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct(const JpegImage* __r
     }
 }
 
+// ---- reduced IDCTs: a block straight to 4x4, 2x2 or 1x1 samples (jidctred.c; a file decoded at 1/2, 1/4, 1/8) ----
+// jpeg_idct_reduced<N> takes the chunks of the components whose IDCT size is N (JpegImage.nk) in a call with reduced
+// records; components left at 8x8 (the chroma of 4:2:0 at scale 2) stay with jpeg_idct.  Whole images only: block b
+// of a chunk is block b of the component's grid (bw a row), and the plane's pitch is JpegImage.pitch.  The lane split
+// follows the live data of each size, not jpeg_idct's 8 lanes: a 4x4 block has 7 live columns of 7 coefficients and
+// 4 output rows -- four lanes; of a 2x2 block 25 coefficients are live and of a 1x1 block one -- a lane each, with no
+// LDS and no barrier.
+
+template <int S>
+__device__ __forceinline__ int descale(int x)
+{
+    return (x + (1 << (S - 1))) >> S;
+}
+
+// jidctred.c's 4-point pass over in[0..3], in[5..7] (in[4] is never read), descaled by S
+template <int S>
+__device__ __forceinline__ void red4(const int (&in)[8], int (&out)[4])
+{
+    const int t0 = in[0] * 16384, t2 = in[2] * 15137 - in[6] * 6270;
+    const int t10 = t0 + t2, t12 = t0 - t2;
+    const int z1 = in[7], z2 = in[5], z3 = in[3], z4 = in[1];
+    const int a = -z1 * 1730 + z2 * 11893 - z3 * 17799 + z4 * 8697;
+    const int b = -z1 * 4176 - z2 * 4926 + z3 * 7373 + z4 * 20995;
+    out[0] = descale<S>(t10 + b), out[1] = descale<S>(t12 + a), out[2] = descale<S>(t12 - a), out[3] = descale<S>(t10 - b);
+}
+
+// its 2-point pass over the values at positions 0, 1, 3, 5, 7
+template <int S>
+__device__ __forceinline__ void red2(int c0, int c1, int c3, int c5, int c7, int& o0, int& o1)
+{
+    const int t10 = c0 * 32768, t0 = -c7 * 5906 + c5 * 6967 - c3 * 10426 + c1 * 29692;
+    o0 = descale<S>(t10 + t0), o1 = descale<S>(t10 - t0);
+}
+
+// block b of a grid of rw blocks a row (jpeg_idct's locate)
+__device__ __forceinline__ void locate_block(int b, int rw, int& row, int& col)
+{
+    row = rw < 512 ? (int)(((float)b + 0.5f) / (float)rw) : b / rw;
+    row -= row * rw > b ? 1 : 0; // (the quotient is not the reciprocal's: settle the last ulp)
+    row += (row + 1) * rw <= b ? 1 : 0;
+    col = b - row * rw;
+}
+
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int N>
+__global__ void jpeg_idct_reduced(const JpegImage* __restrict__ imgs, const JpegChunk* __restrict__ chunks);
+
+// 4x4: four adjacent lanes per block, sixteen blocks per wave, kJpegIdct4Unroll blocks per lane group.  Lane j takes
+// columns j and j + 4 (lane 0's column 4 is dead: nothing is fetched for it) -- rows 0-3 and 5-7 of each: from the
+// sparse stream by the mask / popcount walk, or, for the dense zigzag slots, slots 16j .. 16j + 15 as two 16-byte
+// loads, dequantised, masked and scattered to their natural places in the group's LDS slot, from which the columns
+// are read.  Pass 1 gives four values per column; they cross to rows through the same slot (rows 9 dwords apart),
+// lane j runs pass 2 on row j and stores its four samples as one dword.  Slot stride 68 dwords: the lanes of a wave
+// (g = 0..15, j) read natural column j of row r at bank (4g + 8r + j) % 64, write workspace (r, j) at (4g + 9r + j)
+// and read workspace (j, c) at (4g + 9j + c) -- each conflict-free (9 dj = 4 dg mod 64 only for dj = dg = 0).
+constexpr int kSlot4 = 68;
+
+template <>
+__global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct_reduced<4>(const JpegImage* __restrict__ imgs,
+                                                                       const JpegChunk* __restrict__ chunks)
+{
+    constexpr int G = kJpegIdctLanes / 4, U = kJpegIdct4Unroll;
+    __shared__ int slot[G * kSlot4];
+    const JpegChunk  C = chunks[blockIdx.x];
+    const JpegImage& I = imgs[C.img];
+    const int        k = C.comp, g = threadIdx.x >> 2, j = threadIdx.x & 3;
+    const gp<const JpegBlock> blocks = gaddr<const JpegBlock>(I.blocks[k]);
+    const gp<const int16_t>   vals   = gaddr<const int16_t>(I.values);
+    const gp<const int16_t>   dense  = gaddr<const int16_t>(I.dvals[k]);
+    JpegBlock B[U];
+    int       src[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        src[u] = C.first + min(g + u * G, C.count - 1);
+        B[u]   = blocks[src[u]];
+    }
+    int* const s0 = slot + g * kSlot4;
+    int        col[U][2][8]; // [block][column j, j + 4][row], dequantised
+    if (dense) {
+        uint4 c4[U][2], q4[2];
+#pragma unroll
+        for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) c4[u][h] = *(gp<const uint4>)(dense + (size_t)src[u] * 64 + 16 * j + 8 * h);
+#pragma unroll
+        for (int h = 0; h < 2; h++) q4[h] = *(gp<const uint4>)gaddr<const uint16_t>((uint64_t)&I.qz[k][16 * j + 8 * h]);
+        int nat[16];
+#pragma unroll
+        for (int e = 0; e < 16; e++) nat[e] = kZz[16 * j + e];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t m16 = (uint32_t)(B[u].mask >> (16 * j)) & 0xffffu;
+            if (u) wave_sync(); // the previous block's column reads are done
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const uint32_t cw[4] = {c4[u][h].x, c4[u][h].y, c4[u][h].z, c4[u][h].w};
+                const uint32_t qw[4] = {q4[h].x, q4[h].y, q4[h].z, q4[h].w};
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const int c = (int)(int16_t)(cw[e >> 1] >> (16 * (e & 1)));
+                    const int q = (int)((qw[e >> 1] >> (16 * (e & 1))) & 0xffff);
+                    s0[nat[8 * h + e]] = ((m16 >> (8 * h + e)) & 1) ? c * q : 0;
+                }
+            }
+            wave_sync();
+#pragma unroll
+            for (int h = 0; h < 2; h++)
+#pragma unroll
+                for (int r = 0; r < 8; r++)
+                    if (r != 4) col[u][h][r] = s0[r * 8 + j + 4 * h];
+        }
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const bool live = h == 0 || j != 0; // (column 4)
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                if (r == 4) continue;
+                const int n = r * 8 + j + 4 * h, z = kZzInv[n], qv = I.q[k][n];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    col[u][h][r] = 0;
+                    if (live && ((B[u].mask >> z) & 1))
+                        col[u][h][r] = (int)vals[B[u].val_off + __builtin_popcountll(B[u].mask & ((1ull << z) - 1))] * qv;
+                }
+            }
+        }
+    }
+    const int rw = I.bw[k], pitch = I.pitch[k];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const int bi = g + u * G;
+        int       ws[2][4], in[8], out[4];
+        // pass 1: columns, descaled by CONST_BITS - PASS1_BITS + 1
+        col[u][0][4] = col[u][1][4] = 0;
+        red4<12>(col[u][0], ws[0]);
+        red4<12>(col[u][1], ws[1]);
+        wave_sync(); // the slot's earlier reads are done
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) s0[r * 9 + j + 4 * h] = ws[h][r];
+        wave_sync();
+        // pass 2: row j over workspace columns 0-3, 5-7, descaled by CONST_BITS + PASS1_BITS + 3 + 1; 4 bytes to the plane
+#pragma unroll
+        for (int c = 0; c < 8; c++) in[c] = c != 4 ? s0[j * 9 + c] : 0;
+        red4<19>(in, out);
+        if (bi < C.count) {
+            int by, bx;
+            locate_block(C.first + bi, rw, by, bx);
+            *(gp<uint32_t>)(gaddr<uint8_t>(I.planes[k]) + (size_t)(by * 4 + j) * pitch + bx * 4) =
+                idct_limit(out[0]) | idct_limit(out[1]) << 8 | idct_limit(out[2]) << 16 | idct_limit(out[3]) << 24;
+        }
+    }
+}
+
+// 2x2: a lane per block.  The 25 coefficients at rows and columns 0, 1, 3, 5, 7 sit in registers -- from the sparse
+// stream by the mask / popcount walk, or from the dense zigzag slots, all eight 16-byte groups of which hold some of
+// them (Z: their zigzag places, kZzInv[8 * L[a] + L[b]], every index a constant once unrolled) -- then five column
+// passes, two row passes and a 2-byte store per output row.
+template <>
+__global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct_reduced<2>(const JpegImage* __restrict__ imgs,
+                                                                       const JpegChunk* __restrict__ chunks)
+{
+    constexpr uint8_t L[5]     = {0, 1, 3, 5, 7};
+    constexpr uint8_t Z[5][5]  = {{0, 1, 6, 15, 28}, {2, 4, 13, 26, 42}, {9, 11, 24, 40, 53}, {20, 22, 38, 51, 60},
+                                  {35, 36, 49, 58, 63}};
+    const JpegChunk  C = chunks[blockIdx.x];
+    const JpegImage& I = imgs[C.img];
+    const int        k = C.comp, bi = threadIdx.x;
+    if (bi >= C.count) return;
+    const int       src = C.first + bi;
+    const JpegBlock B   = gaddr<const JpegBlock>(I.blocks[k])[src];
+    const gp<const int16_t> dense = gaddr<const int16_t>(I.dvals[k]);
+    int c[5][5];
+    if (dense) {
+        uint4 d[8];
+#pragma unroll
+        for (int t = 0; t < 8; t++) d[t] = *(gp<const uint4>)(dense + (size_t)src * 64 + 8 * t);
+#pragma unroll
+        for (int a = 0; a < 5; a++)
+#pragma unroll
+            for (int b = 0; b < 5; b++) {
+                const int      z = Z[a][b], e = z & 7;
+                const uint4    v = d[z >> 3];
+                const uint32_t w = e < 2 ? v.x : e < 4 ? v.y : e < 6 ? v.z : v.w;
+                c[a][b] = ((B.mask >> z) & 1) ? (int)(int16_t)(w >> (16 * (e & 1))) * (int)I.qz[k][z] : 0;
+            }
+    } else {
+        const gp<const int16_t> vals = gaddr<const int16_t>(I.values);
+#pragma unroll
+        for (int a = 0; a < 5; a++)
+#pragma unroll
+            for (int b = 0; b < 5; b++) {
+                const int z = Z[a][b];
+                c[a][b]     = 0;
+                if ((B.mask >> z) & 1)
+                    c[a][b] = (int)vals[B.val_off + __builtin_popcountll(B.mask & ((1ull << z) - 1))] * (int)I.q[k][L[a] * 8 + L[b]];
+            }
+    }
+    int ws[2][5], out[2][2];
+#pragma unroll
+    for (int b = 0; b < 5; b++) red2<13>(c[0][b], c[1][b], c[2][b], c[3][b], c[4][b], ws[0][b], ws[1][b]);
+#pragma unroll
+    for (int r = 0; r < 2; r++) red2<20>(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][4], out[r][0], out[r][1]);
+    int by, bx;
+    locate_block(src, I.bw[k], by, bx);
+    const gp<uint8_t> o = gaddr<uint8_t>(I.planes[k]) + (size_t)(by * 2) * I.pitch[k] + bx * 2;
+#pragma unroll
+    for (int r = 0; r < 2; r++)
+        *(gp<uint16_t>)(o + (size_t)r * I.pitch[k]) = (uint16_t)(idct_limit(out[r][0]) | idct_limit(out[r][1]) << 8);
+}
+
+// 1x1: a lane per block reads the DC alone -- the first value of the sparse stream when mask bit 0 is set, or slot 0
+// of the dense block -- and the four lanes that hold four aligned neighbours of a plane row (same wave, same chunk)
+// hand their bytes to the first, which stores a dword; the others store their byte.
+template <>
+__global__ __launch_bounds__(kJpegIdctLanes) void jpeg_idct_reduced<1>(const JpegImage* __restrict__ imgs,
+                                                                       const JpegChunk* __restrict__ chunks)
+{
+    const JpegChunk  C = chunks[blockIdx.x];
+    const JpegImage& I = imgs[C.img];
+    const int        k = C.comp, bi = threadIdx.x, lane = threadIdx.x & 63;
+    const int        b = C.first + min(bi, C.count - 1);
+    const JpegBlock  B = gaddr<const JpegBlock>(I.blocks[k])[b];
+    const gp<const int16_t> dense = gaddr<const int16_t>(I.dvals[k]);
+    int dc = 0;
+    if (B.mask & 1) dc = dense ? (int)dense[(size_t)b * 64] : (int)gaddr<const int16_t>(I.values)[B.val_off];
+    const uint32_t v = idct_limit(descale<3>(dc * (int)I.q[k][0]));
+    const int rw = I.bw[k];
+    int       by, bx;
+    locate_block(b, rw, by, bx);
+    const int      p  = bx & 3;
+    const uint32_t v1 = __shfl_down(v, 1), v2 = __shfl_down(v, 2), v3 = __shfl_down(v, 3);
+    const bool quad = lane - p >= 0 && lane - p + 3 < 64 && bx - p + 3 < rw && bi - p + 3 < C.count;
+    if (bi >= C.count) return;
+    const gp<uint8_t> o = gaddr<uint8_t>(I.planes[k]) + (size_t)by * I.pitch[k] + bx;
+    if (!quad) *o = (uint8_t)v;
+    else if (p == 0) *(gp<uint32_t>)o = v | v1 << 8 | v2 << 16 | v3 << 24;
+}
+
 // The geometry of one component as the colour pass uses it: its staged plane rows [lo, lo + n) in
 // LDS (pitch pw: the component's block rectangle; P is set back by the rectangle's first sample column, so that
 // samples are addressed by their column in the image's plane), upsampler and the whole image's sizes.
@@ -237,10 +491,10 @@ struct CompView {
 
 // The plane rows [lo, hi] of component k that output rows [y0, y1]'s upsampling reads (jdsample.c's
 // context rows for the triangle filters, clamped at the image edges).
-template <bool REGION>
+template <int MODE>
 __device__ __forceinline__ void comp_rows(const JpegImage& I, int k, int y0, int y1, CompView& c, int& hi)
 {
-    c.pw = Geo<REGION>::rw(I, k) * 8, c.dw = I.dw[k], c.dh = I.dh[k], c.up = I.up[k], c.hf = I.hf[k], c.vf = I.vf[k];
+    c.pw = Geo<MODE>::pitch(I, k), c.dw = I.dw[k], c.dh = I.dh[k], c.up = I.up[k], c.hf = I.hf[k], c.vf = I.vf[k];
     if (c.up == UP_H1V2 || c.up == UP_H2V2) c.lo = max((y0 >> 1) - 1, 0), hi = min((y1 >> 1) + 1, c.dh - 1);
     else if (c.up == UP_BOX) c.lo = y0 / c.vf, hi = y1 / c.vf;
     else c.lo = y0, hi = y1;
@@ -279,11 +533,11 @@ __device__ __forceinline__ int upsampled(const CompView& c, int x, int y)
 // one lane per 4 consecutive pixels of the record -- one dword (gray) or three dwords (BGR) when the group is whole
 // and 4-byte aligned, bytewise otherwise.  A pixel is sampled at its place in the image, so the chroma phase
 // and the filters' neighbours are the whole decode's wherever the record starts.
-template <bool REGION>
+template <int MODE>
 __device__ __forceinline__ void color_rows(const JpegImage& I, const CompView* cv, int y0, int nrows)
 {
-    const int W = Geo<REGION>::ow(I), ox = Geo<REGION>::ox(I), cn = I.out_cn, nc = cn == 1 ? 1 : I.ncomp;
-    const gp<uint8_t> out = gaddr<uint8_t>(I.out) - (size_t)Geo<REGION>::oy(I) * I.out_stride; // (row y of the image)
+    const int W = Geo<MODE>::ow(I), ox = Geo<MODE>::ox(I), cn = I.out_cn, nc = cn == 1 ? 1 : I.ncomp;
+    const gp<uint8_t> out = gaddr<uint8_t>(I.out) - (size_t)Geo<MODE>::oy(I) * I.out_stride; // (row y of the image)
     const int         stride = I.out_stride;
     const int groups = (W + 3) >> 2;
     for (int q = threadIdx.x; q < groups * nrows; q += blockDim.x) {
@@ -532,18 +786,22 @@ __device__ __forceinline__ void color_h2v2(const JpegImage& I, const JpegRows& R
 }
 
 // A workgroup per band of output rows: the plane rows the band's upsampling reads are copied into
-// LDS with coalesced 8-byte loads (jpeg_stage_rows bounds them), then color_rows.
-template <bool REGION>
+// LDS with coalesced 8-byte loads (jpeg_stage_rows bounds them), then color_rows.  A scaled call's files all take
+// color_rows: color_h2v2 is the full-size files' (a reduced 4:2:0 file has nothing left to upsample).
+template <int MODE>
 __global__ __launch_bounds__(256) void jpeg_color(const JpegImage* __restrict__ imgs, const JpegRows* __restrict__ rows)
 {
+    constexpr bool REGION = MODE == GEO_REGION;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_b[];
     const JpegRows   R  = rows[blockIdx.x];
     const JpegImage& I  = imgs[R.img];
-    if (I.ncomp == 3 && I.out_cn == 3 && I.up[0] == UP_FULL && I.up[1] == UP_H2V2 && I.up[2] == UP_H2V2 &&
-        ((R.y0 & 1) == 0 || (REGION && R.y0 == I.oy))) { // (a region's first band ends where the even bands start)
-        if (REGION && (I.ox & 1)) color_h2v2<true, REGION>(I, R, lds_b);
-        else color_h2v2<false, REGION>(I, R, lds_b);
-        return;
+    if constexpr (MODE != GEO_SCALED) {
+        if (I.ncomp == 3 && I.out_cn == 3 && I.up[0] == UP_FULL && I.up[1] == UP_H2V2 && I.up[2] == UP_H2V2 &&
+            ((R.y0 & 1) == 0 || (REGION && R.y0 == I.oy))) { // (a region's first band ends where the even bands start)
+            if (REGION && (I.ox & 1)) color_h2v2<true, REGION>(I, R, lds_b);
+            else color_h2v2<false, REGION>(I, R, lds_b);
+            return;
+        }
     }
     const int        nc = I.out_cn == 1 ? 1 : I.ncomp;
     const int        y1 = R.y0 + R.rows - 1;
@@ -553,18 +811,18 @@ __global__ __launch_bounds__(256) void jpeg_color(const JpegImage* __restrict__ 
     for (int k = 0; k < 3; k++) {
         CompView& c = cv[k];
         int       hi;
-        comp_rows<REGION>(I, k, R.y0, y1, c, hi);
-        c.P = lds_b + off - Geo<REGION>::rx(I, k) * 8;
+        comp_rows<MODE>(I, k, R.y0, y1, c, hi);
+        c.P = lds_b + off - Geo<MODE>::rx(I, k) * 8;
         if (k >= nc) continue;
         // stage plane rows [lo, hi]: whole rows of pw bytes (a multiple of 8) are contiguous
-        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)(c.lo - Geo<REGION>::ry(I, k) * 8) * c.pw);
+        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)(c.lo - Geo<MODE>::ry(I, k) * 8) * c.pw);
         uint2*       dst = (uint2*)(lds_b + off);
         const int    n8  = (hi - c.lo + 1) * c.pw / 8;
         for (int e = threadIdx.x; e < n8; e += blockDim.x) dst[e] = src[e];
         off += (hi - c.lo + 1) * c.pw;
     }
     __syncthreads();
-    color_rows<REGION>(I, cv, R.y0, R.rows);
+    color_rows<MODE>(I, cv, R.y0, R.rows);
 }
 
 // ---- CMYK, YCCK and RGB sources ------------------------------------------------------------------
@@ -595,7 +853,7 @@ __device__ __forceinline__ uint32_t convert4(int cs, int cn, int s0, int s1, int
 // A workgroup per band of output rows of a CMYK, YCCK or RGB file: every component's plane rows the
 // band reads staged in LDS as jpeg_color stages them (jpeg_stage_rows bounds them), then one lane per
 // 4 consecutive pixels of the record with color_rows' stores, each sampled at its place in the image.
-template <bool REGION>
+template <int MODE>
 __global__ __launch_bounds__(256) void jpeg_color4(const JpegImage* __restrict__ imgs, const JpegRows* __restrict__ rows)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_b[];
@@ -612,17 +870,17 @@ __global__ __launch_bounds__(256) void jpeg_color4(const JpegImage* __restrict__
             continue;
         }
         int hi;
-        comp_rows<REGION>(I, k, y0, y1, c, hi);
-        c.P = lds_b + off - Geo<REGION>::rx(I, k) * 8;
-        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)(c.lo - Geo<REGION>::ry(I, k) * 8) * c.pw);
+        comp_rows<MODE>(I, k, y0, y1, c, hi);
+        c.P = lds_b + off - Geo<MODE>::rx(I, k) * 8;
+        const gp<const uint2> src = (gp<const uint2>)(gaddr<const uint8_t>(I.planes[k]) + (size_t)(c.lo - Geo<MODE>::ry(I, k) * 8) * c.pw);
         uint2*       dst = (uint2*)(lds_b + off);
         const int    n8  = (hi - c.lo + 1) * c.pw / 8;
         for (int e = threadIdx.x; e < n8; e += blockDim.x) dst[e] = src[e];
         off += (hi - c.lo + 1) * c.pw;
     }
     __syncthreads();
-    const int W = Geo<REGION>::ow(I), ox = Geo<REGION>::ox(I), cn = I.out_cn, cs = I.cs, stride = I.out_stride;
-    const gp<uint8_t> out = gaddr<uint8_t>(I.out) - (size_t)Geo<REGION>::oy(I) * stride; // (row y of the image)
+    const int W = Geo<MODE>::ow(I), ox = Geo<MODE>::ox(I), cn = I.out_cn, cs = I.cs, stride = I.out_stride;
+    const gp<uint8_t> out = gaddr<uint8_t>(I.out) - (size_t)Geo<MODE>::oy(I) * stride; // (row y of the image)
     const int groups = (W + 3) >> 2;
     for (int q = threadIdx.x; q < groups * R.rows; q += blockDim.x) {
         const int y = y0 + q / groups, x0 = (q % groups) * 4;
@@ -664,21 +922,34 @@ static hipError_t launch_color(K kernel, const JpegImage* imgs, const JpegRows* 
     return hipSuccess;
 }
 
-template <bool REGION>
-static hipError_t launch_jpeg_as(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                                 int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, hipStream_t stream)
+template <int MODE>
+static hipError_t launch_jpeg_as(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const int* n_reduced,
+                                 const JpegRows* rows, int n_rows, int color_lds, const JpegRows* rows4, int n_rows4,
+                                 int color4_lds, hipStream_t stream)
 {
-    if (n_chunks > 0) hipLaunchKernelGGL(jpeg_idct<REGION>, dim3(n_chunks), dim3(kJpegIdctLanes), 0, stream, imgs, chunks);
-    hipError_t e = launch_color(jpeg_color<REGION>, imgs, rows, n_rows, color_lds, stream);
-    if (e == hipSuccess) e = launch_color(jpeg_color4<REGION>, imgs, rows4, n_rows4, color4_lds, stream);
+    if (n_chunks > 0)
+        hipLaunchKernelGGL(jpeg_idct<MODE == GEO_REGION>, dim3(n_chunks), dim3(kJpegIdctLanes), 0, stream, imgs, chunks);
+    if constexpr (MODE == GEO_SCALED) { // one launch per IDCT size present; their chunks follow the 8x8 ones
+        const JpegChunk* c = chunks + n_chunks;
+        if (n_reduced[0] > 0) hipLaunchKernelGGL(jpeg_idct_reduced<4>, dim3(n_reduced[0]), dim3(kJpegIdctLanes), 0, stream, imgs, c);
+        c += n_reduced[0];
+        if (n_reduced[1] > 0) hipLaunchKernelGGL(jpeg_idct_reduced<2>, dim3(n_reduced[1]), dim3(kJpegIdctLanes), 0, stream, imgs, c);
+        c += n_reduced[1];
+        if (n_reduced[2] > 0) hipLaunchKernelGGL(jpeg_idct_reduced<1>, dim3(n_reduced[2]), dim3(kJpegIdctLanes), 0, stream, imgs, c);
+    }
+    hipError_t e = launch_color(jpeg_color<MODE>, imgs, rows, n_rows, color_lds, stream);
+    if (e == hipSuccess) e = launch_color(jpeg_color4<MODE>, imgs, rows4, n_rows4, color4_lds, stream);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, bool region, hipStream_t stream)
+hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const int* n_reduced, const JpegRows* rows,
+                       int n_rows, int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, bool region,
+                       hipStream_t stream)
 {
-    return region ? launch_jpeg_as<true>(imgs, chunks, n_chunks, rows, n_rows, color_lds, rows4, n_rows4, color4_lds, stream)
-                  : launch_jpeg_as<false>(imgs, chunks, n_chunks, rows, n_rows, color_lds, rows4, n_rows4, color4_lds, stream);
+    if (n_reduced)
+        return launch_jpeg_as<GEO_SCALED>(imgs, chunks, n_chunks, n_reduced, rows, n_rows, color_lds, rows4, n_rows4, color4_lds, stream);
+    return region ? launch_jpeg_as<GEO_REGION>(imgs, chunks, n_chunks, nullptr, rows, n_rows, color_lds, rows4, n_rows4, color4_lds, stream)
+                  : launch_jpeg_as<GEO_WHOLE>(imgs, chunks, n_chunks, nullptr, rows, n_rows, color_lds, rows4, n_rows4, color4_lds, stream);
 }
 
 } // namespace aeon_hip

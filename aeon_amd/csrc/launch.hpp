@@ -69,9 +69,12 @@ hipError_t launch_box_targets(const BoxLaunch& L, hipStream_t stream);
 hipError_t launch_rcnn_targets(const RcnnLaunch& L, hipStream_t stream);
 // video_kernels.hip
 hipError_t launch_clip_pad(const PadRegion* regions, int n_regions, uint64_t max_bytes, hipStream_t stream);
-// jpeg_kernels.hip (region: some record of the call is a region of its image: the <true> instantiations)
-hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const JpegRows* rows, int n_rows,
-                       int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, bool region, hipStream_t stream);
+// jpeg_kernels.hip (region: some record of the call is a region of its image: the region instantiations).  n_reduced
+// (null but for a call with reduced-size records: the scaled instantiations): the chunks of jpeg_idct_reduced<4>,
+// <2> and <1>, which follow jpeg_idct's n_chunks in `chunks`
+hipError_t launch_jpeg(const JpegImage* imgs, const JpegChunk* chunks, int n_chunks, const int* n_reduced, const JpegRows* rows,
+                       int n_rows, int color_lds, const JpegRows* rows4, int n_rows4, int color4_lds, bool region,
+                       hipStream_t stream);
 // jpeg_huff.hip
 int        jpeg_huff_stage_cap(int lanes);
 // region: some file of the call stores only the blocks inside its components' rectangles (jpeg_huff<LANES, true>)

@@ -117,6 +117,12 @@ int aeon_hip_decode_jpeg_progressive_batch(aeon_hip_ctx*, int, const void* const
 {
     return no_device();
 }
+int aeon_hip_decode_jpeg_scaled_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const aeon_img_desc*,
+                                      const int32_t*, void*, void*)
+{
+    return no_device();
+}
+int aeon_hip_jpeg_launch_counts(aeon_hip_ctx*, int64_t*) { return no_device(); }
 int aeon_hip_jpeg_huff_stage_cap(int, int*) { return no_device(); }
 int aeon_hip_jpeg_huff_lanes(aeon_hip_ctx*, int*) { return no_device(); }
 int aeon_hip_decode_png_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const int*, const aeon_img_desc*, void*,

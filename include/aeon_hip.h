@@ -259,6 +259,28 @@ int aeon_jpeg_prog_emulate(const void* data, size_t size, int* width, int* heigh
  * (may be null) is checked against the region as the decode call checks it, with the same errors. */
 int aeon_jpeg_region_plan(const void* data, size_t size, const aeon_region* region, const aeon_img_desc* desc,
                           int out_channels, int* components, int32_t* out);
+/* As aeon_hip_decode_jpeg_batch, but record i is file i at 1 / scales[i] of its size -- scales[i] = 1, 2, 4 or 8,
+ * libjpeg's DCT-domain scaling (scale_denom; cv::imdecode's IMREAD_REDUCED_COLOR_2 / 4 / 8, Pillow's draft mode), bit
+ * for bit -- and descs[i] describes a record of exactly ceil(W / s) x ceil(H / s).  Every 8x8 block of a component is
+ * inverse-transformed straight to n x n samples by jpeg_idct_reduced<n> (n = 8 / s, doubled per component while the
+ * component stays no finer than the output: the chroma of a 4:2:0 file comes out at the luma's size and is not
+ * upsampled at all); the entropy-coded data is walked whole as ever.  Gray, YCbCr and three-component RGB files;
+ * a four-component file with s > 1 is AEON_HIP_EUNSUPPORTED.  Before any launch: a scale other than 1, 2, 4, 8, or
+ * a descriptor of another size, is AEON_HIP_EINVAL ("JPEG: ... (record i)").  A null `scales`, or all ones, is
+ * aeon_hip_decode_jpeg_batch's call exactly. */
+int aeon_hip_decode_jpeg_scaled_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                      const aeon_img_desc* descs, const int32_t* scales, void* dst_base, void* stream);
+/* The geometry of each component of a JPEG file decoded at 1 / scale, as aeon_hip_decode_jpeg_scaled_batch computes
+ * it.  Host only, no context needed.  out[4 * k ...] = IDCT size n (8, 4, 2 or 1 samples a block side), sample
+ * columns dw, sample rows dh and the upsampler that is left (0 none, 1 h2v1 fancy, 2 h1v2 fancy, 3 h2v2 fancy, 4 box)
+ * of component k (*components of them; zeros for a component the record does not need).  desc (may be null) is
+ * checked against the scale as the decode call checks it, with the same errors. */
+int aeon_jpeg_scaled_plan(const void* data, size_t size, int scale, const aeon_img_desc* desc, int out_channels,
+                          int* components, int32_t* out);
+/* The kernel launches of the context's JPEG calls so far: out[0] jpeg_huff, [1] jpeg_idct, [2..4] jpeg_idct_reduced
+ * <4>, <2>, <1>, [5] jpeg_color, [6] jpeg_color4, [7] the calls that ran the scaled instantiations of the colour
+ * kernels (a call adds one to the slot of each kernel it launched). */
+int aeon_hip_jpeg_launch_counts(aeon_hip_ctx* ctx, int64_t out[8]);
 
 /* ---- video: provider::video (src/provider.cpp:477-517, src/etl_video.{hpp,cpp}) ------------------
  * aeon_avi_frames: video::extractor's demux (MotionJpegCapture, src/cap_mjpeg_decoder.cpp:132-227 over
