@@ -254,6 +254,9 @@ def lib():
         L.aeon_png_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int), P(ctypes.c_int64)]
         L.aeon_png_decoder_route.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
         L.aeon_png_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
+        L.aeon_hip_decode_png_interlaced_batch.argtypes = L.aeon_hip_decode_png_batch.argtypes
+        L.aeon_png_interlaced_route.argtypes = L.aeon_png_decoder_route.argtypes
+        L.aeon_png_gpu_emulate_interlaced.argtypes = L.aeon_png_gpu_emulate.argtypes
         L.aeon_pixmap_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 5
         L.aeon_decode_pixmap.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
                                          P(ctypes.c_int)]
@@ -788,14 +791,24 @@ def png_decoder_route(data):
     return bool(g.value)
 
 
-def png_gpu_emulate(data, mode=PNG_BGR8):
+def png_interlaced_route(data):
+    """Does Context.decode_png_batch(..., interlaced=True) decode this PNG file on the device
+    (aeon_png_interlaced_route)?"""
+    g = ctypes.c_int()
+    _check(lib().aeon_png_interlaced_route(bytes(data), len(data), ctypes.byref(g)))
+    return bool(g.value)
+
+
+def png_gpu_emulate(data, mode=PNG_BGR8, interlaced=False):
     """decode_png through the PNG stage's kernel code run on the host (aeon_png_gpu_emulate).  AeonHipError
-    for a file the stage leaves to the host decoder, or one the device would report as corrupt."""
+    for a file the stage leaves to the host decoder, or one the device would report as corrupt.  interlaced: with
+    the routing and the kernel code of decode_png_batch(..., interlaced=True) (aeon_png_gpu_emulate_interlaced)."""
     w, h, d, c = png_info(data)
     wide = mode == PNG_ANYDEPTH and d == 16 and c != 3
     cn = 3 if mode == PNG_BGR8 else 1
     out = np.zeros((h, w, cn) if cn == 3 else (h, w), np.uint16 if wide else np.uint8)
-    _check(lib().aeon_png_gpu_emulate(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
+    call = lib().aeon_png_gpu_emulate_interlaced if interlaced else lib().aeon_png_gpu_emulate
+    _check(call(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
     return out
 
 
@@ -1105,18 +1118,19 @@ class Context:
         _check(lib().aeon_hip_jpeg_huff_lanes(self._h, ctypes.byref(n)))
         return n.value
 
-    def decode_png_batch(self, files, modes, descs, dst_ptr, stream=0):
+    def decode_png_batch(self, files, modes, descs, dst_ptr, stream=0, interlaced=False):
         """decode_png of PNG files into device memory (aeon_hip_decode_png_batch): files = list of bytes (or
         a JpegFiles, marshalled once), modes[i] = PNG_BGR8 / PNG_GRAY8 / PNG_ANYDEPTH, descs[i] = where
-        record i goes (HWC; ANYDEPTH of a 16-bit file: native uint16)."""
+        record i goes (HWC; ANYDEPTH of a 16-bit file: native uint16).  interlaced: Adam7 files decode on the
+        device too (aeon_hip_decode_png_interlaced_batch, png_interlaced_route)."""
         jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
         n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
         m = modes if isinstance(modes, ctypes.Array) else (ctypes.c_int * n)(*[int(x) for x in modes])
         d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
         if len(m) < n or len(d) < n:
             raise ValueError(f"{len(m)} modes / {len(d)} descriptors for {n} files")
-        _check(lib().aeon_hip_decode_png_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
-                                               ctypes.c_void_p(stream or 0)))
+        call = lib().aeon_hip_decode_png_interlaced_batch if interlaced else lib().aeon_hip_decode_png_batch
+        _check(call(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream or 0)))
 
     def decode_pixmap_batch(self, files, modes, descs, dst_ptr, stream=0):
         """decode_pixmap of BMP / PNM files into device memory (aeon_hip_decode_pixmap_batch): files = list of

@@ -159,6 +159,32 @@ int aeon_png_gpu_emulate(const void* data, size_t size, int mode, void* dst, siz
     });
 }
 
+int aeon_png_interlaced_route(const void* data, size_t size, int* device)
+{
+    return guarded([&] {
+        if (!data || !device) fail(AEON_HIP_EINVAL, "null argument");
+        PngPlan P;
+        png_plan(data, size, AEON_PNG_ANYDEPTH, P, true);
+        *device = P.route;
+        return 0;
+    });
+}
+
+int aeon_png_gpu_emulate_interlaced(const void* data, size_t size, int mode, void* dst, size_t stride)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        if (mode < AEON_PNG_BGR8 || mode > AEON_PNG_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown PNG decode mode");
+        PngPlan P;
+        png_plan(data, size, mode, P, true);
+        if (stride < (size_t)P.w * P.channels * P.elem_bytes || stride > INT32_MAX) fail(AEON_HIP_EINVAL, "stride too small");
+        const int r = png_gpu_emulate(data, size, mode, dst, stride, true);
+        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "PNG: the file is not routed to the device (too wide, or 2^31 bytes or more)");
+        if (r < 0) fail(AEON_HIP_EDEVICE, "PNG: image data corrupt or truncated (GPU stage)");
+        return 0;
+    });
+}
+
 int aeon_pixmap_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* channels, int* format)
 {
     return guarded([&] {

@@ -671,8 +671,10 @@ namespace {
 // The decode call: each file's chunk walk (png_plan) on the pool, the layout of the call's staging -- the jobs,
 // the routed files' zlib streams, the host-decoded files' pixels -- filled on the pool, one H2D, then
 // png_inflate and png_unfilter over the jobs and a strided device copy per host-decoded file, all on `stream`.
+// adam7: the opt-in call -- png_route_adam7 routes, and the interlaced files' jobs stand behind the plain ones in
+// the table: one png_inflate launch over all of them, png_unfilter over the plain ones, png_unfilter_adam7 over the rest.
 int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
-            const aeon_img_desc* descs, void* dst_base, hipStream_t stream)
+            const aeon_img_desc* descs, void* dst_base, hipStream_t stream, bool adam7)
 {
     if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !modes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
     if (n == 0) return 0;
@@ -690,7 +692,7 @@ int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* siz
         if (!data[i] || !sizes[i]) fail(AEON_HIP_EINVAL, "PNG: empty file");
         if (modes[i] < AEON_PNG_BGR8 || modes[i] > AEON_PNG_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown PNG decode mode");
         PngPlan& P = plans[i];
-        png_plan(data[i], sizes[i], modes[i], P);
+        png_plan(data[i], sizes[i], modes[i], P, adam7);
         const aeon_img_desc& d = descs[i];
         if (d.width != P.w || d.height != P.h)
             fail(AEON_HIP_EINVAL, "PNG: record " + std::to_string(i) + " is " + std::to_string(P.w) + "x" + std::to_string(P.h) +
@@ -700,9 +702,12 @@ int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* siz
     // layout: the jobs, then per file its stream (8-byte aligned and padded) or its pixels (16-byte aligned)
     std::vector<size_t> at(n), raw_at(n);
     std::vector<int>    job_of(n, -1);
-    int                 n_gpu = 0, lds = 0;
+    int                 n_gpu = 0, lds = 0, n_plain = 0, lds7 = 0;
     for (int i = 0; i < n; i++)
-        if (plans[i].route) job_of[i] = n_gpu++;
+        if (plans[i].route && !plans[i].interlace) job_of[i] = n_gpu++;
+    n_plain = n_gpu;
+    for (int i = 0; i < n; i++)
+        if (plans[i].route && plans[i].interlace) job_of[i] = n_gpu++;
     size_t total = (size_t)n_gpu * sizeof(PngJob), scratch = 0;
     for (int i = 0; i < n; i++) {
         const PngPlan& P = plans[i];
@@ -741,7 +746,10 @@ int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* siz
         J.stride = descs[i].stride;
     });
     for (int i = 0; i < n; i++)
-        if (plans[i].route) lds = std::max(lds, png_unfilter_lds(jobs[job_of[i]].rowb));
+        if (plans[i].route) {
+            int& l = plans[i].interlace ? lds7 : lds;
+            l      = std::max(l, png_unfilter_lds(jobs[job_of[i]].rowb));
+        }
     KernelTimer t{};
     bool        timed = false;
     if (ctx->timing && n_gpu) {
@@ -750,7 +758,7 @@ int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* siz
     }
     HIP_OK(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, stream));
     if (timed) HIP_OK(hipEventRecord(t.start, stream));
-    HIP_OK(launch_png((const PngJob*)st.dev, n_gpu, lds, stream_error(ctx, stream), stream));
+    HIP_OK(launch_png((const PngJob*)st.dev, n_plain, lds, n_gpu - n_plain, lds7, stream_error(ctx, stream), stream));
     if (timed) {
         HIP_OK(hipEventRecord(t.stop, stream));
         std::lock_guard<std::mutex> tl(ctx->mu);
@@ -1033,7 +1041,13 @@ int aeon_hip_decode_pixmap_batch(aeon_hip_ctx* ctx, int n, const void* const* da
 int aeon_hip_decode_png_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
                               const aeon_img_desc* descs, void* dst_base, void* stream)
 {
-    return guarded([&] { return run_png(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream); });
+    return guarded([&] { return run_png(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream, false); });
+}
+
+int aeon_hip_decode_png_interlaced_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                                         const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return guarded([&] { return run_png(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream, true); });
 }
 
 int aeon_hip_transpose_batch(aeon_hip_ctx* ctx, const void* src_dev, void* dst_dev, int64_t rows, int64_t cols,

@@ -85,8 +85,10 @@ hipError_t launch_jpeg_huff(const JpegHuffFile* files, int n_files, int lanes, i
 hipError_t launch_jpeg_prog_scan(const JpegProgScan* scans, const JpegProgUnit* units, int n_units, int32_t* error,
                                  hipStream_t stream);
 hipError_t launch_jpeg_prog_mask(const JpegProgMask* jobs, int n_jobs, hipStream_t stream);
-// png_kernels.hip: png_inflate then png_unfilter over the jobs, one wave per file each
-hipError_t launch_png(const PngJob* jobs, int n_jobs, int unfilter_lds, int32_t* error, hipStream_t stream);
+// png_kernels.hip: png_inflate over all the jobs, one wave per file; then png_unfilter over the first n_plain, one
+// wave per file, and png_unfilter_adam7 over the n_adam7 interlaced ones behind them, one wave per file and pass
+hipError_t launch_png(const PngJob* jobs, int n_plain, int unfilter_lds, int n_adam7, int adam7_lds, int32_t* error,
+                      hipStream_t stream);
 // pixmap_kernels.hip: pixmap_convert, one workgroup per band
 hipError_t launch_pixmap(const PixmapJob* jobs, const PixmapBand* bands, int n_bands, hipStream_t stream);
 // tiff_kernels.hip: tiff_expand, one wave per compressed strip or tile, tiff_expand_large, one wave per LZW / PackBits

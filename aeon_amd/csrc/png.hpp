@@ -7,6 +7,10 @@
 // png_inflate (one wave per file) inflates the stream into the file's device scratch, png_unfilter (one
 // workgroup per file) undoes the row filters there and converts the rows into the record.  Interlaced files,
 // very wide rows and streams of 2^31 bytes or more stay with png_decode on the host (png_route).
+//
+// The opt-in call (aeon_hip_decode_png_interlaced_batch) takes Adam7 files too (png_route_adam7): their stream
+// inflates to the seven passes' sub-images back to back, and png_unfilter_adam7 (one wave per file and pass)
+// undoes each pass's filters and scatters its pixels into the record.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -41,7 +45,7 @@ struct alignas(16) PngJob {
     uint64_t out;  // the record
     uint32_t clen, need; // compressed bytes, inflated bytes
     int32_t  w, h, depth, ctype, samples, npal, mode, elem_bytes;
-    int32_t  rowb, bpp; // bytes of a row, the filters' byte distance
+    int32_t  rowb, bpp; // bytes of a row (an interlaced file: of its widest pass row), the filters' byte distance
     int32_t  out_row_bytes, stride;
     uint8_t  pal[768];
 };
@@ -50,12 +54,14 @@ static_assert(sizeof(PngJob) % 16 == 0, "PngJob: 16-byte aligned array elements"
 // What the host half learns from a file's chunks without touching its pixels.
 struct PngPlan {
     int    w = 0, h = 0, depth = 0, ctype = 0, interlace = 0, channels = 0, elem_bytes = 1;
-    int    route = 0;   // 1: the device inflates and unfilters the file (png_route)
+    int    route = 0;   // 1: the device inflates and unfilters the file (png_route / png_route_adam7)
     size_t clen = 0;    // bytes of its zlib stream
-    size_t need = 0;    // bytes of its inflated scanlines (routed files)
+    size_t need = 0;    // bytes of its inflated scanlines (routed files; Adam7: of the passes that are present)
 };
-// The chunk walk of png_decode (same refusals, same messages) plus the zlib header check, and the routing rule.
-void png_plan(const void* data, size_t size, int mode, PngPlan& P);
+// The chunk walk of png_decode (same refusals, same messages) plus the zlib header check, and the routing rule:
+// png_route, or with `adam7` (the opt-in call) png_route_adam7, which also takes an interlaced file whose widest
+// pass row with its filter byte fits kPngMaxRow.
+void png_plan(const void* data, size_t size, int mode, PngPlan& P, bool adam7 = false);
 // What the decoder's inspect step asks: does this file go through the stage?  The chunk walk without the CRCs
 // (the batch call checks them), png_plan's routing rule, and the measured one on top: png_inflate's time goes
 // with the symbols it decodes (the compressed bytes), the host decoder's with the inflated bytes, and the
@@ -65,10 +71,12 @@ void png_plan(const void* data, size_t size, int mode, PngPlan& P);
 constexpr size_t kPngDecoderMinRatio = 8;
 bool             png_routed(const void* data, size_t size);
 // A routed file's job (everything but the three addresses) and its zlib stream copied to comp_dst
-// (P.clen bytes; the caller pads).
+// (P.clen bytes; the caller pads).  An interlaced file's job (a plan made with `adam7`) is png_unfilter_adam7's:
+// the same fields, the scratch holding the seven sub-images, whose offsets the kernel works out itself.
 void png_stage(const void* data, size_t size, int mode, const PngPlan& P, PngJob& J, uint8_t* comp_dst);
 // The stage's kernels run on this thread, lane after lane (png_inflate.hpp): 1 decoded, 0 the file is not
-// routed to the device (nothing written), -1 the device would set kPngCorruptBit.
-int png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+// routed to the device (nothing written), -1 the device would set kPngCorruptBit.  adam7: the opt-in call's
+// routing, an interlaced file through png_unfilter_adam7's code, pass after pass.
+int png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride, bool adam7 = false);
 
 } // namespace aeon_hip

@@ -7,7 +7,9 @@
 // filters and the colour reduction to the kernels (png_kernels.hip).  Within one file inflate is a serial bit
 // stream and the filters chain rows and pixels, but a decode window holds hundreds of files: the stage runs a
 // wave per file, with wide copies and a skewed wavefront across rows inside it.  png_gpu_emulate runs the
-// kernels' own code (png_inflate.hpp) on the host.
+// kernels' own code (png_inflate.hpp) on the host.  The opt-in call (aeon_hip_decode_png_interlaced_batch) plans
+// with png_route_adam7: an Adam7 file is staged the same way, its inflated bytes the seven passes' sub-images,
+// for png_unfilter_adam7's wave per file and pass.
 //
 // Output forms (what OpenCV 2.4's PngDecoder asks libpng for):
 //   AEON_PNG_BGR8   -- CV_LOAD_IMAGE_COLOR: 8-bit BGR.  16-bit samples keep their high byte
@@ -291,7 +293,26 @@ static bool png_route(const PngHeader& H, size_t clen, size_t* need)
     return !H.interlace && rowb + 1 <= (size_t)kPngMaxRow && clen < ((size_t)1 << 31) && *need < ((size_t)1 << 31);
 }
 
-void png_plan(const void* data, size_t size, int mode, PngPlan& P)
+// The opt-in call's rule: a file png_route takes, or an interlaced one whose widest pass row (filter byte
+// included) fits png_unfilter_adam7's LDS, with the same bounds on the stream and on the seven sub-images together.
+// widest (optional): bytes of the widest pass row.
+static bool png_route_adam7(const PngHeader& H, size_t clen, size_t* need, int* widest = nullptr)
+{
+    if (!H.interlace) return png_route(H, clen, need);
+    size_t sum = 0;
+    int    wide = 0;
+    for (int k = 0; k < 7; k++) {
+        const pngdev::Pass A = pngdev::adam7_pass(H.w, H.h, H.samples * H.depth, k);
+        if (A.pw <= 0 || A.ph <= 0) continue;
+        sum += ((size_t)A.rowb + 1) * (size_t)A.ph;
+        wide = std::max(wide, A.rowb);
+    }
+    *need = sum;
+    if (widest) *widest = wide;
+    return (size_t)wide + 1 <= (size_t)kPngMaxRow && clen < ((size_t)1 << 31) && sum < ((size_t)1 << 31);
+}
+
+void png_plan(const void* data, size_t size, int mode, PngPlan& P, bool adam7)
 {
     PngHeader H;
     IdatSink  sink;
@@ -300,7 +321,7 @@ void png_plan(const void* data, size_t size, int mode, PngPlan& P)
     P.channels   = mode == AEON_PNG_BGR8 ? 3 : 1;
     P.elem_bytes = (mode == AEON_PNG_ANYDEPTH && H.depth == 16 && H.ctype != 3) ? 2 : 1;
     P.clen       = sink.len;
-    P.route      = png_route(H, size, &P.need) ? 1 : 0;
+    P.route      = (adam7 ? png_route_adam7(H, size, &P.need) : png_route(H, size, &P.need)) ? 1 : 0;
     if (!P.route) return;
     // the zlib header as inflate checks it: deflate, a window of 32 KiB at most, no preset dictionary, FCHECK
     const uint32_t cmf = sink.head[0], flg = sink.head[1];
@@ -336,12 +357,16 @@ void png_stage(const void* data, size_t size, int mode, const PngPlan& P, PngJob
     J.bpp  = std::max(1, H.samples * H.depth / 8);
     J.out_row_bytes = H.w * P.channels * P.elem_bytes;
     std::memcpy(J.pal, H.pal, sizeof(J.pal));
+    if (H.interlace) { // (routed: the plan was made with `adam7`) the widest pass row sizes the launch's LDS
+        size_t need = 0;
+        png_route_adam7(H, size, &need, &J.rowb);
+    }
 }
 
-int png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride)
+int png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride, bool adam7)
 {
     PngPlan P;
-    png_plan(data, size, mode, P);
+    png_plan(data, size, mode, P, adam7);
     if (!P.route) return 0;
     PngJob               J;
     std::vector<uint64_t> comp((P.clen + 7) / 8 + 1, 0), raw((P.need + 15) / 8 + 2, 0); // aligned, zero-padded
@@ -353,6 +378,7 @@ int png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t s
     if (!pngdev::inflate_file(mem[0], S)) return -1;
     const int lds = png_unfilter_lds(J.rowb);
     std::vector<uint64_t> um(lds / 8 + 1);
+    if (P.interlace) return pngdev::unfilter_file_adam7(J, 0, 1, (uint8_t*)um.data(), lds) ? 1 : -1;
     return pngdev::unfilter_file(J, (uint8_t*)um.data(), lds) ? 1 : -1;
 }
 

@@ -1,5 +1,5 @@
 // png_inflate.hpp -- the PNG stage's per-wave logic (png_kernels.hip), written once for the device and for
-// the host: png_inflate and png_unfilter run it on the 64 lanes of one wave; png_host.cpp's png_gpu_emulate
+// the host: png_inflate, png_unfilter and png_unfilter_adam7 run it on the 64 lanes of one wave; png_host.cpp's png_gpu_emulate
 // runs the same code with every lane loop walked serially, so the CPU tests and a sanitizer build cover what
 // the kernels run.  A lane loop is `for (int l = PNG_LANE0; l < n; l += PNG_LANE_STEP)`: lane l, l + 64, ...
 // on the device, 0, 1, 2, ... on the host.  Everything outside a lane loop is wave-uniform: what it loads
@@ -560,6 +560,117 @@ PNG_FN bool unfilter_file(const PngJob& J, uint8_t* mem, int lds)
         if (bad) ok = false;
         PNG_SYNC();
         for (int i = PNG_LANE0; i < rowb; i += PNG_LANE_STEP) prev[i] = b0[(size_t)(rows - 1) * pitch + 1 + i];
+    }
+    return ok;
+}
+
+// ---- Adam7 (png_unfilter_adam7) ------------------------------------------------------------------------
+
+// Pass k (0..6) of a w x h picture of `bits` bits a pixel: pass pixel (i, r) is picture pixel (x0 + i dx,
+// y0 + r dy); pw x ph pixels in rows of rowb bytes behind their filter byte.  pw or ph 0: the pass is absent.
+struct Pass {
+    int x0, y0, dx, dy, pw, ph, rowb;
+};
+PNG_FN Pass adam7_pass(int w, int h, int bits, int k)
+{
+    // (origins and steps a nibble each, pass 0 lowest: a table indexed by a run-time pass is a memory load)
+    Pass A;
+    A.x0 = (0x0102040 >> (4 * k)) & 15, A.y0 = (0x1020400 >> (4 * k)) & 15;
+    A.dx = (0x1224488 >> (4 * k)) & 15, A.dy = (0x2244888 >> (4 * k)) & 15;
+    A.pw = (w - A.x0 + A.dx - 1) / A.dx, A.ph = (h - A.y0 + A.dy - 1) / A.dy; // (x0 < dx: never negative)
+    A.rowb = (int)(((uint32_t)A.pw * (uint32_t)bits + 7) >> 3);
+    return A;
+}
+
+// One pass's sub-image, `off` bytes into the file's scratch, unfiltered band by band as unfilter_file does (the
+// same LDS layout at the pass's own row size; the palette is loaded), and its pixels scattered into the record.
+// The last pass is whole rows of the record: four output bytes per lane and store, as unfilter_file.  Every other
+// pass: a lane takes a pass pixel of the band per step and writes its 1, 2 or 3 output bytes where the pixel
+// belongs.  No two passes share an output byte.
+PNG_FN bool unfilter_pass(const PngJob& J, const Pass& A, uint32_t off, uint8_t* mem, int lds)
+{
+    const int rowb = A.rowb, pitch = rowb + 1, bpp = J.bpp, R = band_rows(rowb, lds);
+    const uint8_t* pal  = mem;
+    uint8_t*       prev = mem + kPngUnfilterFixed;
+    uint8_t*       band = prev + ((rowb + 15) & ~15);
+    const PNG_GLOBAL uint8_t* raw = (const PNG_GLOBAL uint8_t*)J.raw;
+    PNG_GLOBAL uint8_t*       out = (PNG_GLOBAL uint8_t*)J.out;
+    if (R < 1) return false;
+    const uint32_t opx = J.mode == AEON_PNG_BGR8 ? 3u : (uint32_t)J.elem_bytes; // output bytes of a pixel
+    const uint32_t pw  = (uint32_t)A.pw;
+    bool           ok = true, bad = false;
+    PNG_SYNC();
+    for (int i = PNG_LANE0; i < rowb; i += PNG_LANE_STEP) prev[i] = 0;
+    for (int y0 = 0; y0 < A.ph; y0 += R) {
+        const int rows = A.ph - y0 < R ? A.ph - y0 : R;
+        // whole words of the scratch, the band at its own offset mod 4 (a pass starts at any byte)
+        const size_t   g0 = (size_t)off + (size_t)y0 * pitch, g1 = g0 + (size_t)rows * pitch;
+        const uint32_t sh = (uint32_t)(g0 & 3);
+        PNG_SYNC();
+        {
+            const PNG_GLOBAL uint32_t* gw = (const PNG_GLOBAL uint32_t*)(raw + (g0 - sh));
+            uint32_t*                  lw = (uint32_t*)band;
+            const int                  nw = (int)((g1 - (g0 - sh) + 3) >> 2);
+            for (int i = PNG_LANE0; i < nw; i += PNG_LANE_STEP) lw[i] = gw[i];
+        }
+        uint8_t* b0 = band + sh;
+        if (!unfilter_band(b0, prev, rows, rowb, pitch, bpp)) ok = false;
+        if (A.dx == 1) {
+            const uint32_t ob = (uint32_t)J.out_row_bytes;
+            for (int r = 0; r < rows; r++) {
+                const uint8_t*      row = b0 + (size_t)r * pitch + 1;
+                PNG_GLOBAL uint8_t* d   = out + (size_t)(A.y0 + (y0 + r) * A.dy) * J.stride;
+                const bool          al  = (((uint64_t)(size_t)d) & 3) == 0;
+                for (uint32_t k = 4 * PNG_LANE0; k < ob; k += 4 * PNG_LANE_STEP) {
+                    uint32_t       v = 0;
+                    const uint32_t n = ob - k < 4 ? ob - k : 4;
+                    for (uint32_t j = 0; j < n; j++) v |= out_byte(J, pal, row, k + j, &bad) << (8 * j);
+                    if (al && n == 4) *(PNG_GLOBAL uint32_t*)(d + k) = v;
+                    else
+                        for (uint32_t j = 0; j < n; j++) d[k + j] = (uint8_t)(v >> (8 * j));
+                }
+            }
+        } else {
+            const uint32_t npx = (uint32_t)rows * pw; // (at most 64 rows of kPngMaxRow * 8 pixels)
+            for (uint32_t e = PNG_LANE0; e < npx; e += PNG_LANE_STEP) {
+                const uint32_t      r = e / pw, i = e - r * pw;
+                const uint8_t*      row = b0 + (size_t)r * pitch + 1;
+                PNG_GLOBAL uint8_t* d   = out + (size_t)(A.y0 + (y0 + (int)r) * A.dy) * J.stride +
+                                        (size_t)(A.x0 + (int)i * A.dx) * opx;
+                if (opx == 2) {
+                    const uint32_t v = out_byte(J, pal, row, 2 * i, &bad) | out_byte(J, pal, row, 2 * i + 1, &bad) << 8;
+                    if ((((uint64_t)(size_t)d) & 1) == 0) *(PNG_GLOBAL uint16_t*)d = (uint16_t)v;
+                    else d[0] = (uint8_t)v, d[1] = (uint8_t)(v >> 8);
+                } else {
+                    for (uint32_t j = 0; j < opx; j++) d[j] = (uint8_t)out_byte(J, pal, row, i * opx + j, &bad);
+                }
+            }
+        }
+        PNG_SYNC();
+        for (int i = PNG_LANE0; i < rowb; i += PNG_LANE_STEP) prev[i] = b0[(size_t)(rows - 1) * pitch + 1 + i];
+    }
+    return ok && !bad;
+}
+
+// The passes k0, k0 + kstep, ... of an interlaced file: one pass per wave on the device (k0 the wave's, kstep 7),
+// all seven in turn in the emulation.  mem: `lds` bytes, 16-byte aligned, png_unfilter_lds of the widest pass
+// row at least.  False: a filter byte above 4 or a palette index past PLTE in one of these passes.
+PNG_FN bool unfilter_file_adam7(const PngJob& J, int k0, int kstep, uint8_t* mem, int lds)
+{
+    bool     ok = true, loaded = false;
+    uint32_t off = 0; // where pass k starts in the scratch: the sub-images before it (below 2^31 together)
+    for (int k = 0; k < 7; k++) {
+        const Pass A = adam7_pass(J.w, J.h, J.samples * J.depth, k);
+        if (A.pw <= 0 || A.ph <= 0) continue; // absent from the stream
+        const uint32_t at = off;
+        off += ((uint32_t)A.rowb + 1) * (uint32_t)A.ph;
+        if (k < k0 || (k - k0) % kstep) continue;
+        if (!loaded) {
+            PNG_SYNC();
+            for (int i = PNG_LANE0; i < 768; i += PNG_LANE_STEP) mem[i] = J.pal[i];
+            loaded = true;
+        }
+        if (!unfilter_pass(J, A, at, mem, lds)) ok = false;
     }
     return ok;
 }

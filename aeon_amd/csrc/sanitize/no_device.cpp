@@ -130,6 +130,11 @@ int aeon_hip_decode_png_batch(aeon_hip_ctx*, int, const void* const*, const size
 {
     return no_device();
 }
+int aeon_hip_decode_png_interlaced_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const int*,
+                                         const aeon_img_desc*, void*, void*)
+{
+    return no_device();
+}
 int aeon_hip_decode_pixmap_batch(aeon_hip_ctx*, int, const void* const*, const size_t*, const int*, const aeon_img_desc*,
                                  void*, void*)
 {

@@ -413,6 +413,19 @@ int aeon_png_decoder_route(const void* data, size_t size, int* device);
  * for CPU tests and sanitizer builds): decodes like aeon_decode_png.  AEON_HIP_EUNSUPPORTED: the file is not
  * routed to the device; AEON_HIP_EDEVICE: what the device reports as corrupt. */
 int aeon_png_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+/* Opt-in: aeon_hip_decode_png_batch with Adam7-interlaced files decoded on the device too.  A file the plain call
+ * routes goes the same way; an interlaced file whose widest pass row with its filter byte is at most 16 KiB (stream
+ * and the seven sub-images together below 2^31 bytes) is inflated by the same launch as the plain files and
+ * unfiltered by png_unfilter_adam7, one wave per file and pass, each pass's pixels scattered into the record.
+ * Same results, errors and error reporting as the plain call (a bad filter byte or palette index in any pass,
+ * a stream shorter or longer than the sub-images: AEON_HIP_EDEVICE at aeon_hip_synchronize).  The decoder and
+ * the stager keep the plain call.  aeon_png_interlaced_route: *device 1 when this call decodes the file on
+ * the device (errors: the chunk walk's).  aeon_png_gpu_emulate_interlaced: aeon_png_gpu_emulate with this call's
+ * routing and kernel code. */
+int aeon_hip_decode_png_interlaced_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes,
+                                         const int* modes, const aeon_img_desc* descs, void* dst_base, void* stream);
+int aeon_png_interlaced_route(const void* data, size_t size, int* device);
+int aeon_png_gpu_emulate_interlaced(const void* data, size_t size, int mode, void* dst, size_t stride);
 
 /* Pixmap decode -- the same extractors on BMP and PNM (PBM / PGM / PPM) files, the uncompressed containers
  * cv::imdecode reads.  Modes are the PNG entries' under container-neutral names.  aeon_pixmap_info (header

@@ -6,6 +6,8 @@ decoder (image + mask, both PNG) end to end.  Classes:
   mask    512 x 512 palette masks, five classes in blobs
   depth   512 x 512 16-bit gray
   c5      Decoder over photo + mask records (C5: 512 x 512 outputs), whatever route the library takes
+  photo_i, mask_i, depth_i   the Adam7-interlaced twins: the same pixels re-encoded (adam7_twin).  Their device
+          route is the opt-in call, aeon_hip_decode_png_interlaced_batch (png_inflate + png_unfilter_adam7)
 Prints one JSON line per class: records/s, H2D bytes per record and, on the device route, the two kernels' GPU
 time per record (aeon_hip_kernel_times).  The same script runs against a parent commit's library, where only
 `--route host` and c5 exist; compare fresh processes, alternating.
@@ -14,8 +16,10 @@ import argparse
 import io
 import json
 import os
+import struct
 import sys
 import time
+import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -44,7 +48,67 @@ def _blobs(rng, side):
 VOC = [v for c in range(5) for v in (c * 30, c * 50, 255 - c * 40)]
 
 
+def _chunks(png):
+    at = 8
+    while at < len(png):
+        n = struct.unpack(">I", png[at:at + 4])[0]
+        yield png[at + 4:at + 8], png[at + 8:at + 8 + n]
+        at += 12 + n
+
+
+def _filtered(sub, bpp):
+    """Scanlines of a (rows, bytes) uint8 sub-image, each row with the filter (none, sub, up, Paeth) whose output has
+    the least sum of absolute values, as encoders choose."""
+    cur = sub.astype(np.int16)
+    a = np.pad(cur, ((0, 0), (bpp, 0)))[:, :-bpp]
+    b = np.pad(cur, ((1, 0), (0, 0)))[:-1]
+    c = np.pad(b, ((0, 0), (bpp, 0)))[:, :-bpp]
+    p = a + b - c
+    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+    cand = np.stack([cur, cur - a, cur - b, cur - paeth]).astype(np.uint8)  # filter types 0, 1, 2, 4
+    best = np.abs(cand.view(np.int8).astype(np.int16)).sum(2).argmin(0)
+    rows = cand[best, np.arange(len(sub))]
+    return np.concatenate([np.array([0, 1, 2, 4], np.uint8)[best][:, None], rows], 1).tobytes()
+
+
+def adam7_twin(png):
+    """The same pixels (8-bit gray, palette or RGB, or 16-bit gray) as an Adam7-interlaced file, zlib level 6."""
+    ch = list(_chunks(png))
+    w, h, depth, ctype = struct.unpack(">IIBB", ch[0][1][:10])
+    bpp = max(1, {0: 1, 2: 3, 3: 1}[ctype] * depth // 8)
+    px = A.decode_png(png, 0 if ctype == 2 else 2)
+    if ctype == 3:  # the indices, not the colours
+        from PIL import Image
+        px = np.asarray(Image.open(io.BytesIO(png)))
+    rows = (px[:, :, ::-1] if ctype == 2 else px.astype(">u2") if depth == 16 else px)
+    rows = np.ascontiguousarray(rows).view(np.uint8).reshape(h, w, -1)
+
+    def packed(s):  # a pass's rows as bytes: below 8 bits, 8 / depth pixels a byte, the first one highest
+        s = s.reshape(s.shape[0], -1)
+        if depth >= 8:
+            return s
+        per = 8 // depth
+        s = np.pad(s, ((0, 0), (0, -s.shape[1] % per))).reshape(s.shape[0], -1, per)
+        return (s << (8 - depth * (1 + np.arange(per, dtype=np.uint8)))).sum(2).astype(np.uint8)
+    raw = b"".join(_filtered(packed(s), bpp) for s in
+                   (rows[y0::dy, x0::dx] for x0, y0, dx, dy in zip((0, 4, 0, 2, 0, 1, 0), (0, 0, 4, 0, 2, 0, 1),
+                                                                   (8, 8, 4, 4, 2, 2, 1), (8, 8, 8, 4, 4, 2, 2))) if s.size)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data))
+    out = png[:8] + chunk(b"IHDR", ch[0][1][:12] + b"\x01")
+    out += b"".join(chunk(t, d) for t, d in ch if t == b"PLTE")
+    return out + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b"")
+
+
 def make_files(kind, n, distinct=32):
+    if kind.endswith("_i"):  # the interlaced twin of a class: the same pixels re-encoded
+        plain = make_files(kind[:-2], distinct, distinct)
+        twins = [adam7_twin(b) for b in plain]
+        for b, t in zip(plain[:4], twins):
+            assert np.array_equal(A.decode_png(b, MODE[kind]), A.decode_png(t, MODE[kind]))
+        return [twins[i % distinct] for i in range(n)]
     rng = np.random.default_rng(7)
     out = []
     for i in range(distinct):
@@ -58,7 +122,7 @@ def make_files(kind, n, distinct=32):
     return [out[i % distinct] for i in range(n)]
 
 
-MODE = {"photo": 0, "mask": 2, "depth": 2}
+MODE = {"photo": 0, "mask": 2, "depth": 2, "photo_i": 0, "mask_i": 2, "depth_i": 2}
 
 
 def run_stage(kind, route, n, windows, warmup):
@@ -78,15 +142,24 @@ def run_stage(kind, route, n, windows, warmup):
     res = {"class": kind, "route": route, "records": n, "windows": windows,
            "file_bytes_per_record": sum(len(b) for b in files) / n}
     if route == "device":
-        staged = [A.png_host_stage(b, mode) for b in files[:32]]
+        inter = kind.endswith("_i")
+        if inter:  # the opt-in call; staged: the job and the stream padded, as aeon_png_host_stage counts a plain file
+            assert all(A.png_interlaced_route(b) and not A.png_host_stage(b, mode)[0] for b in files[:32])
+            plain = make_files(kind[:-2], 1)[0]
+            idat = lambda b: sum(len(v) for t, v in _chunks(b) if t == b"IDAT")  # noqa: E731
+            job = A.png_host_stage(plain, mode)[1] - (idat(plain) + 7) // 8 * 8
+            staged = [(True, job + (idat(b) + 7) // 8 * 8) for b in files[:32]]
+        else:
+            staged = [A.png_host_stage(b, mode) for b in files[:32]]
         assert all(r for r, _ in staged), "a file of the class is not routed to the device"
         res["h2d_bytes_per_record"] = sum(s for _, s in staged) / len(staged)
         jf = A.JpegFiles(files)
         d = (A.ImgDesc * n)(*descs)
         m = (A.ctypes.c_int * n)(*([mode] * n))
+        kw = {"interlaced": True} if inter else {}
 
         def window():
-            ctx.decode_png_batch(jf, m, d, dst.data_ptr(), stream)
+            ctx.decode_png_batch(jf, m, d, dst.data_ptr(), stream, **kw)
     else:
         res["h2d_bytes_per_record"] = off / n
         pinned = torch.empty(off, dtype=torch.uint8).pin_memory()
