@@ -265,6 +265,11 @@ def lib():
         L.aeon_pixmap_host_stage.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, P(ctypes.c_int),
                                              P(ctypes.c_int64)]
         L.aeon_pixmap_gpu_emulate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
+        L.aeon_pixmap_packed_info.argtypes = L.aeon_pixmap_info.argtypes
+        L.aeon_decode_pixmap_packed.argtypes = L.aeon_decode_pixmap.argtypes
+        L.aeon_hip_decode_pixmap_packed_batch.argtypes = L.aeon_hip_decode_pixmap_batch.argtypes
+        L.aeon_pixmap_packed_route.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_int)]
+        L.aeon_pixmap_gpu_emulate_packed.argtypes = L.aeon_pixmap_gpu_emulate.argtypes
         L.aeon_tiff_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [P(ctypes.c_int)] * 4
         L.aeon_decode_tiff.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t, P(ctypes.c_int)]
         L.aeon_hip_decode_tiff_batch.argtypes = [vp, ctypes.c_int, P(vp), P(ctypes.c_size_t), P(ctypes.c_int), P(ImgDesc),
@@ -816,26 +821,30 @@ DECODE_BGR8, DECODE_GRAY8, DECODE_ANYDEPTH = PNG_BGR8, PNG_GRAY8, PNG_ANYDEPTH
 PIXMAP_BMP = 0  # pixmap_info's format of a BMP file; a PNM file's is its magic digit (1..6)
 
 
-def pixmap_info(data):
+def pixmap_info(data, packed=False):
     """(width, height, decoded bits per sample, the file's channels, format) of a BMP or PNM file
-    (aeon_pixmap_info); format is PIXMAP_BMP or the PNM magic's digit."""
+    (aeon_pixmap_info); format is PIXMAP_BMP or the PNM magic's digit.  packed: RLE8 / RLE4 and 16-bit BMP files
+    too (aeon_pixmap_packed_info), as in every packed=True call below."""
     v = [ctypes.c_int() for _ in range(5)]
-    _check(lib().aeon_pixmap_info(bytes(data), len(data), *[ctypes.byref(x) for x in v]))
+    call = lib().aeon_pixmap_packed_info if packed else lib().aeon_pixmap_info
+    _check(call(bytes(data), len(data), *[ctypes.byref(x) for x in v]))
     return tuple(x.value for x in v)
 
 
-def _pixmap_out(data, mode):
-    w, h, d, _, _ = pixmap_info(data)
+def _pixmap_out(data, mode, packed=False):
+    w, h, d, _, _ = pixmap_info(data, packed)
     cn = 3 if mode == DECODE_BGR8 else 1
     return np.zeros((h, w, cn) if cn == 3 else (h, w), np.uint16 if (mode == DECODE_ANYDEPTH and d == 16) else np.uint8)
 
 
-def decode_pixmap(data, mode=DECODE_BGR8):
+def decode_pixmap(data, mode=DECODE_BGR8, packed=False):
     """cv::imdecode of a BMP or PNM file as aeon's extractors ask for it (aeon_decode_pixmap): HxWx3 uint8 BGR
-    (DECODE_BGR8), HxW uint8 (DECODE_GRAY8), or HxW uint8 / uint16 (a PNM with maxval > 255) (DECODE_ANYDEPTH)."""
-    out = _pixmap_out(data, mode)
+    (DECODE_BGR8), HxW uint8 (DECODE_GRAY8), or HxW uint8 / uint16 (a PNM with maxval > 255) (DECODE_ANYDEPTH).
+    packed: aeon_decode_pixmap_packed."""
+    out = _pixmap_out(data, mode, packed)
     eb = ctypes.c_int()
-    _check(lib().aeon_decode_pixmap(bytes(data), len(data), mode, out.ctypes.data, out.strides[0], ctypes.byref(eb)))
+    call = lib().aeon_decode_pixmap_packed if packed else lib().aeon_decode_pixmap
+    _check(call(bytes(data), len(data), mode, out.ctypes.data, out.strides[0], ctypes.byref(eb)))
     return out
 
 
@@ -847,12 +856,22 @@ def pixmap_host_stage(data, mode=DECODE_BGR8):
     return bool(g.value), nb.value
 
 
-def pixmap_gpu_emulate(data, mode=DECODE_BGR8):
+def pixmap_gpu_emulate(data, mode=DECODE_BGR8, packed=False):
     """decode_pixmap through the pixmap stage's kernel code run on the host (aeon_pixmap_gpu_emulate).
-    AeonHipError for a file the stage leaves to the host decoder (ASCII PNM)."""
-    out = _pixmap_out(data, mode)
-    _check(lib().aeon_pixmap_gpu_emulate(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
+    AeonHipError for a file the stage leaves to the host decoder (ASCII PNM).  packed: the kernel code of
+    decode_pixmap_batch(..., packed=True) (aeon_pixmap_gpu_emulate_packed); AeonHipError with code EDEVICE for an RLE
+    stream the device would report as corrupt."""
+    out = _pixmap_out(data, mode, packed)
+    call = lib().aeon_pixmap_gpu_emulate_packed if packed else lib().aeon_pixmap_gpu_emulate
+    _check(call(bytes(data), len(data), mode, out.ctypes.data, out.strides[0]))
     return out
+
+
+def pixmap_packed_route(data):
+    """Does Context.decode_pixmap_batch(..., packed=True) decode this file on the device (aeon_pixmap_packed_route)?"""
+    g = ctypes.c_int()
+    _check(lib().aeon_pixmap_packed_route(bytes(data), len(data), ctypes.byref(g)))
+    return bool(g.value)
 
 
 def tiff_info(data):
@@ -1132,18 +1151,19 @@ class Context:
         call = lib().aeon_hip_decode_png_interlaced_batch if interlaced else lib().aeon_hip_decode_png_batch
         _check(call(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream or 0)))
 
-    def decode_pixmap_batch(self, files, modes, descs, dst_ptr, stream=0):
+    def decode_pixmap_batch(self, files, modes, descs, dst_ptr, stream=0, packed=False):
         """decode_pixmap of BMP / PNM files into device memory (aeon_hip_decode_pixmap_batch): files = list of
         bytes (or a JpegFiles, marshalled once), modes[i] = DECODE_BGR8 / DECODE_GRAY8 / DECODE_ANYDEPTH,
-        descs[i] = where record i goes (HWC; ANYDEPTH of a 16-bit PNM: native uint16)."""
+        descs[i] = where record i goes (HWC; ANYDEPTH of a 16-bit PNM: native uint16).  packed: RLE8 / RLE4 and
+        16-bit BMP files decode on the device too (aeon_hip_decode_pixmap_packed_batch, pixmap_packed_route)."""
         jf = files if isinstance(files, JpegFiles) else JpegFiles(files)
         n, ptrs, sizes = len(jf), jf.ptrs, jf.sizes
         m = modes if isinstance(modes, ctypes.Array) else (ctypes.c_int * n)(*[int(x) for x in modes])
         d = descs if isinstance(descs, ctypes.Array) else (ImgDesc * n)(*descs)
         if len(m) < n or len(d) < n:
             raise ValueError(f"{len(m)} modes / {len(d)} descriptors for {n} files")
-        _check(lib().aeon_hip_decode_pixmap_batch(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr),
-                                                  ctypes.c_void_p(stream or 0)))
+        call = lib().aeon_hip_decode_pixmap_packed_batch if packed else lib().aeon_hip_decode_pixmap_batch
+        _check(call(self._h, n, ptrs, sizes, m, d, ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream or 0)))
 
     def decode_tiff_batch(self, files, modes, descs, dst_ptr, stream=0, large_strips=False):
         """decode_tiff of TIFF files into device memory (aeon_hip_decode_tiff_batch): files = list of bytes (or a

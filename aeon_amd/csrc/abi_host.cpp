@@ -196,10 +196,10 @@ int aeon_pixmap_info(const void* data, size_t size, int* width, int* height, int
 
 namespace {
 // the header parse, the mode and the stride of the three pixmap entries that write a record
-void pixmap_checked_plan(const void* data, size_t size, int mode, size_t stride, PixmapPlan& P)
+void pixmap_checked_plan(const void* data, size_t size, int mode, size_t stride, PixmapPlan& P, bool packed = false)
 {
     if (mode < AEON_DECODE_BGR8 || mode > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown pixmap decode mode");
-    pixmap_plan(data, size, mode, P);
+    pixmap_plan(data, size, mode, P, packed);
     if (stride < (size_t)P.w * P.channels * P.elem_bytes || stride > INT32_MAX) fail(AEON_HIP_EINVAL, "stride too small");
 }
 } // namespace
@@ -246,6 +246,50 @@ int aeon_pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, 
         pixmap_checked_plan(data, size, mode, stride, P);
         if (!pixmap_gpu_emulate(data, size, mode, dst, stride))
             fail(AEON_HIP_EUNSUPPORTED, "PNM: the file is not routed to the device (ASCII samples)");
+        return 0;
+    });
+}
+
+int aeon_pixmap_packed_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* channels, int* format)
+{
+    return guarded([&] {
+        if (!data || !width || !height || !bit_depth || !channels || !format) fail(AEON_HIP_EINVAL, "null argument");
+        pixmap_header(data, size, width, height, bit_depth, channels, format, true);
+        return 0;
+    });
+}
+
+int aeon_decode_pixmap_packed(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        PixmapPlan P;
+        pixmap_checked_plan(data, size, mode, stride, P, true);
+        pixmap_decode(data, size, mode, dst, stride, elem_bytes, true);
+        return 0;
+    });
+}
+
+int aeon_pixmap_packed_route(const void* data, size_t size, int* device)
+{
+    return guarded([&] {
+        if (!data || !device) fail(AEON_HIP_EINVAL, "null argument");
+        PixmapPlan P;
+        pixmap_plan(data, size, AEON_DECODE_ANYDEPTH, P, true);
+        *device = P.route;
+        return 0;
+    });
+}
+
+int aeon_pixmap_gpu_emulate_packed(const void* data, size_t size, int mode, void* dst, size_t stride)
+{
+    return guarded([&] {
+        if (!data || !dst) fail(AEON_HIP_EINVAL, "null argument");
+        PixmapPlan P;
+        pixmap_checked_plan(data, size, mode, stride, P, true);
+        const int r = pixmap_gpu_emulate(data, size, mode, dst, stride, true);
+        if (r == 0) fail(AEON_HIP_EUNSUPPORTED, "BMP / PNM: the file is not routed to the device (ASCII samples, or 2^31 bytes or more)");
+        if (r < 0) fail(AEON_HIP_EDEVICE, "BMP: RLE data corrupt or truncated (GPU stage)");
         return 0;
     });
 }

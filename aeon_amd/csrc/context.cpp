@@ -36,7 +36,8 @@ std::string device_error_text(int err)
                 {256, "JPEG entropy-coded data corrupt or truncated (GPU Huffman decoder)"},
                 {512, "separable resize band wider than its workgroup"},
                 {1024, "PNG image data corrupt or truncated (GPU inflate / unfilter)"},
-                {2048, "TIFF strip data corrupt or truncated (GPU LZW / PackBits / Deflate decoder)"}};
+                {2048, "TIFF strip data corrupt or truncated (GPU LZW / PackBits / Deflate decoder)"},
+                {4096, "BMP RLE data corrupt or truncated (GPU RLE expand)"}};
     std::string s;
     for (const auto& b : bits)
         if (err & b.bit) s += (s.empty() ? "" : "; ") + std::string(b.what);

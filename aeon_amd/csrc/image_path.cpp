@@ -781,9 +781,12 @@ int run_png(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* siz
 // jobs, the band table, the routed files as they are (each at a 16-byte-aligned offset, at least 16 zero bytes
 // behind it, so the kernel's aligned over-reads stay inside the buffer), the host-decoded ASCII files' pixels --
 // filled on the pool, one H2D, then pixmap_convert over the bands and a strided device copy per host-decoded
-// file, all on `stream`.  The staging ring is a PngStage of the stage's own (its scratch unused).
+// file, all on `stream`.  The staging ring is a PngStage of the stage's own (its scratch unused by the plain call).
+// packed: the opt-in call -- the packed plan, and for the RLE files a table of expand jobs behind the bands and an
+// index scratch each (one byte per pixel, cleared by one memset): bmp_rle_expand over them, then the one
+// pixmap_convert launch over all bands, the RLE files' reading their scratch.
 int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
-               const aeon_img_desc* descs, void* dst_base, hipStream_t stream)
+               const aeon_img_desc* descs, void* dst_base, hipStream_t stream, bool packed)
 {
     if (!ctx || n < 0 || (n > 0 && (!data || !sizes || !modes || !descs || !dst_base))) fail(AEON_HIP_EINVAL, "null argument");
     if (n == 0) return 0;
@@ -801,7 +804,7 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
         if (!data[i] || !sizes[i]) fail(AEON_HIP_EINVAL, "BMP / PNM: empty file");
         if (modes[i] < AEON_DECODE_BGR8 || modes[i] > AEON_DECODE_ANYDEPTH) fail(AEON_HIP_EINVAL, "unknown pixmap decode mode");
         PixmapPlan& P = plans[i];
-        pixmap_plan(data[i], sizes[i], modes[i], P);
+        pixmap_plan(data[i], sizes[i], modes[i], P, packed);
         const aeon_img_desc& d = descs[i];
         if (d.width != P.w || d.height != P.h)
             fail(AEON_HIP_EINVAL, "BMP / PNM: record " + std::to_string(i) + " is " + std::to_string(P.w) + "x" +
@@ -812,22 +815,31 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
     // the band table needs the geometry only: built before the staging is laid out
     std::vector<int>        job_of(n, -1);
     std::vector<PixmapBand> bands;
-    int                     n_gpu = 0;
+    std::vector<int>        rle_of(n, -1);
+    std::vector<size_t>     idx_at(n, 0);
+    int                     n_gpu = 0, n_rle = 0;
+    size_t                  scratch = 0;
     double                  bytes = 0;
     for (int i = 0; i < n; i++) {
         const PixmapPlan& P = plans[i];
         if (!P.route) continue;
         job_of[i] = n_gpu++;
+        if (P.rle) {
+            rle_of[i] = n_rle++, idx_at[i] = scratch;
+            scratch += (pixmap_rle_scratch(P) + 15) & ~(size_t)15;
+            bytes += (double)P.rle_bytes + (double)P.w * P.h;
+        }
         PixmapJob g{};
         g.pitch = P.pitch, g.w = P.w, g.h = P.h, g.sbits = P.sbits;
         pixmap_bands(g, job_of[i], bands);
         bytes += (double)P.h * (((double)P.w * P.sbits + 7) / 8 + (double)P.w * P.channels * P.elem_bytes);
     }
     if (bands.size() > (size_t)INT32_MAX) fail(AEON_HIP_EUNSUPPORTED, "BMP / PNM: too many bands for one call");
-    // layout: the jobs, the bands, then per file the file itself or its pixels (16-byte aligned)
+    // layout: the jobs, the bands, the expand jobs, then per file the file itself or its pixels (16-byte aligned)
     std::vector<size_t> at(n);
     const size_t        bands_at = (size_t)n_gpu * sizeof(PixmapJob);
-    size_t              total    = bands_at + bands.size() * sizeof(PixmapBand);
+    const size_t        rle_at   = bands_at + bands.size() * sizeof(PixmapBand);
+    size_t              total    = rle_at + (size_t)n_rle * sizeof(PixmapRleJob);
     for (int i = 0; i < n; i++) {
         const PixmapPlan& P = plans[i];
         total               = (total + 15) & ~(size_t)15;
@@ -841,7 +853,9 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
     st.pending = false;
     if (total > st.pinned_cap) grow(st.pinned, st.pinned_cap, total + total / 4, true);
     if (total > st.dev_cap) grow(st.dev, st.dev_cap, total + total / 4, false);
-    PixmapJob* jobs = (PixmapJob*)st.pinned;
+    if (scratch > st.scratch_cap) grow(st.scratch, st.scratch_cap, scratch + scratch / 4, false);
+    PixmapJob*    jobs  = (PixmapJob*)st.pinned;
+    PixmapRleJob* files = (PixmapRleJob*)(st.pinned + rle_at);
     if (!bands.empty()) std::memcpy(st.pinned + bands_at, bands.data(), bands.size() * sizeof(PixmapBand));
     each([&](int i) {
         const PixmapPlan& P = plans[i];
@@ -856,6 +870,12 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
         J.src    = (uint64_t)(st.dev + at[i]);
         J.out    = (uint64_t)dst_base + descs[i].offset;
         J.stride = descs[i].stride;
+        if (P.rle) { // the expand reads the file, the convert the scratch
+            PixmapRleJob& R = files[rle_of[i]];
+            pixmap_rle_job(P, R);
+            R.src = J.src, R.idx = (uint64_t)(st.scratch + idx_at[i]);
+            J.src = R.idx;
+        }
     });
     KernelTimer t{};
     bool        timed = false;
@@ -864,8 +884,13 @@ int run_pixmap(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* 
         if ((timed = take_timing(ctx))) t = take_timer(ctx, kTimerPng, bytes);
     }
     HIP_OK(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, stream));
+    if (n_rle) HIP_OK(hipMemsetAsync(st.scratch, 0, scratch, stream));
     if (timed) HIP_OK(hipEventRecord(t.start, stream));
-    HIP_OK(launch_pixmap((const PixmapJob*)st.dev, (const PixmapBand*)(st.dev + bands_at), (int)bands.size(), stream));
+    if (packed)
+        HIP_OK(launch_pixmap_packed((const PixmapRleJob*)(st.dev + rle_at), n_rle, (const PixmapJob*)st.dev,
+                                    (const PixmapBand*)(st.dev + bands_at), (int)bands.size(), stream_error(ctx, stream), stream));
+    else
+        HIP_OK(launch_pixmap((const PixmapJob*)st.dev, (const PixmapBand*)(st.dev + bands_at), (int)bands.size(), stream));
     if (timed) {
         HIP_OK(hipEventRecord(t.stop, stream));
         std::lock_guard<std::mutex> tl(ctx->mu);
@@ -1035,7 +1060,13 @@ int aeon_hip_decode_tiff_large_batch(aeon_hip_ctx* ctx, int n, const void* const
 int aeon_hip_decode_pixmap_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
                                  const aeon_img_desc* descs, void* dst_base, void* stream)
 {
-    return guarded([&] { return run_pixmap(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream); });
+    return guarded([&] { return run_pixmap(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream, false); });
+}
+
+int aeon_hip_decode_pixmap_packed_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                                        const aeon_img_desc* descs, void* dst_base, void* stream)
+{
+    return guarded([&] { return run_pixmap(ctx, n, data, sizes, modes, descs, dst_base, (hipStream_t)stream, true); });
 }
 
 int aeon_hip_decode_png_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,

@@ -30,6 +30,7 @@ struct JpegProgMask;
 struct PngJob;
 struct PixmapJob;
 struct PixmapBand;
+struct PixmapRleJob;
 struct TiffJob;
 struct TiffStrip;
 struct TiffBand;
@@ -91,6 +92,9 @@ hipError_t launch_png(const PngJob* jobs, int n_plain, int unfilter_lds, int n_a
                       hipStream_t stream);
 // pixmap_kernels.hip: pixmap_convert, one workgroup per band
 hipError_t launch_pixmap(const PixmapJob* jobs, const PixmapBand* bands, int n_bands, hipStream_t stream);
+// ... the packed call: bmp_rle_expand, one wave per RLE file, then pixmap_convert over all bands
+hipError_t launch_pixmap_packed(const PixmapRleJob* files, int n_files, const PixmapJob* jobs, const PixmapBand* bands, int n_bands,
+                                int32_t* error, hipStream_t stream);
 // tiff_kernels.hip: tiff_expand, one wave per compressed strip or tile, tiff_expand_large, one wave per LZW / PackBits
 // strip or tile above kTiffStripCap, then tiff_convert, one workgroup per band, and
 // tiff_convert_tiled, one per band of the tiled files (each launched only where its table holds work)

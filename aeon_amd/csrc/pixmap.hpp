@@ -8,6 +8,11 @@
 // file as it is into pinned staging; pixmap_convert (one workgroup per file and band of rows) stages the
 // band's source bytes in LDS with aligned loads and converts them into the record.  ASCII PNM files stay with
 // pixmap_decode on the host (pixmap_route).  The decode rules are DESIGN section 20.
+//
+// The opt-in call (aeon_hip_decode_pixmap_packed_batch, `packed` below) also takes RLE8 / RLE4 and 16-bit BMP files:
+// bmp_rle_expand (one wave per file, pixmap_rle.hpp) writes an RLE file's palette indices into a scratch of one byte
+// per pixel, which the convert kernel then reads as a kPmIndex8 source; 16-bit files are two more kinds of out_byte,
+// held by the packed call's instantiation of the kernel alone (pixmap_convert_packed).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -27,11 +32,16 @@ enum PixmapKind : int32_t {
     kPmRgb16,     // P6, maxval > 255: big-endian R, G, B
     kPmBgr8,      // 24-bit BMP: B, G, R
     kPmBgra8,     // 32-bit BMP: B, G, R, x
+    kPm555,       // 16-bit BMP, little-endian x1 R5 G5 B5 (the packed calls only)
+    kPm565,       // 16-bit BMP, little-endian R5 G6 B5 (the packed calls only)
 };
 
 constexpr int kPixmapLanes     = 256;       // pixmap_convert workgroup
 constexpr int kPixmapBandBytes = 16 * 1024; // most source bytes of one band (LDS: these + 8, and the 1 KiB table)
 constexpr size_t kPixmapMaxPixels = (size_t)1 << 28;
+constexpr int kPixmapCorruptBit = 4096;     // device error word: an RLE stream bmp_rle_expand refuses
+constexpr int kRleBlockWords    = 2048;     // bmp_rle_expand: 16-bit words of the stream staged in LDS at a time ...
+constexpr int kRleAheadWords    = 128;      // ... and behind them what a token that starts in the block's last window spans
 
 // colour -> gray, one formula everywhere (8- and 16-bit samples, palette entries); parity unpinned
 constexpr uint32_t pixmap_gray(uint32_t b, uint32_t g, uint32_t r) { return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14; }
@@ -51,6 +61,19 @@ struct alignas(16) PixmapJob {
 };
 static_assert(sizeof(PixmapJob) % 16 == 0, "PixmapJob: 16-byte aligned array elements");
 
+// One RLE file of the packed call: its stream expanded into its index scratch (bmp_rle_expand), which the file's
+// PixmapJob names as its source.
+struct alignas(16) PixmapRleJob {
+    uint64_t src;    // the file in the staging, as PixmapJob::src
+    uint64_t idx;    // the index scratch: h rows of `pitch` bytes, stored (bottom-up) row y at y * pitch; zero on entry
+    uint32_t off;    // byte offset of the stream in the file, unaligned as it comes
+    uint32_t bytes;  // the stream's bytes: to the end of the file
+    int32_t  w, h;
+    int32_t  pitch;  // w rounded up to 4
+    int32_t  depth;  // 8: RLE8, 4: RLE4
+};
+static_assert(sizeof(PixmapRleJob) % 16 == 0, "PixmapRleJob: 16-byte aligned array elements");
+
 // One workgroup's work: rows [y0, y0 + rows) of a job, pixels [p0, p0 + np) of them (p0 > 0 only where one row's
 // source is wider than a band: then rows == 1 and p0 is a multiple of 8, a whole source byte at every depth).
 struct alignas(16) PixmapBand {
@@ -67,17 +90,21 @@ struct PixmapPlan {
     int64_t off  = 0;       // as PixmapJob::off; ASCII PNM: where the samples start
     int32_t pitch = 0;      // as PixmapJob::pitch
     uint32_t table[256] = {};
+    // an RLE file (packed): off / pitch above then describe the index scratch, bottom-up, and these the stream
+    int      rle = 0;       // 0, or the depth: 8 / 4
+    uint32_t rle_off = 0, rle_bytes = 0;
 };
 
 // header only: AEON_PIXMAP_* format, width, height, decoded bits per sample (8 or 16), the file's channels
-void pixmap_header(const void* data, size_t size, int* w, int* h, int* bit_depth, int* channels, int* format);
+// packed (here and below): also the RLE8 / RLE4 and 16-bit BMP files of the opt-in calls
+void pixmap_header(const void* data, size_t size, int* w, int* h, int* bit_depth, int* channels, int* format, bool packed = false);
 // true when the first bytes are a BMP's or a PNM's as the decoder's inspect step sniffs them (strict: anything
 // else is left to the JPEG parser and its error)
 bool pixmap_sniff(const void* data, size_t size);
 // the whole decode on the calling thread into rows `stride` bytes apart; out_elem_bytes (optional): 1 or 2
-void pixmap_decode(const void* data, size_t size, int mode, void* dst, size_t stride, int* out_elem_bytes);
+void pixmap_decode(const void* data, size_t size, int mode, void* dst, size_t stride, int* out_elem_bytes, bool packed = false);
 // The header parse of pixmap_decode (same refusals, same messages), the table and the routing rule.
-void pixmap_plan(const void* data, size_t size, int mode, PixmapPlan& P);
+void pixmap_plan(const void* data, size_t size, int mode, PixmapPlan& P, bool packed = false);
 // The routing rule: binary PNM and uncompressed BMP below 2^31 bytes go to the device.
 bool pixmap_route(const PixmapPlan& P, size_t size);
 // What the decoder's inspect step asks: does this file go through the stage?  pixmap_route's plain rule (DESIGN
@@ -87,6 +114,9 @@ bool pixmap_routed(const void* data, size_t size);
 // A routed file's job (everything but the two addresses and the stride) and the file copied to file_dst (size bytes;
 // the caller pads).
 void pixmap_stage(const void* data, size_t size, int mode, const PixmapPlan& P, PixmapJob& J, uint8_t* file_dst);
+// An RLE file's expand job (everything but the two addresses) and the bytes of its index scratch.
+void   pixmap_rle_job(const PixmapPlan& P, PixmapRleJob& R);
+inline size_t pixmap_rle_scratch(const PixmapPlan& P) { return (size_t)((P.w + 3) & ~3) * P.h; }
 // The bands of job `job`, appended.
 template <typename Vec>
 inline void pixmap_bands(const PixmapJob& J, int job, Vec& bands)
@@ -101,8 +131,8 @@ inline void pixmap_bands(const PixmapJob& J, int job, Vec& bands)
     for (int y = 0; y < J.h; y++)
         for (int p0 = 0; p0 < J.w; p0 += P) bands.push_back(PixmapBand{job, y, 1, p0, J.w - p0 < P ? J.w - p0 : P, {0, 0, 0}});
 }
-// The stage's kernel code run on this thread, lane after lane (pixmap_rows.hpp): true decoded, false the file is
-// not routed to the device (nothing written).
-bool pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+// The stage's kernel code run on this thread, lane after lane (pixmap_rows.hpp, pixmap_rle.hpp): 1 decoded, 0 the
+// file is not routed to the device (nothing written), -1 the device would set kPixmapCorruptBit.
+int pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride, bool packed = false);
 
 } // namespace aeon_hip

@@ -5,10 +5,13 @@
 // calling thread (aeon_decode_pixmap, and the ASCII files the stage leaves to the host), and the host half of
 // the pixmap stage (aeon_hip_decode_pixmap_batch): pixmap_plan / pixmap_stage parse the header, refuse what a
 // file can be refused for, build the table and copy the file; the conversion is the kernel's
-// (pixmap_kernels.hip).  pixmap_gpu_emulate runs the kernel's own code (pixmap_rows.hpp) on the host.
+// (pixmap_kernels.hip).  pixmap_gpu_emulate runs the kernel's own code (pixmap_rows.hpp) on the host.  `packed`: the
+// opt-in calls, which also take RLE8 / RLE4 and 16-bit BMP files (rle_decode the serial host decoder,
+// pixmap_rle.hpp the wave's code for the emulation).
 //
 // Every read of the file is checked against `size` first: the header reader never passes the end, and the
 // pixel data's extent is checked before a byte of it is read.
+#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <string>
@@ -17,6 +20,7 @@
 #include "../../include/aeon_hip.h"
 #include "error.hpp" // jpeg_error: an error carrying its AEON_HIP_E* code
 #include "pixmap.hpp"
+#include "pixmap_rle.hpp"
 #include "pixmap_rows.hpp"
 
 namespace aeon_hip {
@@ -96,7 +100,9 @@ void plan_pnm(const uint8_t* d, size_t size, PixmapPlan& P, bool need_data)
     if (ascii && (bits ? ns : 2 * ns - 1) > size - p) pnm_bad("the file ends before its samples");
 }
 
-void plan_bmp(const uint8_t* d, size_t size, PixmapPlan& P, bool need_data)
+// packed: the opt-in calls' files too -- RLE8 / RLE4 (bottom-up), 16-bit 5-5-5 and 5-6-5, and BI_BITFIELDS files whose
+// masks are one of those two or, at 32 bits, the BI_RGB layout's own
+void plan_bmp(const uint8_t* d, size_t size, PixmapPlan& P, bool need_data, bool packed)
 {
     P.format = AEON_PIXMAP_BMP;
     const uint32_t offbits = le32(d + 10), hs = le32(d + 14);
@@ -111,10 +117,28 @@ void plan_bmp(const uint8_t* d, size_t size, PixmapPlan& P, bool need_data)
     }
     const int64_t ah = h < 0 ? -h : h;
     if (w < 1 || ah < 1 || (uint64_t)w * (uint64_t)ah > kPixmapMaxPixels) bmp_bad("bad image size");
-    if (comp == 1 || comp == 2) bmp_bad(std::string(comp == 1 ? "RLE8" : "RLE4") + " compressed files are not supported", AEON_HIP_EUNSUPPORTED);
-    if (comp == 3 || bpp == 16) bmp_bad("16-bit (555 / 565 / bitfields) files are not supported", AEON_HIP_EUNSUPPORTED);
-    if (comp != 0) bmp_bad("unknown compression " + std::to_string(comp));
-    if (bpp != 1 && bpp != 4 && bpp != 8 && bpp != 24 && bpp != 32) bmp_bad("bad bit count " + std::to_string(bpp));
+    if (!packed) {
+        if (comp == 1 || comp == 2) bmp_bad(std::string(comp == 1 ? "RLE8" : "RLE4") + " compressed files are not supported", AEON_HIP_EUNSUPPORTED);
+        if (comp == 3 || bpp == 16) bmp_bad("16-bit (555 / 565 / bitfields) files are not supported", AEON_HIP_EUNSUPPORTED);
+    } else if (comp == 4 || comp == 5) {
+        bmp_bad(std::string(comp == 4 ? "BI_JPEG" : "BI_PNG") + " files are not supported", AEON_HIP_EUNSUPPORTED);
+    }
+    if (comp > 3) bmp_bad("unknown compression " + std::to_string(comp));
+    const bool rle = comp == 1 || comp == 2;
+    if (rle) {
+        if (bpp != (comp == 1 ? 8u : 4u)) bmp_bad(std::string(comp == 1 ? "RLE8" : "RLE4") + " compression at bit count " + std::to_string(bpp));
+        if (h < 0) bmp_bad("top-down RLE");
+    }
+    bool is565 = false;
+    if (comp == 3) { // the three masks lie behind the 40 header bytes, inside a longer header or not
+        if (bpp != 16 && bpp != 32) bmp_bad("BI_BITFIELDS at bit count " + std::to_string(bpp));
+        if (size < 66) bmp_bad("truncated header");
+        const uint32_t mr = le32(d + 54), mg = le32(d + 58), mb = le32(d + 62);
+        is565 = bpp == 16 && mr == 0xF800 && mg == 0x07E0 && mb == 0x001F;
+        const bool known = bpp == 16 ? is565 || (mr == 0x7C00 && mg == 0x03E0 && mb == 0x001F) : mr == 0x00FF0000 && mg == 0x0000FF00 && mb == 0x000000FF;
+        if (!known) bmp_bad("BI_BITFIELDS with masks other than 5-5-5, 5-6-5 or 8-8-8 are not supported", AEON_HIP_EUNSUPPORTED);
+    }
+    if (bpp != 1 && bpp != 4 && bpp != 8 && bpp != 16 && bpp != 24 && bpp != 32) bmp_bad("bad bit count " + std::to_string(bpp));
     if (bpp <= 8) {
         const uint32_t n = (hs == 12 || used == 0) ? 1u << bpp : used, esz = hs == 12 ? 3 : 4;
         if (n > 256) bmp_bad("a palette of more than 256 entries");
@@ -123,21 +147,28 @@ void plan_bmp(const uint8_t* d, size_t size, PixmapPlan& P, bool need_data)
         for (uint32_t i = 0; i < n; i++) P.table[i] = table_entry(d[at + i * esz], d[at + i * esz + 1], d[at + i * esz + 2]);
         // (entries past the stored ones stay zero: an index past the palette decodes as black)
     }
+    P.w = (int)w, P.h = (int)ah, P.bit_depth = 8, P.file_channels = 3, P.sbits = (int)bpp;
+    if (rle) { // the stream runs to the file's end; the rows are those of the index scratch, a byte per pixel
+        if (need_data && offbits > size) bmp_bad("truncated pixel data");
+        const int64_t sp = (w + 3) & ~(int64_t)3;
+        P.rle = (int)bpp, P.rle_off = offbits, P.rle_bytes = need_data ? (uint32_t)std::min<size_t>(size - offbits, UINT32_MAX) : 0;
+        P.kind = kPmIndex8, P.sbits = 8, P.off = sp * (ah - 1), P.pitch = -(int32_t)sp;
+        return;
+    }
     const uint64_t pitch = ((((uint64_t)w * bpp + 7) / 8) + 3) & ~(uint64_t)3;
     if (need_data && (offbits > size || pitch * (uint64_t)ah > size - offbits)) bmp_bad("truncated pixel data");
-    P.w = (int)w, P.h = (int)ah, P.bit_depth = 8, P.file_channels = 3, P.sbits = (int)bpp;
-    P.kind  = bpp == 1 ? kPmBits1 : bpp == 4 ? kPmBits4 : bpp == 8 ? kPmIndex8 : bpp == 24 ? kPmBgr8 : kPmBgra8;
+    P.kind  = bpp == 1 ? kPmBits1 : bpp == 4 ? kPmBits4 : bpp == 8 ? kPmIndex8 : bpp == 16 ? (is565 ? kPm565 : kPm555) : bpp == 24 ? kPmBgr8 : kPmBgra8;
     // height > 0: bottom-up, output row 0 is the last stored row
     P.off   = h < 0 ? (int64_t)offbits : (int64_t)offbits + (int64_t)pitch * (ah - 1);
     P.pitch = h < 0 ? (int32_t)pitch : -(int32_t)pitch;
 }
 
 // need_data false: the header alone (aeon_pixmap_info), the pixel data's extent unchecked
-void plan_any(const void* data, size_t size, PixmapPlan& P, bool need_data = true)
+void plan_any(const void* data, size_t size, PixmapPlan& P, bool need_data = true, bool packed = false)
 {
     const uint8_t* d = (const uint8_t*)data;
     if (sniff_pnm(d, size)) plan_pnm(d, size, P, need_data);
-    else if (size >= 18 && d[0] == 'B' && d[1] == 'M') plan_bmp(d, size, P, need_data);
+    else if (size >= 18 && d[0] == 'B' && d[1] == 'M') plan_bmp(d, size, P, need_data, packed);
     else throw jpeg_error(AEON_HIP_EINVAL, "BMP / PNM: neither a BMP nor a PNM file");
 }
 
@@ -184,6 +215,40 @@ void emit(uint8_t* dst, size_t x, int mode, bool out16, bool wide, uint32_t b, u
     }
 }
 
+// A BMP RLE stream, token after token, into a canvas of palette indices (rows as the plan's pitch has them, stored
+// row y at y * pitch; entry 0 where nothing is written).  DESIGN section 20 holds the rules.
+void rle_decode(const uint8_t* s, size_t n, const PixmapPlan& P, std::vector<uint8_t>& canvas)
+{
+    const size_t pitch = (size_t)-(int64_t)P.pitch;
+    const int64_t W = P.w, H = P.h;
+    canvas.assign(pitch * (size_t)P.h, 0);
+    int64_t x = 0, y = 0;
+    for (size_t p = 0; p < n;) {
+        if (n - p < 2) bmp_bad("truncated RLE data");
+        const uint32_t a = s[p], b = s[p + 1];
+        p += 2;
+        if (a == 0 && b == 0) {
+            x = 0, y++;
+        } else if (a == 0 && b == 1) {
+            return;
+        } else if (a == 0 && b == 2) {
+            if (n - p < 2) bmp_bad("truncated RLE data");
+            x += s[p], y += s[p + 1], p += 2;
+        } else {
+            const uint32_t cnt = a ? a : b;
+            const size_t   pay = a ? 0 : (P.rle == 8 ? (size_t)((b + 1) & ~1u) : (size_t)(((b + 3) >> 2) << 1));
+            if (pay > n - p) bmp_bad("truncated RLE data");
+            if (x + cnt > W || y >= H) bmp_bad("RLE data outside the image");
+            uint8_t* o = canvas.data() + (size_t)y * pitch + (size_t)x;
+            for (uint32_t k = 0; k < cnt; k++) {
+                const uint32_t v = a ? b : s[p + (P.rle == 8 ? k : k >> 1)];
+                o[k] = (uint8_t)(P.rle == 8 ? v : (k & 1) ? v & 15 : v >> 4);
+            }
+            x += cnt, p += pay;
+        }
+    }
+}
+
 void set_mode(PixmapPlan& P, int mode)
 {
     P.channels   = mode == AEON_DECODE_BGR8 ? 3 : 1;
@@ -194,16 +259,16 @@ void set_mode(PixmapPlan& P, int mode)
 
 bool pixmap_sniff(const void* data, size_t size) { return sniff_pnm((const uint8_t*)data, size) || sniff_bmp((const uint8_t*)data, size); }
 
-void pixmap_header(const void* data, size_t size, int* w, int* h, int* bit_depth, int* channels, int* format)
+void pixmap_header(const void* data, size_t size, int* w, int* h, int* bit_depth, int* channels, int* format, bool packed)
 {
     PixmapPlan P;
-    plan_any(data, size, P, false);
+    plan_any(data, size, P, false, packed);
     *w = P.w, *h = P.h, *bit_depth = P.bit_depth, *channels = P.file_channels, *format = P.format;
 }
 
-void pixmap_plan(const void* data, size_t size, int mode, PixmapPlan& P)
+void pixmap_plan(const void* data, size_t size, int mode, PixmapPlan& P, bool packed)
 {
-    plan_any(data, size, P);
+    plan_any(data, size, P, true, packed);
     set_mode(P, mode);
     P.route = pixmap_route(P, size) ? 1 : 0;
 }
@@ -224,13 +289,18 @@ bool pixmap_routed(const void* data, size_t size)
     return pixmap_route(P, size);
 }
 
-void pixmap_decode(const void* data, size_t size, int mode, void* dst_, size_t stride, int* out_elem_bytes)
+void pixmap_decode(const void* data, size_t size, int mode, void* dst_, size_t stride, int* out_elem_bytes, bool packed)
 {
     PixmapPlan P;
-    plan_any(data, size, P);
+    plan_any(data, size, P, true, packed);
     set_mode(P, mode);
     if (out_elem_bytes) *out_elem_bytes = P.elem_bytes;
     const uint8_t* d     = (const uint8_t*)data;
+    std::vector<uint8_t> canvas;
+    if (P.rle) { // the indices first; the rows below then read them as an 8-bit file's
+        rle_decode(d + P.rle_off, size - P.rle_off, P, canvas);
+        d = canvas.data();
+    }
     uint8_t*       dst   = (uint8_t*)dst_;
     const bool     out16 = P.elem_bytes == 2, wide = P.bit_depth == 16;
     if (P.format >= 1 && P.format <= 3) {
@@ -270,6 +340,14 @@ void pixmap_decode(const void* data, size_t size, int mode, void* dst_, size_t s
                 break;
             }
             case kPmBgr8: b = row[3 * (size_t)x], g = row[3 * (size_t)x + 1], r = row[3 * (size_t)x + 2]; break;
+            case kPm555:
+            case kPm565: {
+                const uint32_t v = le16(row + 2 * (size_t)x);
+                b = (v << 3) & 0xF8;
+                g = P.kind == kPm555 ? (v >> 2) & 0xF8 : (v >> 3) & 0xFC;
+                r = P.kind == kPm555 ? (v >> 7) & 0xF8 : (v >> 8) & 0xF8;
+                break;
+            }
             default: b = row[4 * (size_t)x], g = row[4 * (size_t)x + 1], r = row[4 * (size_t)x + 2]; break; // kPmBgra8
             }
             emit(o, (size_t)x, mode, out16, wide, b, g, r, gray);
@@ -286,20 +364,39 @@ void pixmap_stage(const void* data, size_t size, int mode, const PixmapPlan& P, 
     std::memcpy(file_dst, data, size);
 }
 
-bool pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride)
+void pixmap_rle_job(const PixmapPlan& P, PixmapRleJob& R)
+{
+    R = PixmapRleJob{};
+    R.off = P.rle_off, R.bytes = P.rle_bytes, R.w = P.w, R.h = P.h, R.pitch = -P.pitch, R.depth = P.rle;
+}
+
+int pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride, bool packed)
 {
     PixmapPlan P;
-    pixmap_plan(data, size, mode, P);
-    if (!P.route) return false;
+    pixmap_plan(data, size, mode, P, packed);
+    if (!P.route) return 0;
     PixmapJob             J;
     std::vector<uint64_t> file((size + 15) / 16 * 2 + 2, 0); // 16-byte aligned, 16 zero bytes behind the file
     pixmap_stage(data, size, mode, P, J, (uint8_t*)file.data());
     J.src = (uint64_t)file.data(), J.out = (uint64_t)dst, J.stride = (int32_t)stride;
+    std::vector<uint32_t> idx;
+    if (P.rle) { // bmp_rle_expand's wave, then the convert over the scratch
+        PixmapRleJob R;
+        pixmap_rle_job(P, R);
+        idx.assign(pixmap_rle_scratch(P) / 4 + 1, 0);
+        R.src = J.src, R.idx = (uint64_t)idx.data();
+        std::vector<pmdev::RleMem> M(1);
+        if (!pmdev::rle_expand(R, M[0])) return -1;
+        J.src = R.idx;
+    }
     std::vector<PixmapBand> bands;
     pixmap_bands(J, 0, bands);
     std::vector<uint32_t> tab(256), lds(kPixmapBandBytes / 4 + 2);
-    for (const PixmapBand& B : bands) pmdev::convert_band(J, B, tab.data(), (uint8_t*)lds.data());
-    return true;
+    for (const PixmapBand& B : bands) {
+        if (packed) pmdev::convert_band<true>(J, B, tab.data(), (uint8_t*)lds.data());
+        else pmdev::convert_band(J, B, tab.data(), (uint8_t*)lds.data());
+    }
+    return 1;
 }
 
 } // namespace aeon_hip

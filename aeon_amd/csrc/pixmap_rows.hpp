@@ -16,7 +16,11 @@
 #define PM_SYNC() __syncthreads()
 #define PM_GLOBAL __attribute__((address_space(1)))
 #else
+#if defined(__HIP__) // (the host pass over a .hip file: the kernels' calls of the templates must resolve there too)
+#define PM_FN __host__ __device__ inline
+#else
 #define PM_FN inline
+#endif
 #define PM_LANE0 0
 #define PM_LANE_STEP 1
 #define PM_SYNC() ((void)0)
@@ -33,6 +37,8 @@ struct RowForm {
 };
 
 // Byte k of an output row from the staged source row; `row` points at source byte `s0` of the row.
+// Packed: the packed call's kernel, which alone knows the 16-bit kinds -- the plain kernel's code does not hold them.
+template <bool Packed>
 PM_FN uint32_t out_byte(const RowForm& F, const uint32_t* tab, const uint8_t* row, uint32_t s0, uint32_t k)
 {
     const uint32_t px = F.bgr ? k / 3 : F.out16 ? k >> 1 : k;
@@ -57,6 +63,12 @@ PM_FN uint32_t out_byte(const RowForm& F, const uint32_t* tab, const uint8_t* ro
         const uint32_t r = (uint32_t)p[0] << 8 | p[1], g = (uint32_t)p[2] << 8 | p[3], b = (uint32_t)p[4] << 8 | p[5];
         return (pixmap_gray(b, g, r) >> (8 * (k & 1))) & 0xff;
     }
+    if (Packed && F.kind >= kPm555) { // OpenCV's shifts, no bit replication
+        const uint8_t* p = row + (2 * px - s0);
+        const uint32_t v = (uint32_t)p[0] | (uint32_t)p[1] << 8, b = (v << 3) & 0xf8;
+        const uint32_t g = F.kind == kPm555 ? (v >> 2) & 0xf8 : (v >> 3) & 0xfc, r = F.kind == kPm555 ? (v >> 7) & 0xf8 : (v >> 8) & 0xf8;
+        return F.bgr ? (ch == 0 ? b : ch == 1 ? g : r) : pixmap_gray(b, g, r);
+    }
     const uint32_t spp = F.kind == kPmBgra8 ? 4 : 3;
     const uint8_t* p   = row + (spp * px - s0);
     if (F.kind == kPmRgb8) return F.bgr ? p[2 - ch] : pixmap_gray(p[2], p[1], p[0]);
@@ -67,6 +79,7 @@ PM_FN uint32_t out_byte(const RowForm& F, const uint32_t* tab, const uint8_t* ro
 // placed at their own offset mod 4; then every lane four consecutive output bytes of a row per step, stored
 // as one dword where the destination is aligned and bytewise at a row's unaligned head and tail.
 // tab: 256 words; lds: kPixmapBandBytes + 8 bytes, 4-byte aligned.
+template <bool Packed = false>
 PM_FN void convert_band(const PixmapJob& J, const PixmapBand& B, uint32_t* tab, uint8_t* lds)
 {
     const int     kind = J.kind, rows = B.rows;
@@ -100,7 +113,7 @@ PM_FN void convert_band(const PixmapJob& J, const PixmapBand& B, uint32_t* tab, 
         if (start >= end) continue;
         const uint8_t* row = lds + sh + (size_t)(pitch < 0 ? rows - 1 - (int)r : (int)r) * ap;
         uint32_t       v   = 0;
-        for (uint32_t j = start; j < end; j++) v |= out_byte(F, tab, row, (uint32_t)sb0, k0 + j) << (8 * (j - start));
+        for (uint32_t j = start; j < end; j++) v |= out_byte<Packed>(F, tab, row, (uint32_t)sb0, k0 + j) << (8 * (j - start));
         PM_GLOBAL uint8_t* d = (PM_GLOBAL uint8_t*)(da + start);
         if (end - start == 4 && g) *(PM_GLOBAL uint32_t*)d = v;
         else

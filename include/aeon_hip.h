@@ -346,7 +346,8 @@ int aeon_hip_set_timing(aeon_hip_ctx* ctx, int every);
  * [2]=pre-passes (resize_short, CUBIC / AREA / LANCZOS4 resize, 2x-area ahead of photometric),
  * [3]=JPEG IDCT + colour kernels of aeon_hip_decode_jpeg_batch (bytes: decoded pixels),
  * [4]=PNG and pixmap decode kernels (png_inflate + png_unfilter of aeon_hip_decode_png_batch, bytes: inflated
- * scanlines; pixmap_convert of aeon_hip_decode_pixmap_batch, bytes: source rows plus records): total ms,
+ * scanlines; pixmap_convert of aeon_hip_decode_pixmap_batch, bytes: source rows plus records; the packed call's
+ * bmp_rle_expand is timed with its pixmap_convert): total ms,
  * total algorithmic bytes, launches.  The arrays hold `kinds` entries (AEON_HIP_TIMER_KINDS = all;
  * fewer are filled, more are left alone).  Resets the totals of every kind. */
 #define AEON_HIP_TIMER_KINDS 5
@@ -459,6 +460,30 @@ int aeon_pixmap_host_stage(const void* data, size_t size, int mode, int* gpu_rou
 /* The stage's kernel code run on the calling thread, lane after lane, no device (for CPU tests and sanitizer
  * builds): decodes like aeon_decode_pixmap.  AEON_HIP_EUNSUPPORTED: the file is not routed to the device. */
 int aeon_pixmap_gpu_emulate(const void* data, size_t size, int mode, void* dst, size_t stride);
+/* The opt-in calls: everything above, and the BMP files the plain calls refuse -- 8-bit BI_RLE8 and 4-bit BI_RLE4
+ * (bottom-up; a negative height is refused, "BMP: top-down RLE"), 16-bit BI_RGB (5-5-5), 16-bit BI_BITFIELDS with the
+ * masks 7C00/03E0/001F or F800/07E0/001F, and 32-bit BI_BITFIELDS with 00FF0000/0000FF00/000000FF (the 32-bit
+ * BI_RGB file it equals).  Other masks, BI_JPEG and BI_PNG stay refused.  A 16-bit pixel decodes with OpenCV's
+ * shifts, no bit replication: 5-5-5 B = (v << 3) & F8, G = (v >> 2) & F8, R = (v >> 7) & F8; 5-6-5 G = (v >> 3) & FC,
+ * R = (v >> 8) & F8.  An RLE canvas starts as palette entry 0 at the bottom row's left end; a run or literal past
+ * the row's end or at y >= height, or a token cut off by the end of the file, is corrupt (data that ends between
+ * tokens ends the stream).  aeon_pixmap_packed_info and aeon_decode_pixmap_packed are aeon_pixmap_info and
+ * aeon_decode_pixmap over these files too (a BMP: 3 channels, 8 bits); the host decoder refuses a corrupt stream
+ * with AEON_HIP_EINVAL.  aeon_hip_decode_pixmap_packed_batch takes every file aeon_hip_decode_pixmap_batch takes the
+ * same way and decodes the new ones on the device, byte for byte as aeon_decode_pixmap_packed: bmp_rle_expand, one
+ * wave per RLE file, writes the stream's palette indices into device scratch (windows of 64 sixteen-bit words, a
+ * word per lane), and pixmap_convert reads that as an 8-bit file's rows; 16-bit files go through pixmap_convert as
+ * they lie.  A corrupt stream sets a bit of the stream's device error word (4096), reported by
+ * aeon_hip_synchronize; that file's record is unspecified, the others' are right.  The decoder, the stager and the
+ * plain calls keep refusing these files.  aeon_pixmap_packed_route: *device 1 when this call decodes the file on
+ * the device (errors: the header parser's).  aeon_pixmap_gpu_emulate_packed: aeon_pixmap_gpu_emulate with this
+ * call's files; AEON_HIP_EDEVICE where the device would set the corrupt bit. */
+int aeon_pixmap_packed_info(const void* data, size_t size, int* width, int* height, int* bit_depth, int* channels, int* format);
+int aeon_decode_pixmap_packed(const void* data, size_t size, int mode, void* dst, size_t stride, int* elem_bytes);
+int aeon_hip_decode_pixmap_packed_batch(aeon_hip_ctx* ctx, int n, const void* const* data, const size_t* sizes, const int* modes,
+                                        const aeon_img_desc* descs, void* dst_base, void* stream);
+int aeon_pixmap_packed_route(const void* data, size_t size, int* device);
+int aeon_pixmap_gpu_emulate_packed(const void* data, size_t size, int mode, void* dst, size_t stride);
 
 /* TIFF decode -- the same extractors on classic TIFF files in strips or tiles (first IFD, both byte orders).  Modes are
  * AEON_DECODE_*.  aeon_tiff_info: size, the file's channels (3 for RGB and palette files, else 1) and the element

@@ -6,6 +6,9 @@ code, not the kernel under test).  Classes:
   p5w     512 x 512 16-bit P5 (depth-like), decoded at ANYDEPTH
   bmp8    512 x 512 8-bit palette BMP masks, decoded at ANYDEPTH (the gray of the palette entry)
   p4      512 x 512 P4 bitmaps, decoded to GRAY8
+  rle8    the bmp8 masks as BI_RLE8 files, rle4 the same blobs as 4-bit BI_RLE4 files, bmp16 512 x 512 5-6-5
+          BI_BITFIELDS files decoded to BGR8: the packed classes, through aeon_hip_decode_pixmap_packed_batch
+          (bmp_rle_expand, then pixmap_convert) or, `--route host`, aeon_decode_pixmap_packed on the 16 threads
 Prints one JSON line per class: records/s, H2D bytes per record and, on the device route, the kernel's GPU time per
 record (aeon_hip_kernel_times, kind "png": the PNG and pixmap decode kernels).  `--runs N` starts N fresh processes
 per class and route, alternating the routes, and prints min..max.
@@ -44,6 +47,31 @@ def _bmp8(idx, palette):
     return b"BM" + struct.pack("<IHHI", off + pitch * h, 0, 0, off) + info + pal + rows.tobytes()
 
 
+def _rle(idx, palette, depth):
+    """A BI_RLE8 / BI_RLE4 file of the indices: each row as runs of at most 255 (RLE4: the index in both nibbles), an EOL."""
+    h, w = idx.shape
+    s = bytearray()
+    for row in idx[::-1]:
+        cuts = np.flatnonzero(np.diff(row)) + 1
+        for a, b in zip(np.r_[0, cuts], np.r_[cuts, w]):
+            v = int(row[a]) * (17 if depth == 4 else 1)
+            for n in [255] * ((b - a) // 255) + [(b - a) % 255] * bool((b - a) % 255):
+                s += bytes([n, v])
+        s += b"\0\0"
+    s += b"\0\1"
+    pal = np.concatenate([palette[:1 << depth], np.zeros((1 << depth, 1), np.uint8)], 1).tobytes()
+    off = 14 + 40 + len(pal)
+    info = struct.pack("<IiiHHIIiiII", 40, w, h, 1, depth, 1 if depth == 8 else 2, len(s), 2835, 2835, 0, 0)
+    return b"BM" + struct.pack("<IHHI", off + len(s), 0, 0, off) + info + pal + bytes(s)
+
+
+def _bmp565(bgr):
+    h, w = bgr.shape[:2]
+    v = (bgr[:, :, 2].astype(np.uint16) >> 3 << 11 | bgr[:, :, 1].astype(np.uint16) >> 2 << 5 | bgr[:, :, 0] >> 3).astype("<u2")
+    info = struct.pack("<IiiHHIIiiII", 40, w, h, 1, 16, 3, 2 * w * h, 2835, 2835, 0, 0) + struct.pack("<III", 0xF800, 0x07E0, 0x001F)
+    return b"BM" + struct.pack("<IHHI", 66 + 2 * w * h, 0, 0, 66) + info + v[::-1].tobytes()
+
+
 def _blobs(rng, side):
     cls = rng.integers(0, 5, (side // 64, side // 64)).astype(np.uint8)
     return np.roll(np.kron(cls, np.ones((64, 64), np.uint8)), int(rng.integers(0, 64)), axis=1)
@@ -60,21 +88,27 @@ def make_files(kind, n, distinct=32):
             out.append(_pnm(5, (ramp + rng.integers(0, 64, (512, 512)).astype(np.uint16)).astype(np.uint16), 65535))
         elif kind == "bmp8":
             out.append(_bmp8(_blobs(rng, 512), rng.integers(0, 256, (256, 3)).astype(np.uint8)))
+        elif kind in ("rle8", "rle4"):
+            out.append(_rle(_blobs(rng, 512), rng.integers(0, 256, (256, 3)).astype(np.uint8), int(kind[3])))
+        elif kind == "bmp16":
+            out.append(_bmp565(A.synthetic_image(100 + i, 512, 512, 3)))
         else:
             out.append(_pnm(4, _blobs(rng, 512) & 1, 1))
     return [out[i % distinct] for i in range(n)]
 
 
-MODE = {"p6": A.DECODE_BGR8, "p5w": A.DECODE_ANYDEPTH, "bmp8": A.DECODE_ANYDEPTH, "p4": A.DECODE_GRAY8}
+MODE = {"p6": A.DECODE_BGR8, "p5w": A.DECODE_ANYDEPTH, "bmp8": A.DECODE_ANYDEPTH, "p4": A.DECODE_GRAY8,
+        "rle8": A.DECODE_ANYDEPTH, "rle4": A.DECODE_ANYDEPTH, "bmp16": A.DECODE_BGR8}
+PACKED = ("rle8", "rle4", "bmp16")
 
 
 def run_stage(kind, route, n, windows, warmup):
     import torch
     files = make_files(kind, n)
-    mode = MODE[kind]
+    mode, packed = MODE[kind], kind in PACKED
     descs, off = [], 0
     for b in files:
-        w, h, d, _, _ = A.pixmap_info(b)
+        w, h, d, _, _ = A.pixmap_info(b, packed)
         eb = 2 if (mode == A.DECODE_ANYDEPTH and d == 16) else 1
         cn = 3 if mode == A.DECODE_BGR8 else 1
         descs.append(A.ImgDesc(offset=off, width=w, height=h, stride=w * cn * eb, channels=cn, elem_bytes=eb))
@@ -85,7 +119,7 @@ def run_stage(kind, route, n, windows, warmup):
     res = {"class": kind, "route": route, "records": n, "windows": windows,
            "file_bytes_per_record": sum(len(b) for b in files) / n, "record_bytes": off / n}
     if route == "device":
-        staged = [A.pixmap_host_stage(b, mode) for b in files[:32]]
+        staged = [(A.pixmap_packed_route(b), len(b)) if packed else A.pixmap_host_stage(b, mode) for b in files[:32]]
         assert all(r for r, _ in staged), "a file of the class is not routed to the device"
         res["h2d_bytes_per_record"] = sum(s for _, s in staged) / len(staged)
         jf = A.JpegFiles(files)
@@ -93,17 +127,18 @@ def run_stage(kind, route, n, windows, warmup):
         m = (A.ctypes.c_int * n)(*([mode] * n))
 
         def window():
-            ctx.decode_pixmap_batch(jf, m, d, dst.data_ptr(), stream)
+            ctx.decode_pixmap_batch(jf, m, d, dst.data_ptr(), stream, packed=packed)
     else:
         res["h2d_bytes_per_record"] = off / n
         pinned = torch.empty(off, dtype=torch.uint8).pin_memory()
         base = pinned.data_ptr()
         pool = ThreadPoolExecutor(16)
         lib = A.lib()
+        decode = lib.aeon_decode_pixmap_packed if packed else lib.aeon_decode_pixmap
 
         def one(i):
             de = descs[i]
-            rc = lib.aeon_decode_pixmap(files[i], len(files[i]), mode, A.ctypes.c_void_p(base + de.offset), de.stride, None)
+            rc = decode(files[i], len(files[i]), mode, A.ctypes.c_void_p(base + de.offset), de.stride, None)
             assert rc == 0
 
         def window():
